@@ -29,6 +29,9 @@ line on rank 0.  Outside `value`, the same line carries (N = 1 unless said other
 `--config 3` / `--config 4` / `--config 5` make one of those the timed `value` instead; CWC_GRAPH_BIN=<file.bin> runs a
 real graph (synthetic inputs by its input count) in place of the generated authV2-class one.
 
+`--dump-outputs DIR` writes, after the timed steps, what the last of them computed (witness rows and status words of rank 0's
+shard, float64 .npy, at most 64 MB: dump_outputs) -- the inputs depend on the arguments alone, so two builds can be compared file by file.
+
 `--gpus N` with N > 1 and no RANK in the environment starts the N ranks itself: a CHILD `python -m torch.distributed.run
 --nproc-per-node N bench.py ...` spawned before anything touches a GPU, its JSON line relayed (never an exec).  `--dry-run`
 runs the same multi-rank flow on CPU (gloo, the program emulator of tests/ instead of the kernels, a toy graph): what the
@@ -141,6 +144,45 @@ def run_steps(g, d_in, d_out, d_st, steps, warmup, distributed):
     return time.perf_counter() - t0
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs: all files together stay under this
+DUMP_SEED = 0xD0C5      # the sample of sets / witness columns when the whole output does not fit
+
+
+def dump_outputs(path, witness, status, first_set=0):
+    """--dump-outputs: what the timed path returned in its last step, as float64 .npy files a run of another build can be
+    compared with element for element.  `witness` uint8 [B, W, 32] (torch, any device, or numpy), `status` [B].
+      status.npy       [B]        the status word of every set
+      witness.npy      [S, W', 8] the field elements of the sampled sets / columns as eight 32-bit limbs, least significant
+                                  first (a float64 holds a 32-bit limb exactly; a 254-bit element would not fit)
+      set_index.npy    [S]        the global index of each dumped set
+      witness_index.npy [W']      the witness column of each dumped element
+    Everything is dumped when it fits in DUMP_BYTES; otherwise a sample seeded by DUMP_SEED, sorted, fixed for given arguments."""
+    import torch
+    b, w = int(witness.shape[0]), int(witness.shape[1])
+    elem = 8 * 8                                               # bytes of one dumped field element
+    budget = DUMP_BYTES - 16 * b - (1 << 16)                   # (status and set index of every set, .npy headers)
+    rng = np.random.default_rng(DUMP_SEED)
+    cols = np.arange(w)
+    if w * (elem + 8) > budget:                                # (+ its entry in witness_index)
+        cols = np.sort(rng.choice(w, size=budget // (elem + 8), replace=False))
+    budget -= 8 * len(cols)
+    sets = np.arange(b)
+    if b * len(cols) * elem > budget:
+        sets = np.sort(rng.choice(b, size=max(1, budget // (len(cols) * elem)), replace=False))
+    wt = torch.as_tensor(witness)
+    if len(sets) < b:
+        wt = wt[torch.as_tensor(sets, device=wt.device)]
+    if len(cols) < w:
+        wt = wt[:, torch.as_tensor(cols, device=wt.device)]
+    limbs = wt.contiguous().cpu().numpy().view("<u4")          # [S, W', 8]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "witness.npy"), limbs.astype(np.float64))
+    np.save(os.path.join(path, "status.npy"), torch.as_tensor(status).cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "set_index.npy"), (sets + first_set).astype(np.float64))
+    np.save(os.path.join(path, "witness_index.npy"), cols.astype(np.float64))
+    log("bench.py: dumped %d of %d sets x %d of %d witness elements to %s" % (len(sets), b, len(cols), w, path))
+
+
 def kernel_times(g, steps):
     """HIP events the library recorded on the launch stream around each kernel of the timed steps (read after the run:
     no synchronization inside the timed region) -> per-step interpreter / pack milliseconds"""
@@ -237,16 +279,18 @@ def dry_run(args, real_stdout):
             blob = cdist.broadcast_blob(blob, src=0, device="cpu")
     prog = pe.Blob(blob)
 
+    last = [None, None]   # witness rows and status words of the latest evaluate()
+
     def evaluate(lo, hi):
         rows = synth_inputs("field", prog.n_inputs, hi - lo, SEED + 4, lo)
         wit = np.zeros((hi - lo, prog.n_witness, 32), dtype=np.uint8)
-        bad = 0
+        st = np.zeros(hi - lo, dtype=np.int32)
         for k in range(hi - lo):
-            vals, status = pe.run(prog, [int.from_bytes(rows[k, q].tobytes(), "little") for q in range(prog.n_inputs)])
-            bad += status != 0
-            if status == 0:
+            vals, st[k] = pe.run(prog, [int.from_bytes(rows[k, q].tobytes(), "little") for q in range(prog.n_inputs)])
+            if st[k] == 0:
                 wit[k] = np.frombuffer(b"".join(v.to_bytes(32, "little") for v in vals), dtype=np.uint8).reshape(-1, 32)
-        return cdist.set_checksums(torch.from_numpy(wit)), bad
+        last[:] = [wit, st]
+        return cdist.set_checksums(torch.from_numpy(wit)), int((st != 0).sum())
     lo, hi = cdist.shard_range(total, rank, world)
     if distributed:
         dist.barrier()
@@ -256,6 +300,8 @@ def dry_run(args, real_stdout):
     if distributed:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0], last[1], lo)
     if distributed:
         te = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
@@ -315,7 +361,11 @@ def main():
     ap.add_argument("--config5-graph", choices=["rsa", "bigint"], default="rsa", help="--config 5: the class BASELINE names (zk-email RSA / long_div: 121-bit registers x 17) or the "
                                                                                        "builder's first generator (64-bit limbs x 32, division by one limb)")
     ap.add_argument("--dry-run", action="store_true", help="CPU rehearsal of the multi-rank flow: gloo, program emulator, toy graph (no GPU, no timing claim)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (rank 0's shard) as "
+                                                                        "float64 .npy files under DIR (bench.dump_outputs; at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "RANK" not in os.environ:
         # One command for the N-GPU run: start the ranks as a CHILD launcher (nothing in this process has touched a GPU:
         # `import torch` does not initialise one) and relay its line.  Never an exec.
@@ -390,6 +440,8 @@ def main():
         dist.barrier()
     bad_sets = int((d_st != 0).sum().item())
     tm, interp_ms, pack_ms = kernel_times(g, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_out, d_st, lo)
 
     out = None
     if rank == 0:

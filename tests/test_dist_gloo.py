@@ -219,3 +219,49 @@ def test_bench_watchdog_exits_nonzero():
             "    time.sleep(30)\n") % ROOT
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
     assert r.returncode == 3 and "watchdog: test block did not finish" in r.stderr
+
+
+@pytest.mark.timeout(300)
+def test_bench_dump_outputs_dry_run_is_repeatable(tmp_path):
+    """`--dump-outputs DIR` writes what the last timed step computed as float64 .npy files; the same arguments give the same
+    inputs and therefore the same files, and `--steps` is the number of timed steps the line reports."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0", "--dry-run",
+                            "--batch-per-gpu", "3", "--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=240, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads(r.stdout.strip().splitlines()[-1])["steps"] == 2
+        dumps.append({f: np.load(str(tmp_path / name / f)) for f in sorted(os.listdir(str(tmp_path / name)))})
+    a, b = dumps
+    assert sorted(a) == ["set_index.npy", "status.npy", "witness.npy", "witness_index.npy"]
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["witness.npy"].shape == (3, len(a["witness_index.npy"]), 8) and list(a["set_index.npy"]) == [0, 1, 2]
+    assert not a["status.npy"].any() and a["witness.npy"][:, 0].tolist() == [[1, 0, 0, 0, 0, 0, 0, 0]] * 3  # witness 0 is the constant 1
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry-run"], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_bench_dump_outputs_samples_within_the_limit(tmp_path):
+    """An output larger than the limit is dumped as a seeded sample of sets (and of witness columns when one set alone is too large):
+    under 64 MB in all, the same sample every time, every dumped element exactly the limbs of the element it names."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    for shape in ((3000, 700), (2, 2100000)):
+        wit = rng.integers(0, 256, size=shape + (32,), dtype=np.uint8)
+        st = rng.integers(0, 3, size=shape[0], dtype=np.int32)
+        for name in ("a", "b"):
+            bench.dump_outputs(str(tmp_path / name), wit, st, first_set=10)
+        files = sorted(os.listdir(str(tmp_path / "a")))
+        assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= 64 << 20
+        assert all(np.array_equal(np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))) for f in files)
+        got = np.load(str(tmp_path / "a" / "witness.npy"))
+        sets = np.load(str(tmp_path / "a" / "set_index.npy")).astype(np.int64) - 10
+        cols = np.load(str(tmp_path / "a" / "witness_index.npy")).astype(np.int64)
+        assert 0 < len(sets) <= shape[0] and 0 < len(cols) <= shape[1] and len(sets) * len(cols) < shape[0] * shape[1]
+        assert np.array_equal(got, wit[sets][:, cols].view("<u4").astype(np.float64))
+        assert np.array_equal(np.load(str(tmp_path / "a" / "status.npy")), st.astype(np.float64))
