@@ -94,6 +94,8 @@ def build(verbose=False, diag=False):
     if not verbose:
         cmd.insert(1, "-s")
     subprocess.check_call(cmd)
+    # the R1CS check (libcwc_r1cs.so + check-witness): a library of its own, outside csrc/
+    subprocess.check_call(["make"] + ([] if verbose else ["-s"]) + ["-C", os.path.join(_HERE, "r1cs"), "-j4"])
 
 
 DIAG_LIB_PATH = os.path.join(_HERE, "libcircom_witnesscalc_amd_diag.so")
@@ -480,6 +482,120 @@ class Graph:
         if lib().gwb_last_timing(self._h, ctypes.byref(t)) != 0:
             raise WitnessCalcError("gwb_last_timing failed")
         return {n: getattr(t, n) for n, _ in Timing._fields_}
+
+
+# -- R1CS satisfaction check (include/graph_witness_r1cs.h, libcwc_r1cs.so built from r1cs/) ------------------------------
+R1CS_LIB_PATH = os.environ.get("CWC_R1CS_LIB_PATH") or os.path.join(_HERE, "libcwc_r1cs.so")
+R1CS_SATISFIED = 0xFFFFFFFF
+_r1cs_lib = None
+
+
+class R1csInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("n_wires", "n_pub_out", "n_pub_in", "n_prv_in", "n_constraints")] + \
+               [(n, ctypes.c_uint64) for n in ("n_labels", "n_factors_a", "n_factors_b", "n_factors_c")]
+
+
+def r1cs_lib():
+    """ctypes handle of libcwc_r1cs.so, loaded after torch (one HIP runtime per process, as in lib())."""
+    global _r1cs_lib
+    if _r1cs_lib is None:
+        if not os.path.exists(R1CS_LIB_PATH):
+            raise WitnessCalcError("R1CS library %s is missing: run __graft_entry__.build()" % R1CS_LIB_PATH)
+        try:
+            import torch  # noqa: F401
+        except ImportError:
+            pass
+        L = ctypes.CDLL(R1CS_LIB_PATH)
+        vp, sz, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32
+        stp = ctypes.POINTER(GwStatus)
+        L.gwb_r1cs_load.argtypes = [vp, sz, ctypes.POINTER(vp), stp]
+        L.gwb_r1cs_free.restype = None
+        L.gwb_r1cs_free.argtypes = [vp]
+        L.gwb_r1cs_info.argtypes = [vp, ctypes.POINTER(R1csInfo)]
+        L.gwb_r1cs_set_tile_width.argtypes = [vp, u32]
+        L.gwb_r1cs_check_batch_device.argtypes = [vp, vp, sz, sz, u32, vp, vp, vp, stp]
+        L.gwb_r1cs_check_batch_host.argtypes = [vp, vp, sz, sz, vp, vp, stp]
+        L.gwb_r1cs_check_wtns.argtypes = [vp, vp, sz, vp, vp, stp]
+        _r1cs_lib = L
+    return _r1cs_lib
+
+
+def _r1cs_check(rc, st):
+    msg = ctypes.string_at(st.error_msg).decode("utf-8", "replace") if st.error_msg else ""
+    if st.error_msg:
+        _libc.free(st.error_msg)
+    if rc != 0:
+        raise WitnessCalcError(msg or "call failed")
+
+
+class R1cs:
+    """A circuit's constraint system (`.r1cs` bytes, iden3 binfile v1; BN254, no custom gates) for checking witness rows on the
+    GPU: per row, the smallest failing constraint index (R1CS_SATISFIED if none) and the number of failing constraints."""
+
+    def __init__(self, data):
+        self._h = ctypes.c_void_p()
+        data = bytes(data)
+        st = GwStatus()
+        rc = r1cs_lib().gwb_r1cs_load(data, len(data), ctypes.byref(self._h), ctypes.byref(st))
+        _r1cs_check(rc, st)
+        info = R1csInfo()
+        r1cs_lib().gwb_r1cs_info(self._h, ctypes.byref(info))
+        self.info = {n: int(getattr(info, n)) for n, _ in R1csInfo._fields_}
+
+    def close(self):
+        if getattr(self, "_h", None) and _r1cs_lib is not None:
+            _r1cs_lib.gwb_r1cs_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def set_tile_width(self, t):
+        """Witness rows per wavefront of the check kernel: a power of two in 1..64, or 0 = from the batch size."""
+        if r1cs_lib().gwb_r1cs_set_tile_width(self._h, t) != 0:
+            raise WitnessCalcError("tile width must be 0 or a power of two in 1..64")
+
+    def check_batch(self, witness_rows):
+        """Host rows uint8 [B, W, 32] (canonical), or the (witness, status) pair of Graph.calc_witness_batch ->
+        (first_failed uint32 [B], n_failed uint32 [B]).  Synchronous."""
+        if isinstance(witness_rows, tuple):
+            witness_rows = witness_rows[0]
+        w = np.ascontiguousarray(witness_rows, dtype=np.uint8)
+        assert w.ndim == 3 and w.shape[2] == 32, w.shape
+        b = w.shape[0]
+        first = np.zeros(b, dtype=np.uint32)
+        nfail = np.zeros(b, dtype=np.uint32)
+        st = GwStatus()
+        rc = r1cs_lib().gwb_r1cs_check_batch_host(self._h, w.ctypes.data, w.shape[1], b, first.ctypes.data, nfail.ctypes.data, ctypes.byref(st))
+        _r1cs_check(rc, st)
+        return first, nfail
+
+    def check_batch_device(self, d_witness, stream=None, montgomery=False):
+        """Device rows (torch uint8 cuda tensor [B, W, 32], canonical or Montgomery form) -> (first_failed, n_failed) as int32
+        cuda tensors [B] (first_failed -1 = R1CS_SATISFIED).  Asynchronous on `stream` (torch.cuda.Stream) or the current
+        torch stream: put it behind Graph.calc_witness_batch_device on the same stream."""
+        import torch
+        assert d_witness.is_cuda and d_witness.is_contiguous() and d_witness.dtype == torch.uint8
+        assert d_witness.dim() == 3 and d_witness.shape[2] == 32, tuple(d_witness.shape)
+        b = d_witness.shape[0]
+        s = stream if stream is not None else torch.cuda.current_stream(d_witness.device)
+        first = torch.empty(b, dtype=torch.int32, device=d_witness.device)
+        nfail = torch.empty(b, dtype=torch.int32, device=d_witness.device)
+        st = GwStatus()
+        with torch.cuda.device(d_witness.device):
+            rc = r1cs_lib().gwb_r1cs_check_batch_device(self._h, d_witness.data_ptr(), d_witness.shape[1], b,
+                                                        FORM_MONTGOMERY if montgomery else FORM_CANONICAL, first.data_ptr(),
+                                                        nfail.data_ptr(), s.cuda_stream, ctypes.byref(st))
+        _r1cs_check(rc, st)
+        return first, nfail
+
+    def check_wtns(self, wtns):
+        """One `.wtns` image -> (first_failed, n_failed); first_failed is R1CS_SATISFIED when every constraint holds."""
+        wtns = bytes(wtns)
+        first, nfail = ctypes.c_uint32(), ctypes.c_uint32()
+        st = GwStatus()
+        rc = r1cs_lib().gwb_r1cs_check_wtns(self._h, wtns, len(wtns), ctypes.byref(first), ctypes.byref(nfail), ctypes.byref(st))
+        _r1cs_check(rc, st)
+        return int(first.value), int(nfail.value)
 
 
 from . import graphgen  # noqa: E402,F401  (graph generator library on top of the C-ABI producer)

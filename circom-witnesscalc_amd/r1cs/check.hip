@@ -1,0 +1,352 @@
+// R1CS satisfaction check on gfx950: for every (witness row s, constraint j)
+//     ok(s, j) <=> (sum_A a w) * (sum_B b w) - sum_C c w == 0 (mod r)
+// with per-row results first_failed[s] (smallest failing original index) and n_failed[s].
+//
+// Exactness with one Montgomery product per general factor: coefficients are stored as c * R, so fr_mul(w, cR) = c * w
+// for a canonical w and c * w * R for a Montgomery-form w, fully reduced either way; +1 / -1 factors add or subtract w
+// itself.  The comparison is fr_mul(A, B) (= AB / R) against C / R (canonical rows: fr_mul(C, 1)) or against C
+// (Montgomery rows: AB / R = ab * R = c * R).  An element at or above r in a row (not a field element; .wtns images are
+// refused on the host) is reduced where it is added directly, so the result is still exact mod r.
+//
+// Lane mapping: a wavefront covers T rows x 64/T constraints (T a power of two in 1..64).  At T = 64 the constraint is
+// wave-uniform: its factor stream and coefficients come through scalar loads, every lane gathers the 32 bytes of its own
+// row.  At small T (T = 1: the single-file case) every lane walks a constraint of its own; the host buckets constraints
+// by length so that the lanes of a wave do similar work.
+#include <hip/hip_runtime.h>
+
+#include <string.h>
+
+#include <string>
+
+#include "r1cs_internal.hpp"
+
+using namespace cwc_r1cs;
+using cwc::Fr;
+
+namespace {
+
+constexpr int WAVES_PER_BLOCK = 4;
+
+__device__ __forceinline__ Fr load_elem(const uint8_t* row, uint32_t wire) {
+    const uint4* p = reinterpret_cast<const uint4*>(row + (size_t)wire * 32);
+    const uint4 lo = p[0], hi = p[1];
+    return Fr{{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}};
+}
+
+// w mod r for any w < 2^256 (rare: rows from the witness calculator are already below r)
+__device__ __forceinline__ Fr reduce_any(Fr w) {
+    if (!cwc::u256_lt(w, cwc::fr_p())) {
+        const Fr one{{1, 0, 0, 0, 0, 0, 0, 0}};
+        w = cwc::fr_mul(cwc::fr_mul(w, cwc::fr_r2()), one);  // (w R) / R
+    }
+    return w;
+}
+
+__device__ __forceinline__ Fr accumulate(const Fr& acc, Fr w, uint32_t kind, const Fr* __restrict__ coef, uint32_t ci) {
+    if (kind == KIND_GENERAL) return cwc::fr_add(acc, cwc::fr_mul(w, coef[ci]));  // w may be any value below 2^256 as the first operand
+    w = reduce_any(w);
+    return kind == KIND_PLUS ? cwc::fr_add(acc, w) : cwc::fr_sub(acc, w);
+}
+
+// Four factors at a time: their four witness gathers are in flight together before the arithmetic that needs the first.
+__device__ __forceinline__ Fr lin_comb(const uint32_t* __restrict__ fac, const uint32_t* __restrict__ cidx, const Fr* __restrict__ coef,
+                                       uint32_t k, uint32_t end, const uint8_t* row) {
+    constexpr int U = 4;
+    Fr acc = cwc::fr_zero();
+    for (; k + U <= end; k += U) {
+        uint32_t f[U];
+        Fr w[U];
+#pragma unroll
+        for (int i = 0; i < U; ++i) f[i] = fac[k + i];
+#pragma unroll
+        for (int i = 0; i < U; ++i) w[i] = load_elem(row, f[i] & WIRE_MASK);
+#pragma unroll
+        for (int i = 0; i < U; ++i) acc = accumulate(acc, w[i], f[i] >> 30, coef, cidx[k + i]);
+    }
+    for (; k < end; ++k) {
+        const uint32_t f = fac[k];
+        acc = accumulate(acc, load_elem(row, f & WIRE_MASK), f >> 30, coef, cidx[k]);
+    }
+    return acc;
+}
+
+template <int T>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void r1cs_check_kernel(
+    const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ fac, const uint32_t* __restrict__ cidx,
+    const Fr* __restrict__ coef, const uint32_t* __restrict__ perm, uint32_t n_constraints, const uint8_t* __restrict__ witness,
+    uint32_t n_witness, uint32_t batch, uint32_t montgomery, uint32_t* __restrict__ first_failed, uint32_t* __restrict__ n_failed) {
+    constexpr uint32_t G = 64 / T;  // constraints per wave step
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t set = blockIdx.x * T + lane % T;
+    const bool set_ok = set < batch;
+    if (!set_ok) set = batch - 1;  // (a duplicate of a real row; its result is dropped)
+    const uint8_t* row = witness + (size_t)set * n_witness * 32;
+    const uint32_t n_groups = (n_constraints + G - 1) / G;
+    const Fr one{{1, 0, 0, 0, 0, 0, 0, 0}};
+    for (uint32_t g = blockIdx.y * WAVES_PER_BLOCK + wave; g < n_groups; g += gridDim.y * WAVES_PER_BLOCK) {
+        uint32_t c = g * G + lane / T;  // T = 64: wave-uniform
+        const bool c_ok = c < n_constraints;
+        if (!c_ok) c = n_constraints - 1;
+        const uint32_t ka = rowptr[3 * c], kb = rowptr[3 * c + 1], kc = rowptr[3 * c + 2], ke = rowptr[3 * c + 3];
+        const Fr a = lin_comb(fac, cidx, coef, ka, kb, row);
+        const Fr b = ka == kb ? cwc::fr_zero() : lin_comb(fac, cidx, coef, kb, kc, row);  // (linear constraints: A, B empty)
+        const Fr cc = lin_comb(fac, cidx, coef, kc, ke, row);
+        const Fr lhs = cwc::fr_mul(a, b);
+        const Fr rhs = montgomery ? cc : cwc::fr_mul(cc, one);
+        if (!cwc::u256_eq(lhs, rhs) && set_ok && c_ok) {  // rare: failing sets only
+            atomicMin(first_failed + set, perm[c]);
+            atomicAdd(n_failed + set, 1u);
+        }
+    }
+}
+
+typedef void (*KernelFn)(const uint32_t*, const uint32_t*, const uint32_t*, const Fr*, const uint32_t*, uint32_t, const uint8_t*, uint32_t,
+                         uint32_t, uint32_t, uint32_t*, uint32_t*);
+
+KernelFn kernel_for(uint32_t t) {
+    switch (t) {
+        case 1: return r1cs_check_kernel<1>;
+        case 2: return r1cs_check_kernel<2>;
+        case 4: return r1cs_check_kernel<4>;
+        case 8: return r1cs_check_kernel<8>;
+        case 16: return r1cs_check_kernel<16>;
+        case 32: return r1cs_check_kernel<32>;
+        default: return r1cs_check_kernel<64>;
+    }
+}
+
+// rows per wave: the batch rounded up to a power of two, at most 64 (full waves of rows once there are 64 of them)
+uint32_t pick_tile_width(size_t batch) {
+    uint32_t t = 1;
+    while (t < 64 && t < batch) t <<= 1;
+    return t;
+}
+
+std::string hip_err(const char* what, hipError_t e) { return std::string("r1cs: ") + what + ": " + hipGetErrorString(e); }
+
+template <class V>
+bool upload(void** d, const V& v, std::string& err) {
+    const size_t bytes = std::max<size_t>(v.size() * sizeof(v[0]), 4);
+    hipError_t e = hipMalloc(d, bytes);
+    if (e == hipSuccess && !v.empty()) e = hipMemcpy(*d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        err = hip_err("uploading the constraint arrays", e);
+        return false;
+    }
+    return true;
+}
+
+void release_device(gwb_r1cs* r) {
+    for (void** p : {&r->d_rowptr, &r->d_fac, &r->d_cidx, &r->d_coef, &r->d_perm}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    r->device = -1;
+}
+
+// The constraint arrays go to the current device on the first check and stay there.
+bool ensure_device(gwb_r1cs* r, std::string& err) {
+    int dev = -1, n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+        err = "r1cs: no HIP device (the check runs on the GPU only)";
+        return false;
+    }
+    if (hipGetDevice(&dev) != hipSuccess) {
+        err = "r1cs: hipGetDevice failed";
+        return false;
+    }
+    if (r->device >= 0) {
+        if (dev != r->device) {
+            err = "r1cs: the handle's constraint arrays live on device " + std::to_string(r->device) + ", the current device is " + std::to_string(dev);
+            return false;
+        }
+        return true;
+    }
+    if (!upload(&r->d_rowptr, r->rowptr, err) || !upload(&r->d_fac, r->fac, err) || !upload(&r->d_cidx, r->cidx, err) ||
+        !upload(&r->d_coef, r->coef, err) || !upload(&r->d_perm, r->perm, err)) {
+        release_device(r);
+        return false;
+    }
+    r->device = dev;
+    return true;
+}
+
+bool check_args(gwb_r1cs* r, size_t n_witness, size_t batch, std::string& err) {
+    if (n_witness != r->info.n_wires) {
+        err = "r1cs: the witness has " + std::to_string(n_witness) + " elements, the circuit " + std::to_string(r->info.n_wires) + " wires";
+        return false;
+    }
+    if (batch > 0xffffffffull) {
+        err = "r1cs: batch above 2^32 - 1";
+        return false;
+    }
+    return true;
+}
+
+// enqueue: result initialisation + the check kernel on `stream`
+bool enqueue(gwb_r1cs* r, const void* d_witness, size_t batch, uint32_t form, uint32_t* d_first, uint32_t* d_nfail, hipStream_t stream,
+             std::string& err) {
+    hipError_t e = hipMemsetAsync(d_first, 0xff, batch * 4, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_nfail, 0, batch * 4, stream);
+    if (e != hipSuccess) {
+        err = hip_err("clearing the results", e);
+        return false;
+    }
+    const uint32_t nc = r->info.n_constraints;
+    if (nc == 0) return true;
+    const uint32_t t = r->tile_width ? r->tile_width : pick_tile_width(batch);
+    const uint32_t g = 64 / t;
+    const uint64_t n_groups = (nc + (uint64_t)g - 1) / g;
+    const uint64_t tiles = (batch + t - 1) / t;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, r->device) != hipSuccess || cus <= 0) cus = 256;
+    // about eight blocks (32 waves) per CU in all, each wave striding over the constraint groups
+    const uint64_t want_y = std::max<uint64_t>(1, (uint64_t)cus * 8 / std::max<uint64_t>(tiles, 1));
+    const uint64_t gy = std::min<uint64_t>({want_y, (n_groups + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 65535});
+    if (tiles > 0x7fffffffull) {
+        err = "r1cs: batch too large for one launch";
+        return false;
+    }
+    hipLaunchKernelGGL(kernel_for(t), dim3((uint32_t)tiles, (uint32_t)gy), dim3(64 * WAVES_PER_BLOCK), 0, stream, (const uint32_t*)r->d_rowptr,
+                       (const uint32_t*)r->d_fac, (const uint32_t*)r->d_cidx, (const Fr*)r->d_coef, (const uint32_t*)r->d_perm, nc,
+                       (const uint8_t*)d_witness, r->info.n_wires, (uint32_t)batch, form == GWB_FORM_MONTGOMERY ? 1u : 0u, d_first, d_nfail);
+    e = hipGetLastError();
+    if (e != hipSuccess) {
+        err = hip_err("launching the check kernel", e);
+        return false;
+    }
+    return true;
+}
+
+int fail(gw_status_t* st, const std::string& msg) {
+    set_status(st, msg);
+    return 1;
+}
+
+// host rows -> device -> results back; synchronous
+int check_host(gwb_r1cs* r, const void* witness, size_t n_witness, size_t batch, uint32_t* first, uint32_t* nfail, gw_status_t* status) {
+    std::string err;
+    if (!check_args(r, n_witness, batch, err)) return fail(status, err);
+    if (batch == 0) {
+        set_ok(status);
+        return 0;
+    }
+    if (!ensure_device(r, err)) return fail(status, err);
+    void *d_w = nullptr, *d_out = nullptr;
+    hipStream_t s = nullptr;
+    const size_t wbytes = batch * n_witness * 32;
+    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc(&d_w, wbytes);
+    if (e == hipSuccess) e = hipMalloc(&d_out, batch * 8);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_w, witness, wbytes, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) err = hip_err("staging the witness rows", e);
+    uint32_t* d_first = (uint32_t*)d_out;
+    uint32_t* d_nfail = d_first + batch;
+    bool ok = e == hipSuccess && enqueue(r, d_w, batch, GWB_FORM_CANONICAL, d_first, d_nfail, s, err);
+    if (ok) {
+        e = hipMemcpyAsync(first, d_first, batch * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(nfail, d_nfail, batch * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            err = hip_err("running the check", e);
+            ok = false;
+        }
+    }
+    if (d_w) (void)hipFree(d_w);
+    if (d_out) (void)hipFree(d_out);
+    if (s) (void)hipStreamDestroy(s);
+    if (!ok) return fail(status, err);
+    set_ok(status);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+void gwb_r1cs_free(gwb_r1cs_t* r) {
+    if (!r) return;
+    if (r->device >= 0) {
+        int cur = -1;
+        const bool switch_dev = hipGetDevice(&cur) == hipSuccess && cur != r->device;
+        if (switch_dev) (void)hipSetDevice(r->device);
+        release_device(r);
+        if (switch_dev) (void)hipSetDevice(cur);
+    }
+    delete r;
+}
+
+int gwb_r1cs_check_batch_device(gwb_r1cs_t* r, const void* d_witness, size_t n_witness, size_t batch, uint32_t form, uint32_t* d_first_failed,
+                                uint32_t* d_n_failed, void* hip_stream, gw_status_t* status) {
+    if (!r || (batch && (!d_witness || !d_first_failed || !d_n_failed))) return fail(status, "gwb_r1cs_check_batch_device: NULL argument");
+    if (form != GWB_FORM_CANONICAL && form != GWB_FORM_MONTGOMERY) return fail(status, "gwb_r1cs_check_batch_device: unknown form " + std::to_string(form));
+    std::string err;
+    if (!check_args(r, n_witness, batch, err)) return fail(status, err);
+    if (batch == 0) {
+        set_ok(status);
+        return 0;
+    }
+    if (!ensure_device(r, err) || !enqueue(r, d_witness, batch, form, d_first_failed, d_n_failed, (hipStream_t)hip_stream, err))
+        return fail(status, err);
+    set_ok(status);
+    return 0;
+}
+
+int gwb_r1cs_check_batch_host(gwb_r1cs_t* r, const void* witness, size_t n_witness, size_t batch, uint32_t* first_failed, uint32_t* n_failed,
+                              gw_status_t* status) {
+    if (!r || (batch && (!witness || !first_failed || !n_failed))) return fail(status, "gwb_r1cs_check_batch_host: NULL argument");
+    return check_host(r, witness, n_witness, batch, first_failed, n_failed, status);
+}
+
+int gwb_r1cs_check_wtns(gwb_r1cs_t* r, const void* wtns, size_t len, uint32_t* first_failed, uint32_t* n_failed, gw_status_t* status) {
+    if (!r || !wtns || !first_failed || !n_failed) return fail(status, "gwb_r1cs_check_wtns: NULL argument");
+    // "wtns", u32 version (1 or 2), u32 nSections, sections {u32 type, u64 size}: 1 = {u32 n8, prime, u32 nWitness}, 2 = the values
+    const uint8_t* p = (const uint8_t*)wtns;
+    if (len < 12 || memcmp(p, "wtns", 4) != 0) return fail(status, "wtns: bad magic (not a .wtns image)");
+    uint32_t version, nsec;
+    memcpy(&version, p + 4, 4);
+    memcpy(&nsec, p + 8, 4);
+    if (version != 1 && version != 2) return fail(status, "wtns: unsupported version " + std::to_string(version));
+    size_t off = 12;
+    const uint8_t* values = nullptr;
+    uint64_t values_size = 0, n_wit = 0;
+    bool have_hdr = false;
+    for (uint32_t i = 0; i < nsec; ++i) {
+        if (len - off < 12) return fail(status, "wtns: truncated section header");
+        uint32_t type;
+        uint64_t size;
+        memcpy(&type, p + off, 4);
+        memcpy(&size, p + off + 4, 8);
+        off += 12;
+        if (size > len - off) return fail(status, "wtns: truncated section " + std::to_string(type));
+        if (type == 1) {
+            if (have_hdr) return fail(status, "wtns: duplicate header section");
+            if (size != 40) return fail(status, "wtns: header section size " + std::to_string(size) + " (40 expected)");
+            uint32_t n8, nw;
+            memcpy(&n8, p + off, 4);
+            Fr prime;
+            memcpy(prime.v, p + off + 4, 32);
+            memcpy(&nw, p + off + 36, 4);
+            if (n8 != 32 || !cwc::u256_eq(prime, cwc::fr_p())) return fail(status, "wtns: field is not BN254's r");
+            n_wit = nw;
+            have_hdr = true;
+        } else if (type == 2) {
+            if (values) return fail(status, "wtns: duplicate witness section");
+            values = p + off;
+            values_size = size;
+        }
+        off += size;
+    }
+    if (off != len) return fail(status, "wtns: " + std::to_string(len - off) + " trailing bytes");
+    if (!have_hdr || !values) return fail(status, "wtns: missing header or witness section");
+    if (values_size != n_wit * 32) return fail(status, "wtns: witness section size disagrees with nWitness x 32");
+    for (uint64_t i = 0; i < n_wit; ++i) {
+        Fr v;
+        memcpy(v.v, values + 32 * i, 32);
+        if (!cwc::u256_lt(v, cwc::fr_p())) return fail(status, "wtns: witness element " + std::to_string(i) + " is not below r");
+    }
+    return check_host(r, values, n_wit, 1, first_failed, n_failed, status);
+}
+
+}  // extern "C"
