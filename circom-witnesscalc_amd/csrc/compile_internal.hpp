@@ -11,6 +11,7 @@
 #include <chrono>
 #include <deque>
 #include <mutex>
+#include <optional>
 #include <unordered_map>
 
 #include "flat_map.hpp"
@@ -192,17 +193,74 @@ struct CycleTable {
 // (round 2, bigint-class graph with every operand and result canonical: BIT 2 650, IDIVMOD 2 880, CMPS 1 900 net of stamps)
 static const double kCyclesBitStraight = 1500;  // what a Shr-only / Band-only bundle saves against the per-lane select over all bit operations
 static const double kCyclesBitx = 1300, kCyclesCoopRiders = 60, kCyclesOperandForm = 1200, kCyclesResultForm = 1450, kCyclesBitxOperandForm = 600;
+// Every CWC_* variable the graph compiler reads (A/B and diagnostic knobs), read once per compile_program / probe_graph
+// call -- tests change them between calls.  An unset optional: the knob is not set.
+struct CompileKnobs {
+    std::optional<uint32_t> coop_fill, coop_slack;  // CWC_COOP_FILL / CWC_COOP_SLACK: force one narrow-bundle policy
+    bool no_coop_mul, no_schedule_variants, no_bit_fusion, no_rep_inference, conv_always, no_fuse;
+    std::optional<uint32_t> fuse;                   // CWC_FUSE: the one fused-chain policy tried, whatever it costs
+    std::optional<bool> witness_slots;              // CWC_WITNESS_SLOTS: force witness-ordered slots on / off
+    bool debug_compile_times, no_load_optimize, random_eval, no_lin_heavy_weights, no_tree_reduction;
+    std::optional<uint32_t> sched_lin_cost, sched_mul_cost;  // overrides of the priority weights
+    std::optional<size_t> tree_leaves;
+    bool no_scan, no_bit_graph, no_mul_cc, no_conv;
+    uint32_t sched_div_wait = 3;  // (measured 3 against 6 and 10: +1.4 % at 1024 sets and +2.6 % at 2048 with divider waves, +1.4 % at 8192 and 16384 sets with inline inversions)
+    bool sched_tie_reverse, no_ride_along, scan_eager;
+    double stream_prologue = 30000;  // (cycles of dependent operations from the inputs that still count as prologue)
+    bool debug_critical_path, debug_streams, debug_node_mix;
+    uint32_t debug_sched = 0;  // CWC_DEBUG_SCHED=n: the first n bundles, node by node
+    bool nowhere = true;       // (CWC_NOWHERE=0: the zero constant's slot and the trash slot as before round 4, for A/B runs)
+};
+CompileKnobs read_compile_knobs();
+
+// The options of one schedule variant (compile_program compiles several and keeps the cheapest).
 // When a multiplication step becomes a narrow (four lanes per product) bundle: `fill` or more ready multiplications make
 // a full-width bundle instead (it costs the same with 10 or 32 nodes); otherwise a narrow one if the multiplications
 // within `slack_levels` multiplication levels (in the scheduler's cost units) of the most urgent ready node fit it.  The
 // rest stays ready.  fill = 0: never narrow.
-struct CoopPolicy {
+struct VariantOptions {
     uint32_t fill;
     uint32_t slack_levels;  // ~0u: everything ready counts as urgent
     bool all_montgomery = false;  // no representation inference: every value in Montgomery form
-    bool witness_slots = false;   // the slots of witness elements in witness order (see the slot allocation)
     bool no_conv = false;         // schoolbook limb products stay unfused (detect_convolutions off): a competitor where many small blocks run side by side
     bool no_scans = false;        // no scan chains at all (detect_scans / detect_bit_scans / detect_convolutions off): the fallback when a fused form cannot be scheduled
     uint32_t fuse = 0;            // fused narrow chains (fuse_narrow_chains): 0 off, else 1 + the slack, in thousandths of the critical path, within which nodes are fused; + 0x10000: product + sum nodes only
 };
+
+// ---- what the phases of compile_variant (compile.cc) hand each other ----
+// the form of every value and the scan / convolution side tables (choose_forms)
+struct NodeForms {
+    std::vector<uint8_t> rep, vflags;
+    std::vector<uint32_t> scan_imm, scan_partner;
+    uint64_t n_mul_cc = 0;
+};
+// a scan step's shift: CARRY n; DIV k of the constant 2^k
+inline uint32_t scan_shift_of(const Graph& g, const NodeForms& f, uint32_t i) {
+    if (!(g.nodes[i].op & SCAN_OP_DIV)) return f.scan_imm[i];
+    const Fr& v = g.const_values[g.nodes[f.scan_imm[i]].a];
+    for (int w = 0; w < 8; ++w)
+        if (v.v[w]) return 32u * w + (uint32_t)__builtin_ctz(v.v[w]);
+    return 0;
+}
+static const uint32_t REQ_FLAG = 0x80000000u;  // Schedule::order entry: the request half of a division
+// The bundles of every stream, one after the other (schedule_program).
+struct Schedule {
+    std::vector<uint32_t> order;          // evaluated nodes (inputs + ops) in bundle order
+    std::vector<uint32_t> bundle_start;   // index into order, one per bundle and a final one
+    std::vector<uint8_t> bundle_coop;     // 1: narrow multiplication bundle (C_MULQ: four lanes per product), 2: fused narrow bundle
+    std::vector<uint32_t> order_pos;      // record position of every entry of `order` inside its bundle
+    std::vector<uint32_t> bundle_flags;   // HDR_POST / HDR_WAIT (programs of several streams)
+    std::vector<uint32_t> bundle_of;      // bundle that produces the node's value
+    std::vector<uint32_t> use_bundle_of;  // bundle that reads the node's operands (differs for a division handed to the divider wave: request vs. collect)
+    std::vector<uint8_t> stream_of;       // stream of every node
+    uint32_t P = 1;                       // streams
+    uint32_t s_first[MAX_STREAMS] = {0, 0, 0, 0}, s_count[MAX_STREAMS] = {0, 0, 0, 0}, s_div[MAX_STREAMS] = {0, 0, 0, 0};
+    double s_chain[MAX_STREAMS] = {0, 0, 0, 0};  // longest dependent chain of each stream, lone-wave cycles (divisions at the divider wave's latency)
+    std::vector<uint32_t> div_lanes;      // active lanes of each division request
+    uint32_t n_div_requests = 0;
+};
+// refuse_one_part: a stream program whose graph has one independent part is an error (compile_program's siblings include
+// the one-stream program)
+bool schedule_program(const Graph& g, const NodeForms& f, const ProgramStats& st, const uint32_t* class_cost, const VariantOptions& opt, const CompileKnobs& k,
+                      uint32_t T, uint32_t divider, uint32_t streams, bool refuse_one_part, Schedule& sc, std::string& err);
 }  // namespace cwc

@@ -73,7 +73,7 @@ def test_hostile_json_never_crashes(pkg):
 def test_corrupted_program_blobs_are_rejected(pkg):
     """gwb_graph_import is what the ranks of a node feed with the broadcast program: a truncated, padded, bit-flipped or
     internally inconsistent blob must be refused before anything is uploaded or launched (checksum + structural
-    validation of every offset / index / LDS address, validate_program in compile.cc).  On this CPU-only machine a
+    validation of every offset / index / LDS address, validate_program in program_blob.cc).  On this CPU-only machine a
     VALID blob gets as far as the device check and fails there; everything else must fail earlier with its own message."""
     import struct
     rnd = random.Random(5)

@@ -261,7 +261,7 @@ def test_graph_compiler_emulated(pkg, tile):
 
 def test_fused_narrow_chains_are_exact(pkg, monkeypatch):
     """Round 3: the compiler fuses (s * s) * m + c and a * b +- c chains near the critical path into single nodes of narrow
-    bundles (class MULF; compile.cc fuse_narrow_chains).  With the fusion forced for every eligible chain (CWC_FUSE=1001)
+    bundles (class MULF; rewrite.cc fuse_narrow_chains).  With the fusion forced for every eligible chain (CWC_FUSE=1001)
     the emulator -- which computes on the stored words, Montgomery or canonical -- gives the reference's witnesses, for
     tile widths 1 and 2, with divider waves and as stream programs; the additions of canonical-form values read the
     canonical copies of their constants (the bug the first GPU soak of this class found)."""
@@ -786,7 +786,7 @@ def test_bit_recurrence_scans_are_exact(pkg, monkeypatch):
 def test_scan_chains_are_exact(pkg):
     """Round 4: the steps of serial limb recurrences -- carry chains `t = x + c; limb = t % 2^n; c' = t \\ 2^n`, remainder
     chains `t = r * 2^k + x; q = t \\ d; r' = t % d` -- become pairs of N_SCAN nodes that the scheduler places in consecutive
-    pairs of node slots of scan bundles (class SCAN; compile.cc detect_scans).  The emulator runs the compiled programs on
+    pairs of node slots of scan bundles (class SCAN; rewrite.cc detect_scans).  The emulator runs the compiled programs on
     the stored words: every shift / base width, chains longer than a bundle, chains that fork, a step whose x is another
     step's output, operands outside the limb range, d == 0; tile widths 1 and 2, with divider waves and as stream programs
     (wider tiles keep the unfused nodes)."""
@@ -821,7 +821,7 @@ def test_scan_chains_are_exact(pkg):
 
 
 def test_value_numbering_lists_and_overflow(pkg):
-    """The tree-height reduction numbers its Add / Mul nodes through per-node lists (compile.cc reduce_tree_height: the
+    """The tree-height reduction numbers its Add / Mul nodes through per-node lists (rewrite.cc reduce_tree_height: the
     nodes whose larger operand a value is), and a value combined with more than 24 earlier ones moves into a hash table.
     A late value multiplied with / added to 60 inputs, every pair twice and in both operand orders, summed in long chains
     that the reduction opens: duplicates merge, and the emulator gives the reference's witnesses for every tile width."""
@@ -1028,7 +1028,7 @@ def test_batched_json_front_end_and_wtns_writer(pkg, tmp_path):
 
 
 def test_power_of_two_division_rewrite_is_exact(pkg):
-    """Idiv/Mod by a constant 2^k are compiled as Shr/Band (compile.cc rewrite_pow2_divisions): same values."""
+    """Idiv/Mod by a constant 2^k are compiled as Shr/Band (rewrite.cc rewrite_pow2_divisions): same values."""
     import cwc_import
     Builder = cwc_import.load().graphgen.builder.Builder
     b = Builder()
@@ -1172,7 +1172,7 @@ def test_field_inversion_on_host(tmp_path, constant_time):
 
 def test_schedule_quality_guard(pkg):
     """The schedule of the bench workloads must not silently regress.  A wave's time is the sum of its bundles, priced per
-    class with the cycles measured on MI355X (compile.cc kCycles): authV2-class at T = 2 with the divider wave 30.5 M
+    class with the cycles measured on MI355X (kCycles: compile_internal.hpp, costmodel.cc): authV2-class at T = 2 with the divider wave 30.5 M
     cycles in round 2 (narrow four-lane multiplication bundles; 33.0 M without them), sha256_512 at T = 1: 5 399 bundles."""
     g = pkg.Graph(C.build_authv2_class().to_bin())
     bl = pe.Blob(g.export_blob(2 | DIVIDER))

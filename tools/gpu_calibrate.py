@@ -1,10 +1,10 @@
-"""Re-measures the cost model's cycle table on the machine at hand (the table in csrc/compile.cc was taken on one MI355X box).
+"""Re-measures the cost model's cycle table on the machine at hand (the table in csrc/compile_internal.hpp was taken on one MI355X box).
 
 The stamped interpreter build (gwb_profile_classes) runs the bench graphs -- the authV2-class graph at the headline's
 program and as a lone-wave stream program, with and without divider waves, the bigint-class graph for the integer classes --
 and the cycles per bundle of every class it sees, net of the build's own time stamps, are set beside the table the
 library loaded.  `--write` leaves them as "class:cycles,..." in model_cycles.txt of the program cache's directory (or the
-path given), which the library reads when it is loaded (CycleTable in csrc/compile.cc; CWC_MODEL_CYCLES_FILE names another
+path given), which the library reads when it is loaded (CycleTable in csrc/compile_internal.hpp; CWC_MODEL_CYCLES_FILE names another
 file); without it nothing changes.
 
     python tools/gpu_calibrate.py [--write [PATH]]
