@@ -2,9 +2,12 @@
 
 - write_r1cs: a pure-Python writer of the iden3 binfile "r1cs" v1 format circom writes;
 - check / check_constraint: the semantics as big-integer arithmetic, the model the kernel is compared with;
-- derive_r1cs: an R1CS derived from a graphgen Builder -- what circom would have kept of the `===` constraints the graph dropped.
+- derive_r1cs: an R1CS derived from a graphgen Builder -- what circom would have kept of the `===` constraints the graph dropped;
+- planted_system: random constraint systems that every completed row satisfies by construction.
 
-Constraints are (A, B, C) triples of {wire: coefficient} dicts, coefficients reduced mod r.
+Constraints are (A, B, C) triples of combinations.  A combination is a {wire: coefficient} dict (written sorted by wire,
+coefficients reduced mod r) or a list of (wire, coefficient) pairs (written in the given order, duplicates kept, coefficients
+passed through as they are, so a test can write values the loader must refuse).
 """
 import contextlib
 import struct
@@ -14,9 +17,10 @@ R = 2188824287183927522224640574525727508854836440041603434369820418657580849561
 
 # -- writer ------------------------------------------------------------------------------------------------------------------
 def _lc_bytes(lc):
-    out = [struct.pack("<I", len(lc))]
-    for wire, c in sorted(lc.items()):
-        out.append(struct.pack("<I", wire) + (c % R).to_bytes(32, "little"))
+    items = [(wire, c % R) for wire, c in sorted(lc.items())] if isinstance(lc, dict) else lc
+    out = [struct.pack("<I", len(items))]
+    for wire, c in items:
+        out.append(struct.pack("<I", wire) + c.to_bytes(32, "little"))
     return b"".join(out)
 
 
@@ -50,8 +54,13 @@ def write_r1cs(n_wires, constraints, n_pub_out=0, n_pub_in=0, n_prv_in=0, order=
 
 
 # -- checker ------------------------------------------------------------------------------------------------------------------
+def terms(lc):
+    """the (wire, coefficient) pairs of a combination in either form"""
+    return lc.items() if isinstance(lc, dict) else lc
+
+
 def _dot(lc, w):
-    return sum(c * w[i] for i, c in lc.items()) % R
+    return sum(c * w[i] for i, c in terms(lc)) % R
 
 
 def check_constraint(con, w):
@@ -69,10 +78,129 @@ def check(constraints, w, indices=None):
     return first, n
 
 
+MONT_R = (1 << 256) % R           # R mod r: the Montgomery form of 1
+MONT_R_INV = pow(1 << 256, -1, R)  # R^-1 mod r
+MONT_R2 = (1 << 512) % R          # R^2 mod r
+
+
+def to_montgomery(x):
+    return x * MONT_R % R
+
+
+def from_montgomery(x):
+    return x * MONT_R_INV % R
+
+
 def row_ints(row):
     """uint8 [W, 32] -> list of ints"""
     b = bytes(row)
     return [int.from_bytes(b[i:i + 32], "little") for i in range(0, len(b), 32)]
+
+
+def rows_array(rows):
+    """list of rows (lists of ints below 2^256) -> uint8 [B, W, 32]"""
+    import numpy as np
+    data = b"".join(x.to_bytes(32, "little") for row in rows for x in row)
+    return np.frombuffer(data, dtype=np.uint8).reshape(len(rows), len(rows[0]) if rows else 0, 32).copy()
+
+
+# -- planted systems ----------------------------------------------------------------------------------------------------------
+class Planted:
+    """A satisfied-by-construction constraint system.  Wires: 0 = the constant 1, then one output wire per constraint that owns
+    one (in constraint order), then the zero wire (0 in every row), then the free wires; the last wire is free.
+
+    complete(rnd, fixed=None) -> a row (list of ints below r) satisfying every constraint: free wires random (or `fixed`
+    {wire: value}), each output o_j = (A_j B_j - C_j without o_j) / c_o mod r, computed in constraint order."""
+
+    def __init__(self, n_wires, constraints, plan, zero_wire, free):
+        self.n_wires, self.constraints, self._plan = n_wires, constraints, plan
+        self.zero_wire, self.free = zero_wire, free
+
+    def complete(self, rnd, fixed=None):
+        w = [0] * self.n_wires
+        w[0] = 1
+        for f in self.free:
+            w[f] = rnd.randrange(R)
+        for f, v in (fixed or {}).items():
+            assert f in self.free or f == 0 and v == 1, f
+            w[f] = v % R
+        for j, out, inv_co, rest in self._plan:
+            if out is None:
+                continue
+            a, b, _ = self.constraints[j]
+            w[out] = (_dot(a, w) * _dot(b, w) - _dot(rest, w)) * inv_co % R
+        return w
+
+
+def _pick(rnd, pool):
+    c = rnd.choice(pool)
+    return rnd.randrange(R) if c is None else c
+
+
+def planted_system(rnd, n_free, shapes, coef_pool):
+    """Constraints from `shapes` (one per constraint, in file order), each a dict:
+        a, b, c    lengths of A, B and of C without its output term (c = 0 and out=False: C empty)
+        out        True (default): C_j holds an output wire o_j with a nonzero coefficient, at a random position in C
+                   False: no output; A then reads only the zero wire (or is empty), so A B = 0, and C must be empty
+        dup        duplicate wires: about a quarter of the terms repeat an earlier wire of the same combination, and a side
+                   of length >= 3 holds a cancelling pair (w, c), (w, r - c)
+        edge       wire 0 and the last wire appear in every side of length >= 2
+        pools      (pool_a, pool_b, pool_c) overriding coef_pool per side
+    Pools are lists of coefficients; None in a pool is a fresh random field element.  Combinations are lists of
+    (wire, coefficient) pairs.  -> Planted."""
+    n_out = sum(1 for s in shapes if s.get("out", True))
+    zero_wire = 1 + n_out
+    free = list(range(zero_wire + 1, zero_wire + 1 + n_free))
+    n_wires = zero_wire + 1 + n_free
+    last = n_wires - 1
+    assert n_free >= 1
+    constraints, plan = [], []
+    outs = []  # output wires of earlier constraints
+    for j, s in enumerate(shapes):
+        pools = s.get("pools", (coef_pool,) * 3)
+        has_out = s.get("out", True)
+        readable = [0, zero_wire] + free + outs
+
+        def side(n, pool, zero_only=False):
+            lc = []
+            if zero_only:
+                for _ in range(n):
+                    lc.append((zero_wire, _pick(rnd, pool)))
+                return lc
+            for i in range(n):
+                if s.get("dup") and lc and rnd.random() < 0.25:
+                    wire = rnd.choice(lc)[0]
+                else:
+                    wire = rnd.choice(readable)
+                lc.append((wire, _pick(rnd, pool)))
+            if s.get("dup") and n >= 3:
+                p = rnd.randrange(n - 1)
+                wire, c = rnd.choice(readable), rnd.choice((1, 2, rnd.randrange(1, R)))  # 1, r - 1: a +1 / -1 pair
+                lc[p], lc[p + 1] = (wire, c), (wire, R - c)
+            if s.get("edge") and n >= 2:
+                i0, i1 = rnd.sample(range(n), 2)
+                lc[i0] = (0, lc[i0][1])
+                lc[i1] = (last, lc[i1][1])
+            return lc
+
+        a = side(s["a"], pools[0], zero_only=not has_out)
+        b = side(s["b"], pools[1])
+        rest = side(s["c"], pools[2])
+        if has_out:
+            out = 1 + len(outs)
+            co = 0
+            while co % R == 0:
+                co = _pick(rnd, pools[2])
+            c = list(rest)
+            c.insert(rnd.randrange(len(c) + 1), (out, co))
+            plan.append((j, out, pow(co, -1, R), rest))
+            outs.append(out)
+        else:
+            assert not rest, "a constraint without an output wire has an empty C"
+            c = []
+            plan.append((j, None, None, None))
+        constraints.append((a, b, c))
+    return Planted(n_wires, constraints, plan, zero_wire, free)
 
 
 # -- derivation from a graphgen Builder --------------------------------------------------------------------------------------

@@ -209,3 +209,96 @@ def test_check_witness_cli_usage_errors(pkg, tmp_path):
     assert p.returncode == 2 and "3 elements" in p.stderr
     p = subprocess.run([CLI, str(tmp_path / "c.r1cs"), str(tmp_path / "c.r1cs")], capture_output=True, text=True)
     assert p.returncode == 2 and "bad magic" in p.stderr
+
+
+# -- fixture extensions: list-form combinations, Montgomery helpers, planted systems -----------------------------------------
+EDGE_COEFS = [0, 1, F.R - 1, 2, F.R - 2, (F.R + 1) // 2, F.MONT_R, F.MONT_R_INV, F.MONT_R2, (1 << 255) % F.R]
+
+
+def _lc_bytes_dict_only(lc):
+    """the writer's dict form as it was before list-form combinations existed (a frozen copy)"""
+    out = [struct.pack("<I", len(lc))]
+    for wire, c in sorted(lc.items()):
+        out.append(struct.pack("<I", wire) + (c % F.R).to_bytes(32, "little"))
+    return b"".join(out)
+
+
+def test_dict_form_output_is_unchanged(pkg):
+    rnd = random.Random(31)
+    unreduced = [({3: -1, 1: F.R + 5}, {0: 2 * F.R - 1}, {4: -7, 2: 1 << 300})]
+    rand = [tuple({rnd.randrange(50): rnd.choice([rnd.randrange(F.R), -rnd.randrange(F.R), 1, F.R - 1])
+                   for _ in range(rnd.randrange(6))} for _ in range(3)) for _ in range(40)]
+    for cons in (CONS, unreduced, rand, F.derive_r1cs(_poseidon_builder())):
+        want = b"".join(_lc_bytes_dict_only(a) + _lc_bytes_dict_only(b) + _lc_bytes_dict_only(c) for a, b, c in cons)
+        assert F.constraints_section(cons) == want
+
+
+def test_list_form_round_trip(pkg):
+    lists = [([(1, 1), (1, F.R - 1), (0, 5), (1, 3)], [], [(3, 0), (3, 0)]),
+             ([(4, c) for c in EDGE_COEFS], [(0, c) for c in reversed(EDGE_COEFS)], [(2, 1), (4, F.R - 1), (2, 7)]),
+             ([], [(4, 1)] * 5, [])]
+    r = _load(F.write_r1cs(5, lists))
+    assert r.info["n_constraints"] == 3
+    assert (r.info["n_factors_a"], r.info["n_factors_b"], r.info["n_factors_c"]) == (4 + len(EDGE_COEFS), len(EDGE_COEFS) + 5, 5)
+    # list form writes pairs as given: order and duplicates in the bytes, and the loader refuses r and 2^256 - 1
+    sec = F.constraints_section(lists[:1])
+    assert struct.unpack_from("<I", sec, 0)[0] == 4 and struct.unpack_from("<I", sec, 4 + 36 * 3)[0] == 1
+    for bad in (F.R, (1 << 256) - 1):
+        _rejects(F.write_r1cs(5, [([(1, 1), (2, bad)], [], [])]), "constraint 0 has a coefficient >= r")
+    _rejects(F.write_r1cs(5, [([(1, 1)], [], [(5, 1)])]), "references wire 5")
+
+
+def test_list_checker_agrees_with_dict_checker(pkg):
+    rnd = random.Random(32)
+    for _ in range(30):
+        dicts = [tuple({rnd.randrange(8): rnd.choice([1, F.R - 1, rnd.randrange(F.R)]) for _ in range(rnd.randrange(5))}
+                       for _ in range(3)) for _ in range(12)]
+        lists = [tuple(list(lc.items())[::-1] for lc in con) for con in dicts]
+        w = [1] + [rnd.randrange(F.R) for _ in range(7)]
+        assert F.check(lists, w) == F.check(dicts, w)
+        # satisfy constraint 0 by construction of C, then compare again
+        a, b, c = dicts[0]
+        dicts[0] = (a, b, {0: F._dot(a, w) * F._dot(b, w) % F.R})
+        lists[0] = (list(a.items()), list(b.items()), [(0, 1), (0, F._dot(a, w) * F._dot(b, w) - 1)])
+        assert F.check_constraint(dicts[0], w) and F.check_constraint(lists[0], w)
+        assert F.check(lists, w) == F.check(dicts, w)
+    # duplicates are summed
+    w = [1, 10, 20]
+    assert F.check_constraint(([(1, 2), (1, 3)], [(0, 1)], [(1, 5)]), w)
+    assert F.check_constraint(([(2, 1), (2, F.R - 1)], [(1, 1)], []), w)
+    assert not F.check_constraint(([(1, 2), (1, 3)], [(0, 1)], [(1, 4)]), w)
+
+
+def test_montgomery_helpers(pkg):
+    rnd = random.Random(33)
+    for x in [0, 1, 2, F.R - 1] + [rnd.randrange(F.R) for _ in range(100)]:
+        assert F.from_montgomery(F.to_montgomery(x)) == x and F.to_montgomery(F.from_montgomery(x)) == x
+        assert F.to_montgomery(x) == x * (1 << 256) % F.R
+    assert F.to_montgomery(1) == F.MONT_R and F.MONT_R * F.MONT_R_INV % F.R == 1 and F.MONT_R2 == F.MONT_R ** 2 % F.R
+
+
+def test_planted_systems_are_satisfied(pkg):
+    rnd = random.Random(34)
+    for pool, dup, edge in (([1, F.R - 1, None], False, False), (EDGE_COEFS + [None], True, True), ([None], True, False)):
+        shapes = [dict(a=rnd.randrange(6), b=rnd.randrange(6), c=rnd.randrange(6), dup=dup, edge=edge) for _ in range(60)]
+        shapes += [dict(a=4, b=2, c=0, out=False), dict(a=0, b=3, c=0, out=False), dict(a=0, b=0, c=0, out=False)]
+        P = F.planted_system(rnd, 8, shapes, pool)
+        assert P.n_wires == 1 + 60 + 1 + 8 and P.free[-1] == P.n_wires - 1
+        if edge:
+            assert all(any(w == 0 for w, _ in lc) and any(w == P.n_wires - 1 for w, _ in lc)
+                       for a, b, c in P.constraints[:60] for lc, n in ((a, 2), (b, 2)) if len(lc) >= n)
+        if dup:
+            assert any(len({w for w, _ in lc}) < len(lc) for con in P.constraints for lc in con)
+        for j, (a, b, c) in enumerate(P.constraints[60:]):
+            assert not c and all(w == P.zero_wire for w, _ in a)
+        for _ in range(4):
+            w = P.complete(rnd)
+            assert w[0] == 1 and w[P.zero_wire] == 0 and all(0 <= x < F.R for x in w)
+            assert F.check(P.constraints, w) == (0xFFFFFFFF, 0)
+        # an output wire changed: its own constraint (C holds it with a nonzero coefficient) is the first to fail
+        w[5] = (w[5] + 1) % F.R
+        first, n = F.check(P.constraints, w)
+        assert first == 4 and n >= 1
+        # fixed free values are honoured
+        w = P.complete(rnd, fixed={P.free[0]: 12345})
+        assert w[P.free[0]] == 12345 and F.check(P.constraints, w) == (0xFFFFFFFF, 0)
