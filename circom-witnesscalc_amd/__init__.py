@@ -94,7 +94,7 @@ def build(verbose=False, diag=False):
     if not verbose:
         cmd.insert(1, "-s")
     subprocess.check_call(cmd)
-    # the R1CS check (libcwc_r1cs.so + check-witness): a library of its own, outside csrc/
+    # the R1CS check and QAP witness map (libcwc_r1cs.so + check-witness, witness-h): a library of its own, outside csrc/
     subprocess.check_call(["make"] + ([] if verbose else ["-s"]) + ["-C", os.path.join(_HERE, "r1cs"), "-j4"])
 
 
@@ -495,6 +495,11 @@ class R1csInfo(ctypes.Structure):
                [(n, ctypes.c_uint64) for n in ("n_labels", "n_factors_a", "n_factors_b", "n_factors_c")]
 
 
+class R1csQapInfo(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_uint64), ("domain_power", ctypes.c_uint32), ("domain_size", ctypes.c_uint64),
+                ("workspace_bytes_per_row", ctypes.c_uint64)]
+
+
 def r1cs_lib():
     """ctypes handle of libcwc_r1cs.so, loaded after torch (one HIP runtime per process, as in lib())."""
     global _r1cs_lib
@@ -516,6 +521,13 @@ def r1cs_lib():
         L.gwb_r1cs_check_batch_device.argtypes = [vp, vp, sz, sz, u32, vp, vp, vp, stp]
         L.gwb_r1cs_check_batch_host.argtypes = [vp, vp, sz, sz, vp, vp, stp]
         L.gwb_r1cs_check_wtns.argtypes = [vp, vp, sz, vp, vp, stp]
+        L.gwb_r1cs_qap_info.argtypes = [vp, ctypes.POINTER(R1csQapInfo), stp]
+        L.gwb_r1cs_qap_batch_device.argtypes = [vp, vp, sz, sz, u32, vp, u32, vp, stp]
+        L.gwb_r1cs_qap_batch_host.argtypes = [vp, vp, sz, sz, vp, u32, stp]
+        L.gwb_r1cs_qap_wtns.argtypes = [vp, vp, sz, vp, u32, stp]
+        L.gwb_r1cs_qap_time_phases.argtypes = [vp, ctypes.c_int]
+        L.gwb_r1cs_qap_phase_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        L.gwb_r1cs_modmul_rate.argtypes = [ctypes.POINTER(ctypes.c_double)]
         _r1cs_lib = L
     return _r1cs_lib
 
@@ -526,6 +538,14 @@ def _r1cs_check(rc, st):
         _libc.free(st.error_msg)
     if rc != 0:
         raise WitnessCalcError(msg or "call failed")
+
+
+def modmul_rate():
+    """Measurement aid: Montgomery products per second of the current device (a short probe kernel)."""
+    rate = ctypes.c_double()
+    if r1cs_lib().gwb_r1cs_modmul_rate(ctypes.byref(rate)) != 0:
+        raise WitnessCalcError("gwb_r1cs_modmul_rate failed")
+    return rate.value
 
 
 class R1cs:
@@ -596,6 +616,75 @@ class R1cs:
         rc = r1cs_lib().gwb_r1cs_check_wtns(self._h, wtns, len(wtns), ctypes.byref(first), ctypes.byref(nfail), ctypes.byref(st))
         _r1cs_check(rc, st)
         return int(first.value), int(nfail.value)
+
+    # -- Groth16 witness map (h, the scalars of the prover's H-point MSM; definition in include/graph_witness_r1cs.h) --------
+    def qap_info(self):
+        """{n_rows, domain_power, domain_size, workspace_bytes_per_row} of the QAP domain; raises for a domain above 2^27."""
+        info = R1csQapInfo()
+        st = GwStatus()
+        rc = r1cs_lib().gwb_r1cs_qap_info(self._h, ctypes.byref(info), ctypes.byref(st))
+        _r1cs_check(rc, st)
+        return {n: int(getattr(info, n)) for n, _ in R1csQapInfo._fields_}
+
+    def qap_batch(self, witness_rows, montgomery_out=False):
+        """Host rows uint8 [B, W, 32] (canonical), or the (witness, status) pair of Graph.calc_witness_batch -> h as uint8
+        [B, n, 32] (canonical, or Montgomery with montgomery_out).  Synchronous."""
+        if isinstance(witness_rows, tuple):
+            witness_rows = witness_rows[0]
+        w = np.ascontiguousarray(witness_rows, dtype=np.uint8)
+        assert w.ndim == 3 and w.shape[2] == 32, w.shape
+        b = w.shape[0]
+        n = self.qap_info()["domain_size"]
+        h = np.zeros((b, n, 32), dtype=np.uint8)
+        st = GwStatus()
+        rc = r1cs_lib().gwb_r1cs_qap_batch_host(self._h, w.ctypes.data, w.shape[1], b, h.ctypes.data,
+                                                FORM_MONTGOMERY if montgomery_out else FORM_CANONICAL, ctypes.byref(st))
+        _r1cs_check(rc, st)
+        return h
+
+    def qap_batch_device(self, d_witness, stream=None, montgomery=False, montgomery_out=False):
+        """Device rows (torch uint8 cuda tensor [B, W, 32], canonical or Montgomery form) -> h as a uint8 cuda tensor [B, n, 32].
+        Asynchronous on `stream` (torch.cuda.Stream) or the current torch stream: put it behind
+        Graph.calc_witness_batch_device on the same stream."""
+        import torch
+        assert d_witness.is_cuda and d_witness.is_contiguous() and d_witness.dtype == torch.uint8
+        assert d_witness.dim() == 3 and d_witness.shape[2] == 32, tuple(d_witness.shape)
+        b = d_witness.shape[0]
+        n = self.qap_info()["domain_size"]
+        s = stream if stream is not None else torch.cuda.current_stream(d_witness.device)
+        h = torch.empty((b, n, 32), dtype=torch.uint8, device=d_witness.device)
+        st = GwStatus()
+        with torch.cuda.device(d_witness.device):
+            rc = r1cs_lib().gwb_r1cs_qap_batch_device(self._h, d_witness.data_ptr(), d_witness.shape[1], b,
+                                                      FORM_MONTGOMERY if montgomery else FORM_CANONICAL, h.data_ptr(),
+                                                      FORM_MONTGOMERY if montgomery_out else FORM_CANONICAL, s.cuda_stream,
+                                                      ctypes.byref(st))
+        _r1cs_check(rc, st)
+        if b:
+            h.record_stream(s)
+        return h
+
+    def qap_time_phases(self, on=True):
+        """Measurement aid: record HIP events around the phases of later QAP calls (see qap_phase_ms)."""
+        if r1cs_lib().gwb_r1cs_qap_time_phases(self._h, 1 if on else 0) != 0:
+            raise WitnessCalcError("gwb_r1cs_qap_time_phases failed")
+
+    def qap_phase_ms(self):
+        """Waits for the last QAP call -> {evaluation, inverse_outer, fused_inner, forward_outer} in ms (its last sub-batch)."""
+        ms = (ctypes.c_float * 4)()
+        if r1cs_lib().gwb_r1cs_qap_phase_ms(self._h, ms) != 0:
+            raise WitnessCalcError("no QAP phase times (qap_time_phases not on, or no QAP call yet)")
+        return dict(zip(("evaluation", "inverse_outer", "fused_inner", "forward_outer"), (float(x) for x in ms)))
+
+    def qap_wtns(self, wtns, montgomery_out=False):
+        """One `.wtns` image -> h as uint8 [n, 32]."""
+        wtns = bytes(wtns)
+        h = np.zeros((self.qap_info()["domain_size"], 32), dtype=np.uint8)
+        st = GwStatus()
+        rc = r1cs_lib().gwb_r1cs_qap_wtns(self._h, wtns, len(wtns), h.ctypes.data,
+                                          FORM_MONTGOMERY if montgomery_out else FORM_CANONICAL, ctypes.byref(st))
+        _r1cs_check(rc, st)
+        return h
 
 
 from . import graphgen  # noqa: E402,F401  (graph generator library on top of the C-ABI producer)

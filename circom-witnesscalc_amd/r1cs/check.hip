@@ -18,6 +18,7 @@
 
 #include <string>
 
+#include "lincomb.hpp"
 #include "r1cs_internal.hpp"
 
 using namespace cwc_r1cs;
@@ -26,49 +27,6 @@ using cwc::Fr;
 namespace {
 
 constexpr int WAVES_PER_BLOCK = 4;
-
-__device__ __forceinline__ Fr load_elem(const uint8_t* row, uint32_t wire) {
-    const uint4* p = reinterpret_cast<const uint4*>(row + (size_t)wire * 32);
-    const uint4 lo = p[0], hi = p[1];
-    return Fr{{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}};
-}
-
-// w mod r for any w < 2^256 (rare: rows from the witness calculator are already below r)
-__device__ __forceinline__ Fr reduce_any(Fr w) {
-    if (!cwc::u256_lt(w, cwc::fr_p())) {
-        const Fr one{{1, 0, 0, 0, 0, 0, 0, 0}};
-        w = cwc::fr_mul(cwc::fr_mul(w, cwc::fr_r2()), one);  // (w R) / R
-    }
-    return w;
-}
-
-__device__ __forceinline__ Fr accumulate(const Fr& acc, Fr w, uint32_t kind, const Fr* __restrict__ coef, uint32_t ci) {
-    if (kind == KIND_GENERAL) return cwc::fr_add(acc, cwc::fr_mul(w, coef[ci]));  // w may be any value below 2^256 as the first operand
-    w = reduce_any(w);
-    return kind == KIND_PLUS ? cwc::fr_add(acc, w) : cwc::fr_sub(acc, w);
-}
-
-// Four factors at a time: their four witness gathers are in flight together before the arithmetic that needs the first.
-__device__ __forceinline__ Fr lin_comb(const uint32_t* __restrict__ fac, const uint32_t* __restrict__ cidx, const Fr* __restrict__ coef,
-                                       uint32_t k, uint32_t end, const uint8_t* row) {
-    constexpr int U = 4;
-    Fr acc = cwc::fr_zero();
-    for (; k + U <= end; k += U) {
-        uint32_t f[U];
-        Fr w[U];
-#pragma unroll
-        for (int i = 0; i < U; ++i) f[i] = fac[k + i];
-#pragma unroll
-        for (int i = 0; i < U; ++i) w[i] = load_elem(row, f[i] & WIRE_MASK);
-#pragma unroll
-        for (int i = 0; i < U; ++i) acc = accumulate(acc, w[i], f[i] >> 30, coef, cidx[k + i]);
-    }
-    for (; k < end; ++k) {
-        const uint32_t f = fac[k];
-        acc = accumulate(acc, load_elem(row, f & WIRE_MASK), f >> 30, coef, cidx[k]);
-    }
-    return acc;
-}
 
 template <int T>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void r1cs_check_kernel(
@@ -116,6 +74,11 @@ KernelFn kernel_for(uint32_t t) {
     }
 }
 
+}  // namespace
+
+// Host helpers shared with qap.hip (declared in r1cs_internal.hpp).
+namespace cwc_r1cs {
+
 // rows per wave: the batch rounded up to a power of two, at most 64 (full waves of rows once there are 64 of them)
 uint32_t pick_tile_width(size_t batch) {
     uint32_t t = 1;
@@ -126,7 +89,7 @@ uint32_t pick_tile_width(size_t batch) {
 std::string hip_err(const char* what, hipError_t e) { return std::string("r1cs: ") + what + ": " + hipGetErrorString(e); }
 
 template <class V>
-bool upload(void** d, const V& v, std::string& err) {
+static bool upload(void** d, const V& v, std::string& err) {
     const size_t bytes = std::max<size_t>(v.size() * sizeof(v[0]), 4);
     hipError_t e = hipMalloc(d, bytes);
     if (e == hipSuccess && !v.empty()) e = hipMemcpy(*d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
@@ -137,7 +100,7 @@ bool upload(void** d, const V& v, std::string& err) {
     return true;
 }
 
-void release_device(gwb_r1cs* r) {
+static void release_device(gwb_r1cs* r) {
     for (void** p : {&r->d_rowptr, &r->d_fac, &r->d_cidx, &r->d_coef, &r->d_perm}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
@@ -184,6 +147,71 @@ bool check_args(gwb_r1cs* r, size_t n_witness, size_t batch, std::string& err) {
     return true;
 }
 
+int fail(gw_status_t* st, const std::string& msg) {
+    set_status(st, msg);
+    return 1;
+}
+
+static bool parse_fail(std::string& err, const std::string& msg) {
+    err = msg;
+    return false;
+}
+
+bool parse_wtns(const void* wtns, size_t len, const uint8_t** values_out, uint64_t* n_wit_out, std::string& err) {
+    // "wtns", u32 version (1 or 2), u32 nSections, sections {u32 type, u64 size}: 1 = {u32 n8, prime, u32 nWitness}, 2 = the values
+    const uint8_t* p = (const uint8_t*)wtns;
+    if (len < 12 || memcmp(p, "wtns", 4) != 0) return parse_fail(err, "wtns: bad magic (not a .wtns image)");
+    uint32_t version, nsec;
+    memcpy(&version, p + 4, 4);
+    memcpy(&nsec, p + 8, 4);
+    if (version != 1 && version != 2) return parse_fail(err, "wtns: unsupported version " + std::to_string(version));
+    size_t off = 12;
+    const uint8_t* values = nullptr;
+    uint64_t values_size = 0, n_wit = 0;
+    bool have_hdr = false;
+    for (uint32_t i = 0; i < nsec; ++i) {
+        if (len - off < 12) return parse_fail(err, "wtns: truncated section header");
+        uint32_t type;
+        uint64_t size;
+        memcpy(&type, p + off, 4);
+        memcpy(&size, p + off + 4, 8);
+        off += 12;
+        if (size > len - off) return parse_fail(err, "wtns: truncated section " + std::to_string(type));
+        if (type == 1) {
+            if (have_hdr) return parse_fail(err, "wtns: duplicate header section");
+            if (size != 40) return parse_fail(err, "wtns: header section size " + std::to_string(size) + " (40 expected)");
+            uint32_t n8, nw;
+            memcpy(&n8, p + off, 4);
+            Fr prime;
+            memcpy(prime.v, p + off + 4, 32);
+            memcpy(&nw, p + off + 36, 4);
+            if (n8 != 32 || !cwc::u256_eq(prime, cwc::fr_p())) return parse_fail(err, "wtns: field is not BN254's r");
+            n_wit = nw;
+            have_hdr = true;
+        } else if (type == 2) {
+            if (values) return parse_fail(err, "wtns: duplicate witness section");
+            values = p + off;
+            values_size = size;
+        }
+        off += size;
+    }
+    if (off != len) return parse_fail(err, "wtns: " + std::to_string(len - off) + " trailing bytes");
+    if (!have_hdr || !values) return parse_fail(err, "wtns: missing header or witness section");
+    if (values_size != n_wit * 32) return parse_fail(err, "wtns: witness section size disagrees with nWitness x 32");
+    for (uint64_t i = 0; i < n_wit; ++i) {
+        Fr v;
+        memcpy(v.v, values + 32 * i, 32);
+        if (!cwc::u256_lt(v, cwc::fr_p())) return parse_fail(err, "wtns: witness element " + std::to_string(i) + " is not below r");
+    }
+    *values_out = values;
+    *n_wit_out = n_wit;
+    return true;
+}
+
+}  // namespace cwc_r1cs
+
+namespace {
+
 // enqueue: result initialisation + the check kernel on `stream`
 bool enqueue(gwb_r1cs* r, const void* d_witness, size_t batch, uint32_t form, uint32_t* d_first, uint32_t* d_nfail, hipStream_t stream,
              std::string& err) {
@@ -217,11 +245,6 @@ bool enqueue(gwb_r1cs* r, const void* d_witness, size_t batch, uint32_t form, ui
         return false;
     }
     return true;
-}
-
-int fail(gw_status_t* st, const std::string& msg) {
-    set_status(st, msg);
-    return 1;
 }
 
 // host rows -> device -> results back; synchronous
@@ -271,9 +294,11 @@ void gwb_r1cs_free(gwb_r1cs_t* r) {
         int cur = -1;
         const bool switch_dev = hipGetDevice(&cur) == hipSuccess && cur != r->device;
         if (switch_dev) (void)hipSetDevice(r->device);
+        release_qap(r);
         release_device(r);
         if (switch_dev) (void)hipSetDevice(cur);
     }
+    (void)gwb_r1cs_qap_time_phases(r, 0);
     delete r;
 }
 
@@ -301,51 +326,10 @@ int gwb_r1cs_check_batch_host(gwb_r1cs_t* r, const void* witness, size_t n_witne
 
 int gwb_r1cs_check_wtns(gwb_r1cs_t* r, const void* wtns, size_t len, uint32_t* first_failed, uint32_t* n_failed, gw_status_t* status) {
     if (!r || !wtns || !first_failed || !n_failed) return fail(status, "gwb_r1cs_check_wtns: NULL argument");
-    // "wtns", u32 version (1 or 2), u32 nSections, sections {u32 type, u64 size}: 1 = {u32 n8, prime, u32 nWitness}, 2 = the values
-    const uint8_t* p = (const uint8_t*)wtns;
-    if (len < 12 || memcmp(p, "wtns", 4) != 0) return fail(status, "wtns: bad magic (not a .wtns image)");
-    uint32_t version, nsec;
-    memcpy(&version, p + 4, 4);
-    memcpy(&nsec, p + 8, 4);
-    if (version != 1 && version != 2) return fail(status, "wtns: unsupported version " + std::to_string(version));
-    size_t off = 12;
     const uint8_t* values = nullptr;
-    uint64_t values_size = 0, n_wit = 0;
-    bool have_hdr = false;
-    for (uint32_t i = 0; i < nsec; ++i) {
-        if (len - off < 12) return fail(status, "wtns: truncated section header");
-        uint32_t type;
-        uint64_t size;
-        memcpy(&type, p + off, 4);
-        memcpy(&size, p + off + 4, 8);
-        off += 12;
-        if (size > len - off) return fail(status, "wtns: truncated section " + std::to_string(type));
-        if (type == 1) {
-            if (have_hdr) return fail(status, "wtns: duplicate header section");
-            if (size != 40) return fail(status, "wtns: header section size " + std::to_string(size) + " (40 expected)");
-            uint32_t n8, nw;
-            memcpy(&n8, p + off, 4);
-            Fr prime;
-            memcpy(prime.v, p + off + 4, 32);
-            memcpy(&nw, p + off + 36, 4);
-            if (n8 != 32 || !cwc::u256_eq(prime, cwc::fr_p())) return fail(status, "wtns: field is not BN254's r");
-            n_wit = nw;
-            have_hdr = true;
-        } else if (type == 2) {
-            if (values) return fail(status, "wtns: duplicate witness section");
-            values = p + off;
-            values_size = size;
-        }
-        off += size;
-    }
-    if (off != len) return fail(status, "wtns: " + std::to_string(len - off) + " trailing bytes");
-    if (!have_hdr || !values) return fail(status, "wtns: missing header or witness section");
-    if (values_size != n_wit * 32) return fail(status, "wtns: witness section size disagrees with nWitness x 32");
-    for (uint64_t i = 0; i < n_wit; ++i) {
-        Fr v;
-        memcpy(v.v, values + 32 * i, 32);
-        if (!cwc::u256_lt(v, cwc::fr_p())) return fail(status, "wtns: witness element " + std::to_string(i) + " is not below r");
-    }
+    uint64_t n_wit = 0;
+    std::string err;
+    if (!parse_wtns(wtns, len, &values, &n_wit, err)) return fail(status, err);
     return check_host(r, values, n_wit, 1, first_failed, n_failed, status);
 }
 

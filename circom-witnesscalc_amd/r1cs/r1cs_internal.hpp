@@ -1,5 +1,7 @@
-// Host representation of a loaded `.r1cs` file, shared by the loader (loader.cc) and the device check (check.hip).
+// Host representation of a loaded `.r1cs` file, shared by the loader (loader.cc), the device check (check.hip) and the QAP
+// witness map (qap.hip).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include <string>
 #include <vector>
@@ -25,6 +27,19 @@ void set_ok(gw_status_t* st);
 
 }  // namespace cwc_r1cs
 
+struct gwb_r1cs;
+
+// Host helpers of check.hip, shared with qap.hip.
+namespace cwc_r1cs {
+uint32_t pick_tile_width(size_t batch);                  // rows per wave for a batch
+bool ensure_device(gwb_r1cs* r, std::string& err);       // constraint arrays on the current device (first call)
+bool check_args(gwb_r1cs* r, size_t n_witness, size_t batch, std::string& err);
+int fail(gw_status_t* st, const std::string& msg);      // set_status + return 1
+// A `.wtns` image as gwb_r1cs_check_wtns validates it: the witness values (elements below r) and their count.
+bool parse_wtns(const void* wtns, size_t len, const uint8_t** values, uint64_t* n_wit, std::string& err);
+void release_qap(gwb_r1cs* r);                           // qap.hip: the QAP tables and workspace
+}  // namespace cwc_r1cs
+
 struct gwb_r1cs {
     gwb_r1cs_info_t info{};
     // Constraints in device order (bucketed by length, stable inside a bucket): constraint k's A factors are
@@ -36,4 +51,9 @@ struct gwb_r1cs {
     // device copies (first check call)
     int device = -1;
     void *d_rowptr = nullptr, *d_fac = nullptr, *d_cidx = nullptr, *d_coef = nullptr, *d_perm = nullptr;
+    // QAP witness map (qap.hip, first QAP call, on the same device): twiddles w_n^e and per-position coset factors, n each;
+    // the A / B workspace, grown on demand
+    void *d_qap_tw = nullptr, *d_qap_coset = nullptr, *d_qap_ws = nullptr;
+    size_t qap_ws_bytes = 0;
+    void* qap_events[5] = {};  // phase timing (gwb_r1cs_qap_time_phases): hipEvent_t, recorded around each phase
 };

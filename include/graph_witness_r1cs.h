@@ -63,6 +63,56 @@ int gwb_r1cs_check_batch_host(gwb_r1cs_t *r, const void *witness, size_t n_witne
 int gwb_r1cs_check_wtns(gwb_r1cs_t *r, const void *wtns, size_t wtns_len, uint32_t *first_failed, uint32_t *n_failed,
                         gw_status_t *status);
 
+/* ---- Groth16 witness map: the quotient evaluations h of witness rows (what snarkjs `groth16 prove` and rapidsnark feed
+ * to the MSM against the zkey's H points).
+ *
+ * For a loaded `.r1cs` with nC constraints, nPub = nPubOut + nPubIn, and a witness row w (wire i = element i, wire 0 = 1):
+ *   Rows.    N = nC + nPub + 1.  Row i < nC is constraint i in file order: a_i = sum_A coeff * w[wire],
+ *            b_i = sum_B coeff * w[wire] (the file's C side is not read).  Row nC + s, s = 0..nPub, is a = w[s], b = 0
+ *            (the input constraints snarkjs `zkey new` adds for the constant wire and every public signal).  Rows N..n-1
+ *            are a = b = 0.  c_i = a_i * b_i for every row (snarkjs buildABC1, rapidsnark), so a witness that does not
+ *            satisfy the system still gets its h.
+ *   Domain.  n = 2^p, p the smallest integer >= 1 with 2^p >= N; p > 27 is refused (the coset needs a 2n-th root of unity
+ *            and the 2-adicity of r is 28).
+ *   Roots.   w_28 = 5^((r-1)/2^28) mod r (5 is the smallest quadratic non-residue; ffjavascript's and arkworks' root),
+ *            w_n = w_28^(2^(28-p)), g = w_2n = w_28^(2^(27-p)).
+ *   Output.  A(X) is the polynomial of degree < n with A(w_n^i) = a_i, B and C likewise;
+ *            h_j = A(g w_n^j) * B(g w_n^j) - C(g w_n^j) for j = 0..n-1, natural order (snarkjs's buffPodd_T),
+ *            canonical (GWB_FORM_CANONICAL) or Montgomery (GWB_FORM_MONTGOMERY) as asked.
+ *   Input.   Rows canonical or Montgomery, as for the check; elements >= r in a row are reduced mod r.
+ *
+ * The twiddle and coset tables (2 n x 32 B) are built on the handle's device at the first QAP call and kept.  The device
+ * workspace (the A and B evaluations, workspace_bytes_per_row per row) belongs to the handle, grows on demand and is
+ * released by gwb_r1cs_free.  A batch larger than the workspace cap (environment variable CWC_R1CS_QAP_WORKSPACE_MB,
+ * read once per process, default 4096) runs in sub-batches of cap / workspace_bytes_per_row rows (at least one).
+ * QAP calls on one handle share its workspace: enqueue them on one stream, or wait for the previous call before the next. */
+typedef struct {
+  uint64_t n_rows;                  /* N = nC + nPub + 1 */
+  uint32_t domain_power;            /* p */
+  uint64_t domain_size;             /* n = 2^p */
+  uint64_t workspace_bytes_per_row; /* device workspace per witness row */
+} gwb_r1cs_qap_info_t;
+
+/* Fails (return 1, status filled) for p > 27. */
+int gwb_r1cs_qap_info(const gwb_r1cs_t *r, gwb_r1cs_qap_info_t *info, gw_status_t *status);
+/* Device rows [batch][n_witness][32 B] in form_in (n_witness must equal nWires) -> d_h [batch][n][32 B] in form_out.
+ * Asynchronous on hip_stream, with the ordering contract of gwb_r1cs_check_batch_device. */
+int gwb_r1cs_qap_batch_device(gwb_r1cs_t *r, const void *d_witness, size_t n_witness, size_t batch, uint32_t form_in, void *d_h,
+                              uint32_t form_out, void *hip_stream, gw_status_t *status);
+/* The same with host rows (canonical) and host h [batch][n][32 B]; synchronous. */
+int gwb_r1cs_qap_batch_host(gwb_r1cs_t *r, const void *witness, size_t n_witness, size_t batch, void *h, uint32_t form_out,
+                            gw_status_t *status);
+/* One `.wtns` image, validated as gwb_r1cs_check_wtns validates it -> h_out [n][32 B] in form_out. */
+int gwb_r1cs_qap_wtns(gwb_r1cs_t *r, const void *wtns, size_t wtns_len, void *h_out, uint32_t form_out, gw_status_t *status);
+/* Measurement aid: with on != 0, later QAP calls record HIP events around their phases (for the last sub-batch of a call);
+ * gwb_r1cs_qap_phase_ms waits for the last call and writes ms[4] = evaluation (a, b, c and padding), inverse outer passes,
+ * the fused inner pass (inverse, coset scaling, forward), forward outer passes with A B - C.  Return 0 on success. */
+int gwb_r1cs_qap_time_phases(gwb_r1cs_t *r, int on);
+int gwb_r1cs_qap_phase_ms(gwb_r1cs_t *r, float *ms);
+/* Measurement aid: the current device's rate of dependent BN254 Montgomery products (the fr_mul the kernels use), from a
+ * short probe kernel (8 waves per SIMD, 4 independent chains per lane). */
+int gwb_r1cs_modmul_rate(double *products_per_s);
+
 #ifdef __cplusplus
 }
 #endif
