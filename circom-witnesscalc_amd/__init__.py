@@ -500,6 +500,10 @@ class R1csQapInfo(ctypes.Structure):
                 ("workspace_bytes_per_row", ctypes.c_uint64)]
 
 
+class ZkeyInfo(ctypes.Structure):
+    _fields_ = [("n_vars", ctypes.c_uint32), ("n_public", ctypes.c_uint32), ("domain_size", ctypes.c_uint32), ("n_coefs", ctypes.c_uint64)]
+
+
 def r1cs_lib():
     """ctypes handle of libcwc_r1cs.so, loaded after torch (one HIP runtime per process, as in lib())."""
     global _r1cs_lib
@@ -528,6 +532,15 @@ def r1cs_lib():
         L.gwb_r1cs_qap_time_phases.argtypes = [vp, ctypes.c_int]
         L.gwb_r1cs_qap_phase_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.gwb_r1cs_modmul_rate.argtypes = [ctypes.POINTER(ctypes.c_double)]
+        L.gwb_zkey_load.argtypes = [vp, sz, ctypes.POINTER(vp), stp]
+        L.gwb_zkey_free.restype = None
+        L.gwb_zkey_free.argtypes = [vp]
+        L.gwb_zkey_info.argtypes = [vp, ctypes.POINTER(ZkeyInfo)]
+        L.gwb_groth16_prove_batch_device.argtypes = [vp, vp, vp, sz, sz, u32, vp, vp, vp, stp]
+        L.gwb_groth16_prove_batch_host.argtypes = [vp, vp, vp, sz, sz, vp, vp, stp]
+        L.gwb_groth16_prove_wtns.argtypes = [vp, vp, vp, sz, vp, vp, stp]
+        L.gwb_groth16_time_phases.argtypes = [vp, ctypes.c_int]
+        L.gwb_groth16_phase_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         _r1cs_lib = L
     return _r1cs_lib
 
@@ -685,6 +698,130 @@ class R1cs:
                                           FORM_MONTGOMERY if montgomery_out else FORM_CANONICAL, ctypes.byref(st))
         _r1cs_check(rc, st)
         return h
+
+
+
+# -- Groth16 prover (include/graph_witness_groth16.h, libcwc_r1cs.so) ----------------------------------------------------------
+GROTH16_PROOF_BYTES = 256
+GROTH16_PHASES = ("witness_map", "scalars_sort", "g1_msms", "g2_msm", "assembly")
+
+
+def _rs_array(rs, b):
+    """None, or r / s pairs (ints below r) / uint8 [B, 2, 32] -> a contiguous uint8 array or None"""
+    if rs is None:
+        return None
+    if isinstance(rs, np.ndarray):
+        a = np.ascontiguousarray(rs, dtype=np.uint8)
+    else:
+        a = np.frombuffer(b"".join(int(x).to_bytes(32, "little") for pair in rs for x in pair), dtype=np.uint8).copy()
+    assert a.size == b * 64, "rs must hold [batch][2][32 B]"
+    return a
+
+
+def _dec(b):
+    return str(int.from_bytes(bytes(b), "little"))
+
+
+def proof_json(proof):
+    """256 proof bytes -> snarkjs's proof.json dict (decimal strings; z = "1", or "0" for the point at infinity)"""
+    p = bytes(proof)
+    c = [_dec(p[32 * k:32 * k + 32]) for k in range(8)]
+    z = lambda lo, hi: "1" if any(p[lo:hi]) else "0"  # noqa: E731
+    return {"pi_a": [c[0], c[1], z(0, 64)], "pi_b": [[c[2], c[3]], [c[4], c[5]], [z(64, 192), "0"]],
+            "pi_c": [c[6], c[7], z(192, 256)], "protocol": "groth16", "curve": "bn128"}
+
+
+class Groth16:
+    """A circuit's Groth16 proving key (`.zkey` bytes, snarkjs's Groth16 format) with its constraint system (an R1cs of the same
+    circuit, which supplies the witness map): proofs of witness rows on the GPU, 256 bytes per row (A.x, A.y, B.x.c0, B.x.c1,
+    B.y.c0, B.y.c1, C.x, C.y, canonical little-endian)."""
+
+    def __init__(self, zkey_bytes, r1cs):
+        self._h = ctypes.c_void_p()
+        self.r1cs = r1cs
+        data = bytes(zkey_bytes)
+        st = GwStatus()
+        rc = r1cs_lib().gwb_zkey_load(data, len(data), ctypes.byref(self._h), ctypes.byref(st))
+        _r1cs_check(rc, st)
+        info = ZkeyInfo()
+        r1cs_lib().gwb_zkey_info(self._h, ctypes.byref(info))
+        self.info = {n: int(getattr(info, n)) for n, _ in ZkeyInfo._fields_}
+
+    def close(self):
+        if getattr(self, "_h", None) and _r1cs_lib is not None:
+            _r1cs_lib.gwb_zkey_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def prove_batch(self, rows, rs=None):
+        """Host rows uint8 [B, nVars, 32] (canonical), or the (witness, status) pair of Graph.calc_witness_batch -> uint8
+        [B, 256].  rs: [B] pairs (r, s) of ints below r, or uint8 [B, 2, 32]; None draws them from getrandom().  Synchronous."""
+        if isinstance(rows, tuple):
+            rows = rows[0]
+        w = np.ascontiguousarray(rows, dtype=np.uint8)
+        assert w.ndim == 3 and w.shape[2] == 32, w.shape
+        b = w.shape[0]
+        rsa = _rs_array(rs, b)
+        out = np.zeros((b, GROTH16_PROOF_BYTES), dtype=np.uint8)
+        st = GwStatus()
+        rc = r1cs_lib().gwb_groth16_prove_batch_host(self._h, self.r1cs._h, w.ctypes.data, w.shape[1], b,
+                                                     None if rsa is None else rsa.ctypes.data, out.ctypes.data, ctypes.byref(st))
+        _r1cs_check(rc, st)
+        return out
+
+    def prove_batch_device(self, d_w, stream=None, montgomery=False, rs=None):
+        """Device rows (torch uint8 cuda tensor [B, nVars, 32], canonical or Montgomery form) -> a uint8 cuda tensor [B, 256].
+        Asynchronous on `stream` or the current torch stream (rs is read before the call returns)."""
+        import torch
+        assert d_w.is_cuda and d_w.is_contiguous() and d_w.dtype == torch.uint8
+        assert d_w.dim() == 3 and d_w.shape[2] == 32, tuple(d_w.shape)
+        b = d_w.shape[0]
+        rsa = _rs_array(rs, b)
+        s = stream if stream is not None else torch.cuda.current_stream(d_w.device)
+        out = torch.empty((b, GROTH16_PROOF_BYTES), dtype=torch.uint8, device=d_w.device)
+        st = GwStatus()
+        with torch.cuda.device(d_w.device):
+            rc = r1cs_lib().gwb_groth16_prove_batch_device(self._h, self.r1cs._h, d_w.data_ptr(), d_w.shape[1], b,
+                                                           FORM_MONTGOMERY if montgomery else FORM_CANONICAL,
+                                                           None if rsa is None else rsa.ctypes.data, out.data_ptr(),
+                                                           s.cuda_stream, ctypes.byref(st))
+        _r1cs_check(rc, st)
+        if b:
+            out.record_stream(s)
+        return out
+
+    def prove_wtns(self, wtns, rs=None):
+        """One `.wtns` image -> (proof dict, public signals) in snarkjs's proof.json / public.json shape."""
+        wtns = bytes(wtns)
+        rsa = _rs_array(rs, 1)
+        out = np.zeros(GROTH16_PROOF_BYTES, dtype=np.uint8)
+        st = GwStatus()
+        rc = r1cs_lib().gwb_groth16_prove_wtns(self._h, self.r1cs._h, wtns, len(wtns), None if rsa is None else rsa.ctypes.data,
+                                               out.ctypes.data, ctypes.byref(st))
+        _r1cs_check(rc, st)
+        # the values section of the (validated) image: wire i at 32 i
+        n_sec = int.from_bytes(wtns[8:12], "little")
+        off, values = 12, None
+        for _ in range(n_sec):
+            t, size = int.from_bytes(wtns[off:off + 4], "little"), int.from_bytes(wtns[off + 4:off + 12], "little")
+            if t == 2:
+                values = wtns[off + 12:off + 12 + size]
+            off += 12 + size
+        public = [_dec(values[32 * i:32 * i + 32]) for i in range(1, self.info["n_public"] + 1)]
+        return proof_json(out), public
+
+    def time_phases(self, on=True):
+        """Measurement aid: record HIP events around the phases of later prove calls (see phase_ms)."""
+        if r1cs_lib().gwb_groth16_time_phases(self._h, 1 if on else 0) != 0:
+            raise WitnessCalcError("gwb_groth16_time_phases failed")
+
+    def phase_ms(self):
+        """Waits for the last prove call -> {witness_map, scalars_sort, g1_msms, g2_msm, assembly} in ms (its last sub-batch)."""
+        ms = (ctypes.c_float * 5)()
+        if r1cs_lib().gwb_groth16_phase_ms(self._h, ms) != 0:
+            raise WitnessCalcError("no prover phase times (time_phases not on, or no prove call yet)")
+        return dict(zip(GROTH16_PHASES, (float(x) for x in ms)))
 
 
 from . import graphgen  # noqa: E402,F401  (graph generator library on top of the C-ABI producer)

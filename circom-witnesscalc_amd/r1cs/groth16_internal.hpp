@@ -1,0 +1,35 @@
+// Host representation of a loaded `.zkey` (zkey.cc), shared with the prover (msm.hip).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/graph_witness_groth16.h"
+#include "r1cs_internal.hpp"
+
+constexpr size_t G1_BYTES = 64, G2_BYTES = 128;
+
+struct gwb_zkey {
+    gwb_zkey_info_t info{};
+    // affine points as stored (x, y; x.c0, x.c1, y.c0, y.c1), Montgomery form mod q, all-zero = infinity
+    uint8_t alpha1[G1_BYTES], beta1[G1_BYTES], delta1[G1_BYTES], beta2[G2_BYTES], gamma2[G2_BYTES], delta2[G2_BYTES];
+    std::vector<uint8_t> ic, a, b1, b2, c, h;  // sections 3, 5, 6, 7, 8, 9
+    // device copies (first prove call): A, B1, B2 with two more points each, the bases of the scalars r and s
+    // (A: delta1, O; B1: O, delta1; B2: O, delta2), then C and H as stored
+    int device = -1;
+    void *d_a = nullptr, *d_b1 = nullptr, *d_b2 = nullptr, *d_c = nullptr, *d_h = nullptr;
+    void* d_ws = nullptr;
+    size_t ws_bytes = 0;
+    void* h_rs = nullptr;  // pinned staging of r, s (h_rs_bytes), and the event after its last copy
+    size_t h_rs_bytes = 0;
+    void* rs_done = nullptr;
+    void* events[8] = {};  // phase timing (gwb_groth16_time_phases): recorded around each phase of the last sub-batch
+};
+
+namespace cwc_r1cs {
+// qap.hip: the witness map of device rows into d_h, as gwb_r1cs_qap_batch_device enqueues it (arguments checked by the caller)
+bool qap_enqueue(gwb_r1cs* r, const void* d_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out, void* stream,
+                 std::string& err);
+}  // namespace cwc_r1cs

@@ -1,0 +1,124 @@
+// groth16-prove <circuit.r1cs> <circuit.zkey> <witness.wtns> <proof.json> <public.json>: a Groth16 proof of the witness on
+// the GPU (snarkjs `groth16 prove`), written in snarkjs's proof.json / public.json shape.  Exit status 0 on success; 2 on a
+// usage, file, format or mismatch error.
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <fstream>
+#include <iterator>
+#include <string>
+#include <vector>
+
+#include "../../include/graph_witness_groth16.h"
+
+static bool read_file(const char* path, std::vector<char>& out) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) return false;
+    out.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+    return !f.bad();
+}
+
+// 32-byte little-endian integer -> decimal string
+static std::string decimal(const uint8_t* le) {
+    uint32_t w[8];
+    memcpy(w, le, 32);
+    std::string out;
+    for (;;) {
+        bool zero = true;
+        uint64_t rem = 0;
+        for (int i = 7; i >= 0; --i) {
+            const uint64_t cur = (rem << 32) | w[i];
+            w[i] = (uint32_t)(cur / 1000000000u);
+            rem = cur % 1000000000u;
+            zero = zero && w[i] == 0;
+        }
+        char buf[16];
+        snprintf(buf, sizeof buf, zero ? "%llu" : "%09llu", (unsigned long long)rem);
+        out = buf + out;
+        if (zero) return out;
+    }
+}
+
+// the witness values of a `.wtns` image the library has already validated (section 2)
+static const uint8_t* wtns_values(const std::vector<char>& w) {
+    const uint8_t* p = (const uint8_t*)w.data();
+    uint32_t nsec;
+    memcpy(&nsec, p + 8, 4);
+    size_t off = 12;
+    for (uint32_t i = 0; i < nsec; ++i) {
+        uint32_t type;
+        uint64_t size;
+        memcpy(&type, p + off, 4);
+        memcpy(&size, p + off + 4, 8);
+        off += 12;
+        if (type == 2) return p + off;
+        off += size;
+    }
+    return nullptr;
+}
+
+static bool write_text(const char* path, const std::string& s) {
+    FILE* f = fopen(path, "wb");
+    if (!f) return false;
+    const bool ok = fwrite(s.data(), 1, s.size(), f) == s.size();
+    return fclose(f) == 0 && ok;
+}
+
+int main(int argc, char** argv) {
+    if (argc != 6) {
+        fprintf(stderr, "usage: %s <circuit.r1cs> <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n", argv[0]);
+        return 2;
+    }
+    std::vector<char> files[3];
+    for (int i = 0; i < 3; ++i) {
+        if (!read_file(argv[1 + i], files[i])) {
+            fprintf(stderr, "error: cannot read %s\n", argv[1 + i]);
+            return 2;
+        }
+    }
+    gw_status_t st = {OK, NULL};
+    gwb_r1cs_t* r = NULL;
+    gwb_zkey_t* z = NULL;
+    if (gwb_r1cs_load(files[0].data(), files[0].size(), &r, &st) != 0) {
+        fprintf(stderr, "error: %s: %s\n", argv[1], st.error_msg ? st.error_msg : "load failed");
+        gw_free_status(&st);
+        return 2;
+    }
+    if (gwb_zkey_load(files[1].data(), files[1].size(), &z, &st) != 0) {
+        fprintf(stderr, "error: %s: %s\n", argv[2], st.error_msg ? st.error_msg : "load failed");
+        gw_free_status(&st);
+        gwb_r1cs_free(r);
+        return 2;
+    }
+    uint8_t proof[GWB_GROTH16_PROOF_BYTES];
+    const int rc = gwb_groth16_prove_wtns(z, r, files[2].data(), files[2].size(), NULL, proof, &st);
+    gwb_zkey_info_t zi;
+    gwb_zkey_info(z, &zi);
+    gwb_zkey_free(z);
+    gwb_r1cs_free(r);
+    if (rc != 0) {
+        fprintf(stderr, "error: %s: %s\n", argv[3], st.error_msg ? st.error_msg : "prove failed");
+        gw_free_status(&st);
+        return 2;
+    }
+    auto d = [&](int k) { return "\"" + decimal(proof + 32 * k) + "\""; };
+    // snarkjs writes projective coordinates with z = 1 (or 0 for the point at infinity)
+    auto z1 = [&](int k, int words) {
+        for (int i = 0; i < words * 32; ++i)
+            if (proof[32 * k + i]) return std::string("\"1\"");
+        return std::string("\"0\"");
+    };
+    std::string pj = "{\n \"pi_a\": [\n  " + d(0) + ",\n  " + d(1) + ",\n  " + z1(0, 2) + "\n ],\n \"pi_b\": [\n  [\n   " + d(2) + ",\n   " + d(3) +
+                     "\n  ],\n  [\n   " + d(4) + ",\n   " + d(5) + "\n  ],\n  [\n   " + z1(2, 4) + ",\n   \"0\"\n  ]\n ],\n \"pi_c\": [\n  " + d(6) +
+                     ",\n  " + d(7) + ",\n  " + z1(6, 2) + "\n ],\n \"protocol\": \"groth16\",\n \"curve\": \"bn128\"\n}\n";
+    const uint8_t* w = wtns_values(files[2]);
+    std::string pub = "[";
+    for (uint32_t i = 1; i <= zi.n_public; ++i) pub += std::string(i > 1 ? ",\n " : "\n ") + "\"" + decimal(w + 32 * (size_t)i) + "\"";
+    pub += zi.n_public ? "\n]\n" : "]\n";
+    if (!write_text(argv[4], pj) || !write_text(argv[5], pub)) {
+        fprintf(stderr, "error: cannot write %s / %s\n", argv[4], argv[5]);
+        return 2;
+    }
+    return 0;
+}

@@ -28,6 +28,7 @@
 #include <string>
 
 #include "lincomb.hpp"
+#include "groth16_internal.hpp"
 #include "r1cs_internal.hpp"
 
 namespace cwc_r1cs {
@@ -529,6 +530,11 @@ int qap_host(gwb_r1cs* r, const void* witness, size_t n_witness, size_t batch, v
 }  // namespace
 
 namespace cwc_r1cs {
+
+bool qap_enqueue(gwb_r1cs* r, const void* d_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out, void* stream,
+                 std::string& err) {
+    return enqueue_qap(r, d_witness, batch, form_in, d_h, form_out, (hipStream_t)stream, err);
+}
 
 void release_qap(gwb_r1cs* r) {
     for (void** p : {&r->d_qap_tw, &r->d_qap_coset, &r->d_qap_ws}) {
