@@ -8,10 +8,15 @@ A step = one pass of the hot path (interpreter + witness pack kernels) over one 
 resident in HBM.  `value` is BASELINE config 2 -- authV2-class graph, 1024 input sets per GPU, weak scaling: every rank
 evaluates its own shard of a global batch of 1024 x N counter-generated sets; rank 0 compiles, asks the cost model for
 the program of a 1024-set shard and broadcasts that program once over RCCL (no data-path collective).  Prints ONE JSON
-line on rank 0.  Outside `value`, the same line carries (N = 1 unless said otherwise):
+line on rank 0.
+
+A plain run does only what `value` needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the line,
+whose other figures come from the timed steps themselves (the kernels' HIP events, the compiled program's statistics, the
+committed PMC summaries).  `--full` adds everything that takes runs of its own; then the line also carries (N = 1 unless
+said otherwise):
 
   roofline.compute   the ceiling that binds (instruction issue): modmul-equivalents/s against the chip's one-lane
-                     Montgomery product rate measured in this run (gwb_ubench_modmul)
+                     Montgomery product rate measured in this run (gwb_ubench_modmul; peak and frac are null without --full)
   cpu_baseline       the oracle's C port of the reference evaluate() on one host core, same input sets, byte-compared
   config3            BASELINE config 3: sha256_512 graph, 4096 sets, every digest checked against hashlib
   config4_per_gpu    BASELINE config 4's per-GPU share: 8192 authV2-class sets, sampled sets against the oracle
@@ -25,9 +30,11 @@ line on rank 0.  Outside `value`, the same line carries (N = 1 unless said other
   json_front_end     sets/s of the batched NDJSON -> rows front-end
   e2e_json_to_wtns   NDJSON -> `.wtns` files on tmpfs through the streaming pipeline (parse | kernels | D2H slices | writers)
   pcie_inclusive     the host-buffer entry point (never `value`)
+  n1_ms_per_step_same_run, efficiency_vs_n1   (N > 1) rank 0 alone repeats its shard's steps while the other ranks wait
 
-`--config 3` / `--config 4` / `--config 5` make one of those the timed `value` instead; CWC_GRAPH_BIN=<file.bin> runs a
-real graph (synthetic inputs by its input count) in place of the generated authV2-class one.
+`--cpu-sample` and `--extras` trim a `--full` run.  `--config 3` / `--config 4` / `--config 5` make one of those the timed
+`value` instead; CWC_GRAPH_BIN=<file.bin> runs a real graph (synthetic inputs by its input count) in place of the generated
+authV2-class one.
 
 `--dump-outputs DIR` writes, after the timed steps, what the last of them computed (witness rows and status words of rank 0's
 shard, float64 .npy, at most 64 MB: dump_outputs) -- the inputs depend on the arguments alone, so two builds can be compared file by file.
@@ -352,8 +359,10 @@ def main():
     ap.add_argument("--batch-per-gpu", type=int, default=0, help="0 = the config's own (1024 / 4096 / 8192 / 32)")
     ap.add_argument("--graph", choices=["authv2", "sha256"], default=None, help="(old spelling of --config 2 / 3)")
     ap.add_argument("--tile-width", type=int, default=0, help="0 = the library's cost model")
-    ap.add_argument("--cpu-sample", type=int, default=1024, help="input sets timed on one host core (0 = skip)")
-    ap.add_argument("--extras", type=int, default=1, help="0 = only the timed metric (no sub-records)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what takes runs of its own: CPU baselines, the sub-records of the "
+                                                        "other configurations, the chip's modmul rate behind roofline.compute, the N = 1 step of a multi-GPU run")
+    ap.add_argument("--cpu-sample", type=int, default=1024, help="with --full: input sets timed on one host core (0 = skip)")
+    ap.add_argument("--extras", type=int, default=1, help="with --full: 0 = no sub-records")
     ap.add_argument("--extra-batch", type=int, default=None, help=argparse.SUPPRESS)   # (round-1 flags, still accepted)
     ap.add_argument("--host-path", type=int, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--pmc-selfcheck", action="store_true", help="fail (exit 5) unless the committed PMC summary behind roofline.traffic is of this library's kernel sources "
@@ -376,6 +385,8 @@ def main():
         args.config = 3
     if args.extra_batch == 0 and args.host_path == 0:
         args.extras = 0
+    if not args.full:  # a plain run: set-up, warm-up, timed steps, dump, the line
+        args.extras, args.cpu_sample = 0, 0
     global CPU_SAMPLE
     CPU_SAMPLE = args.cpu_sample
     cfg = args.config
@@ -435,7 +446,7 @@ def main():
         per_rank_ms = [float(x.item()) / args.steps * 1e3 for x in all_t]
         elapsed = max(float(x.item()) for x in all_t)
         # the N = 1 step of the same run: rank 0 alone repeats its shard while the other ranks wait at the barrier
-        if rank == 0:
+        if rank == 0 and args.full:
             n1_ms = run_steps(g, d_in, d_out, d_st, args.steps, 1, False) / args.steps * 1e3
         dist.barrier()
     bad_sets = int((d_st != 0).sum().item())
@@ -457,16 +468,18 @@ def main():
         eq_per_set = modmul_equivalents(wl.stats["hist"], g.n_witness)
         # the ceiling that binds: one-lane Montgomery products per second, chip-wide, with the multiplier the interpreter's
         # full-width bundles use (fr_mul_wave, 322 issue slots; its pinned accumulators allow two waves per SIMD) -- beside it
-        # the generic 380-slot multiplier at four waves per SIMD (round 2's denominator, which flattered the fraction)
-        peak_blk2, peak_blk1 = pkg.ubench_modmul(2, 1000, block=True), pkg.ubench_modmul(1, 1000, block=True)
-        peak4 = pkg.ubench_modmul(4, 1000)
-        peak = max(peak_blk2, peak_blk1, peak4)
+        # the generic 380-slot multiplier at four waves per SIMD (round 2's denominator, which flattered the fraction); --full only
+        peak_blk2 = peak_blk1 = peak4 = peak = None
+        if args.full:
+            peak_blk2, peak_blk1 = pkg.ubench_modmul(2, 1000, block=True), pkg.ubench_modmul(1, 1000, block=True)
+            peak4 = pkg.ubench_modmul(4, 1000)
+            peak = max(peak_blk2, peak_blk1, peak4)
         PEAK["modmul_per_s"] = peak or None
         ps = g.program_stats()
         out = {
             "metric": "witnesses/sec", "value": value, "unit": "witnesses/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+            "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic", "full": args.full,
             "config": {"workload": "%s, %d input sets per GPU (BASELINE config %d)" % (wl.name, B, cfg),
                        "graph": wl.source, "inputs": "uniform in [0, r) by rejection (bits for sha256), SplitMix64 of seed 0xC1C0000%d and element id = "
                        "global set index * n_inputs + k; set 0 = the reference's input file" % cfg,

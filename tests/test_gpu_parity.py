@@ -1216,3 +1216,28 @@ def test_streams_two_and_four_wavefronts_per_tile(pkg):
             assert np.array_equal(st2 != 0, wst2 != 0), (seed, key)
             ok = wst2 == 0
             assert np.array_equal(got2[ok], want2[ok]), (seed, key)
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_and_full_run():
+    """A plain `bench.py` run prints the headline line and nothing that takes runs of its own (no CPU baseline, no sub-records,
+    no measured modmul peak); `--full` measures the peak behind roofline.compute (sub-records and CPU baselines trimmed here
+    by --extras 0 --cpu-sample 0).  Own processes, a small batch."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    lines = []
+    for extra in ([], ["--full", "--extras", "0", "--cpu-sample", "0"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "64"] + extra,
+                           capture_output=True, text=True, timeout=280, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(out) == 1, r.stdout
+        lines.append(json.loads(out[0]))
+    plain, full = lines
+    for j in lines:
+        assert j["metric"] == "witnesses/sec" and j["value"] > 0 and j["ms_per_step"] > 0 and j["steps"] == 2 and j["warmup"] == 1
+        assert j["config"]["batch_per_gpu"] == 64 and j["config"]["sets_with_error_status"] == 0 and j["roofline"]["avg_launch_ms"] > 0
+    assert plain["full"] is False and full["full"] is True
+    assert plain["roofline"]["compute"]["peak"] is None and plain["roofline"]["frac"] is None
+    assert full["roofline"]["compute"]["peak"] > 0 and full["roofline"]["frac"] > 0
+    for k in ("cpu_baseline", "config3", "config4_per_gpu", "config4", "config5", "single_shot", "extras_seconds"):
+        assert k not in plain and k not in full, k

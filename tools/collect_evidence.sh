@@ -13,7 +13,7 @@ if [ "$want" != "$have" ]; then echo "libcircom_witnesscalc_amd.so was built fro
 echo "$have" > $O/ksrc_$R.txt   # (tools/profile_summary.py stamps the PMC summary with it: bench.py --pmc-selfcheck compares)
 BENCH="python3 bench.py --steps 5 --warmup 1 --cpu-sample 0 --extras 0"
 python -m pytest tests -q -m gpu > $O/gputest_$R.log 2>&1; tail -1 $O/gputest_$R.log
-python bench.py > $O/bench_$R.json 2> $O/bench_$R.err
+python bench.py --full > $O/bench_$R.json 2> $O/bench_$R.err
 # rocprofv3 passes: each its own command with the program directly behind `--`; counter passes carry no trace domains.  The rocpd databases are
 # summarised HERE (tools/profile_summary.py -> $O/summary_$R/, what gets committed under profiles/) and deleted: four configurations of them do not
 # fit the 64 MiB a lease copies back.
@@ -57,9 +57,9 @@ CWC_FUSE=1001 SOAK_SEEDS=2000 SOAK_BASE=20261004 python tools/gpu_soak.py > $O/s
 SOAK_KINDS=limb SOAK_SEEDS=3000 SOAK_BASE=20261104 python tools/gpu_soak.py > $O/soak_scan_$R.log 2>&1
 SOAK_KINDS=limb SOAK_WIDE_SHARE=1.0 SOAK_SEEDS=3000 SOAK_BASE=20261105 python tools/gpu_soak.py > $O/soak_wide_$R.log 2>&1
 CWC_FUSE=11 PROBE_B=256 PROBE_T=4353 python tools/gpu_classprof.py > $O/classprof_fused_$R.log 2>&1
-python bench.py --config 3 --cpu-sample 128 > $O/bench_config3_$R.json 2> $O/bench_config3_$R.err
-python bench.py --config 4 --cpu-sample 0 > $O/bench_config4_$R.json 2> $O/bench_config4_$R.err
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 5 --warmup 1 --cpu-sample 0 \
+python bench.py --full --config 3 --cpu-sample 128 > $O/bench_config3_$R.json 2> $O/bench_config3_$R.err
+python bench.py --full --config 4 --cpu-sample 0 > $O/bench_config4_$R.json 2> $O/bench_config4_$R.err
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --steps 5 --warmup 1 --cpu-sample 0 \
     > $O/bench_dist1_$R.json 2> $O/bench_dist1_$R.err
 python tools/gpu_host_path.py > $O/hostpath_$R.log 2>&1
 python tools/gpu_calibrate.py > $O/calibration_$R.log 2>&1
@@ -70,8 +70,8 @@ echo "---- third process, no cache, where the first call's time goes" >> $O/sing
 CWC_PROGRAM_CACHE=0 CWC_DEBUG_SINGLE=1 SHOTS=2 python tools/gpu_single_shot.py >> $O/single_shot_$R.log 2>&1
 BIGINT_ROUNDS=4000 PROBE_T=0 python tools/gpu_bigint.py > $O/config5_$R.log 2>&1
 RSA_MULS=310 PROBE_T=0,1,2 RSA_CHECK=32 python tools/gpu_rsa.py > $O/config5_rsa_$R.log 2>&1
-python bench.py --config 5 --cpu-sample 32 > $O/bench_config5_$R.json 2> $O/bench_config5_$R.err
-python bench.py --config 5 --config5-graph bigint --cpu-sample 32 > $O/bench_config5_bigint_$R.json 2> $O/bench_config5_bigint_$R.err
+python bench.py --full --config 5 --cpu-sample 32 > $O/bench_config5_$R.json 2> $O/bench_config5_$R.err
+python bench.py --full --config 5 --config5-graph bigint --cpu-sample 32 > $O/bench_config5_bigint_$R.json 2> $O/bench_config5_bigint_$R.err
 python tools/gpu_streams.py > $O/streams_$R.log 2>&1
 SOAK_SEEDS=20000 SOAK_BASE=20261003 python tools/gpu_soak.py > $O/soak_$R.log 2>&1
 bash tools/gpu_policies.sh "X=0 --" "CWC_NO_COOP_MUL=1 --" "CWC_COOP_FILL=32 CWC_COOP_SLACK=4000000000 --" "CWC_COOP_FILL=16 CWC_COOP_SLACK=2 --" \

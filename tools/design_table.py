@@ -55,7 +55,7 @@ if d:
     e = d.get("e2e_json_to_wtns") or {}
     if j and e:
         row("host sides (SURVEY 8(f) f3)", "JSON front-end %.0f k sets/s; NDJSON -> `.wtns` files %.1f k witnesses/s (%.0f GB/s off the device)" % (j["value"] / 1e3, e["value"] / 1e3, e["link_rate_GBs"]), "bench_line.json")
-    row("wall time of the default `python bench.py`", "sub-records %.0f s" % d.get("extras_seconds", 0), "bench_line.json")
+    row("wall time of `python bench.py --full`", "sub-records %.0f s" % d.get("extras_seconds", 0), "bench_line.json")
 for name, what in (("bench_line_config3.json", "config 3 as the timed metric"), ("bench_line_config4.json", "config 4 as the timed metric"), ("bench_line_config5.json", "config 5 (RSA class) as the timed metric"), ("bench_line_config5_bigint.json", "config 5 (first generator) as the timed metric"), ("bench_line_rccl_1rank.json", "the bench under torch.distributed.run with one rank (RCCL broadcast through the C-ABI)")):
     d2 = load(name)
     if d2:
