@@ -541,6 +541,16 @@ def r1cs_lib():
         L.gwb_groth16_prove_wtns.argtypes = [vp, vp, vp, sz, vp, vp, stp]
         L.gwb_groth16_time_phases.argtypes = [vp, ctypes.c_int]
         L.gwb_groth16_phase_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        L.gwb_g16vk_from_zkey.argtypes = [vp, ctypes.POINTER(vp), stp]
+        L.gwb_g16vk_load.argtypes = [vp, sz, u32, ctypes.POINTER(vp), stp]
+        L.gwb_g16vk_info.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
+        L.gwb_g16vk_points.argtypes = [vp, vp, sz]
+        L.gwb_g16vk_alphabeta.argtypes = [vp, vp, stp]
+        L.gwb_g16vk_free.restype = None
+        L.gwb_g16vk_free.argtypes = [vp]
+        L.gwb_groth16_verify_batch_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, stp]
+        L.gwb_groth16_verify_batch_host.argtypes = [vp, vp, vp, sz, sz, vp, stp]
+        L.gwb_bn254_pairing_batch_device.argtypes = [vp, vp, sz, vp, vp, stp]
         _r1cs_lib = L
     return _r1cs_lib
 
@@ -811,6 +821,10 @@ class Groth16:
         public = [_dec(values[32 * i:32 * i + 32]) for i in range(1, self.info["n_public"] + 1)]
         return proof_json(out), public
 
+    def verifying_key(self):
+        """The zkey's verifying key (Groth16VerifyingKey)."""
+        return Groth16VerifyingKey._from_zkey_handle(self._h)
+
     def time_phases(self, on=True):
         """Measurement aid: record HIP events around the phases of later prove calls (see phase_ms)."""
         if r1cs_lib().gwb_groth16_time_phases(self._h, 1 if on else 0) != 0:
@@ -822,6 +836,217 @@ class Groth16:
         if r1cs_lib().gwb_groth16_phase_ms(self._h, ms) != 0:
             raise WitnessCalcError("no prover phase times (time_phases not on, or no prove call yet)")
         return dict(zip(GROTH16_PHASES, (float(x) for x in ms)))
+
+
+# -- Groth16 verifier (include/graph_witness_groth16_verify.h, libcwc_r1cs.so) ------------------------------------------------
+GT_BYTES = 384
+VERIFY_VALID, VERIFY_PUBLIC, VERIFY_POINT, VERIFY_SUBGROUP, VERIFY_EQUATION = 0, 1, 2, 3, 4
+VERIFY_STATUS_NAMES = {0: "VALID", 1: "PUBLIC", 2: "POINT", 3: "SUBGROUP", 4: "EQUATION"}
+
+
+def _json_g1(b):
+    """64 canonical bytes -> snarkjs [x, y, z] (z "0" and x = y = "0" for infinity)"""
+    if not any(b):
+        return ["0", "1", "0"]
+    return [_dec(b[:32]), _dec(b[32:64]), "1"]
+
+
+def _json_g2(b):
+    if not any(b):
+        return [["0", "0"], ["1", "0"], ["0", "0"]]
+    return [[_dec(b[:32]), _dec(b[32:64])], [_dec(b[64:96]), _dec(b[96:128])], ["1", "0"]]
+
+
+def _int32(x, what):
+    v = int(x)
+    if not 0 <= v < (1 << 256):
+        raise WitnessCalcError("%s: %d is not in [0, 2^256)" % (what, v))
+    return v.to_bytes(32, "little")
+
+
+def _from_json_g1(p, what):
+    if not isinstance(p, (list, tuple)) or len(p) != 3:
+        raise WitnessCalcError("%s: a G1 point is [x, y, z]" % what)
+    if str(p[2]) == "0":
+        return bytes(64)
+    if str(p[2]) != "1":
+        raise WitnessCalcError("%s: z must be \"1\" (affine) or \"0\" (infinity)" % what)
+    return _int32(p[0], what) + _int32(p[1], what)
+
+
+def _from_json_g2(p, what):
+    if not isinstance(p, (list, tuple)) or len(p) != 3 or any(not isinstance(c, (list, tuple)) or len(c) != 2 for c in p):
+        raise WitnessCalcError("%s: a G2 point is [[x0, x1], [y0, y1], [z0, z1]]" % what)
+    z = [str(c) for c in p[2]]
+    if z == ["0", "0"]:
+        return bytes(128)
+    if z != ["1", "0"]:
+        raise WitnessCalcError("%s: z must be [\"1\", \"0\"] (affine) or [\"0\", \"0\"] (infinity)" % what)
+    return b"".join(_int32(c, what) for c in (p[0][0], p[0][1], p[1][0], p[1][1]))
+
+
+def _gt_json(b):
+    """384 GT bytes -> snarkjs's vk_alphabeta_12 nesting [[[c0.b0.a0, c0.b0.a1], ...], [...]]"""
+    v = [_dec(b[32 * k:32 * k + 32]) for k in range(12)]
+    return [[[v[6 * i + 2 * j], v[6 * i + 2 * j + 1]] for j in range(3)] for i in range(2)]
+
+
+def _public_array(publics, b, n):
+    """[B] lists of ints / uint8 [B, n, 32] -> contiguous uint8 [B, n, 32]; ints must lie in [0, 2^256)"""
+    if isinstance(publics, np.ndarray):
+        a = np.ascontiguousarray(publics, dtype=np.uint8).reshape(b, n, 32)
+    else:
+        publics = list(publics)
+        assert len(publics) == b, "one list of public signals per proof"
+        a = np.zeros((b, n, 32), dtype=np.uint8)
+        for i, row in enumerate(publics):
+            row = list(row)
+            if len(row) != n:
+                raise WitnessCalcError("%d public signals in row %d, the key has nPublic %d" % (len(row), i, n))
+            for k, x in enumerate(row):
+                a[i, k] = np.frombuffer(_int32(x, "public signal"), dtype=np.uint8)
+    return a
+
+
+class Groth16VerifyingKey:
+    """A Groth16 verifying key (nPublic, alpha1, beta2, gamma2, delta2, IC) for checking proofs on the GPU: one status per proof
+    (VERIFY_VALID, VERIFY_PUBLIC, VERIFY_POINT, VERIFY_SUBGROUP, VERIFY_EQUATION; include/graph_witness_groth16_verify.h)."""
+
+    def __init__(self, points, n_public):
+        """points: canonical bytes alpha1 (64), beta2, gamma2, delta2 (128 each), IC (64 each)"""
+        points = bytes(points)
+        self._h = ctypes.c_void_p()
+        st = GwStatus()
+        rc = r1cs_lib().gwb_g16vk_load(points, len(points), int(n_public), ctypes.byref(self._h), ctypes.byref(st))
+        _r1cs_check(rc, st)
+        self.n_public = int(n_public)
+
+    @classmethod
+    def _from_zkey_handle(cls, zh):
+        self = cls.__new__(cls)
+        self._h = ctypes.c_void_p()
+        st = GwStatus()
+        rc = r1cs_lib().gwb_g16vk_from_zkey(zh, ctypes.byref(self._h), ctypes.byref(st))
+        _r1cs_check(rc, st)
+        n = ctypes.c_uint32()
+        r1cs_lib().gwb_g16vk_info(self._h, ctypes.byref(n))
+        self.n_public = int(n.value)
+        return self
+
+    @classmethod
+    def from_zkey(cls, zkey_bytes):
+        """The verifying key of a `.zkey` (bytes)."""
+        zh = ctypes.c_void_p()
+        data = bytes(zkey_bytes)
+        st = GwStatus()
+        rc = r1cs_lib().gwb_zkey_load(data, len(data), ctypes.byref(zh), ctypes.byref(st))
+        _r1cs_check(rc, st)
+        try:
+            return cls._from_zkey_handle(zh)
+        finally:
+            r1cs_lib().gwb_zkey_free(zh)
+
+    @classmethod
+    def from_json(cls, vk):
+        """snarkjs's verification_key.json (dict); vk_alphabeta_12 is ignored, as snarkjs ignores it."""
+        if not isinstance(vk, dict):
+            raise WitnessCalcError("verification key: not a JSON object")
+        for k in ("protocol", "nPublic", "vk_alpha_1", "vk_beta_2", "vk_gamma_2", "vk_delta_2", "IC"):
+            if k not in vk:
+                raise WitnessCalcError("verification key: no \"%s\"" % k)
+        if vk["protocol"] != "groth16":
+            raise WitnessCalcError("verification key: protocol is not \"groth16\"")
+        pts = _from_json_g1(vk["vk_alpha_1"], "vk_alpha_1")
+        for k in ("vk_beta_2", "vk_gamma_2", "vk_delta_2"):
+            pts += _from_json_g2(vk[k], k)
+        pts += b"".join(_from_json_g1(p, "IC[%d]" % i) for i, p in enumerate(vk["IC"]))
+        return cls(pts, int(vk["nPublic"]))
+
+    def points(self):
+        """canonical bytes alpha1, beta2, gamma2, delta2, IC (the constructor's layout)"""
+        out = ctypes.create_string_buffer(448 + 64 * (self.n_public + 1))
+        if r1cs_lib().gwb_g16vk_points(self._h, out, len(out)) != 0:
+            raise WitnessCalcError("gwb_g16vk_points failed")
+        return out.raw
+
+    def alphabeta(self):
+        """e(alpha1, beta2) as GT_BYTES bytes (computed on the GPU at the first call)"""
+        out = ctypes.create_string_buffer(GT_BYTES)
+        st = GwStatus()
+        rc = r1cs_lib().gwb_g16vk_alphabeta(self._h, out, ctypes.byref(st))
+        _r1cs_check(rc, st)
+        return out.raw
+
+    def to_json(self):
+        """snarkjs's verification_key.json shape (vk_alphabeta_12 from the GPU)"""
+        p = self.points()
+        return {"protocol": "groth16", "curve": "bn128", "nPublic": self.n_public, "vk_alpha_1": _json_g1(p[:64]),
+                "vk_beta_2": _json_g2(p[64:192]), "vk_gamma_2": _json_g2(p[192:320]), "vk_delta_2": _json_g2(p[320:448]),
+                "vk_alphabeta_12": _gt_json(self.alphabeta()),
+                "IC": [_json_g1(p[448 + 64 * i:512 + 64 * i]) for i in range(self.n_public + 1)]}
+
+    def close(self):
+        if getattr(self, "_h", None) and _r1cs_lib is not None:
+            _r1cs_lib.gwb_g16vk_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def verify_batch(self, proofs, publics):
+        """Host proofs uint8 [B, 256] and public signals ([B] lists of ints, or uint8 [B, nPublic, 32]) -> uint32 status [B].
+        Synchronous."""
+        p = np.ascontiguousarray(proofs, dtype=np.uint8).reshape(-1, GROTH16_PROOF_BYTES)
+        b = p.shape[0]
+        s = _public_array(publics, b, self.n_public)
+        out = np.zeros(b, dtype=np.uint32)
+        st = GwStatus()
+        rc = r1cs_lib().gwb_groth16_verify_batch_host(self._h, p.ctypes.data, s.ctypes.data, self.n_public, b, out.ctypes.data,
+                                                      ctypes.byref(st))
+        _r1cs_check(rc, st)
+        return out
+
+    def verify_batch_device(self, d_proofs, d_public, stream=None):
+        """Device proofs (torch uint8 cuda [B, 256]) and signals (uint8 cuda [B, nPublic, 32], canonical) -> an int32 cuda
+        tensor [B] of statuses.  Asynchronous on `stream` or the current torch stream."""
+        import torch
+        assert d_proofs.is_cuda and d_proofs.is_contiguous() and d_proofs.dtype == torch.uint8 and d_proofs.dim() == 2
+        assert d_proofs.shape[1] == GROTH16_PROOF_BYTES, tuple(d_proofs.shape)
+        b = d_proofs.shape[0]
+        assert d_public.is_cuda and d_public.is_contiguous() and d_public.dtype == torch.uint8
+        assert tuple(d_public.shape) == (b, self.n_public, 32), tuple(d_public.shape)
+        s = stream if stream is not None else torch.cuda.current_stream(d_proofs.device)
+        out = torch.empty(b, dtype=torch.int32, device=d_proofs.device)
+        st = GwStatus()
+        with torch.cuda.device(d_proofs.device):
+            rc = r1cs_lib().gwb_groth16_verify_batch_device(self._h, d_proofs.data_ptr(), d_public.data_ptr() if self.n_public else None,
+                                                            self.n_public, b, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
+        _r1cs_check(rc, st)
+        if b:
+            out.record_stream(s)
+        return out
+
+    def verify(self, proof, public):
+        """snarkjs proof.json (dict) and public.json (list of decimal strings) -> True when VERIFY_VALID."""
+        pb = _from_json_g1(proof["pi_a"], "pi_a") + _from_json_g2(proof["pi_b"], "pi_b") + _from_json_g1(proof["pi_c"], "pi_c")
+        return int(self.verify_batch(np.frombuffer(pb, dtype=np.uint8).reshape(1, -1), [[int(x) for x in public]])[0]) == VERIFY_VALID
+
+
+def bn254_pairing_batch_device(d_g1, d_g2, stream=None):
+    """Measurement and test aid: device G1 points (uint8 cuda [n, 64]) and G2 points ([n, 128]), canonical, in their groups
+    (not validated) -> e(P_i, Q_i) as a uint8 cuda tensor [n, GT_BYTES].  Asynchronous on `stream` or the current stream."""
+    import torch
+    n = d_g1.shape[0]
+    assert tuple(d_g1.shape) == (n, 64) and tuple(d_g2.shape) == (n, 128)
+    assert d_g1.is_cuda and d_g2.is_cuda and d_g1.is_contiguous() and d_g2.is_contiguous()
+    s = stream if stream is not None else torch.cuda.current_stream(d_g1.device)
+    out = torch.empty((n, GT_BYTES), dtype=torch.uint8, device=d_g1.device)
+    st = GwStatus()
+    with torch.cuda.device(d_g1.device):
+        rc = r1cs_lib().gwb_bn254_pairing_batch_device(d_g1.data_ptr(), d_g2.data_ptr(), n, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
+    _r1cs_check(rc, st)
+    if n:
+        out.record_stream(s)
+    return out
 
 
 from . import graphgen  # noqa: E402,F401  (graph generator library on top of the C-ABI producer)
