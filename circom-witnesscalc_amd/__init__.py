@@ -83,7 +83,7 @@ EXPORTED_SYMBOLS = [
     "gwb_builder_witness", "gwb_builder_input_signal", "gwb_builder_node_count", "gwb_builder_finish",
     "gwb_ubench_modmul_block", "gwb_program_stats", "gwb_calc_witness_json_to_wtns", "gwb_model_class_cycles",
     "gwb_graphgen_bigint_class", "gwb_graphgen_rsa_long_div_class", "gwb_graph_op_histogram",
-    "gwb_kernel_source_hash", "gwb_rccl_unique_id", "gwb_rccl_comm_init", "gwb_rccl_comm_ranks", "gwb_rccl_comm_destroy",
+    "gwb_kernel_source_hash", "gwb_pack_schedule", "gwb_pack_schedule_of_blob", "gwb_rccl_unique_id", "gwb_rccl_comm_init", "gwb_rccl_comm_ranks", "gwb_rccl_comm_destroy",
 ]
 
 
@@ -158,6 +158,9 @@ def lib():
         L.gwb_model_class_cycles.argtypes = [ctypes.c_uint32]
         L.gwb_ubench_modmul_block.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
         L.gwb_program_stats.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ProgramStats)]
+        if hasattr(L, "gwb_pack_schedule"):  # (absent from an older build loaded through CWC_LIB_PATH for a same-box A/B)
+            L.gwb_pack_schedule.argtypes = [vp, ctypes.c_uint32, vp, sz, vp, sz, u32p, u32p, u32p, stp]
+            L.gwb_pack_schedule_of_blob.argtypes = [vp, sz, vp, sz, vp, sz, u32p, u32p, u32p, stp]
         L.gwb_calc_witness_json_to_wtns.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.POINTER(sz), vp, sz, ctypes.POINTER(E2eStats), stp]
         L.gwb_graph_pick_tile_width.restype = ctypes.c_uint32
         L.gwb_graph_pick_tile_width.argtypes = [vp, sz]
@@ -461,6 +464,8 @@ class Graph:
         res["_sections"] = {"MUL": tuple(int(x) for x in out[48:54]), "LIN": tuple(int(x) for x in out[56:62])}
         # the issue part of section 1 (reads, record refill, previous stores ISSUED; the rest of the section is the wait for the LDS reads)
         res["_issue_part"] = {"MUL": int(out[92]), "LIN": int(out[93])}
+        # the divider waves' inline pack (sampled divider waves): cycles spent in pack passes, passes
+        res["_pack"] = {"cycles": int(out[94]), "passes": int(out[95])}
         n = int(out[63])
         res["_waves"] = {"n": n, "max_cycles": int(out[54]), "min_cycles": (1 << 40) - int(out[55]) if n else 0,
                          "mean_cycles": int(out[62]) // n if n else 0}
@@ -477,11 +482,29 @@ class Graph:
                 "class_bundles": {CLASS_NAMES[c]: int(ps.class_bundles[c]) for c in range(n) if ps.class_bundles[c]},
                 "class_nodes": {CLASS_NAMES[c]: int(ps.class_nodes[c]) for c in range(n) if ps.class_nodes[c]}}
 
+    def pack_schedule(self, key):
+        """The pack schedule of the program for `key` (gwb_pack_schedule; host only): (pack_order, pack_ready, n_inline)."""
+        return _pack_schedule(lambda *a: lib().gwb_pack_schedule(self._h, key, *a))
+
     def last_timing(self):
         t = Timing()
         if lib().gwb_last_timing(self._h, ctypes.byref(t)) != 0:
             raise WitnessCalcError("gwb_last_timing failed")
         return {n: getattr(t, n) for n, _ in Timing._fields_}
+
+
+def _pack_schedule(call):
+    nw, nr, ni, st = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32(), GwStatus()
+    _check(call(None, 0, None, 0, ctypes.byref(nw), ctypes.byref(nr), ctypes.byref(ni), ctypes.byref(st)), st)
+    order, ready = np.zeros(nw.value, dtype=np.uint32), np.zeros(nr.value, dtype=np.uint32)
+    _check(call(order.ctypes.data, order.size, ready.ctypes.data, ready.size, ctypes.byref(nw), ctypes.byref(nr), ctypes.byref(ni), ctypes.byref(st)), st)
+    return order, ready, int(ni.value)
+
+
+def pack_schedule_of_blob(blob):
+    """The pack schedule a replica derives from an exported program (gwb_pack_schedule_of_blob; host only)."""
+    blob = bytes(blob)
+    return _pack_schedule(lambda *a: lib().gwb_pack_schedule_of_blob(blob, len(blob), *a))
 
 
 # -- R1CS satisfaction check (include/graph_witness_r1cs.h, libcwc_r1cs.so built from r1cs/) ------------------------------

@@ -42,6 +42,12 @@ struct InterpDims {
     // streams: interpreter wave w of a workgroup evaluates bundles [stream_first[s], stream_first[s] + stream_count[s]),
     // s = w % n_streams, of tile w / n_streams (program.hpp); with divider waves, divider d serves interpreter wave d
     uint32_t n_streams, stream_first[MAX_STREAMS], stream_count[MAX_STREAMS], stream_div_requests[MAX_STREAMS], stream_cref_first[MAX_STREAMS];
+    // inline pack (W == 1 instances, read by the divider branch alone): the divider wave converts and stores the first n_inline
+    // entries of the pack order between its requests (pack_schedule.cc); n_inline == 0: it serves requests only
+    uint4* pack_out;               // the launch's output rows
+    const uint2* pack_entries;     // {witness index, witness reference} in pack order, zero-padded by PACK_ENTRY_PAD entries
+    const uint32_t* pack_ready;    // [n_div_requests + 1] entries that may be packed once k posts have been seen
+    uint32_t n_inline, pack_mont, n_witness;
 };
 static const uint32_t ST_DIVIDER_TIMEOUT = 0x80000000u;  // internal: a mailbox wait gave up (never expected)
 static const uint32_t ST_SYNC_TIMEOUT = 0x40000000u;     // internal: the wait for stream 0's post gave up (never expected)
@@ -155,7 +161,81 @@ __global__ __launch_bounds__((W > 0 ? (W + 1) * PACK : PACK) * 64) void interp_k
             const uint32_t n_requests = NS > 1 ? p.stream_div_requests[first_w % NS] : p.n_div_requests;  // (streams: W = 1, its one interpreter's)
             uint32_t div_lanes_base = 0;  // (the requests of the streams in front of this one come first in div_lanes)
             for (uint32_t q = 0; NS > 1 && q < first_w % NS; ++q) div_lanes_base += p.stream_div_requests[q];
+            // ---- inline pack (W == 1, one stream): between requests this wave converts and stores witness rows of its tile, in
+            // the order and up to the counts of the pack schedule (pack_schedule.cc).  One pass = 64 lanes = G entries x T sets.
+            // VISIBILITY: pack_ready[k] counts the rows whose producing bundle lies in front of request k - 2 (a lag of one
+            // request).  This wave has seen the post of request k - 1; its interpreter issued that post in an iteration that
+            // began with the loop's counted wait (`s_waitcnt vmcnt(7)` at the top of every iteration, below), which retires
+            // every vector-memory operation issued two iterations earlier -- the delayed result stores of every bundle in
+            // front of request k - 2 among them, requests being at least two bundles apart (REQ, GET, REQ).  The rows are
+            // read with ordinary loads behind a workgroup-scope acquire: both waves share the CU's vector L1.
+            [[maybe_unused]] uint32_t pk_next = 0;  // entries packed so far (whole groups of G until the final drain)
+            [[maybe_unused]] uint2 pk_e0 = make_uint2(0u, 0u), pk_e1 = pk_e0;  // entries of the groups at pk_next and pk_next + G, this lane's
+            [[maybe_unused]] unsigned long long pk_cycles = 0, pk_passes = 0;
+            const bool inl = W == 1 && NS == 1 && p.n_inline > 0;
+            const char* const pk_tile = reinterpret_cast<const char*>(wst.base[first_tile / wst.tiles_per_chunk]) + (uint64_t)(first_tile % wst.tiles_per_chunk) * tile_bytes;
+            const uint32_t pk_set = first_tile * T + t;
+            auto pk_load = [&](const uint2& e, uint4& lo, uint4& hi) {  // the two halves of an entry's slot (REF_CANON, REF_CONST as in pack_kernel_v3)
+                const uint32_t ref = e.y & ~REF_CANON;
+                const uint32_t slot = (ref & REF_CONST) ? (ref & ~REF_CONST) : p.n_const + ref;
+                const uint4* q = reinterpret_cast<const uint4*>(pk_tile) + (size_t)slot * (2 * T);
+                lo = q[t];
+                hi = q[T + t];
+            };
+            auto pk_store = [&](const uint2& e, const uint4& lo, const uint4& hi, uint32_t limit) {
+                const bool valid = pk_next + j < limit && pk_set < batch, canon = (e.y & REF_CANON) != 0;
+                const Fr v = fr_from_u4(lo, hi);
+                Fr c = v;
+                if (p.pack_mont) {  // pack_form<true>
+                    if (wave_any(both(valid, canon))) c = u256_select(canon, fr_mul(v, fr_r2()), v);
+                } else {            // pack_form<false>
+                    if (wave_any(both(valid, !canon))) c = u256_select(canon, v, fr_from_mont(v));
+                }
+                if (valid) {
+                    uint4* o = p.pack_out + ((size_t)pk_set * p.n_witness + e.x) * 2;
+                    o[0] = make_uint4(c.v[0], c.v[1], c.v[2], c.v[3]);
+                    o[1] = make_uint4(c.v[4], c.v[5], c.v[6], c.v[7]);
+                }
+            };
+            // packs [pk_next, limit) until `need` posts have been seen: the posted word is read once per pass, a new post ends
+            // the packing behind the pass in hand (the request waits for one pass at most); the loads of the next pass are
+            // issued before the conversion of the current one
+            auto pk_run = [&](uint32_t limit, uint32_t need) {
+                if (pk_next >= limit) return;
+                unsigned long long t0 = 0;
+                if (PROF) t0 = __builtin_amdgcn_s_memtime();
+                uint4 lo, hi;
+                pk_load(pk_e0, lo, hi);
+                for (;;) {
+                    const uint32_t nb = pk_next + (uint32_t)G;
+                    const bool more = nb < limit && seq[first_w] < need;
+                    uint4 lo1 = lo, hi1 = hi;
+                    if (more) pk_load(pk_e1, lo1, hi1);
+                    const uint2 e2 = p.pack_entries[nb + (uint32_t)G + j];
+                    pk_store(pk_e0, lo, hi, limit);
+                    pk_next = nb;
+                    pk_e0 = pk_e1;
+                    pk_e1 = e2;
+                    if (PROF) ++pk_passes;
+                    if (!more) break;
+                    lo = lo1;
+                    hi = hi1;
+                }
+                if (PROF) pk_cycles += __builtin_amdgcn_s_memtime() - t0;
+            };
+            if constexpr (W == 1) {
+                if (inl) {
+                    pk_e0 = p.pack_entries[j];
+                    pk_e1 = p.pack_entries[(uint32_t)G + j];
+                }
+            }
             for (uint32_t k = 0; k < n_requests; ++k) {
+                if constexpr (W == 1) {
+                    if (inl) {  // k posts seen and served: the gap in front of request k
+                        const uint32_t lim = p.pack_ready[k] < p.n_inline ? p.pack_ready[k] : p.n_inline;
+                        pk_run(lim / (uint32_t)G * (uint32_t)G, k + 1);
+                    }
+                }
                 bool ok = true;
                 for (uint32_t w = 0; w < n_active; ++w) ok = ok && mbox_wait(seq + first_w + w, k + 1);
                 if (!ok) {
@@ -184,6 +264,15 @@ __global__ __launch_bounds__((W > 0 ? (W + 1) * PACK : PACK) * 64) void interp_k
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 if (lane == 0) seq[wave] = k + 1;  // (served word of divider d = seq[NW + d])
+            }
+            if constexpr (W == 1) {
+                if (inl) {  // the rest of its share; never waits for the interpreter's end (what is produced later is the pack kernel's)
+                    pk_run(p.pack_ready[n_requests] < p.n_inline ? p.pack_ready[n_requests] : p.n_inline, 0xffffffffu);
+                    if (PROF && lane == 0 && first_tile % 64u == 0) {
+                        atomicAdd(&prof[94], pk_cycles);
+                        atomicAdd(&prof[95], pk_passes);
+                    }
+                }
             }
             return;
         }
@@ -1191,10 +1280,11 @@ __device__ __forceinline__ Fr pack_form(const Fr& v, bool canon) {
 // the waves of a block: twice / four times the read requests for the same lines, 4.6 TB/s; CWC_PACK_V1=1 keeps it for A/B.)
 // MONT: the rows keep the interpreter's Montgomery form (x * 2^256 mod r) for a consumer that computes in it.
 template <bool MONT, int TT>
-__global__ __launch_bounds__(256) void pack_kernel(ProgramDev p, WsTable wst, uint4* __restrict__ out, uint32_t batch, uint32_t T_) {
+__global__ __launch_bounds__(256) void pack_kernel(ProgramDev p, WsTable wst, uint4* __restrict__ out, uint32_t batch, uint32_t T_, uint32_t first) {
     const uint32_t T = TT ? (uint32_t)TT : T_;
-    const uint32_t w = blockIdx.x * 256u + threadIdx.x;
-    if (w >= p.n_witness) return;
+    const uint32_t wi = first + blockIdx.x * 256u + threadIdx.x;
+    if (wi >= p.n_witness) return;
+    const uint32_t w = first ? p.pack_order[wi] : wi;  // (first > 0: the rest of the pack order behind the divider waves' share)
     const uint32_t ref_raw = p.witness_refs[w];
     const bool canon = (ref_raw & REF_CANON) != 0;  // the slot holds the canonical integer (representation inference, compile.cc)
     const uint32_t ref = ref_raw & ~REF_CANON;
@@ -1237,10 +1327,11 @@ __global__ __launch_bounds__(256) void pack_kernel(ProgramDev p, WsTable wst, ui
 // touches 64 / T slots, each in runs of 16 T contiguous bytes (the thread-per-slot shape above makes every lane fetch a
 // different line: 64 lines per instruction at T = 4), and a wave's stores are 64 / T consecutive rows of 32 bytes per set.
 template <bool MONT, int TT>
-__global__ __launch_bounds__(256) void pack_kernel_v3(ProgramDev p, WsTable wst, uint4* __restrict__ out, uint32_t batch) {
+__global__ __launch_bounds__(256) void pack_kernel_v3(ProgramDev p, WsTable wst, uint4* __restrict__ out, uint32_t batch, uint32_t first) {
     constexpr uint32_t T = TT, WPB = 256u / T;
-    const uint32_t t = threadIdx.x % T, w = blockIdx.x * WPB + threadIdx.x / T;
-    if (w >= p.n_witness) return;
+    const uint32_t t = threadIdx.x % T, wi = first + blockIdx.x * WPB + threadIdx.x / T;
+    if (wi >= p.n_witness) return;
+    const uint32_t w = first ? p.pack_order[wi] : wi;  // (first > 0: the rest of the pack order behind the divider waves' share)
     const uint32_t ref_raw = p.witness_refs[w];
     const bool canon = (ref_raw & REF_CANON) != 0;
     const uint32_t ref = ref_raw & ~REF_CANON;
@@ -1261,9 +1352,10 @@ __global__ __launch_bounds__(256) void pack_kernel_v3(ProgramDev p, WsTable wst,
 
 // (round-1 shape: block = 64 witness indices x min(T, 4) sets of one tile; what tiles wider than 4 sets use)
 template <bool MONT>
-__global__ __launch_bounds__(256) void pack_kernel_v1(ProgramDev p, WsTable wst, uint4* __restrict__ out, uint32_t batch, uint32_t T) {
-    const uint32_t w = blockIdx.x * 64u + threadIdx.x;
-    if (w >= p.n_witness) return;
+__global__ __launch_bounds__(256) void pack_kernel_v1(ProgramDev p, WsTable wst, uint4* __restrict__ out, uint32_t batch, uint32_t T, uint32_t first) {
+    const uint32_t wi = first + blockIdx.x * 64u + threadIdx.x;
+    if (wi >= p.n_witness) return;
+    const uint32_t w = first ? p.pack_order[wi] : wi;
     const uint32_t ref_raw = p.witness_refs[w];
     const bool canon = (ref_raw & REF_CANON) != 0;
     const uint32_t ref = ref_raw & ~REF_CANON;
@@ -1287,13 +1379,17 @@ __global__ __launch_bounds__(256) void pack_kernel_v1(ProgramDev p, WsTable wst,
 
 // ---- launchers (called from pipeline.cc) -----------------------------------------------------------
 hipError_t launch_interp(uint32_t T, uint32_t W, uint32_t pack, uint32_t n_div_requests, const uint32_t* div_lanes, const ProgramDev& p,
-                         const WsTable& wst, const void* inputs, uint32_t* status, uint32_t batch, hipStream_t stream, unsigned long long* prof) {
+                         const WsTable& wst, const void* inputs, uint32_t* status, uint32_t batch, hipStream_t stream, unsigned long long* prof,
+                         void* out, uint32_t n_inline, bool montgomery) {
     const uint32_t tiles = (batch + T - 1) / T, nw = (W ? W : 1u) * pack, ns = p.n_streams ? p.n_streams : 1u;
     if (nw == 0 || nw % ns != 0 || (ns > 1 && W > 1)) return hipErrorInvalidValue;
     const uint32_t tiles_per_wg = nw / ns;
     dim3 grid((tiles + tiles_per_wg - 1) / tiles_per_wg), block((W ? (W + 1) * pack : pack) * 64);
     const uint4* in = (const uint4*)inputs;
-    InterpDims dims{p.n_bundles, p.n_slots, p.n_inputs, batch, p.n_const, n_div_requests, p.trash_off, div_lanes, ns, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    InterpDims dims{p.n_bundles, p.n_slots, p.n_inputs, batch, p.n_const, n_div_requests, p.trash_off, div_lanes, ns, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0},
+                    (uint4*)out, reinterpret_cast<const uint2*>(p.pack_entries), p.pack_ready, 0u, montgomery ? 1u : 0u, p.n_witness};
+    // the divider waves' share of the pack order: programs with one divider wave per interpreter and one stream only (pack_schedule.cc)
+    if (W == 1 && ns == 1 && out && p.pack_entries && p.pack_ready) dims.n_inline = n_inline < p.n_ready_last ? n_inline : p.n_ready_last;
     for (uint32_t s = 0; s < MAX_STREAMS; ++s) {
         dims.stream_first[s] = p.stream_first[s];
         dims.stream_count[s] = p.stream_count[s];
@@ -1393,21 +1489,22 @@ hipError_t launch_fill_consts(uint32_t T, const ProgramDev& p, const WsTable& ws
     return hipGetLastError();
 }
 
-hipError_t launch_pack(uint32_t T, const ProgramDev& p, const WsTable& wst, void* out, uint32_t batch, hipStream_t stream, bool montgomery) {
-    if (p.n_witness == 0 || batch == 0) return hipSuccess;
+hipError_t launch_pack(uint32_t T, const ProgramDev& p, const WsTable& wst, void* out, uint32_t batch, hipStream_t stream, bool montgomery, uint32_t first) {
+    if (p.n_witness == 0 || batch == 0 || first >= p.n_witness) return hipSuccess;
+    const uint32_t count = p.n_witness - first;  // (first == 0: every witness index, today's grid)
     const uint32_t n_tiles = (batch + T - 1) / T;
     static const bool v1 = getenv("CWC_PACK_V1") != nullptr;
     if (v1 || T > 4) {  // (tiles of 8 sets and more: a thread walking all sets of its slot serialises 8..64 conversions -- 22.6 ms
                         // against 9.5 ms for the 8192-set pack at T = 8; the sets of a slot stay spread over the waves of a block)
-        dim3 grid((p.n_witness + 63) / 64, n_tiles < 32768u ? n_tiles : 32768u), block(64, T < 4 ? T : 4);
-        if (montgomery) pack_kernel_v1<true><<<grid, block, 0, stream>>>(p, wst, (uint4*)out, batch, T);
-        else pack_kernel_v1<false><<<grid, block, 0, stream>>>(p, wst, (uint4*)out, batch, T);
+        dim3 grid((count + 63) / 64, n_tiles < 32768u ? n_tiles : 32768u), block(64, T < 4 ? T : 4);
+        if (montgomery) pack_kernel_v1<true><<<grid, block, 0, stream>>>(p, wst, (uint4*)out, batch, T, first);
+        else pack_kernel_v1<false><<<grid, block, 0, stream>>>(p, wst, (uint4*)out, batch, T, first);
         return hipGetLastError();
     }
     static const int pack_shape = getenv("CWC_PACK") ? atoi(getenv("CWC_PACK")) : 3;  // (2: one thread per slot, the round-2 shape, for A/B)
     if (pack_shape == 3 && T >= 2) {  // (T = 1: the two shapes are the same kernel)
-        dim3 grid3((p.n_witness + 256 / T - 1) / (256 / T), n_tiles < 32768u ? n_tiles : 32768u), block3(256);
-#define CWC_PACK3(MM, TT) pack_kernel_v3<MM, TT><<<grid3, block3, 0, stream>>>(p, wst, (uint4*)out, batch)
+        dim3 grid3((count + 256 / T - 1) / (256 / T), n_tiles < 32768u ? n_tiles : 32768u), block3(256);
+#define CWC_PACK3(MM, TT) pack_kernel_v3<MM, TT><<<grid3, block3, 0, stream>>>(p, wst, (uint4*)out, batch, first)
         if (montgomery) {
             if (T == 2) CWC_PACK3(true, 2); else CWC_PACK3(true, 4);
         } else {
@@ -1416,8 +1513,8 @@ hipError_t launch_pack(uint32_t T, const ProgramDev& p, const WsTable& wst, void
 #undef CWC_PACK3
         return hipGetLastError();
     }
-    dim3 grid((p.n_witness + 255) / 256, n_tiles < 32768u ? n_tiles : 32768u), block(256);
-#define CWC_PACK(MM, TT) pack_kernel<MM, TT><<<grid, block, 0, stream>>>(p, wst, (uint4*)out, batch, T)
+    dim3 grid((count + 255) / 256, n_tiles < 32768u ? n_tiles : 32768u), block(256);
+#define CWC_PACK(MM, TT) pack_kernel<MM, TT><<<grid, block, 0, stream>>>(p, wst, (uint4*)out, batch, T, first)
     if (montgomery) {
         if (T == 1) CWC_PACK(true, 1); else if (T == 2) CWC_PACK(true, 2); else CWC_PACK(true, 4);
     } else {

@@ -27,7 +27,13 @@ std::string upload_program(DeviceProgram& dp) {
     // (the interpreter reads the header two bundles ahead without a clamp: 16 bytes of zero padding behind the array)
     const size_t o_hdr = 0, o_recs = o_hdr + al(p.hdr.size() * 4 + 16), o_crefs = o_recs + al(p.recs.size() * 4 + REC_AHEAD * 1024u),  // (records are staged REC_AHEAD bundles ahead, unclamped)
                  o_consts = o_crefs + al(p.crefs.size() * 4 + 256), o_wit = o_consts + al(p.consts.size() * 4 + 32),
-                 o_div = o_wit + al(p.witness_refs.size() * 4 + 4), total = o_div + al(p.div_lanes.size() * 4 + 4);
+                 o_div = o_wit + al(p.witness_refs.size() * 4 + 4), o_order = o_div + al(p.div_lanes.size() * 4 + 4),
+                 o_entries = o_order + al(p.witness_refs.size() * 4 + 4), o_ready = o_entries + al((p.witness_refs.size() + PACK_ENTRY_PAD) * 8),
+                 total = o_ready + al(((size_t)p.n_div_requests + 1) * 4);
+    {   // the pack schedule (pack_schedule.cc): derived here so that compiled, imported and cached programs all get one
+        const std::string serr = make_pack_schedule(p, dp.sched);
+        if (!serr.empty()) return serr;
+    }
     HIP_TRY(hipMalloc(&dp.d_blob, total));
     char* d = (char*)dp.d_blob;
     HIP_TRY(hipMemset(d, 0, total));
@@ -63,6 +69,22 @@ std::string upload_program(DeviceProgram& dp) {
                 dp.dev.has_fused = 3u;
                 break;
             }
+    {
+        const PackSchedule& sc = dp.sched;
+        std::vector<uint32_t> entries(sc.order.size() * 2);
+        for (size_t i = 0; i < sc.order.size(); ++i) {
+            entries[2 * i] = sc.order[i];
+            entries[2 * i + 1] = p.witness_refs[sc.order[i]];
+        }
+        if (!sc.order.empty()) HIP_TRY(hipMemcpy(d + o_order, sc.order.data(), sc.order.size() * 4, hipMemcpyHostToDevice));
+        if (!entries.empty()) HIP_TRY(hipMemcpy(d + o_entries, entries.data(), entries.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d + o_ready, sc.ready.data(), sc.ready.size() * 4, hipMemcpyHostToDevice));
+        dp.dev.pack_order = (const uint32_t*)(d + o_order);
+        dp.dev.pack_entries = (const uint32_t*)(d + o_entries);
+        dp.dev.pack_ready = (const uint32_t*)(d + o_ready);
+        dp.dev.n_inline = sc.n_inline;
+        dp.dev.n_ready_last = sc.ready.back();
+    }
     dp.dev.n_streams = p.n_streams;
     for (uint32_t s = 0; s < MAX_STREAMS; ++s) {
         dp.dev.stream_first[s] = p.stream_first[s];
@@ -396,6 +418,7 @@ std::string get_program(gwb_graph* g, uint32_t key, DeviceProgram** out) {
     return "";
 }
 
+static const bool kInlinePackDefault = true;  // (same-box A/B: profiles/inline_pack_ab.txt)
 std::string run_device(gwb_graph* g, const void* d_inputs, size_t batch, void* d_witness, uint32_t* d_status,
                        hipStream_t stream, bool montgomery, hipEvent_t done_event) {
     if (batch == 0) return "";
@@ -486,6 +509,11 @@ std::string run_device(gwb_graph* g, const void* d_inputs, size_t batch, void* d
     g->timing.streams = p.n_streams;
     g->timing.n_bundles = p.n_bundles;
     g->timing.n_slots = p.n_slots;
+    // CWC_INLINE_PACK (read per call: one process can run both paths): 0 the pack kernel packs every row, 1 the divider
+    // waves take the schedule's prefix, 2 everything that is ever ready in front of the last request (tests, measurements)
+    uint32_t n_inline = kInlinePackDefault ? dp->dev.n_inline : 0u;
+    if (const char* e = getenv("CWC_INLINE_PACK")) n_inline = atoi(e) >= 2 ? dp->dev.n_ready_last : atoi(e) == 1 ? dp->dev.n_inline : 0u;
+    if (const char* e = getenv("CWC_INLINE_PACK_ROWS")) n_inline = std::min<uint32_t>(n_inline, (uint32_t)atol(e));  // (measurements: a cap on the divider waves' share)
     const size_t launch_sets = per_launch * chunk_sets;
     for (size_t s0 = 0; s0 < batch; s0 += launch_sets) {
         const uint32_t nb = (uint32_t)((batch - s0) < launch_sets ? (batch - s0) : launch_sets);
@@ -509,9 +537,11 @@ std::string run_device(gwb_graph* g, const void* d_inputs, size_t batch, void* d
         }
         g->pending.push_back(gwb_graph::ChunkEvents{e0, e1, e2});  // (owned by the handle from here on, also on an early return)
         HIP_TRY(hipEventRecord(e0, stream));
-        HIP_TRY(launch_interp(T, p.divider, waves_per_workgroup(p.divider, (nb + T - 1) / T, p.n_streams), p.n_div_requests, dp->dev.div_lanes, dp->dev, wst, (const char*)d_inputs + s0 * p.n_inputs * 32, d_status + s0, nb, stream, g->d_prof));
-        HIP_TRY(hipEventRecord(e1, stream));
-        HIP_TRY(launch_pack(T, dp->dev, wst, (char*)d_witness + s0 * (size_t)p.n_witness * 32, nb, stream, montgomery));
+        void* const out = (char*)d_witness + s0 * (size_t)p.n_witness * 32;
+        HIP_TRY(launch_interp(T, p.divider, waves_per_workgroup(p.divider, (nb + T - 1) / T, p.n_streams), p.n_div_requests, dp->dev.div_lanes, dp->dev, wst, (const char*)d_inputs + s0 * p.n_inputs * 32, d_status + s0, nb, stream, g->d_prof,
+                              out, n_inline, montgomery));
+        HIP_TRY(hipEventRecord(e1, stream));  // (interp_ms includes the rows the divider waves packed, pack_ms is the rest's)
+        HIP_TRY(launch_pack(T, dp->dev, wst, out, nb, stream, montgomery, n_inline));
         HIP_TRY(hipEventRecord(e2, stream));
         g->last_call_launches++;
         g->timing.n_launches++;

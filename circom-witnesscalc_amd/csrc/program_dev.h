@@ -178,7 +178,13 @@ struct ProgramDev {
     uint32_t trash_off;            // where results without a slot go: OFF_NOWHERE, or (programs compiled with CWC_NOWHERE=0) the tile's trash slot
     uint32_t has_fused;            // 1: the program has C_MULF bundles, 2: C_SCAN bundles, 3: C_SCAN bundles of the wide-register kinds (the interpreter instance with their path is launched)
     uint32_t n_streams, stream_first[4], stream_count[4], stream_div_requests[4], stream_cref_first[4];  // (program.hpp; MAX_STREAMS entries)
+    // pack schedule (pack_schedule.cc; programs with one divider wave per interpreter and one stream, else n_inline = 0)
+    const uint32_t* pack_order;    // [n_witness] witness indices in the order they become ready
+    const uint32_t* pack_entries;  // [n_witness + padding][2] the same order as {witness index, witness reference}: one load per entry for the divider wave
+    const uint32_t* pack_ready;    // [n_div_requests + 1] entries that may be packed once k posts have been seen
+    uint32_t n_inline, n_ready_last;  // the divider wave's prefix of the order; pack_ready[n_div_requests]
 };
+static const uint32_t PACK_ENTRY_PAD = 192;  // entries of zero padding behind pack_entries (the divider wave reads two groups ahead, unclamped)
 
 // A launch covers up to WS_MAX_CHUNKS separately allocated workspaces: tile i lives in chunk i / tiles_per_chunk.
 static const uint32_t WS_MAX_CHUNKS = 32;

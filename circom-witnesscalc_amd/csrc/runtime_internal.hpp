@@ -34,9 +34,13 @@
 #include "program.hpp"
 
 namespace cwc {
+// n_inline > 0 (programs with one divider wave per interpreter, one stream): the divider waves convert and store the first n_inline
+// entries of the program's pack order into `out` between their requests; launch_pack(..., first = n_inline) takes the rest.
 hipError_t launch_interp(uint32_t T, uint32_t W, uint32_t pack, uint32_t n_div_requests, const uint32_t* div_lanes, const ProgramDev& p,
-                         const WsTable& wst, const void* inputs, uint32_t* status, uint32_t batch, hipStream_t stream, unsigned long long* prof);
-hipError_t launch_pack(uint32_t T, const ProgramDev& p, const WsTable& wst, void* out, uint32_t batch, hipStream_t stream, bool montgomery);
+                         const WsTable& wst, const void* inputs, uint32_t* status, uint32_t batch, hipStream_t stream, unsigned long long* prof,
+                         void* out = nullptr, uint32_t n_inline = 0, bool montgomery = false);
+// first > 0: entries [first, n_witness) of the program's pack order; 0: every witness index in its own order (no indirection)
+hipError_t launch_pack(uint32_t T, const ProgramDev& p, const WsTable& wst, void* out, uint32_t batch, hipStream_t stream, bool montgomery, uint32_t first = 0);
 hipError_t launch_modmul_ubench(uint32_t n_cus, uint32_t waves_per_simd, uint32_t iters, uint32_t* sink, hipStream_t stream, bool block_multiplier);
 hipError_t launch_fill_consts(uint32_t T, const ProgramDev& p, const WsTable& wst, uint32_t n_tiles, hipStream_t stream);
 hipError_t launch_warm(hipStream_t stream);
@@ -68,8 +72,17 @@ int guarded(gw_status_t* st, F&& f) {
         if (e_ != hipSuccess) return std::string(#expr) + ": " + hipGetErrorString(e_);    \
     } while (0)
 
+// pack_schedule.cc: which witness rows the divider wave may convert and store while the interpreter runs
+struct PackSchedule {
+    std::vector<uint32_t> order;  // [n_witness] witness indices by the request at which they are ready, then by index
+    std::vector<uint32_t> ready;  // [n_div_requests + 1] ready[k]: entries of `order` that may be packed once k posts have been seen
+    uint32_t n_inline = 0;        // the prefix of `order` the divider wave takes (0: the program is out of scope)
+};
+std::string make_pack_schedule(const Program& p, PackSchedule& out);
+
 struct DeviceProgram {
     Program host;
+    PackSchedule sched;
     void* d_blob = nullptr;
     ProgramDev dev{};
     DeviceProgram() = default;

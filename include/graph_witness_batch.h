@@ -235,6 +235,20 @@ typedef struct {
 } gwb_program_stats_t;
 int gwb_program_stats(gwb_graph_t *g, uint32_t program_key, gwb_program_stats_t *out);
 
+/* The pack schedule of a compiled program (program key as above; the program is compiled on the host if it has not been yet,
+ * no device is touched): the order in which witness rows become final while the interpreter runs, and how much of it the
+ * divider waves of a program with one divider wave per interpreter and one stream convert and store between their requests
+ * (CWC_INLINE_PACK=0 leaves every row to the pack kernel).
+ *   pack_order[n_witness]            witness indices, by the division request at which their row is ready, then by index
+ *   pack_ready[n_div_requests + 1]   pack_ready[k]: entries of pack_order that may be packed once k request posts have been seen
+ *   n_inline                         the prefix of pack_order the divider waves take (0: the program is out of scope)
+ * The counts are always returned; an array is filled when its capacity (in entries) is large enough. */
+int gwb_pack_schedule(gwb_graph_t *g, uint32_t program_key, uint32_t *pack_order, size_t order_cap, uint32_t *pack_ready, size_t ready_cap,
+                      uint32_t *n_witness, uint32_t *n_ready, uint32_t *n_inline, gw_status_t *status);
+/* ... of an exported program (gwb_graph_export): what a replica that imports the blob derives for itself. */
+int gwb_pack_schedule_of_blob(const void *blob, size_t blob_len, uint32_t *pack_order, size_t order_cap, uint32_t *pack_ready, size_t ready_cap,
+                              uint32_t *n_witness, uint32_t *n_ready, uint32_t *n_inline, gw_status_t *status);
+
 /* `.wtns` framing of one witness row (wtns_from_witness, src/lib.rs:114-123): out holds gwb_wtns_size bytes. */
 size_t gwb_wtns_size(size_t n_witness);
 int gwb_wtns_from_witness(const void *witness_row, size_t n_witness, void *out);

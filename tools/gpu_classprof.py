@@ -42,9 +42,12 @@ for tw in [int(x) for x in os.environ.get("PROBE_T", "1,4,64").split(",")]:
     issue_part = prof.pop("_issue_part", {})
     scan_kinds = prof.pop("_scan_kinds")
     wv = prof.pop("_waves")
+    pack = prof.pop("_pack", {"cycles": 0, "passes": 0})
     tot = sum(v[0] for v in prof.values())
     print("T=%d%s B=%d product interp %.1f ms; stamped build: sampled waves=%d total cycles/wave %.3g" % (tw & 0xff, " + divider wave" if tw & 0x100 else "", B, t["interp_ms"], nw, tot / nw))
     print("   interpreter waves %d: loop cycles min %.3g mean %.3g max %.3g" % (wv["n"], wv["min_cycles"], wv["mean_cycles"], wv["max_cycles"]))
+    if pack["passes"]:  # (the divider waves' inline pack, CWC_INLINE_PACK: what pack_schedule.cc's kCyclesPackPass is set from)
+        print("   inline pack: passes/divider wave %d  cycles/pass %.0f  (program's n_inline %d of %d rows)" % (pack["passes"] // nw, pack["cycles"] / pack["passes"], g.pack_schedule(tw)[2], g.n_witness))
     for k, (cyc, _a, _b, n) in prof.items():
         if n:
             print("   %-8s bundles/wave %7d  cycles/bundle %8.0f  share %.1f%%" % (k, n // nw, cyc / n, 100.0 * cyc / tot))
