@@ -84,6 +84,7 @@ EXPORTED_SYMBOLS = [
     "gwb_ubench_modmul_block", "gwb_program_stats", "gwb_calc_witness_json_to_wtns", "gwb_model_class_cycles",
     "gwb_graphgen_bigint_class", "gwb_graphgen_rsa_long_div_class", "gwb_graph_op_histogram",
     "gwb_kernel_source_hash", "gwb_pack_schedule", "gwb_pack_schedule_of_blob", "gwb_rccl_unique_id", "gwb_rccl_comm_init", "gwb_rccl_comm_ranks", "gwb_rccl_comm_destroy",
+    "gwb_wave_census",
 ]
 
 
@@ -146,6 +147,8 @@ def lib():
             L.gwb_graphgen_rsa_long_div_class.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
             L.gwb_graph_op_histogram.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), sz]
         L.gwb_profile_classes.argtypes = [vp, vp, sz, vp, vp, vp, stp]
+        if hasattr(L, "gwb_wave_census"):  # (absent from an older build loaded through CWC_LIB_PATH for a same-box A/B)
+            L.gwb_wave_census.argtypes = [vp, vp, sz, vp, vp, vp, sz, stp]
         L.gwb_inputs_from_json_batch.argtypes = [vp, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz), stp]
         L.gwb_wtns_save_batch.argtypes = [vp, sz, sz, ctypes.c_char_p, stp]
         L.gwb_calc_witness_batch_handoff.argtypes = [vp, vp, sz, vp, vp, ctypes.POINTER(Handoff), stp]
@@ -469,6 +472,25 @@ class Graph:
         n = int(out[63])
         res["_waves"] = {"n": n, "max_cycles": int(out[54]), "min_cycles": (1 << 40) - int(out[55]) if n else 0,
                          "mean_cycles": int(out[62]) // n if n else 0}
+        return res
+
+    def wave_census(self, d_inputs, d_witness, d_status):
+        """Diagnostic stamped build (gwb_wave_census): one record per wave of the batch's last interpreter launch that started --
+        {"workgroup", "wave" (of the workgroup), "xcc", "se", "sh", "cu", "simd", "divider", "stream", "has_tile", "start", "end"}
+        (s_memtime; end 0: the wave had nothing to do).  At most the launch's first 8192 waves."""
+        out = np.zeros(3 * 8192, dtype=np.uint64)
+        st = GwStatus()
+        rc = lib().gwb_wave_census(self._h, d_inputs.data_ptr(), d_inputs.shape[0], d_witness.data_ptr(),
+                                   d_status.data_ptr(), out.ctypes.data, out.size, ctypes.byref(st))
+        _check(rc, st)
+        rec = out.reshape(-1, 3)
+        idx = [i for i in range(rec.shape[0]) if rec[i, 1]]
+        res = []
+        for i in idx:
+            w0 = int(rec[i, 0])
+            role, wpw = (w0 >> 40) & 255, (w0 >> 48) & 255  # (wpw: waves per workgroup)
+            res.append({"workgroup": i // wpw, "wave": i % wpw, "xcc": (w0 >> 32) & 15, "se": (w0 >> 13) & 7, "sh": (w0 >> 12) & 1, "cu": (w0 >> 8) & 15, "simd": (w0 >> 4) & 3,
+                        "divider": role & 1, "stream": (role >> 1) & 7, "has_tile": (role >> 4) & 1, "start": int(rec[i, 1]), "end": int(rec[i, 2])})
         return res
 
     def program_stats(self, key=0):

@@ -725,29 +725,52 @@ int gwb_timing_history(gwb_graph_t* g, size_t max_launches, float* interp_ms, fl
     return 0;
 }
 
-int gwb_profile_classes(gwb_graph_t* g, const void* d_inputs, size_t batch, void* d_witness, uint32_t* d_set_status,
-                        uint64_t* out36, gw_status_t* status) {
-    return guarded(status, [&]() -> int {
-    // Diagnostic: one batch through the stamped interpreter build; out36[class*4 + {load, compute, store, count}]
-    // in shader cycles, summed over the sampled waves (lane 0 of every 64th tile).
-    if (!g || !out36) return fail(status, "null argument");
+// One batch through the stamped interpreter instances (diagnostic library): the counters (PROF_WORDS words) and / or the wave
+// census (CENSUS_MAX_WAVES records of CENSUS_WORDS words, program_dev.h) of its last launch.  The device buffer always holds both:
+// the stamped instances write both.
+static int run_stamped(gwb_graph_t* g, const void* d_inputs, size_t batch, void* d_witness, uint32_t* d_set_status, uint64_t* counters,
+                       uint64_t* census, gw_status_t* status) {
     if (!gwb_kernels_have_diagnostics())
         return fail(status, "class profiling needs the diagnostic library (make -C circom-witnesscalc_amd/csrc diag; load it with CWC_LIB_PATH=<path of "
                             "libcircom_witnesscalc_amd_diag.so>): the product library carries no stamped interpreter instances");
     std::lock_guard<std::mutex> lk(g->mu);
     std::string err = check_device();
     if (!err.empty()) return fail(status, err);
+    const size_t census_bytes = (size_t)CENSUS_MAX_WAVES * CENSUS_WORDS * 8, bytes = PROF_WORDS * 8 + census_bytes;
     unsigned long long* d = nullptr;
-    if (hipMalloc(&d, 96 * 8) != hipSuccess || hipMemset(d, 0, 96 * 8) != hipSuccess) return fail(status, "hipMalloc failed");
+    if (hipMalloc(&d, bytes) != hipSuccess) return fail(status, "hipMalloc failed");
+    if (hipMemset(d, 0, bytes) != hipSuccess) {
+        (void)hipFree(d);
+        return fail(status, "hipMemset failed");
+    }
     g->d_prof = d;
     err = run_device(g, d_inputs, batch, d_witness, d_set_status, nullptr);
     g->d_prof = nullptr;
     if (err.empty() && hipDeviceSynchronize() != hipSuccess) err = "hipDeviceSynchronize failed";
-    if (err.empty() && hipMemcpy(out36, d, 96 * 8, hipMemcpyDeviceToHost) != hipSuccess) err = "hipMemcpy failed";
+    if (err.empty() && counters && hipMemcpy(counters, d, PROF_WORDS * 8, hipMemcpyDeviceToHost) != hipSuccess) err = "hipMemcpy failed";
+    if (err.empty() && census && hipMemcpy(census, d + PROF_WORDS, census_bytes, hipMemcpyDeviceToHost) != hipSuccess) err = "hipMemcpy failed";
     (void)hipFree(d);
     if (!err.empty()) return fail(status, err);
     set_status(status, OK, "");
     return 0;
+}
+
+int gwb_profile_classes(gwb_graph_t* g, const void* d_inputs, size_t batch, void* d_witness, uint32_t* d_set_status,
+                        uint64_t* out36, gw_status_t* status) {
+    return guarded(status, [&]() -> int {
+    // Diagnostic: one batch through the stamped interpreter build; out36[class*4 + {load, compute, store, count}]
+    // in shader cycles, summed over the sampled waves (lane 0 of every 64th tile).
+    if (!g || !out36) return fail(status, "null argument");
+    return run_stamped(g, d_inputs, batch, d_witness, d_set_status, out36, nullptr, status);
+    });
+}
+
+int gwb_wave_census(gwb_graph_t* g, const void* d_inputs, size_t batch, void* d_witness, uint32_t* d_set_status,
+                    uint64_t* out, size_t out_words, gw_status_t* status) {
+    return guarded(status, [&]() -> int {
+    if (!g || !out) return fail(status, "null argument");
+    if (out_words < (size_t)CENSUS_MAX_WAVES * CENSUS_WORDS) return fail(status, "gwb_wave_census: the output buffer is too small");
+    return run_stamped(g, d_inputs, batch, d_witness, d_set_status, nullptr, out, status);
     });
 }
 

@@ -120,6 +120,22 @@ __global__ __launch_bounds__((W > 0 ? (W + 1) * PACK : PACK) * 64) void interp_k
     const uint32_t tile = tile_raw < n_tiles ? tile_raw : n_tiles - 1;  // (divider wave / absent interpreters: any valid tile)
     const uint32_t set = tile * T + t;
     const uint32_t set_c = set < batch ? set : batch - 1;  // padded lanes of the last tile re-evaluate a real set
+    // Diagnostic build, wave census (program_dev.h CENSUS_*, gwb_wave_census): where this wave sits (HW_ID: SIMD, CU, SH, SE; XCC_ID)
+    // and when it starts and ends, written by lane 0 with ordinary stores.  Waves without work record their start only.
+    [[maybe_unused]] auto census_slot = [&]() -> unsigned long long* {
+        const uint32_t wv = blockIdx.x * (blockDim.x >> 6) + wave;
+        return lane == 0 && wv < CENSUS_MAX_WAVES ? prof + PROF_WORDS + CENSUS_WORDS * wv : nullptr;
+    };
+    if constexpr (PROF) {
+        if (unsigned long long* c = census_slot()) {
+            const uint32_t w_of = wave < NW ? wave : (wave - NW) * WD;  // (a divider wave: its first interpreter)
+            const uint32_t has_tile = blockIdx.x * (NW / NS) + w_of / NS < n_tiles ? 1u : 0u;
+            const unsigned long long role = (wave >= NW ? 1u : 0u) | (w_of % NS) << 1 | has_tile << 4 | (blockDim.x >> 6) << 8;
+            constexpr int HWREG_HW_ID = 4 | 31 << 11, HWREG_XCC_ID = 20 | 31 << 11;  // s_getreg_b32 hwreg(id, 0, 32)
+            c[0] = (unsigned long long)__builtin_amdgcn_s_getreg(HWREG_HW_ID) | (unsigned long long)(__builtin_amdgcn_s_getreg(HWREG_XCC_ID) & 15u) << 32 | role << 40;
+            c[1] = __builtin_amdgcn_s_memtime();
+        }
+    }
     // One buffer descriptor per tile: every operand / destination is a 32-bit tile-relative byte offset.
     const uint64_t tile_bytes = ws_tile_bytes(p.n_const, p.n_slots, T);
     const uint32_t chunk = tile / wst.tiles_per_chunk, tile_in_chunk = tile % wst.tiles_per_chunk;
@@ -273,6 +289,9 @@ __global__ __launch_bounds__((W > 0 ? (W + 1) * PACK : PACK) * 64) void interp_k
                         atomicAdd(&prof[95], pk_passes);
                     }
                 }
+            }
+            if constexpr (PROF) {
+                if (unsigned long long* c = census_slot()) c[2] = __builtin_amdgcn_s_memtime();
             }
             return;
         }
@@ -1227,6 +1246,9 @@ __global__ __launch_bounds__((W > 0 ? (W + 1) * PACK : PACK) * 64) void interp_k
         atomicMax(&prof[55], (1ull << 40) - cyc);
         atomicAdd(&prof[62], cyc);
         atomicAdd(&prof[63], 1ull);
+    }
+    if constexpr (PROF) {
+        if (unsigned long long* c = census_slot()) c[2] = __builtin_amdgcn_s_memtime();
     }
     if (PROF && lane == 0 && (tile % 64u) == 0u) {
 #pragma unroll

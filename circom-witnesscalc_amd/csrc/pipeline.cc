@@ -95,11 +95,25 @@ std::string upload_program(DeviceProgram& dp) {
     return "";
 }
 
+// two-stream programs with divider waves: are two tiles one workgroup of eight waves? (see waves_per_workgroup)
+static bool stream_pair_workgroups(uint32_t divider, uint64_t tiles, uint32_t streams) {
+    if (streams != 2 || divider != 1) return false;
+    if (const char* e = getenv("CWC_STREAM_TILES_PER_WORKGROUP")) return atoi(e) == 2;
+    return tiles > 256;
+}
 // Interpreter waves per workgroup for programs without a divider wave: workgroups of four deal the waves evenly round
 // the four SIMDs of a CU (kernels.hip); below one wave per SIMD of the chip single-wave workgroups spread further.
 // CWC_WAVES_PER_WORKGROUP (1 or 4) overrides.
 uint32_t waves_per_workgroup(uint32_t divider, uint64_t tiles, uint32_t streams) {
-    // programs of several streams: the streams of a tile (and their divider waves) are one workgroup
+    // Two streams with their divider waves, more tiles than CUs: two tiles are ONE workgroup of eight waves, [A.s0, A.s1, B.s0, B.s1,
+    // then the four divider waves in that order].  The waves of a workgroup are dealt round the CU's four SIMDs, so waves w and
+    // w + 4 share one: every stream sits with its own divider wave, which mostly sleeps while the stream runs (stream 0 of the
+    // authV2-class graph has 5 requests), and one such workgroup fills a CU's LDS -- 256 workgroups = 512 tiles at once.  As
+    // four-wave workgroups, two per CU, the second workgroup's waves land on the first one's SIMDs role by role (s0 + s1 on one
+    // SIMD, the two dividers on another: tools/gpu_wave_census.py), 12.4 against 9.95 ms of interpreter launch at 1024 sets
+    // (profiles/asym_streams_ab.txt).  CWC_STREAM_TILES_PER_WORKGROUP (1 or 2) overrides for measurements.
+    if (stream_pair_workgroups(divider, tiles, streams)) return 4u;
+    // other programs of several streams: the streams of a tile (and their divider waves) are one workgroup
     if (streams > 1) return divider ? streams : 4u;
     const char* e = getenv("CWC_WAVES_PER_WORKGROUP");
     if (divider == 1) return e ? (atoi(e) >= 4 ? 2u : 1u) : (tiles > 256 ? 2u : 1u);  // units of (interpreter + divider)
@@ -180,6 +194,26 @@ double estimate_cycles(const Program& p, size_t batch) {
         // per CU, 256 tiles at a time), 49 KiB for two; without, four waves of 20 KiB.  More live waves than SIMDs
         // (2 x 512 tiles + dividers measured x1.3) slow each other down.
         const double tiles = (double)((batch + p.T - 1) / p.T);
+        if (stream_pair_workgroups(p.divider, (uint64_t)tiles, p.n_streams)) {
+            // Two tiles per eight-wave workgroup (waves_per_workgroup): every stream shares its SIMD with its own divider wave and
+            // with nothing else, 512 tiles at a time.  A stream takes the longer of its lone time and the work of its SIMD --
+            // its bundles and its divider's inversions -- at the rate of two waves on one SIMD: kTwoWaves of their sum.
+            // Fitted at 1024 sets, authV2-class (profiles/asym_streams_ab.txt): stream 0 (25.2 M modelled, 5 requests) ran 42.0 M
+            // stamped cycles, stream 1 (17.1 M of bundles + 263 inversions = 30.8 M) 31.9 M, i.e. 0.76 of stream 0's = 19.0 M
+            // modelled: 0.62 of the sum; the launch took 9.95 ms where the one-stream program (29.0 M modelled) took 11.54:
+            // 25.0 M on that scale -- stream 0 runs as a lone wave does, no factor for T = 2.  These programs have no inline
+            // pack: the rows the divider waves of a one-stream program would have stored come back as pack kernel time, which
+            // the programs they are compared with do not pay (0.87 ms per 1024 sets x 76 876 rows = 0.028 modelled cycles per value).
+            constexpr double kTwoWaves = 0.62, kPackCyclesPerValue = 0.028;
+            double t = 0;
+            for (uint32_t s = 0; s < p.n_streams; ++s) {
+                const double own = std::max(p.stream_cycles[s], p.stream_chain_cycles[s]);
+                const double simd = (p.stream_cycles[s] + model_class_cycles(C_DIV) * p.stream_div_requests[s]) * kTwoWaves;
+                t = std::max(t, std::max(own, simd));
+            }
+            const double rounds = std::max(1.0, tiles / 512.0);
+            return t * (p.T >= 4 ? 1.2 * wide : 1.0) * rounds + kPackCyclesPerValue * (double)p.n_witness * (double)batch;
+        }
         const double t = program_wave_cycles(p);
         double busy = 0;  // SIMDs' worth of work per tile: every stream and divider wave for the share of t it is busy
         for (uint32_t s = 0; s < p.n_streams; ++s) busy += (p.stream_cycles[s] + model_class_cycles(C_DIV) * p.stream_div_requests[s]) / t;
@@ -228,6 +262,14 @@ std::vector<uint32_t> candidate_keys(const ProgramStats& stats, size_t batch, ui
             if ((mode == 0 || mode == KEY_DIVIDER) && t < 64 && !getenv("CWC_NO_STREAMS")) {
                 if (tiles <= 256) keys.push_back(t | mode | KEY_STREAMS4);
                 else if (tiles <= 340) keys.push_back(t | mode | KEY_STREAMS2);
+                // ... and up to two tiles per CU where every stream has a divider wave to share its SIMD with (waves_per_workgroup).
+                // Not at T = 1: 512 sets measured 9.49 ms against 9.42-9.49 for T = 2 with four streams, what is chosen there today.
+                // Not while an inline-pack switch is set (CWC_INLINE_PACK, CWC_INLINE_PACK_ROWS: measurements and tests of the divider
+                // waves' pack through the automatic choice, profiles/inline_pack_ab.txt 2 and 4): the switches act on one-stream
+                // programs only, so under them the choice stays among the candidates it had before this offer existed and both
+                // arms of such an A/B run the program the switch acts on.
+                else if (mode == KEY_DIVIDER && t >= 2 && tiles <= 512 && !getenv("CWC_INLINE_PACK") && !getenv("CWC_INLINE_PACK_ROWS"))
+                    keys.push_back(t | mode | KEY_STREAMS2);
             }
         }
     return keys;

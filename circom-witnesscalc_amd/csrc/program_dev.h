@@ -132,6 +132,11 @@ static const uint32_t HDR_B_CANON = 1u << 14, HDR_A_CANON = 1u << 17, HDR_OUT_CA
 // the bundle three further on and the third-operand loads of the next bundle.
 static const uint32_t HDR_POST = 1u << 15, HDR_WAIT = 1u << 16;
 static const uint32_t MAX_STREAMS = 4;
+// Diagnostic buffer of the stamped interpreter instances: PROF_WORDS 64-bit counters (gwb_profile_classes), then the wave census
+// (gwb_wave_census): CENSUS_WORDS words for each of the launch's first CENSUS_MAX_WAVES waves, wave = workgroup * waves per
+// workgroup + wave of the workgroup -- {HW_ID | XCC_ID << 32 | role << 40, s_memtime at its start, at its end}.
+// role: bit 0 divider wave, bits 1-3 stream, bit 4 the wave has a tile, bits 8-15 waves per workgroup.
+static const uint32_t PROF_WORDS = 96, CENSUS_MAX_WAVES = 8192, CENSUS_WORDS = 3;
 static const uint32_t CTRL_SUB_MASK = 7u, CTRL_ACTIVE = 8u, CTRL_MASK = 15u;
 static const uint32_t RING_BUNDLES = 4, OPND_AHEAD = 2, REC_AHEAD = 4;
 static const uint32_t RING_SLOT_BYTES = 2048, LDS_HALF_BYTES = 1024, STAGE_BYTES = 4096, REC_BYTES = 1024;

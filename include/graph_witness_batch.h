@@ -203,6 +203,13 @@ int gwb_timing_history(gwb_graph_t *g, size_t max_launches, float *interp_ms, fl
  * last stage.  out64 must hold 96 words. */
 int gwb_profile_classes(gwb_graph_t *g, const void *d_inputs, size_t batch, void *d_witness,
                         uint32_t *d_set_status, uint64_t *out64, gw_status_t *status);
+/* Diagnostic library as well: the wave census of one batch's (last) interpreter launch -- where every wavefront sat and when
+ * it ran.  Three words for each of the launch's first 8192 waves, wave = workgroup * waves per workgroup + wave of the
+ * workgroup: out64[3 i] = HW_ID register (bits 5:4 SIMD, 11:8 CU, 12 SH, 15:13 SE) | XCC_ID << 32 | role << 40 (bit 0 divider
+ * wave, bits 3:1 stream, bit 4 the wave has a tile, bits 15:8 waves per workgroup), out64[3 i + 1] / [3 i + 2] = s_memtime at its start / end (0: the wave
+ * had nothing to do, or was never launched: all three words 0).  out_words: size of out64, at least 3 * 8192. */
+int gwb_wave_census(gwb_graph_t *g, const void *d_inputs, size_t batch, void *d_witness,
+                    uint32_t *d_set_status, uint64_t *out64, size_t out_words, gw_status_t *status);
 
 /* Diagnostic: chip-wide one-lane Montgomery products per second with waves_per_simd (1..4) wavefronts on every SIMD, each
  * lane running a dependent chain of 2 * iters products (the compute ceiling bench.py reports beside the HBM model);

@@ -2,6 +2,8 @@
 batch sizes and program keys (tile widths, divider modes), byte-compared with the C oracle.  Exit code 1 on mismatch.
 
     SOAK_SEEDS=300 python tools/gpu_soak.py
+    SOAK_KEYS=0x901,0x902,0x904 CWC_STREAM_TILES_PER_WORKGROUP=2 python tools/gpu_soak.py    # these keys only (here: two-stream divider
+                                                                  # programs as eight-wave workgroups of two tiles, whatever the batch)
 """
 import os, random, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,6 +22,8 @@ KEYS = [1, 2, 4, 8, 16, 32, 64, 1 | 0x100, 2 | 0x100, 8 | 0x100, 32 | 0x100, 1 |
         1 | 0x800, 2 | 0x1000, 1 | 0x100 | 0x1000, 4 | 0x100 | 0x800, 8 | 0x1000, 16 | 0x100 | 0x1000]  # (0x800 / 0x1000: two / four streams per tile)
 KINDS = os.environ.get("SOAK_KINDS", "dag,dag,dag_panic,chains,forest,forest_panic,limb").split(",")
 LIMB_KEYS = [1, 2, 1 | 0x100, 2 | 0x100, 1 | 0x1000, 2 | 0x100 | 0x1000, 4, 8]  # (scan bundles exist at tile widths 1 and 2)
+if os.environ.get("SOAK_KEYS"):
+    KEYS = LIMB_KEYS = [int(x, 0) for x in os.environ["SOAK_KEYS"].split(",")]
 
 
 def run(n_seeds, base, verbose=True):
@@ -73,7 +77,7 @@ def run(n_seeds, base, verbose=True):
         og = cbind.Graph(data)
         want, wst = og.evaluate_batch(inp)
         g = pkg.Graph(data)
-        for key in rnd.sample(KEYS if kind != "limb" else LIMB_KEYS, 3) + [0]:
+        for key in rnd.sample(KEYS if kind != "limb" else LIMB_KEYS, min(3, len(KEYS))) + [0]:
             g.set_tile_width(key)
             got, st = g.calc_witness_batch(inp)
             ok = wst == 0
