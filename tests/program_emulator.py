@@ -89,8 +89,10 @@ class Blob:
         assert self.divider in (0, 1, 3, 4) and pos <= len(data)  # (an exported blob carries the input map behind the program)
 
 
-def run(blob: Blob, inputs_row):
-    """Evaluate one input set (list of ints) through the format-v4 program the way the interpreter kernel does, for
+def run(blob: Blob, inputs_row, observe=None):
+    """(observe: optional callback (class name, stored operand words) for every node of a narrow bundle -- ("MULQ", (a, b, sub)) and
+    ("MULF", (a, b, op2, x2, op3, x3)) -- so that a test can see which words the four lanes of a product really receive.)
+    Evaluate one input set (list of ints) through the format-v4 program the way the interpreter kernel does, for
     t = 0; returns (witness ints, status bits).  Values are held the way the kernel holds them -- the Montgomery form
     x * 2^256 mod r, or the canonical integer where the compiler's representation inference keeps one -- and every
     operation is done on those words: a value read in the wrong form gives a wrong witness.  Models the timing rules of the pipeline: the staging load of bundle b
@@ -322,14 +324,19 @@ def run(blob: Blob, inputs_row):
                     if code == FOP_ADD:
                         return (acc + x) % model.M
                     return (acc - x) % model.M if code == FOP_SUB else (x - acc) % model.M
+                x2 = x3 = None
                 if op2:
-                    acc = stage_op(op2, acc, fetch(xa_off, xlds & 0xFFFF, 0, j * rep + 1))
+                    x2 = fetch(xa_off, xlds & 0xFFFF, 0, j * rep + 1)
+                    acc = stage_op(op2, acc, x2)
                 else:
                     assert xa_off == zero_off
                 if op3:
-                    acc = stage_op(op3, acc, fetch(xb_off, xlds >> 16, 1, j * rep + 1))
+                    x3 = fetch(xb_off, xlds >> 16, 1, j * rep + 1)
+                    acc = stage_op(op3, acc, x3)
                 else:
                     assert xb_off == zero_off
+                if observe:
+                    observe("MULF", (ops[0], ops[1], op2, x2, op3, x3))
                 results.append((dst, acc))
                 continue
 
@@ -349,6 +356,8 @@ def run(blob: Blob, inputs_row):
                 op = SUB_NAMES[name][sub]
                 assert op is not None
                 if name in ("LIN", "MUL", "MULQ"):
+                    if observe and name == "MULQ":
+                        observe("MULQ", (ops[0], ops[1], sub))
                     if op != "Mul":
                         lin_seen |= (1 << 11) if op == "Sub" else (1 << 12)
                         v = model.eval_duo(op, ops[0], ops[1])  # (a +- b mod r: the same words in either form)
