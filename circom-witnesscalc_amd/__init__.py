@@ -95,7 +95,7 @@ def build(verbose=False, diag=False):
     if not verbose:
         cmd.insert(1, "-s")
     subprocess.check_call(cmd)
-    # the R1CS check and QAP witness map (libcwc_r1cs.so + check-witness, witness-h): a library of its own, outside csrc/
+    # the R1CS check, QAP witness map and Groth16 layers (libcwc_r1cs.so and its CLIs): a library of its own, outside csrc/
     subprocess.check_call(["make"] + ([] if verbose else ["-s"]) + ["-C", os.path.join(_HERE, "r1cs"), "-j4"])
 
 
@@ -596,6 +596,11 @@ def r1cs_lib():
         L.gwb_groth16_verify_batch_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, stp]
         L.gwb_groth16_verify_batch_host.argtypes = [vp, vp, vp, sz, sz, vp, stp]
         L.gwb_bn254_pairing_batch_device.argtypes = [vp, vp, sz, vp, vp, stp]
+        L.gwb_groth16_setup.argtypes = [vp, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
+        L.gwb_groth16_setup_free.restype = None
+        L.gwb_groth16_setup_free.argtypes = [vp]
+        L.gwb_bn254_gen_mul_batch_device.argtypes = [vp, sz, u32, vp, vp, stp]
+        L.gwb_groth16_setup_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_float)]
         _r1cs_lib = L
     return _r1cs_lib
 
@@ -866,6 +871,11 @@ class Groth16:
         public = [_dec(values[32 * i:32 * i + 32]) for i in range(1, self.info["n_public"] + 1)]
         return proof_json(out), public
 
+    @classmethod
+    def setup(cls, r1cs, trapdoor=None):
+        """A proving key made for `r1cs` by groth16_setup (single party: see its trust statement), loaded against it."""
+        return cls(groth16_setup(r1cs, trapdoor), r1cs)
+
     def verifying_key(self):
         """The zkey's verifying key (Groth16VerifyingKey)."""
         return Groth16VerifyingKey._from_zkey_handle(self._h)
@@ -881,6 +891,66 @@ class Groth16:
         if r1cs_lib().gwb_groth16_phase_ms(self._h, ms) != 0:
             raise WitnessCalcError("no prover phase times (time_phases not on, or no prove call yet)")
         return dict(zip(GROTH16_PHASES, (float(x) for x in ms)))
+
+
+# -- Groth16 key setup (include/graph_witness_groth16_setup.h, libcwc_r1cs.so) ------------------------------------------------
+GROTH16_SETUP_PHASES = ("lagrange", "column_sums", "key_scalars", "g1_muls", "g2_muls_affine")
+
+
+def groth16_setup(r1cs, trapdoor=None):
+    """The Groth16 proving key of an R1cs as `.zkey` bytes, made on the GPU (circuit-specific setup; synchronous).  trapdoor:
+    (tau, alpha, beta, gamma, delta), ints in [1, r) with tau^2n != 1, or None: drawn and discarded.  Single party: whoever
+    knows the trapdoor can forge proofs, so this is for development, tests and deployments where the key's maker is trusted;
+    it is not an MPC ceremony.  Section 10 of the file has no circuit hash and no contributions."""
+    buf = None
+    if trapdoor is not None:
+        vals = [int(x) for x in trapdoor]
+        if len(vals) != 5:
+            raise WitnessCalcError("trapdoor: 5 values expected (tau, alpha, beta, gamma, delta), %d given" % len(vals))
+        for name, v in zip(("tau", "alpha", "beta", "gamma", "delta"), vals):
+            if not 0 <= v < (1 << 256):
+                raise WitnessCalcError("trapdoor: %s is not in [0, 2^256)" % name)
+        buf = ctypes.create_string_buffer(b"".join(v.to_bytes(32, "little") for v in vals), 160)
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    st = GwStatus()
+    try:
+        rc = r1cs_lib().gwb_groth16_setup(r1cs._h, buf, ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
+    finally:
+        if buf is not None:
+            ctypes.memset(buf, 0, 160)
+    _r1cs_check(rc, st)
+    try:
+        return ctypes.string_at(out, n.value)
+    finally:
+        r1cs_lib().gwb_groth16_setup_free(out)
+
+
+def bn254_gen_mul_batch_device(d_scalars, group, stream=None):
+    """Measurement and test aid: device scalars (uint8 cuda [n, 32], canonical little-endian; values >= r are reduced) -> k_i
+    times the generator of G1 (group 1: uint8 cuda [n, 64]) or G2 (group 2: [n, 128]), canonical affine coordinates, zero bytes
+    for the point at infinity.  Asynchronous on `stream` or the current stream."""
+    import torch
+    n = d_scalars.shape[0]
+    assert tuple(d_scalars.shape) == (n, 32) and d_scalars.is_cuda and d_scalars.is_contiguous() and d_scalars.dtype == torch.uint8
+    if group not in (1, 2):
+        raise WitnessCalcError("group must be 1 or 2")
+    s = stream if stream is not None else torch.cuda.current_stream(d_scalars.device)
+    out = torch.empty((n, 64 * group), dtype=torch.uint8, device=d_scalars.device)
+    st = GwStatus()
+    with torch.cuda.device(d_scalars.device):
+        rc = r1cs_lib().gwb_bn254_gen_mul_batch_device(d_scalars.data_ptr(), n, group, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
+    _r1cs_check(rc, st)
+    if n:
+        out.record_stream(s)
+    return out
+
+
+def groth16_setup_phase_ms():
+    """{lagrange, column_sums, key_scalars, g1_muls, g2_muls_affine} in ms of the process's last groth16_setup call."""
+    ms = (ctypes.c_float * 5)()
+    if r1cs_lib().gwb_groth16_setup_phase_ms(ms) != 0:
+        raise WitnessCalcError("no setup phase times (no groth16_setup call yet)")
+    return dict(zip(GROTH16_SETUP_PHASES, (float(x) for x in ms)))
 
 
 # -- Groth16 verifier (include/graph_witness_groth16_verify.h, libcwc_r1cs.so) ------------------------------------------------

@@ -32,4 +32,8 @@ namespace cwc_r1cs {
 // qap.hip: the witness map of device rows into d_h, as gwb_r1cs_qap_batch_device enqueues it (arguments checked by the caller)
 bool qap_enqueue(gwb_r1cs* r, const void* d_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out, void* stream,
                  std::string& err);
+// qap.hip: the roots of the domain of 2^p points, Montgomery form: w_n of order n, g of order 2n with g^2 = w_n
+void qap_roots(uint32_t p, cwc::Fr& wn, cwc::Fr& g);
+// msm.hip: a uniform draw from [0, r), by rejection sampling from getrandom()
+bool draw_fr(cwc::Fr& x, std::string& err);
 }  // namespace cwc_r1cs

@@ -1,0 +1,223 @@
+// groth16-setup [--trapdoor FILE] <circuit.r1cs> <circuit.zkey> [verification_key.json]: a Groth16 proving key for the
+// circuit, made on the GPU (the single-party equivalent of snarkjs `groth16 setup`; include/graph_witness_groth16_setup.h).
+// The trapdoor is drawn and discarded, or read from FILE: five decimal integers tau, alpha, beta, gamma, delta separated by
+// whitespace, each in [1, r) (for reproducible keys).  With a third path the verifying key is written too, in snarkjs's
+// verification_key.json shape with vk_alphabeta_12.  Exit status 0 on success; 2 on a usage, file or format error.  Every
+// input is parsed before the device is touched.
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <fstream>
+#include <iterator>
+#include <string>
+#include <vector>
+
+#include "../../include/graph_witness_groth16_setup.h"
+#include "../../include/graph_witness_groth16_verify.h"
+
+static bool read_file(const char* path, std::vector<char>& out) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) return false;
+    out.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+    return !f.bad();
+}
+
+static bool write_file(const char* path, const void* data, size_t n) {
+    FILE* f = fopen(path, "wb");
+    if (!f) return false;
+    const bool ok = fwrite(data, 1, n, f) == n;
+    return fclose(f) == 0 && ok;
+}
+
+// 32-byte little-endian integer -> decimal string
+static std::string decimal(const uint8_t* le) {
+    uint32_t w[8];
+    memcpy(w, le, 32);
+    std::string out;
+    for (;;) {
+        bool zero = true;
+        uint64_t rem = 0;
+        for (int i = 7; i >= 0; --i) {
+            const uint64_t cur = (rem << 32) | w[i];
+            w[i] = (uint32_t)(cur / 1000000000u);
+            rem = cur % 1000000000u;
+            zero = zero && w[i] == 0;
+        }
+        char buf[16];
+        snprintf(buf, sizeof buf, zero ? "%llu" : "%09llu", (unsigned long long)rem);
+        out = buf + out;
+        if (zero) return out;
+    }
+}
+
+// decimal digits -> 32-byte little-endian integer; false for another character, no digit, or a value of 2^256 or more
+static bool parse_decimal(const std::string& tok, uint8_t* le) {
+    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (tok.empty()) return false;
+    for (char c : tok) {
+        if (c < '0' || c > '9') return false;
+        uint64_t carry = (uint64_t)(c - '0');
+        for (int i = 0; i < 8; ++i) {
+            const uint64_t cur = (uint64_t)w[i] * 10 + carry;
+            w[i] = (uint32_t)cur;
+            carry = cur >> 32;
+        }
+        if (carry) return false;
+    }
+    memcpy(le, w, 32);
+    return true;
+}
+
+static bool parse_trapdoor(const char* path, gwb_groth16_trapdoor_t* t) {
+    std::vector<char> text;
+    if (!read_file(path, text)) {
+        fprintf(stderr, "error: cannot read %s\n", path);
+        return false;
+    }
+    std::vector<std::string> toks;
+    std::string cur;
+    for (char c : text) {
+        if (c == ' ' || c == '\n' || c == '\r' || c == '\t') {
+            if (!cur.empty()) toks.push_back(cur);
+            cur.clear();
+        } else {
+            cur += c;
+        }
+    }
+    if (!cur.empty()) toks.push_back(cur);
+    std::fill(text.begin(), text.end(), 0);
+    if (toks.size() != 5) {
+        fprintf(stderr, "error: %s: %zu values, 5 expected (tau alpha beta gamma delta)\n", path, toks.size());
+        return false;
+    }
+    static const char* names[5] = {"tau", "alpha", "beta", "gamma", "delta"};
+    uint8_t* dst[5] = {t->tau, t->alpha, t->beta, t->gamma, t->delta};
+    for (int i = 0; i < 5; ++i)
+        if (!parse_decimal(toks[i], dst[i])) {
+            fprintf(stderr, "error: %s: %s is not a decimal integer below 2^256\n", path, names[i]);
+            return false;
+        }
+    return true;
+}
+
+static std::string g1_json(const uint8_t* p) {
+    bool inf = true;
+    for (int i = 0; i < 64; ++i) inf = inf && p[i] == 0;
+    if (inf) return "[\"0\", \"1\", \"0\"]";
+    return "[\"" + decimal(p) + "\", \"" + decimal(p + 32) + "\", \"1\"]";
+}
+
+static std::string g2_json(const uint8_t* p) {
+    bool inf = true;
+    for (int i = 0; i < 128; ++i) inf = inf && p[i] == 0;
+    if (inf) return "[[\"0\", \"0\"], [\"1\", \"0\"], [\"0\", \"0\"]]";
+    return "[[\"" + decimal(p) + "\", \"" + decimal(p + 32) + "\"], [\"" + decimal(p + 64) + "\", \"" + decimal(p + 96) + "\"], [\"1\", \"0\"]]";
+}
+
+// the verifying key of the written zkey as snarkjs's verification_key.json
+static bool vk_json(const void* zkey, size_t len, std::string& out, std::string& err) {
+    gw_status_t st = {OK, NULL};
+    gwb_zkey_t* z = NULL;
+    gwb_g16vk_t* vk = NULL;
+    auto failed = [&](const char* what) {
+        err = st.error_msg ? st.error_msg : what;
+        gw_free_status(&st);
+        if (vk) gwb_g16vk_free(vk);
+        if (z) gwb_zkey_free(z);
+        return false;
+    };
+    if (gwb_zkey_load(zkey, len, &z, &st) != 0) return failed("loading the written key failed");
+    if (gwb_g16vk_from_zkey(z, &vk, &st) != 0) return failed("extracting the verifying key failed");
+    gwb_g16vk_info_t info;
+    gwb_g16vk_info(vk, &info);
+    std::vector<uint8_t> pts(448 + 64 * ((size_t)info.n_public + 1));
+    uint8_t gt[GWB_GT_BYTES];
+    if (gwb_g16vk_points(vk, pts.data(), pts.size()) != 0) return failed("reading the verifying key's points failed");
+    if (gwb_g16vk_alphabeta(vk, gt, &st) != 0) return failed("computing e(alpha1, beta2) failed");
+    out = "{\n \"protocol\": \"groth16\",\n \"curve\": \"bn128\",\n \"nPublic\": " + std::to_string(info.n_public) + ",\n";
+    out += " \"vk_alpha_1\": " + g1_json(pts.data()) + ",\n";
+    out += " \"vk_beta_2\": " + g2_json(pts.data() + 64) + ",\n";
+    out += " \"vk_gamma_2\": " + g2_json(pts.data() + 192) + ",\n";
+    out += " \"vk_delta_2\": " + g2_json(pts.data() + 320) + ",\n";
+    out += " \"vk_alphabeta_12\": [";
+    for (int i = 0; i < 2; ++i) {
+        out += i ? ", [" : "[";
+        for (int j = 0; j < 3; ++j)
+            out += std::string(j ? ", " : "") + "[\"" + decimal(gt + 32 * (6 * i + 2 * j)) + "\", \"" + decimal(gt + 32 * (6 * i + 2 * j + 1)) + "\"]";
+        out += "]";
+    }
+    out += "],\n \"IC\": [";
+    for (uint32_t i = 0; i <= info.n_public; ++i) out += std::string(i ? ",\n  " : "\n  ") + g1_json(pts.data() + 448 + 64 * (size_t)i);
+    out += "\n ]\n}\n";
+    gwb_g16vk_free(vk);
+    gwb_zkey_free(z);
+    return true;
+}
+
+int main(int argc, char** argv) {
+    const char* trapdoor_path = NULL;
+    std::vector<const char*> pos;
+    for (int i = 1; i < argc; ++i) {
+        if (strcmp(argv[i], "--trapdoor") == 0) {
+            if (i + 1 >= argc || trapdoor_path) {
+                pos.clear();
+                break;
+            }
+            trapdoor_path = argv[++i];
+        } else {
+            pos.push_back(argv[i]);
+        }
+    }
+    if (pos.size() != 2 && pos.size() != 3) {
+        fprintf(stderr, "usage: %s [--trapdoor FILE] <circuit.r1cs> <circuit.zkey> [verification_key.json]\n", argv[0]);
+        return 2;
+    }
+    std::vector<char> file;
+    if (!read_file(pos[0], file)) {
+        fprintf(stderr, "error: cannot read %s\n", pos[0]);
+        return 2;
+    }
+    gw_status_t st = {OK, NULL};
+    gwb_r1cs_t* r = NULL;
+    if (gwb_r1cs_load(file.data(), file.size(), &r, &st) != 0) {
+        fprintf(stderr, "error: %s: %s\n", pos[0], st.error_msg ? st.error_msg : "load failed");
+        gw_free_status(&st);
+        return 2;
+    }
+    gwb_groth16_trapdoor_t t;
+    if (trapdoor_path && !parse_trapdoor(trapdoor_path, &t)) {
+        gwb_r1cs_free(r);
+        return 2;
+    }
+    fprintf(stderr, "groth16-setup: single-party setup: whoever holds the trapdoor can forge proofs for this key; %s\n",
+            trapdoor_path ? "it was read from a file, which remains" : "a drawn trapdoor is discarded before the key is written");
+    void* zkey = NULL;
+    size_t len = 0;
+    const int rc = gwb_groth16_setup(r, trapdoor_path ? &t : NULL, &zkey, &len, &st);
+    explicit_bzero(&t, sizeof t);
+    gwb_r1cs_free(r);
+    if (rc != 0) {
+        fprintf(stderr, "error: %s\n", st.error_msg ? st.error_msg : "setup failed");
+        gw_free_status(&st);
+        return 2;
+    }
+    int code = 0;
+    if (!write_file(pos[1], zkey, len)) {
+        fprintf(stderr, "error: cannot write %s\n", pos[1]);
+        code = 2;
+    }
+    if (code == 0 && pos.size() == 3) {
+        std::string json, err;
+        if (!vk_json(zkey, len, json, err)) {
+            fprintf(stderr, "error: %s\n", err.c_str());
+            code = 2;
+        } else if (!write_file(pos[2], json.data(), json.size())) {
+            fprintf(stderr, "error: cannot write %s\n", pos[2]);
+            code = 2;
+        }
+    }
+    gwb_groth16_setup_free(zkey);
+    return code;
+}

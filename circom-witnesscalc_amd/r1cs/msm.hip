@@ -563,6 +563,29 @@ bool enqueue_sub(gwb_zkey* z, gwb_r1cs* r, const Layout& L, const uint8_t* d_w, 
     return true;
 }
 
+}  // namespace
+
+namespace cwc_r1cs {
+bool draw_fr(Fr& x, std::string& err) {
+    do {
+        uint8_t* p = (uint8_t*)x.v;
+        size_t got = 0;
+        while (got < 32) {
+            const ssize_t k = getrandom(p + got, 32 - got, 0);
+            if (k < 0) {
+                err = "groth16: getrandom failed";
+                return false;
+            }
+            got += (size_t)k;
+        }
+        x.v[7] &= 0x3fffffffu;  // r < 2^254: draw 254 bits, keep those below r
+    } while (!cwc::u256_lt(x, cwc::fr_p()));
+    return true;
+}
+}  // namespace cwc_r1cs
+
+namespace {
+
 // rs for a batch: the caller's (each below r) or uniform draws from getrandom() by rejection
 bool make_rs(const void* rs, size_t batch, std::vector<Fr>& out, std::string& err) {
     out.resize(batch * 2);
@@ -575,21 +598,8 @@ bool make_rs(const void* rs, size_t batch, std::vector<Fr>& out, std::string& er
             }
         return true;
     }
-    for (Fr& x : out) {
-        do {
-            uint8_t* p = (uint8_t*)x.v;
-            size_t got = 0;
-            while (got < 32) {
-                const ssize_t k = getrandom(p + got, 32 - got, 0);
-                if (k < 0) {
-                    err = "groth16: getrandom failed";
-                    return false;
-                }
-                got += (size_t)k;
-            }
-            x.v[7] &= 0x3fffffffu;  // r < 2^254: draw 254 bits, keep those below r
-        } while (!cwc::u256_lt(x, cwc::fr_p()));
-    }
+    for (Fr& x : out)
+        if (!draw_fr(x, err)) return false;
     return true;
 }
 

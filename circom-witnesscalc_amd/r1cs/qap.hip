@@ -321,17 +321,29 @@ Fr fr_pow(Fr base_m, const Fr& e) {  // Montgomery in and out
     return acc;
 }
 
+}  // namespace
+
+namespace cwc_r1cs {
+// w_28 = 5^((r-1) / 2^28); w_n = w_28^(2^(28-p)); g = w_28^(2^(27-p)); Montgomery form
+void qap_roots(uint32_t p, Fr& wn, Fr& g) {
+    Fr rm1 = cwc::fr_p();
+    rm1.v[0] -= 1;  // r is odd
+    g = fr_pow(cwc::fr_to_mont(Fr{{5, 0, 0, 0, 0, 0, 0, 0}}), cwc::u256_shr(rm1, 28));
+    for (uint32_t i = 0; i < MAX_POWER - p; ++i) g = cwc::fr_mul(g, g);
+    wn = cwc::fr_mul(g, g);
+}
+}  // namespace cwc_r1cs
+
+namespace {
+
 // twiddle and coset tables of the handle's domain, on its device (synchronous, first call only)
 bool ensure_tables(gwb_r1cs* r, uint32_t p, std::string& err) {
     if (r->d_qap_tw) return true;
     const uint64_t n = 1ull << p;
-    // w_28 = 5^((r-1) / 2^28); w_n = w_28^(2^(28-p)); g = w_28^(2^(27-p))
     Fr rm1 = cwc::fr_p();
     rm1.v[0] -= 1;  // r is odd
-    const Fr w28 = fr_pow(cwc::fr_to_mont(Fr{{5, 0, 0, 0, 0, 0, 0, 0}}), cwc::u256_shr(rm1, 28));
-    Fr g = w28;
-    for (uint32_t i = 0; i < MAX_POWER - p; ++i) g = cwc::fr_mul(g, g);
-    const Fr wn = cwc::fr_mul(g, g);
+    Fr wn, g;
+    qap_roots(p, wn, g);
     Pows wp, gp;
     wp.v[0] = wn;
     gp.v[0] = g;

@@ -89,7 +89,7 @@ def main():
     lines.append("model per proof (every digit nonzero): %d G1 and %d G2 mixed additions in the bucket accumulation, %.3g Fq "
                  "products, %.2f ms at the probe's rate; not modelled: bucket reduction, sort, witness map" %
                  (adds_g1, adds_g2, fq_products, fq_products / rate * 1e3))
-    lines.append("not measured: a reference prover (none exists on the GPU machine); real zkeys (none available); witnesses of bits "
+    lines.append("not measured: a reference prover (none exists on the GPU machine); zkeys written by snarkjs (none available); witnesses of bits "
                  "(synth inputs give field-sized wires where the circuit computes them)")
     out = "\n".join(lines) + "\n"
     sys.stdout.write(out)
