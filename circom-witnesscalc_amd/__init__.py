@@ -549,6 +549,11 @@ class ZkeyInfo(ctypes.Structure):
     _fields_ = [("n_vars", ctypes.c_uint32), ("n_public", ctypes.c_uint32), ("domain_size", ctypes.c_uint32), ("n_coefs", ctypes.c_uint64)]
 
 
+class PtauInfo(ctypes.Structure):
+    _fields_ = [("power", ctypes.c_uint32), ("ceremony_power", ctypes.c_uint32), ("prepared", ctypes.c_uint32),
+                ("n_contributions", ctypes.c_uint32)]
+
+
 def r1cs_lib():
     """ctypes handle of libcwc_r1cs.so, loaded after torch (one HIP runtime per process, as in lib())."""
     global _r1cs_lib
@@ -601,6 +606,11 @@ def r1cs_lib():
         L.gwb_groth16_setup_free.argtypes = [vp]
         L.gwb_bn254_gen_mul_batch_device.argtypes = [vp, sz, u32, vp, vp, stp]
         L.gwb_groth16_setup_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_float)]
+        L.gwb_ptau_info.argtypes = [vp, sz, ctypes.POINTER(PtauInfo), stp]
+        L.gwb_ptau_check.argtypes = [vp, sz, u32, u32, stp]
+        L.gwb_groth16_setup_ptau.argtypes = [vp, vp, sz, vp, u32, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
+        L.gwb_bn254_point_idft_batch_device.argtypes = [vp, u32, u32, vp, vp, stp]
+        L.gwb_groth16_setup_ptau_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_float)]
         _r1cs_lib = L
     return _r1cs_lib
 
@@ -876,6 +886,12 @@ class Groth16:
         """A proving key made for `r1cs` by groth16_setup (single party: see its trust statement), loaded against it."""
         return cls(groth16_setup(r1cs, trapdoor), r1cs)
 
+    @classmethod
+    def setup_ptau(cls, r1cs, ptau, delta=None, lagrange="auto"):
+        """A proving key made for `r1cs` from a powers-of-tau file by groth16_setup_ptau (see its trust statement), loaded
+        against it."""
+        return cls(groth16_setup_ptau(r1cs, ptau, delta, lagrange), r1cs)
+
     def verifying_key(self):
         """The zkey's verifying key (Groth16VerifyingKey)."""
         return Groth16VerifyingKey._from_zkey_handle(self._h)
@@ -900,8 +916,8 @@ GROTH16_SETUP_PHASES = ("lagrange", "column_sums", "key_scalars", "g1_muls", "g2
 def groth16_setup(r1cs, trapdoor=None):
     """The Groth16 proving key of an R1cs as `.zkey` bytes, made on the GPU (circuit-specific setup; synchronous).  trapdoor:
     (tau, alpha, beta, gamma, delta), ints in [1, r) with tau^2n != 1, or None: drawn and discarded.  Single party: whoever
-    knows the trapdoor can forge proofs, so this is for development, tests and deployments where the key's maker is trusted;
-    it is not an MPC ceremony.  Section 10 of the file has no circuit hash and no contributions."""
+    knows the trapdoor can forge proofs, so this is for development, tests and deployments where the key's maker is trusted
+    with all five values (groth16_setup_ptau takes tau, alpha and beta from a public ceremony instead).  Section 10 of the file has no circuit hash and no contributions."""
     buf = None
     if trapdoor is not None:
         vals = [int(x) for x in trapdoor]
@@ -951,6 +967,110 @@ def groth16_setup_phase_ms():
     if r1cs_lib().gwb_groth16_setup_phase_ms(ms) != 0:
         raise WitnessCalcError("no setup phase times (no groth16_setup call yet)")
     return dict(zip(GROTH16_SETUP_PHASES, (float(x) for x in ms)))
+
+
+# -- Groth16 key setup from a powers-of-tau file (include/graph_witness_groth16_ptau.h, libcwc_r1cs.so) -------------------------
+GROTH16_SETUP_PTAU_PHASES = ("point_check", "idft_g1", "idft_g2", "column_sums_g1", "column_sums_g2", "delta_scale", "affine")
+PTAU_LAGRANGE_MODES = {"auto": 0, "file": 1, "compute": 2}
+
+
+def _ptau_buffer(ptau):
+    """(object that keeps the memory alive, address, length) of bytes, a bytearray, an mmap or a numpy array, without a copy
+    where the object allows it"""
+    if isinstance(ptau, bytes):
+        return ptau, ctypes.cast(ctypes.c_char_p(ptau), ctypes.c_void_p), len(ptau)
+    arr = np.frombuffer(ptau, dtype=np.uint8)
+    return arr, ctypes.c_void_p(arr.ctypes.data), arr.size
+
+
+def _lagrange_mode(lagrange):
+    if lagrange not in PTAU_LAGRANGE_MODES:
+        raise WitnessCalcError("lagrange must be one of %s" % ", ".join(PTAU_LAGRANGE_MODES))
+    return PTAU_LAGRANGE_MODES[lagrange]
+
+
+def ptau_info(ptau):
+    """{power, ceremony_power, prepared, n_contributions} of a `.ptau` image (bytes or any buffer, an mmap included).  Host
+    only: header and section table, no device."""
+    keep, addr, n = _ptau_buffer(ptau)
+    info, st = PtauInfo(), GwStatus()
+    rc = r1cs_lib().gwb_ptau_info(addr, n, ctypes.byref(info), ctypes.byref(st))
+    _r1cs_check(rc, st)
+    del keep
+    return {"power": int(info.power), "ceremony_power": int(info.ceremony_power), "prepared": bool(info.prepared),
+            "n_contributions": int(info.n_contributions)}
+
+
+def ptau_check(ptau, domain_power, lagrange="auto"):
+    """Host only: raises WitnessCalcError with the message groth16_setup_ptau would give for this file and a circuit of domain
+    2^domain_power (the points it would read are checked on the host)."""
+    keep, addr, n = _ptau_buffer(ptau)
+    st = GwStatus()
+    rc = r1cs_lib().gwb_ptau_check(addr, n, int(domain_power), _lagrange_mode(lagrange), ctypes.byref(st))
+    _r1cs_check(rc, st)
+    del keep
+
+
+def groth16_setup_ptau(r1cs, ptau, delta=None, lagrange="auto"):
+    """The Groth16 proving key of an R1cs as `.zkey` bytes, made on the GPU from a powers-of-tau file (what snarkjs
+    `groth16 setup` does; synchronous).  tau, alpha and beta are the ceremony's; gamma = 1.  delta: an int in [1, r), or None:
+    drawn, applied and discarded, after which soundness rests on the ceremony behind the file and on this call's runner
+    having discarded delta (a single-party phase 2; knowing delta alone is enough to forge).  delta = 1 is the state of
+    snarkjs `zkey new`: a key to hand to a phase-2 ceremony, not to use.  lagrange: "auto" reads the file's prepared sections
+    when it has them, "file" requires them, "compute" ignores them."""
+    mode = _lagrange_mode(lagrange)
+    buf = None
+    if delta is not None:
+        d = int(delta)
+        if not 0 <= d < (1 << 256):
+            raise WitnessCalcError("delta is not in [0, 2^256)")
+        buf = ctypes.create_string_buffer(d.to_bytes(32, "little"), 32)
+    keep, addr, n_in = _ptau_buffer(ptau)
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    st = GwStatus()
+    try:
+        rc = r1cs_lib().gwb_groth16_setup_ptau(r1cs._h, addr, n_in, buf, mode, ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
+    finally:
+        if buf is not None:
+            ctypes.memset(buf, 0, 32)
+    del keep
+    _r1cs_check(rc, st)
+    try:
+        return ctypes.string_at(out, n.value)
+    finally:
+        r1cs_lib().gwb_groth16_setup_free(out)
+
+
+def bn254_point_idft_batch_device(d_points, group, stream=None):
+    """Measurement and test aid: device points (uint8 cuda [2^m, 64] for group 1, [2^m, 128] for group 2; canonical affine
+    coordinates, zero bytes for infinity; 1 <= m <= 27) -> their inverse DFT over the group, (1 / N) sum_i w_N^(-k i) P_i, in
+    natural order and the same form.  Asynchronous on `stream` or the current stream."""
+    import torch
+    if group not in (1, 2):
+        raise WitnessCalcError("group must be 1 or 2")
+    n = d_points.shape[0]
+    assert tuple(d_points.shape) == (n, 64 * group) and d_points.is_cuda and d_points.is_contiguous() and d_points.dtype == torch.uint8
+    log_n = n.bit_length() - 1
+    if n < 2 or n != 1 << log_n:
+        raise WitnessCalcError("the number of points must be a power of two, 2 at the least")
+    s = stream if stream is not None else torch.cuda.current_stream(d_points.device)
+    out = torch.empty_like(d_points)
+    st = GwStatus()
+    with torch.cuda.device(d_points.device):
+        rc = r1cs_lib().gwb_bn254_point_idft_batch_device(d_points.data_ptr(), log_n, group, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
+    _r1cs_check(rc, st)
+    d_points.record_stream(s)
+    out.record_stream(s)
+    return out
+
+
+def groth16_setup_ptau_phase_ms():
+    """{point_check, idft_g1, idft_g2, column_sums_g1, column_sums_g2, delta_scale, affine} in ms of the process's last
+    groth16_setup_ptau call."""
+    ms = (ctypes.c_float * 7)()
+    if r1cs_lib().gwb_groth16_setup_ptau_phase_ms(ms) != 0:
+        raise WitnessCalcError("no setup phase times (no groth16_setup_ptau call yet)")
+    return dict(zip(GROTH16_SETUP_PTAU_PHASES, (float(x) for x in ms)))
 
 
 # -- Groth16 verifier (include/graph_witness_groth16_verify.h, libcwc_r1cs.so) ------------------------------------------------

@@ -1,12 +1,20 @@
 // groth16-setup [--trapdoor FILE] <circuit.r1cs> <circuit.zkey> [verification_key.json]: a Groth16 proving key for the
 // circuit, made on the GPU (the single-party equivalent of snarkjs `groth16 setup`; include/graph_witness_groth16_setup.h).
 // The trapdoor is drawn and discarded, or read from FILE: five decimal integers tau, alpha, beta, gamma, delta separated by
-// whitespace, each in [1, r) (for reproducible keys).  With a third path the verifying key is written too, in snarkjs's
+// whitespace, each in [1, r) (for reproducible keys).
+// groth16-setup --ptau FILE [--delta FILE] [--lagrange auto|file|compute] <circuit.r1cs> <circuit.zkey> [verification_key.json]:
+// the key from a powers-of-tau file, which is mapped into memory, not read (include/graph_witness_groth16_ptau.h): tau, alpha
+// and beta are the ceremony's, gamma is 1, and delta is drawn and discarded or read from FILE (one decimal integer in [1, r);
+// 1 gives the state of snarkjs `zkey new`).  --ptau and --trapdoor exclude each other.  With a third path the verifying key is written too, in snarkjs's
 // verification_key.json shape with vk_alphabeta_12.  Exit status 0 on success; 2 on a usage, file or format error.  Every
 // input is parsed before the device is touched.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <fstream>
@@ -14,6 +22,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/graph_witness_groth16_ptau.h"
 #include "../../include/graph_witness_groth16_setup.h"
 #include "../../include/graph_witness_groth16_verify.h"
 
@@ -70,13 +79,13 @@ static bool parse_decimal(const std::string& tok, uint8_t* le) {
     return true;
 }
 
-static bool parse_trapdoor(const char* path, gwb_groth16_trapdoor_t* t) {
+// the whitespace-separated tokens of a file of secrets; the file's text is zeroed
+static bool read_tokens(const char* path, std::vector<std::string>& toks) {
     std::vector<char> text;
     if (!read_file(path, text)) {
         fprintf(stderr, "error: cannot read %s\n", path);
         return false;
     }
-    std::vector<std::string> toks;
     std::string cur;
     for (char c : text) {
         if (c == ' ' || c == '\n' || c == '\r' || c == '\t') {
@@ -88,6 +97,12 @@ static bool parse_trapdoor(const char* path, gwb_groth16_trapdoor_t* t) {
     }
     if (!cur.empty()) toks.push_back(cur);
     std::fill(text.begin(), text.end(), 0);
+    return true;
+}
+
+static bool parse_trapdoor(const char* path, gwb_groth16_trapdoor_t* t) {
+    std::vector<std::string> toks;
+    if (!read_tokens(path, toks)) return false;
     if (toks.size() != 5) {
         fprintf(stderr, "error: %s: %zu values, 5 expected (tau alpha beta gamma delta)\n", path, toks.size());
         return false;
@@ -101,6 +116,45 @@ static bool parse_trapdoor(const char* path, gwb_groth16_trapdoor_t* t) {
         }
     return true;
 }
+
+static bool parse_delta(const char* path, uint8_t* delta) {
+    std::vector<std::string> toks;
+    if (!read_tokens(path, toks)) return false;
+    if (toks.size() != 1) {
+        fprintf(stderr, "error: %s: %zu values, 1 expected (delta)\n", path, toks.size());
+        return false;
+    }
+    if (!parse_decimal(toks[0], delta)) {
+        fprintf(stderr, "error: %s: delta is not a decimal integer below 2^256\n", path);
+        return false;
+    }
+    return true;
+}
+
+// a file mapped read-only; size 0 maps nothing
+struct Mapped {
+    void* data = NULL;
+    size_t len = 0;
+    bool open(const char* path) {
+        const int fd = ::open(path, O_RDONLY);
+        if (fd < 0) return false;
+        struct stat st;
+        bool ok = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
+        if (ok && st.st_size > 0) {
+            void* p = mmap(NULL, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+            ok = p != MAP_FAILED;
+            if (ok) {
+                data = p;
+                len = (size_t)st.st_size;
+            }
+        }
+        close(fd);
+        return ok;
+    }
+    ~Mapped() {
+        if (data) munmap(data, len);
+    }
+};
 
 static std::string g1_json(const uint8_t* p) {
     bool inf = true;
@@ -157,21 +211,38 @@ static bool vk_json(const void* zkey, size_t len, std::string& out, std::string&
 }
 
 int main(int argc, char** argv) {
-    const char* trapdoor_path = NULL;
+    const char *trapdoor_path = NULL, *ptau_path = NULL, *delta_path = NULL, *lagrange = NULL;
     std::vector<const char*> pos;
-    for (int i = 1; i < argc; ++i) {
-        if (strcmp(argv[i], "--trapdoor") == 0) {
-            if (i + 1 >= argc || trapdoor_path) {
-                pos.clear();
-                break;
-            }
-            trapdoor_path = argv[++i];
-        } else {
+    bool usage = false;
+    for (int i = 1; i < argc && !usage; ++i) {
+        const char** opt = strcmp(argv[i], "--trapdoor") == 0 ? &trapdoor_path
+                           : strcmp(argv[i], "--ptau") == 0   ? &ptau_path
+                           : strcmp(argv[i], "--delta") == 0  ? &delta_path
+                           : strcmp(argv[i], "--lagrange") == 0 ? &lagrange
+                                                                : NULL;
+        if (!opt)
             pos.push_back(argv[i]);
-        }
+        else if (i + 1 >= argc || *opt)
+            usage = true;
+        else
+            *opt = argv[++i];
     }
-    if (pos.size() != 2 && pos.size() != 3) {
-        fprintf(stderr, "usage: %s [--trapdoor FILE] <circuit.r1cs> <circuit.zkey> [verification_key.json]\n", argv[0]);
+    uint32_t mode = GWB_PTAU_LAGRANGE_AUTO;
+    if (lagrange) {
+        if (strcmp(lagrange, "file") == 0)
+            mode = GWB_PTAU_LAGRANGE_FILE;
+        else if (strcmp(lagrange, "compute") == 0)
+            mode = GWB_PTAU_LAGRANGE_COMPUTE;
+        else if (strcmp(lagrange, "auto") != 0)
+            usage = true;
+    }
+    // --ptau and --trapdoor exclude each other; --delta and --lagrange belong to --ptau
+    if ((ptau_path && trapdoor_path) || (!ptau_path && (delta_path || lagrange))) usage = true;
+    if (usage || (pos.size() != 2 && pos.size() != 3)) {
+        fprintf(stderr,
+                "usage: %s [--trapdoor FILE] <circuit.r1cs> <circuit.zkey> [verification_key.json]\n"
+                "       %s --ptau FILE [--delta FILE] [--lagrange auto|file|compute] <circuit.r1cs> <circuit.zkey> [verification_key.json]\n",
+                argv[0], argv[0]);
         return 2;
     }
     std::vector<char> file;
@@ -191,11 +262,41 @@ int main(int argc, char** argv) {
         gwb_r1cs_free(r);
         return 2;
     }
-    fprintf(stderr, "groth16-setup: single-party setup: whoever holds the trapdoor can forge proofs for this key; %s\n",
-            trapdoor_path ? "it was read from a file, which remains" : "a drawn trapdoor is discarded before the key is written");
+    Mapped ptau;
+    uint8_t delta[32];
+    if (ptau_path) {
+        if (!ptau.open(ptau_path)) {
+            fprintf(stderr, "error: cannot read %s\n", ptau_path);
+            gwb_r1cs_free(r);
+            return 2;
+        }
+        gwb_ptau_info_t pi;
+        if (gwb_ptau_info(ptau.data, ptau.len, &pi, &st) != 0) {
+            fprintf(stderr, "error: %s: %s\n", ptau_path, st.error_msg ? st.error_msg : "load failed");
+            gw_free_status(&st);
+            gwb_r1cs_free(r);
+            return 2;
+        }
+        if (delta_path && !parse_delta(delta_path, delta)) {
+            gwb_r1cs_free(r);
+            return 2;
+        }
+    }
     void* zkey = NULL;
     size_t len = 0;
-    const int rc = gwb_groth16_setup(r, trapdoor_path ? &t : NULL, &zkey, &len, &st);
+    int rc;
+    if (ptau_path) {
+        fprintf(stderr,
+                "groth16-setup: tau, alpha and beta are those of the ceremony behind %s, which is not verified here; single-party phase 2: "
+                "whoever holds delta can forge proofs for this key; %s\n",
+                ptau_path, delta_path ? "it was read from a file, which remains" : "a drawn delta is discarded before the key is written");
+        rc = gwb_groth16_setup_ptau(r, ptau.data, ptau.len, delta_path ? delta : NULL, mode, &zkey, &len, &st);
+        explicit_bzero(delta, sizeof delta);
+    } else {
+        fprintf(stderr, "groth16-setup: single-party setup: whoever holds the trapdoor can forge proofs for this key; %s\n",
+                trapdoor_path ? "it was read from a file, which remains" : "a drawn trapdoor is discarded before the key is written");
+        rc = gwb_groth16_setup(r, trapdoor_path ? &t : NULL, &zkey, &len, &st);
+    }
     explicit_bzero(&t, sizeof t);
     gwb_r1cs_free(r);
     if (rc != 0) {

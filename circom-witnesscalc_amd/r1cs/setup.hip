@@ -49,6 +49,7 @@
 #include "fq_gfx950.hpp"
 #include "groth16_internal.hpp"
 #include "lincomb.hpp"
+#include "ptau_internal.hpp"
 
 namespace cwc_r1cs {
 std::string hip_err(const char* what, hipError_t e);  // check.hip
@@ -57,6 +58,7 @@ std::string hip_err(const char* what, hipError_t e);  // check.hip
 using namespace cwc_r1cs;
 using namespace cwc_g16;
 using cwc::Fr;
+using cwc_setup::Columns;
 
 namespace {
 
@@ -334,6 +336,10 @@ void enqueue_affine(const void* d_xyzz, uint32_t n, uint8_t* d_out, bool canonic
                        d_out, canonical ? 1u : 0u);
 }
 
+}  // namespace
+
+namespace cwc_setup {
+
 uint32_t segment_terms() {  // CWC_GROTH16_SETUP_SEGMENT: terms per segment of a column; 0 = columns are not split (measurement aid)
     const char* s = getenv("CWC_GROTH16_SETUP_SEGMENT");
     if (!s || !*s) return SEGMENT_DEFAULT;
@@ -341,13 +347,7 @@ uint32_t segment_terms() {  // CWC_GROTH16_SETUP_SEGMENT: terms per segment of a
     return v == 0 || v > 0xffffffffull ? 0xffffffffu : (uint32_t)v;
 }
 
-// The by-wire transpose of the handle's matrices: the terms of column (wire, matrix), key 3 wire + matrix, in key order.
-struct Columns {
-    std::vector<uint32_t> ent, cidx;           // per term: constraint (file index) | kind << 30; coefficient index
-    std::vector<uint32_t> seg_off, seg_key;    // segments: terms seg_off[s] .. seg_off[s + 1] of column seg_key[s]
-    std::vector<uint32_t> wire_seg;            // wire i's segments: wire_seg[i] .. wire_seg[i + 1]
-};
-
+// The by-wire transpose of the handle's matrices (Columns: ptau_internal.hpp)
 void transpose(const gwb_r1cs* r, uint32_t segment, Columns& c) {
     const uint32_t nw = r->info.n_wires, nc = r->info.n_constraints;
     const size_t n_terms = r->fac.size();
@@ -382,6 +382,26 @@ void transpose(const gwb_r1cs* r, uint32_t segment, Columns& c) {
     c.wire_seg[nw] = (uint32_t)c.seg_key.size();
     c.seg_off.push_back((uint32_t)n_terms);
 }
+
+void generator_bytes(uint8_t* g1, uint8_t* g2) {
+    const Affine<G1> a = g1_generator();
+    const Affine<G2> b = g2_generator();
+    memcpy(g1, &a, G1_BYTES);
+    memcpy(g2, &b, G2_BYTES);
+}
+
+void enqueue_affine_g1(const void* d_xyzz, uint32_t n, uint8_t* d_out, bool canonical, void* stream) {
+    enqueue_affine<G1>(d_xyzz, n, d_out, canonical, (hipStream_t)stream);
+}
+void enqueue_affine_g2(const void* d_xyzz, uint32_t n, uint8_t* d_out, bool canonical, void* stream) {
+    enqueue_affine<G2>(d_xyzz, n, d_out, canonical, (hipStream_t)stream);
+}
+
+}  // namespace cwc_setup
+
+using namespace cwc_setup;
+
+namespace {
 
 // Host copies of the trapdoor and what is derived from it; zeroed when the call leaves.
 struct Secrets {
@@ -485,8 +505,10 @@ void put32(std::vector<uint8_t>& v, uint32_t x) { v.insert(v.end(), (const uint8
 void put64(std::vector<uint8_t>& v, uint64_t x) { v.insert(v.end(), (const uint8_t*)&x, (const uint8_t*)&x + 8); }
 void put_fr(std::vector<uint8_t>& v, const Fr& x) { v.insert(v.end(), (const uint8_t*)x.v, (const uint8_t*)x.v + 32); }
 
+}  // namespace
+
 // section 4 as snarkjs `zkey new` lays it out (values value R^2 mod r)
-bool coefficients_section(const gwb_r1cs* r, std::vector<uint8_t>& out, std::string& err) {
+bool cwc_setup::coefficients_section(const gwb_r1cs* r, std::vector<uint8_t>& out, std::string& err) {
     const uint32_t nc = r->info.n_constraints, n_pub = r->info.n_pub_out + r->info.n_pub_in;
     const uint64_t count = r->info.n_factors_a + r->info.n_factors_b + n_pub + 1;
     if (count > 0xffffffffull) {
@@ -518,11 +540,61 @@ bool coefficients_section(const gwb_r1cs* r, std::vector<uint8_t>& out, std::str
     return true;
 }
 
+namespace {
+
 void put_section(std::vector<uint8_t>& v, uint32_t id, const uint8_t* p, size_t n) {
     put32(v, id);
     put64(v, n);
     v.insert(v.end(), p, p + n);
 }
+
+}  // namespace
+
+// -- the file: sections 1 to 10 in ascending order
+int cwc_setup::write_zkey(const KeyPoints& k, const std::vector<uint8_t>& sec4, void** zkey, size_t* zkey_len, gw_status_t* status) {
+    const uint32_t nw = k.n_wires, n_pub = k.n_pub, n = k.n;
+    std::vector<uint8_t> hdr;
+    put32(hdr, 32);
+    put_fr(hdr, fq_p());
+    put32(hdr, 32);
+    put_fr(hdr, cwc::fr_p());
+    put32(hdr, nw);
+    put32(hdr, n_pub);
+    put32(hdr, n);
+    hdr.insert(hdr.end(), k.alpha1, k.alpha1 + G1_BYTES);
+    hdr.insert(hdr.end(), k.beta1, k.beta1 + G1_BYTES);
+    hdr.insert(hdr.end(), k.beta2, k.beta2 + G2_BYTES);
+    hdr.insert(hdr.end(), k.gamma2, k.gamma2 + G2_BYTES);
+    hdr.insert(hdr.end(), k.delta1, k.delta1 + G1_BYTES);
+    hdr.insert(hdr.end(), k.delta2, k.delta2 + G2_BYTES);
+    const size_t n1 = 3 * (size_t)nw + n, points = n1 * G1_BYTES + (size_t)nw * G2_BYTES;
+    std::vector<uint8_t> out;
+    out.reserve(12 + 10 * 12 + 4 + hdr.size() + sec4.size() + points + 68);
+    out.insert(out.end(), {'z', 'k', 'e', 'y'});
+    put32(out, 1);
+    put32(out, 10);
+    const uint32_t protocol = 1;
+    put_section(out, 1, (const uint8_t*)&protocol, 4);
+    put_section(out, 2, hdr.data(), hdr.size());
+    put_section(out, 3, k.ic, (size_t)(n_pub + 1) * G1_BYTES);
+    put_section(out, 4, sec4.data(), sec4.size());
+    put_section(out, 5, k.a, (size_t)nw * G1_BYTES);
+    put_section(out, 6, k.b1, (size_t)nw * G1_BYTES);
+    put_section(out, 7, k.b2, (size_t)nw * G2_BYTES);
+    put_section(out, 8, k.c, (size_t)(nw - n_pub - 1) * G1_BYTES);
+    put_section(out, 9, k.h, (size_t)n * G1_BYTES);
+    const uint8_t no_contributions[68] = {};  // 64 zero bytes in place of the circuit hash, then u32 0 contributions
+    put_section(out, 10, no_contributions, sizeof no_contributions);
+    void* buf = malloc(out.size());
+    if (!buf) return fail(status, "groth16 setup: out of host memory");
+    memcpy(buf, out.data(), out.size());
+    *zkey = buf;
+    *zkey_len = out.size();
+    set_ok(status);
+    return 0;
+}
+
+namespace {
 
 int setup(gwb_r1cs* r, const gwb_groth16_trapdoor_t* trapdoor, void** zkey, size_t* zkey_len, gw_status_t* status) {
     gwb_r1cs_qap_info_t qi;
@@ -622,46 +694,11 @@ int setup(gwb_r1cs* r, const gwb_groth16_trapdoor_t* trapdoor, void** zkey, size
         g_phase_valid = ok;
     }
 
-    // -- the file: sections 1 to 10 in ascending order
     const uint8_t *a = p1.data(), *b1 = a + (size_t)nw * G1_BYTES, *c = b1 + (size_t)nw * G1_BYTES,
                   *h = c + (size_t)(nw - n_pub - 1) * G1_BYTES, *ic = h + (size_t)n * G1_BYTES, *k1 = ic + (size_t)(n_pub + 1) * G1_BYTES;
     const uint8_t *b2 = p2.data(), *k2 = b2 + (size_t)nw * G2_BYTES;
-    std::vector<uint8_t> hdr;
-    put32(hdr, 32);
-    put_fr(hdr, fq_p());
-    put32(hdr, 32);
-    put_fr(hdr, cwc::fr_p());
-    put32(hdr, nw);
-    put32(hdr, n_pub);
-    put32(hdr, n);
-    hdr.insert(hdr.end(), k1, k1 + 2 * G1_BYTES);                                // alpha1, beta1
-    hdr.insert(hdr.end(), k2, k2 + 2 * G2_BYTES);                                // beta2, gamma2
-    hdr.insert(hdr.end(), k1 + 2 * G1_BYTES, k1 + 3 * G1_BYTES);                 // delta1
-    hdr.insert(hdr.end(), k2 + 2 * G2_BYTES, k2 + 3 * G2_BYTES);                 // delta2
-    std::vector<uint8_t> out;
-    out.reserve(12 + 10 * 12 + 4 + hdr.size() + sec4.size() + p1.size() + p2.size() + 68);
-    out.insert(out.end(), {'z', 'k', 'e', 'y'});
-    put32(out, 1);
-    put32(out, 10);
-    const uint32_t protocol = 1;
-    put_section(out, 1, (const uint8_t*)&protocol, 4);
-    put_section(out, 2, hdr.data(), hdr.size());
-    put_section(out, 3, ic, (size_t)(n_pub + 1) * G1_BYTES);
-    put_section(out, 4, sec4.data(), sec4.size());
-    put_section(out, 5, a, (size_t)nw * G1_BYTES);
-    put_section(out, 6, b1, (size_t)nw * G1_BYTES);
-    put_section(out, 7, b2, (size_t)nw * G2_BYTES);
-    put_section(out, 8, c, (size_t)(nw - n_pub - 1) * G1_BYTES);
-    put_section(out, 9, h, (size_t)n * G1_BYTES);
-    const uint8_t no_contributions[68] = {};  // 64 zero bytes in place of the circuit hash, then u32 0 contributions
-    put_section(out, 10, no_contributions, sizeof no_contributions);
-    void* buf = malloc(out.size());
-    if (!buf) return fail(status, "groth16 setup: out of host memory");
-    memcpy(buf, out.data(), out.size());
-    *zkey = buf;
-    *zkey_len = out.size();
-    set_ok(status);
-    return 0;
+    const KeyPoints kp{nw, n_pub, n, k1, k1 + G1_BYTES, k2, k2 + G2_BYTES, k1 + 2 * G1_BYTES, k2 + 2 * G2_BYTES, ic, a, b1, b2, c, h};
+    return write_zkey(kp, sec4, zkey, zkey_len, status);
 }
 
 }  // namespace

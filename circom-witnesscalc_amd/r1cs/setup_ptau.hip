@@ -1,0 +1,643 @@
+// Groth16 setup from a powers-of-tau file on gfx950 (include/graph_witness_groth16_ptau.h has the definition): no trapdoor, so no
+// scalars to multiply generators by; every key point is a linear combination of the ceremony's points.  The host side that
+// does not depend on where the points come from (column transpose and segments, section 4, conversion to affine, the zkey
+// image) is setup.hip's (ptau_internal.hpp); the `.ptau` itself is read by ptau.cc.
+//
+// Loading.  The prefixes that are read are uploaded as stored; one thread per point checks the coordinate ranges and the curve
+// equation and writes the point in XYZZ form (ZZ = ZZZ = 1, or 0 for infinity).  The first fault of an array goes to a flag
+// word with atomicMin; the host turns it into the loader's message after the call's one synchronisation.
+//
+// Group inverse DFT.  Radix 2, decimation in time, in place on XYZZ points in global memory: the load writes point i to slot
+// bitrev(i); stage s (half = 2^s) takes, for k < half and every group of 2 half slots, a = x[j], c = w_N^(-k N / (2 half))
+// x[j + half] and writes a + c, a - c; the output is in natural order.  A twiddle is a 254-bit scalar, so a butterfly is one
+// variable-base multiplication (xyzz_mul_short: double and add from the scalar's top word) and two additions; k = 0 has no
+// multiplication (all of stage 0, and one butterfly per group after it).  The twiddles w_N^(-k), k < N / 2, are computed once
+// per call into a table of canonical values.  While a stage has 64 or more groups, a wave's lanes take the same k in 64
+// groups: the scalar is the same in every lane, so the wave skips the additions of the scalar's zero bits together instead
+// of executing both sides of the branch.  In the last six stages the lanes take consecutive k (coalesced, divergent).  The
+// factor 1 / N is appended: one more multiplication per point, (N / 2)(m - 1) + N in all.  Several transforms of one size
+// (L1, LA, LB and H's) run as one launch per stage.  The conversion to affine is the shared-inversion kernel of setup.hip,
+// once, at the end of the call (the column sums read XYZZ).
+//
+// H needs only the odd outputs of the 2n-point transform M of T1.  With g = w_2n:
+//   M_{2j+1} = (1 / 2n) sum_{i<n} w_n^(-j i) D_i,   D_i = g^(-i) (T1_i - T1_{i+n}),
+// so one pass forms D (n multiplications) and the n-point transform follows, with 1 / 2n as its appended factor.
+//
+// Column sums.  As in setup.hip, with points for values: one thread per segment of at most 64 terms forms sum coef P, one
+// thread per wire adds its segments.  A term with coefficient +1 or -1 (most terms of a real circuit) is one addition; a
+// general coefficient c above r / 2 is applied as -((r - c) P).  Three segment passes: L1 for all three matrices (A, B1, and
+// C's part of K), LB for A's and LA for B's segments (the rest of K), L2 for B's segments (B2).
+//
+// delta.  C and H lie next to each other in the G1 list and are multiplied by 1 / delta in one launch, which delta = 1
+// skips; delta1 and delta2 are the generators times delta.  delta and 1 / delta reach the kernels through a device buffer
+// that is zeroed before it is released.
+//
+// Registers (hipcc -Rpass-analysis=kernel-resource-usage for gfx950; every kernel: 0 bytes of scratch; VGPRs + AGPRs, waves / SIMD):
+//   load_kernel<G1> 69, 7           load_kernel<G2> 121, 4            twiddle_kernel 36, 8        put_fr_kernel 10, 8
+//   idft_stage_kernel<G1> 188, 2    idft_stage_kernel<G2> 256 + 170, 1     odd_half_kernel<G1> 152, 3
+//   scale_kernel<G1> 114, 4         scale_kernel<G2> 256 + 1, 1
+//   segments_kernel<G1> 186, 2      segments_kernel<G2> 256 + 151, 1
+//   wires_g1_kernel 232, 2          wires_one_kernel<G2> 246, 2
+// Launch bounds of 256 threads are one wave per SIMD, which leaves the allocator all 512 registers; the G2 butterfly holds the
+// multiplicand, the accumulator and the other operand (64 registers each) across an inlined double-and-add.
+#include <hip/hip_runtime.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <mutex>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/graph_witness_groth16_ptau.h"
+#include "fq_gfx950.hpp"
+#include "groth16_internal.hpp"
+#include "ptau_internal.hpp"
+
+namespace cwc_r1cs {
+std::string hip_err(const char* what, hipError_t e);  // check.hip
+}
+
+using namespace cwc_r1cs;
+using namespace cwc_g16;
+using namespace cwc_setup;
+using cwc::Fr;
+
+namespace {
+
+using G1 = FqT;
+using G2 = Fq2T;
+
+constexpr uint32_t THREADS = 256;
+constexpr uint32_t MAX_LOG_N = 27;
+constexpr unsigned long long NO_FAULT = ~0ull;
+
+struct Pows {
+    Fr v[MAX_LOG_N + 1];  // base^(2^b), Montgomery form
+};
+
+// k p for a canonical k: double and add from the top nonzero word of k (inside it the doublings of infinity return at once)
+template <class T>
+__device__ __forceinline__ Xyzz<T> xyzz_mul_short(const Xyzz<T>& p, const Fr& k) {
+    Xyzz<T> acc = xyzz_inf<T>();
+    Fr kk = k;  // words move up into kk.v[7] (constant indices: no stack copy of k)
+    for (int w = 0; w < 8; ++w) {
+        const uint32_t word = kk.v[7];
+        if (word != 0 || !xyzz_is_inf(acc)) {
+            for (int b = 31; b >= 0; --b) {
+                acc = xyzz_dbl(acc);
+                if ((word >> b) & 1u) acc = xyzz_add(acc, p);
+            }
+        }
+#pragma unroll
+        for (int i = 7; i > 0; --i) kk.v[i] = kk.v[i - 1];
+    }
+    return acc;
+}
+
+template <class T>
+__device__ __forceinline__ bool get_coords(const uint8_t* in, typename T::E& x, typename T::E& y, bool canonical);
+template <>
+__device__ __forceinline__ bool get_coords<G1>(const uint8_t* in, Fq& x, Fq& y, bool canonical) {
+    const Fq* c = reinterpret_cast<const Fq*>(in);
+    const Fq a = c[0], b = c[1];
+    const bool ok = cwc::both(cwc::u256_lt(a, fq_p()), cwc::u256_lt(b, fq_p()));
+    x = canonical ? fq_to_mont(a) : a;
+    y = canonical ? fq_to_mont(b) : b;
+    return ok;
+}
+template <>
+__device__ __forceinline__ bool get_coords<G2>(const uint8_t* in, Fq2& x, Fq2& y, bool canonical) {
+    const Fq* c = reinterpret_cast<const Fq*>(in);
+    const Fq a = c[0], b = c[1], d = c[2], e = c[3];
+    const bool ok = cwc::both(cwc::both(cwc::u256_lt(a, fq_p()), cwc::u256_lt(b, fq_p())), cwc::both(cwc::u256_lt(d, fq_p()), cwc::u256_lt(e, fq_p())));
+    x = Fq2{canonical ? fq_to_mont(a) : a, canonical ? fq_to_mont(b) : b};
+    y = Fq2{canonical ? fq_to_mont(d) : d, canonical ? fq_to_mont(e) : e};
+    return ok;
+}
+
+// out[slot(i)] = the affine point in[first + i stride] in XYZZ form, slot(i) = i or, for rev_bits != 0, i's rev_bits bits
+// reversed.  flag != nullptr: the point is checked, and the smallest 2 i + fault of the array is left in *flag.
+template <class T>
+__global__ __launch_bounds__(THREADS) void load_kernel(const uint8_t* __restrict__ in, uint32_t n, uint32_t first, uint32_t stride, uint32_t canonical,
+                                                       uint32_t rev_bits, typename T::E curve_b, Xyzz<T>* __restrict__ out,
+                                                       unsigned long long* __restrict__ flag) {
+    using E = typename T::E;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    E x, y;
+    const bool in_range = get_coords<T>(in + ((size_t)first + (size_t)i * stride) * (2 * sizeof(E)), x, y, canonical != 0);
+    Xyzz<T> p = xyzz_inf<T>();
+    if (!cwc::both(T::is_zero(x), T::is_zero(y))) p = Xyzz<T>{x, y, T::one(), T::one()};
+    if (flag) {
+        if (!in_range) {
+            atomicMin(flag, 2ull * i + cwc_ptau::COORDINATE);
+            p = xyzz_inf<T>();
+        } else if (!xyzz_is_inf(p) && !on_curve(Affine<T>{x, y}, curve_b)) {
+            atomicMin(flag, 2ull * i + cwc_ptau::CURVE);
+            p = xyzz_inf<T>();
+        }
+    }
+    out[rev_bits ? __brev(i) >> (32 - rev_bits) : i] = p;
+}
+
+// out[k] = base^k, canonical, for k < count (bp.v[b] = base^(2^b))
+__global__ __launch_bounds__(THREADS) void twiddle_kernel(Fr* __restrict__ out, uint32_t count, Pows bp) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    Fr x = cwc::fr_one();
+    for (uint32_t b = 0; b <= MAX_LOG_N; ++b)
+        if ((k >> b) & 1u) x = cwc::fr_mul(x, bp.v[b]);
+    out[k] = cwc::fr_from_mont(x);
+}
+
+// stage s of `batch` transforms of 2^log_n points each, transform t in x[t 2^log_n ..); tw[k] = w_N^(-k) for k < N / 2
+template <class T>
+__global__ __launch_bounds__(THREADS) void idft_stage_kernel(Xyzz<T>* __restrict__ x, uint32_t log_n, uint32_t s, uint32_t batch,
+                                                             const Fr* __restrict__ tw) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t per = 1u << (log_n - 1);  // butterflies per transform
+    if (t >= (uint64_t)batch * per) return;
+    const uint32_t u = (uint32_t)t & (per - 1), half = 1u << s, groups = per >> s;
+    uint32_t k, grp;
+    if (groups >= 64) {  // a wave: one k, 64 groups
+        grp = u & (groups - 1);
+        k = u >> (log_n - 1 - s);
+    } else {
+        k = u & (half - 1);
+        grp = u >> s;
+    }
+    Xyzz<T>* lo = x + ((t >> (log_n - 1)) << log_n) + ((size_t)grp << (s + 1)) + k;
+    const Xyzz<T> a = lo[0];
+    Xyzz<T> c = lo[half];
+    if (k) c = xyzz_mul_short(c, tw[(size_t)k * groups]);
+    lo[0] = xyzz_add(a, c);
+    lo[half] = xyzz_add(a, xyzz_neg(c));
+}
+
+// d[bitrev(i)] = g^(-i) (t[i] - t[i + n]) for i < n = 2^log_n; twg[i] = g^(-i)
+template <class T>
+__global__ __launch_bounds__(THREADS) void odd_half_kernel(const Xyzz<T>* __restrict__ t, uint32_t log_n, const Fr* __restrict__ twg,
+                                                           Xyzz<T>* __restrict__ d) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, n = 1u << log_n;
+    if (i >= n) return;
+    Xyzz<T> c = xyzz_add(t[i], xyzz_neg(t[(size_t)i + n]));
+    if (i) c = xyzz_mul_short(c, twg[i]);
+    d[__brev(i) >> (32 - log_n)] = c;
+}
+
+// *out = v: a scalar for scale_kernel, without a copy from host memory that the stream would have to wait for
+__global__ __launch_bounds__(64) void put_fr_kernel(Fr* __restrict__ out, Fr v) {
+    if (threadIdx.x == 0) *out = v;
+}
+
+// x[i] = k x[i] for i < count
+template <class T>
+__global__ __launch_bounds__(THREADS) void scale_kernel(Xyzz<T>* __restrict__ x, uint32_t count, const Fr* __restrict__ k) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    x[i] = xyzz_mul_short(x[i], *k);
+}
+
+// part[s] = sum of coefficient x pts[constraint] over the terms ent[seg_off[s] .. seg_off[s + 1]) of one (wire, matrix)
+// column; the points of matrix m are pm (nullptr: the pass leaves this matrix out, part[s] = O)
+template <class T>
+__global__ __launch_bounds__(THREADS) void segments_kernel(const uint32_t* __restrict__ ent, const uint32_t* __restrict__ cidx,
+                                                           const Fr* __restrict__ coef, const uint32_t* __restrict__ seg_off,
+                                                           const uint32_t* __restrict__ seg_key, uint32_t n_seg, const Xyzz<T>* __restrict__ p0,
+                                                           const Xyzz<T>* __restrict__ p1, const Xyzz<T>* __restrict__ p2,
+                                                           Xyzz<T>* __restrict__ part) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_seg) return;
+    const uint32_t m = seg_key[s] % 3u;
+    const Xyzz<T>* pts = m == 0 ? p0 : m == 1 ? p1 : p2;
+    Xyzz<T> acc = xyzz_inf<T>();
+    if (pts) {
+        Fr half_r = cwc::fr_p();  // (r - 1) / 2
+        half_r = cwc::u256_shr(half_r, 1);
+        for (uint32_t j = seg_off[s], end = seg_off[s + 1]; j < end; ++j) {
+            const uint32_t e = ent[j], kind = e >> 30;
+            Xyzz<T> q = pts[e & WIRE_MASK];
+            bool minus = kind == KIND_MINUS;
+            if (kind == KIND_GENERAL) {
+                Fr c = cwc::fr_from_mont(coef[cidx[j]]);
+                minus = cwc::u256_lt(half_r, c);
+                Fr nc;
+                cwc::u256_sub(nc, cwc::fr_p(), c);
+                c = cwc::u256_select(minus, nc, c);
+                q = xyzz_mul_short(q, c);
+            }
+            acc = xyzz_add(acc, minus ? xyzz_neg(q) : q);
+        }
+    }
+    part[s] = acc;
+}
+
+// The G1 points of wire i from its segments (seg_key = 3 wire + matrix): pa holds the L1 pass (A, B1 and C's part of K), pk
+// the LB / LA pass (the rest of K).  list = [A: nW][B1: nW][C: nW - nPub - 1][H: n][IC: nPub + 1][delta1]; K goes to IC or C.
+__global__ __launch_bounds__(THREADS) void wires_g1_kernel(const Xyzz<G1>* __restrict__ pa, const Xyzz<G1>* __restrict__ pk,
+                                                           const uint32_t* __restrict__ seg_key, const uint32_t* __restrict__ wire_seg,
+                                                           const Xyzz<G1>* __restrict__ l1, const Xyzz<G1>* __restrict__ lb, uint32_t n_wires,
+                                                           uint32_t n_constraints, uint32_t n_pub, uint32_t n, Xyzz<G1>* __restrict__ list) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_wires) return;
+    Xyzz<G1> a = xyzz_inf<G1>(), b = a, k = a;
+    for (uint32_t s = wire_seg[i], end = wire_seg[i + 1]; s < end; ++s) {
+        const uint32_t m = seg_key[s] - 3u * i;
+        const Xyzz<G1> p = pa[s];
+        if (m == 2) {
+            k = xyzz_add(k, p);
+        } else {
+            k = xyzz_add(k, pk[s]);
+            if (m == 0)
+                a = xyzz_add(a, p);
+            else
+                b = xyzz_add(b, p);
+        }
+    }
+    if (i <= n_pub) {
+        a = xyzz_add(a, l1[n_constraints + i]);
+        k = xyzz_add(k, lb[n_constraints + i]);
+    }
+    const size_t off_c = 2 * (size_t)n_wires, off_ic = off_c + (n_wires - n_pub - 1) + n;
+    list[i] = a;
+    list[(size_t)n_wires + i] = b;
+    list[i <= n_pub ? off_ic + i : off_c + (i - n_pub - 1)] = k;
+}
+
+// out[i] = the sum of wire i's segments of matrix m
+template <class T>
+__global__ __launch_bounds__(THREADS) void wires_one_kernel(const Xyzz<T>* __restrict__ part, const uint32_t* __restrict__ seg_key,
+                                                            const uint32_t* __restrict__ wire_seg, uint32_t n_wires, uint32_t m,
+                                                            Xyzz<T>* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_wires) return;
+    Xyzz<T> acc = xyzz_inf<T>();
+    for (uint32_t s = wire_seg[i], end = wire_seg[i + 1]; s < end; ++s)
+        if (seg_key[s] - 3u * i == m) acc = xyzz_add(acc, part[s]);
+    out[i] = acc;
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------------
+
+uint32_t blocks_for(uint64_t threads) { return (uint32_t)std::max<uint64_t>(1, (threads + THREADS - 1) / THREADS); }
+
+Fq g1_b() { return fq_to_mont(Fq{{3, 0, 0, 0, 0, 0, 0, 0}}); }
+Fq2 g2_b() {  // 3 / (9 + u), Montgomery form
+    const Fq2 t{fq_to_mont(Fq{{9, 0, 0, 0, 0, 0, 0, 0}}), fq_one()};
+    const Fq three = fq_to_mont(Fq{{3, 0, 0, 0, 0, 0, 0, 0}});
+    const Fq2 i = fq2_inv(t);
+    return Fq2{fq_mul(i.c0, three), fq_mul(i.c1, three)};
+}
+template <class T>
+typename T::E curve_b();
+template <>
+Fq curve_b<G1>() { return g1_b(); }
+template <>
+Fq2 curve_b<G2>() { return g2_b(); }
+
+Pows powers_of(Fr base) {  // Montgomery form
+    Pows p;
+    p.v[0] = base;
+    for (uint32_t b = 1; b <= MAX_LOG_N; ++b) p.v[b] = cwc::fr_mul(p.v[b - 1], p.v[b - 1]);
+    return p;
+}
+
+Fr inverse_of_u32(uint32_t x) {  // canonical 1 / x mod r
+    return cwc::fr_from_mont(cwc::fr_inv_fermat(cwc::fr_to_mont(Fr{{x, 0, 0, 0, 0, 0, 0, 0}})));
+}
+
+// tw[k] = w_N^(-k) for k < N / 2, N = 2^log_n
+void enqueue_twiddles(Fr* tw, uint32_t log_n, hipStream_t s) {
+    Fr wn, g;
+    qap_roots(log_n, wn, g);
+    const uint32_t count = 1u << (log_n - 1);
+    hipLaunchKernelGGL(twiddle_kernel, dim3(blocks_for(count)), dim3(THREADS), 0, s, tw, count, powers_of(cwc::fr_inv_fermat(wn)));
+}
+
+template <class T>
+void enqueue_load(const uint8_t* d_in, uint32_t n, uint32_t first, uint32_t stride, bool canonical, uint32_t rev_bits, Xyzz<T>* out,
+                  unsigned long long* flag, hipStream_t s) {
+    hipLaunchKernelGGL(load_kernel<T>, dim3(blocks_for(n)), dim3(THREADS), 0, s, d_in, n, first, stride, canonical ? 1u : 0u, rev_bits, curve_b<T>(), out,
+                       flag);
+}
+
+// the stages of `batch` transforms in x (inputs in bit-reversed slots), without the factor 1 / N
+template <class T>
+void enqueue_stages(Xyzz<T>* x, uint32_t log_n, uint32_t batch, const Fr* tw, hipStream_t s) {
+    const uint64_t threads = (uint64_t)batch << (log_n - 1);
+    for (uint32_t st = 0; st < log_n; ++st)
+        hipLaunchKernelGGL(idft_stage_kernel<T>, dim3(blocks_for(threads)), dim3(THREADS), 0, s, x, log_n, st, batch, tw);
+}
+
+template <class T>
+void enqueue_scale(Xyzz<T>* x, uint32_t count, const Fr* d_k, hipStream_t s) {
+    if (count) hipLaunchKernelGGL(scale_kernel<T>, dim3(blocks_for(count)), dim3(THREADS), 0, s, x, count, d_k);
+}
+
+struct Carve {
+    size_t o = 0;
+    size_t take(size_t bytes) {
+        const size_t at = o;
+        o += (bytes + 255) & ~(size_t)255;
+        return at;
+    }
+};
+
+// The device side of one call.  `secret` holds delta and 1 / delta and is zeroed before it is released.
+struct Device {
+    hipStream_t s = nullptr;
+    void *secret = nullptr, *work = nullptr;
+    size_t secret_bytes = 0;
+    hipEvent_t ev[8] = {};
+    ~Device() {
+        if (secret) {
+            (void)hipMemsetAsync(secret, 0, secret_bytes, s);
+            (void)hipStreamSynchronize(s);
+            (void)hipFree(secret);
+        }
+        if (work) (void)hipFree(work);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+
+struct Delta {
+    Fr delta, delta_inv;  // canonical
+    ~Delta() { explicit_bzero(this, sizeof *this); }
+};
+
+bool take_delta(const uint8_t* given, Delta& d, std::string& err) {
+    if (given) {
+        memcpy(d.delta.v, given, 32);
+        if (cwc::u256_is_zero(d.delta) || !cwc::u256_lt(d.delta, cwc::fr_p())) {
+            err = "groth16 setup: delta is not in [1, r)";
+            return false;
+        }
+    } else {
+        do {
+            if (!draw_fr(d.delta, err)) return false;
+        } while (cwc::u256_is_zero(d.delta));
+    }
+    d.delta_inv = cwc::fr_from_mont(cwc::fr_inv_fermat(cwc::fr_to_mont(d.delta)));
+    return true;
+}
+
+std::mutex g_phase_mutex;
+float g_phase_ms[7];
+bool g_phase_valid = false;
+
+// an array of points that the device loads and checks: where its indices lie in the file, for the message
+struct Checked {
+    uint32_t section;
+    uint64_t base;
+    uint32_t first, stride;
+    bool g2;
+};
+
+int setup(gwb_r1cs* r, const uint8_t* ptau, size_t ptau_len, const uint8_t* delta, uint32_t mode, void** zkey, size_t* zkey_len, gw_status_t* status) {
+    gwb_r1cs_qap_info_t qi;
+    if (gwb_r1cs_qap_info(r, &qi, status) != 0) return 1;
+    const uint32_t p = qi.domain_power, n = (uint32_t)qi.domain_size;
+    const uint32_t nw = r->info.n_wires, nc = r->info.n_constraints, n_pub = r->info.n_pub_out + r->info.n_pub_in;
+    std::string err;
+    cwc_ptau::View view;
+    cwc_ptau::Plan pl;
+    if (!cwc_ptau::parse(ptau, ptau_len, view, err) || !cwc_ptau::plan(view, p, mode, pl, err) || !cwc_ptau::check_header_points(pl, err))
+        return fail(status, err);
+    Delta dl;
+    if (!take_delta(delta, dl, err)) return fail(status, err);
+    const bool delta_is_one = cwc::u256_eq(dl.delta, Fr{{1, 0, 0, 0, 0, 0, 0, 0}});
+    const uint64_t n1 = 3ull * nw + n + 1, n2 = (uint64_t)nw + 1;  // [A][B1][C][H][IC][delta1], [B2][delta2]
+    if (n1 > 0x7fffffffull) return fail(status, "groth16 setup: more than 2^31 - 1 points");
+    std::vector<uint8_t> sec4;
+    if (!coefficients_section(r, sec4, err)) return fail(status, err);
+    Columns col;
+    transpose(r, segment_terms(), col);
+    const uint32_t n_seg = (uint32_t)col.seg_key.size();
+    const size_t n_terms = col.ent.size();
+    const size_t X1 = sizeof(Xyzz<G1>), X2 = sizeof(Xyzz<G2>);
+    const size_t off_c = 2 * (size_t)nw, off_h = off_c + (nw - n_pub - 1);
+
+    Device D;
+    Carve cw;
+    const size_t o_ent = cw.take(n_terms * 4), o_cidx = cw.take(n_terms * 4), o_coef = cw.take(r->coef.size() * 32),
+                 o_soff = cw.take(((size_t)n_seg + 1) * 4), o_skey = cw.take((size_t)n_seg * 4), o_wseg = cw.take(((size_t)nw + 1) * 4),
+                 o_raw1 = cw.take(5ull * n * G1_BYTES),  // compute: T1 (2n), AT, BT; file: L1, LA, LB, M (2n)
+                 o_raw2 = cw.take((size_t)n * G2_BYTES), o_lag1 = cw.take(4ull * n * X1),  // L1, LA, LB and (compute) D
+                 o_t1 = cw.take(pl.from_file ? 0 : 2ull * n * X1), o_lag2 = cw.take((size_t)n * X2), o_tw = cw.take((size_t)n / 2 * 32),
+                 o_twg = cw.take((size_t)n * 32), o_pa = cw.take((size_t)n_seg * X1), o_pk = cw.take((size_t)n_seg * X1),
+                 o_pq = cw.take((size_t)n_seg * X2), o_x1 = cw.take(n1 * X1), o_x2 = cw.take(n2 * X2), o_p1 = cw.take(n1 * G1_BYTES),
+                 o_p2 = cw.take(n2 * G2_BYTES), o_flag = cw.take(8 * sizeof(unsigned long long)), o_pub = cw.take(2 * 32);
+    D.secret_bytes = 256;
+    hipError_t e = hipStreamCreateWithFlags(&D.s, hipStreamNonBlocking);
+    for (hipEvent_t& ev : D.ev)
+        if (e == hipSuccess) e = hipEventCreate(&ev);
+    if (e == hipSuccess) e = hipMalloc(&D.secret, D.secret_bytes);
+    if (e == hipSuccess) e = hipMalloc(&D.work, cw.o);
+    if (e != hipSuccess) return fail(status, hip_err("allocating the setup workspace", e));
+    uint8_t* W = (uint8_t*)D.work;
+    auto up = [&](size_t off, const void* src, size_t bytes) {
+        if (e == hipSuccess && bytes) e = hipMemcpyAsync(W + off, src, bytes, hipMemcpyHostToDevice, D.s);
+    };
+    up(o_ent, col.ent.data(), n_terms * 4);
+    up(o_cidx, col.cidx.data(), n_terms * 4);
+    up(o_coef, r->coef.data(), r->coef.size() * 32);
+    up(o_soff, col.seg_off.data(), ((size_t)n_seg + 1) * 4);
+    up(o_skey, col.seg_key.data(), (size_t)n_seg * 4);
+    up(o_wseg, col.wire_seg.data(), ((size_t)nw + 1) * 4);
+    const size_t nb1 = (size_t)n * G1_BYTES;
+    if (pl.from_file) {
+        up(o_raw1, pl.l1, nb1);
+        up(o_raw1 + nb1, pl.la, nb1);
+        up(o_raw1 + 2 * nb1, pl.lb, nb1);
+        up(o_raw1 + 3 * nb1, pl.m, 2 * nb1);
+        up(o_raw2, pl.l2, (size_t)n * G2_BYTES);
+    } else {
+        up(o_raw1, pl.t1, 2 * nb1);
+        up(o_raw1 + 2 * nb1, pl.at, nb1);
+        up(o_raw1 + 3 * nb1, pl.bt, nb1);
+        up(o_raw2, pl.t2, (size_t)n * G2_BYTES);
+    }
+    // the generators, which delta1 and delta2 are multiples of, at the end of the two lists
+    Xyzz<G1> gen1{fq_zero(), fq_zero(), fq_one(), fq_one()};
+    Xyzz<G2> gen2{Fq2T::zero(), Fq2T::zero(), Fq2T::one(), Fq2T::one()};
+    uint8_t gb1[G1_BYTES], gb2[G2_BYTES];
+    generator_bytes(gb1, gb2);
+    memcpy(&gen1, gb1, G1_BYTES);
+    memcpy(&gen2, gb2, G2_BYTES);
+    up(o_x1 + (n1 - 1) * X1, &gen1, X1);
+    up(o_x2 + (n2 - 1) * X2, &gen2, X2);
+    const Fr pub[2] = {inverse_of_u32(n), inverse_of_u32(2 * n)};
+    up(o_pub, pub, sizeof pub);
+    if (e == hipSuccess) e = hipMemsetAsync(W + o_flag, 0xff, 8 * sizeof(unsigned long long), D.s);
+    if (e == hipSuccess) e = hipMemcpyAsync(D.secret, &dl, sizeof dl, hipMemcpyHostToDevice, D.s);
+    if (e == hipSuccess) e = hipStreamSynchronize(D.s);  // the copies have left the host arrays
+    if (e != hipSuccess) return fail(status, hip_err("uploading the ceremony points and the transposed constraint matrices", e));
+    const Fr *d_delta = (const Fr*)D.secret, *d_delta_inv = d_delta + 1, *d_inv_n = (const Fr*)(W + o_pub), *d_inv_2n = d_inv_n + 1;
+
+    Xyzz<G1>*lag1 = (Xyzz<G1>*)(W + o_lag1), *l1 = lag1, *la = lag1 + n, *lb = lag1 + 2 * (size_t)n, *dd = lag1 + 3 * (size_t)n;
+    Xyzz<G1>*t1 = (Xyzz<G1>*)(W + o_t1), *x1 = (Xyzz<G1>*)(W + o_x1);
+    Xyzz<G2>*l2 = (Xyzz<G2>*)(W + o_lag2), *x2 = (Xyzz<G2>*)(W + o_x2);
+    unsigned long long* flag = (unsigned long long*)(W + o_flag);
+    Fr *tw = (Fr*)(W + o_tw), *twg = (Fr*)(W + o_twg);
+    std::vector<Checked> checked;
+    (void)hipEventRecord(D.ev[0], D.s);
+    if (pl.from_file) {
+        const uint64_t lvl = (uint64_t)n - 1;
+        checked = {{12, lvl, 0, 1, false}, {14, lvl, 0, 1, false}, {15, lvl, 0, 1, false}, {12, 2 * (uint64_t)n - 1, 1, 2, false}, {13, lvl, 0, 1, true}};
+        enqueue_load<G1>(W + o_raw1, n, 0, 1, false, 0, l1, flag + 0, D.s);
+        enqueue_load<G1>(W + o_raw1 + nb1, n, 0, 1, false, 0, la, flag + 1, D.s);
+        enqueue_load<G1>(W + o_raw1 + 2 * nb1, n, 0, 1, false, 0, lb, flag + 2, D.s);
+        enqueue_load<G1>(W + o_raw1 + 3 * nb1, n, 1, 2, false, 0, x1 + off_h, flag + 3, D.s);  // M's odd points: H before delta
+        enqueue_load<G2>(W + o_raw2, n, 0, 1, false, 0, l2, flag + 4, D.s);
+    } else {
+        checked = {{2, 0, 0, 1, false}, {4, 0, 0, 1, false}, {5, 0, 0, 1, false}, {3, 0, 0, 1, true}};
+        enqueue_load<G1>(W + o_raw1, 2 * n, 0, 1, false, 0, t1, flag + 0, D.s);
+        enqueue_load<G1>(W + o_raw1, n, 0, 1, false, p, l1, nullptr, D.s);  // T1's first half again, to the transform's slots
+        enqueue_load<G1>(W + o_raw1 + 2 * nb1, n, 0, 1, false, p, la, flag + 1, D.s);
+        enqueue_load<G1>(W + o_raw1 + 3 * nb1, n, 0, 1, false, p, lb, flag + 2, D.s);
+        enqueue_load<G2>(W + o_raw2, n, 0, 1, false, p, l2, flag + 3, D.s);
+    }
+    (void)hipEventRecord(D.ev[1], D.s);
+    if (!pl.from_file) {
+        Fr wn, g;
+        qap_roots(p, wn, g);
+        enqueue_twiddles(tw, p, D.s);
+        hipLaunchKernelGGL(twiddle_kernel, dim3(blocks_for(n)), dim3(THREADS), 0, D.s, twg, n, powers_of(cwc::fr_inv_fermat(g)));
+        hipLaunchKernelGGL(odd_half_kernel<G1>, dim3(blocks_for(n)), dim3(THREADS), 0, D.s, (const Xyzz<G1>*)t1, p, (const Fr*)twg, dd);
+        enqueue_stages<G1>(lag1, p, 4, tw, D.s);
+        enqueue_scale<G1>(lag1, 3 * n, d_inv_n, D.s);
+        enqueue_scale<G1>(dd, n, d_inv_2n, D.s);
+        e = hipMemcpyAsync(x1 + off_h, dd, (size_t)n * X1, hipMemcpyDeviceToDevice, D.s);
+        if (e != hipSuccess) return fail(status, hip_err("placing H", e));
+    }
+    (void)hipEventRecord(D.ev[2], D.s);
+    if (!pl.from_file) {
+        enqueue_stages<G2>(l2, p, 1, tw, D.s);
+        enqueue_scale<G2>(l2, n, d_inv_n, D.s);
+    }
+    (void)hipEventRecord(D.ev[3], D.s);
+    const uint32_t *d_ent = (const uint32_t*)(W + o_ent), *d_cidx = (const uint32_t*)(W + o_cidx), *d_soff = (const uint32_t*)(W + o_soff),
+                   *d_skey = (const uint32_t*)(W + o_skey), *d_wseg = (const uint32_t*)(W + o_wseg);
+    const Fr* d_coef = (const Fr*)(W + o_coef);
+    Xyzz<G1>*pa = (Xyzz<G1>*)(W + o_pa), *pk = (Xyzz<G1>*)(W + o_pk);
+    Xyzz<G2>* pq = (Xyzz<G2>*)(W + o_pq);
+    const Xyzz<G1>* none1 = nullptr;
+    const Xyzz<G2>* none2 = nullptr;
+    if (n_seg) {
+        hipLaunchKernelGGL(segments_kernel<G1>, dim3(blocks_for(n_seg)), dim3(THREADS), 0, D.s, d_ent, d_cidx, d_coef, d_soff, d_skey, n_seg,
+                           (const Xyzz<G1>*)l1, (const Xyzz<G1>*)l1, (const Xyzz<G1>*)l1, pa);
+        hipLaunchKernelGGL(segments_kernel<G1>, dim3(blocks_for(n_seg)), dim3(THREADS), 0, D.s, d_ent, d_cidx, d_coef, d_soff, d_skey, n_seg,
+                           (const Xyzz<G1>*)lb, (const Xyzz<G1>*)la, none1, pk);
+    }
+    hipLaunchKernelGGL(wires_g1_kernel, dim3(blocks_for(nw)), dim3(THREADS), 0, D.s, (const Xyzz<G1>*)pa, (const Xyzz<G1>*)pk, d_skey, d_wseg,
+                       (const Xyzz<G1>*)l1, (const Xyzz<G1>*)lb, nw, nc, n_pub, n, x1);
+    (void)hipEventRecord(D.ev[4], D.s);
+    if (n_seg)
+        hipLaunchKernelGGL(segments_kernel<G2>, dim3(blocks_for(n_seg)), dim3(THREADS), 0, D.s, d_ent, d_cidx, d_coef, d_soff, d_skey, n_seg, none2,
+                           (const Xyzz<G2>*)l2, none2, pq);
+    hipLaunchKernelGGL(wires_one_kernel<G2>, dim3(blocks_for(nw)), dim3(THREADS), 0, D.s, (const Xyzz<G2>*)pq, d_skey, d_wseg, nw, 1u, x2);
+    (void)hipEventRecord(D.ev[5], D.s);
+    if (!delta_is_one) enqueue_scale<G1>(x1 + off_c, (nw - n_pub - 1) + n, d_delta_inv, D.s);  // C and H
+    enqueue_scale<G1>(x1 + (n1 - 1), 1, d_delta, D.s);
+    enqueue_scale<G2>(x2 + (n2 - 1), 1, d_delta, D.s);
+    (void)hipEventRecord(D.ev[6], D.s);
+    enqueue_affine_g1(x1, (uint32_t)n1, W + o_p1, false, D.s);
+    enqueue_affine_g2(x2, (uint32_t)n2, W + o_p2, false, D.s);
+    (void)hipEventRecord(D.ev[7], D.s);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(status, hip_err("launching the setup kernels", e));
+    std::vector<uint8_t> p1(n1 * G1_BYTES), p2(n2 * G2_BYTES);
+    unsigned long long faults[8];
+    e = hipMemcpyAsync(p1.data(), W + o_p1, p1.size(), hipMemcpyDeviceToHost, D.s);
+    if (e == hipSuccess) e = hipMemcpyAsync(p2.data(), W + o_p2, p2.size(), hipMemcpyDeviceToHost, D.s);
+    if (e == hipSuccess) e = hipMemcpyAsync(faults, flag, sizeof faults, hipMemcpyDeviceToHost, D.s);
+    if (e == hipSuccess) e = hipMemsetAsync(D.secret, 0, D.secret_bytes, D.s);
+    if (e == hipSuccess) e = hipStreamSynchronize(D.s);
+    if (e != hipSuccess) return fail(status, hip_err("running the setup", e));
+    for (size_t a = 0; a < checked.size(); ++a)
+        if (faults[a] != NO_FAULT) {
+            const Checked& c = checked[a];
+            return fail(status, cwc_ptau::point_message(c.section, c.base + c.first + (faults[a] >> 1) * c.stride, (uint32_t)(faults[a] & 1), c.g2));
+        }
+    {
+        float ms[7];
+        bool ok = true;
+        for (int i = 0; i < 7; ++i) ok = ok && hipEventElapsedTime(ms + i, D.ev[i], D.ev[i + 1]) == hipSuccess;
+        if (pl.from_file) ms[1] = ms[2] = 0.0f;  // nothing was enqueued between those events
+        std::lock_guard<std::mutex> lock(g_phase_mutex);
+        if (ok) memcpy(g_phase_ms, ms, sizeof ms);
+        g_phase_valid = ok;
+    }
+    const uint8_t *a = p1.data(), *b1 = a + (size_t)nw * G1_BYTES, *c = a + off_c * G1_BYTES, *h = a + off_h * G1_BYTES,
+                  *ic = h + (size_t)n * G1_BYTES, *delta1 = a + (n1 - 1) * G1_BYTES;
+    const uint8_t *b2 = p2.data(), *delta2 = b2 + (size_t)nw * G2_BYTES;
+    const KeyPoints kp{nw, n_pub, n, pl.at, pl.bt, pl.beta2, gb2, delta1, delta2, ic, a, b1, b2, c, h};
+    return write_zkey(kp, sec4, zkey, zkey_len, status);
+}
+
+template <class T>
+int idft_aid(const void* d_points, uint32_t log_n, void* d_out, hipStream_t s, gw_status_t* status) {
+    const uint32_t n = 1u << log_n;
+    Carve cw;
+    const size_t o_x = cw.take((size_t)n * sizeof(Xyzz<T>)), o_tw = cw.take((size_t)n / 2 * 32), o_k = cw.take(32);
+    void* ws = nullptr;
+    hipError_t e = hipMallocAsync(&ws, cw.o, s);
+    if (e != hipSuccess) return fail(status, hip_err("allocating the transform's workspace", e));
+    uint8_t* W = (uint8_t*)ws;
+    Xyzz<T>* x = (Xyzz<T>*)(W + o_x);
+    Fr *tw = (Fr*)(W + o_tw), *k = (Fr*)(W + o_k);
+    enqueue_load<T>((const uint8_t*)d_points, n, 0, 1, true, log_n, x, nullptr, s);
+    enqueue_twiddles(tw, log_n, s);
+    hipLaunchKernelGGL(put_fr_kernel, dim3(1), dim3(64), 0, s, k, inverse_of_u32(n));
+    enqueue_stages<T>(x, log_n, 1, tw, s);
+    enqueue_scale<T>(x, n, k, s);
+    if (sizeof(typename T::E) == 32)
+        enqueue_affine_g1(x, n, (uint8_t*)d_out, true, s);
+    else
+        enqueue_affine_g2(x, n, (uint8_t*)d_out, true, s);
+    e = hipGetLastError();
+    const hipError_t ef = hipFreeAsync(ws, s);
+    if (e != hipSuccess) return fail(status, hip_err("launching the transform", e));
+    if (ef != hipSuccess) return fail(status, hip_err("releasing the transform's workspace", ef));
+    set_ok(status);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gwb_groth16_setup_ptau(gwb_r1cs_t* r, const void* ptau, size_t ptau_len, const uint8_t* delta, uint32_t lagrange_mode, void** zkey,
+                           size_t* zkey_len, gw_status_t* status) {
+    if (!r || !zkey || !zkey_len || (!ptau && ptau_len)) return fail(status, "gwb_groth16_setup_ptau: NULL argument");
+    *zkey = nullptr;
+    *zkey_len = 0;
+    try {
+        return setup(r, (const uint8_t*)ptau, ptau_len, delta, lagrange_mode, zkey, zkey_len, status);
+    } catch (const std::bad_alloc&) {
+        return fail(status, "groth16 setup: out of host memory");
+    }
+}
+
+int gwb_bn254_point_idft_batch_device(const void* d_points, uint32_t log_n, uint32_t group, void* d_out, void* hip_stream, gw_status_t* status) {
+    if (!d_points || !d_out) return fail(status, "gwb_bn254_point_idft_batch_device: NULL argument");
+    if (group != 1 && group != 2) return fail(status, "gwb_bn254_point_idft_batch_device: group " + std::to_string(group) + " (1 or 2 expected)");
+    if (log_n < 1 || log_n > MAX_LOG_N)
+        return fail(status, "gwb_bn254_point_idft_batch_device: log_n " + std::to_string(log_n) + " (1 to " + std::to_string(MAX_LOG_N) + " expected)");
+    return group == 1 ? idft_aid<G1>(d_points, log_n, d_out, (hipStream_t)hip_stream, status)
+                      : idft_aid<G2>(d_points, log_n, d_out, (hipStream_t)hip_stream, status);
+}
+
+int gwb_groth16_setup_ptau_phase_ms(float* ms) {
+    if (!ms) return 1;
+    std::lock_guard<std::mutex> lock(g_phase_mutex);
+    if (!g_phase_valid) return 1;
+    memcpy(ms, g_phase_ms, sizeof g_phase_ms);
+    return 0;
+}
+
+}  // extern "C"

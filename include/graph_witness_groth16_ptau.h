@@ -1,0 +1,92 @@
+/* Groth16 proving keys on an MI355X from a circuit's `.r1cs` and a powers-of-tau ceremony file (`.ptau`): what
+ * `snarkjs groth16 setup circuit.r1cs pot.ptau circuit.zkey` does, with tau, alpha and beta taken from the ceremony instead of
+ * from the caller (graph_witness_groth16_setup.h is the setup from a known trapdoor).
+ *
+ * TRUST.  tau, alpha and beta are those of the ceremony behind the file: nobody knows them if one participant of that
+ * ceremony was honest, and this library does not verify the ceremony (no `powersoftau verify`, no contribution records).
+ * gamma is 1, as in snarkjs.  delta is the caller's:
+ *   delta = 1 gives the state of snarkjs `zkey new`: a key that is to be handed to a phase-2 ceremony, NOT to be used, since
+ *   everybody knows its delta and knowing delta alone is enough to forge proofs;
+ *   delta = NULL draws delta, applies it and zeroes it on the host and on the device before the call returns.  The key's
+ *   soundness then rests on two things: the ceremony behind the ptau, and the runner of this call discarding delta.  This is
+ *   a single-party phase 2, not an MPC phase 2: the file's section 10 records no contribution.
+ *   A supplied delta other than 1 makes a reproducible key whose delta the supplier knows (tests).
+ *
+ * Definition.  n = 2^p is the circuit's QAP domain (gwb_r1cs_qap_info), w_N the generator of the domain of N = 2^m points
+ * (graph_witness_r1cs.h: w_n, and g = w_2n).  From the file's monomial sections take the prefixes T1_i = tau^i G1 (i < 2n),
+ * T2_i = tau^i G2, AT_i = alpha tau^i G1, BT_i = beta tau^i G1 (i < n).  For a point sequence P of length N = 2^m
+ *   Lag_m(P)_k = (1 / N) sum_i w_N^(-k i) P_i           (the inverse DFT over the group: tau^i G -> L_k(tau) G)
+ * and L1 = Lag_p(T1), L2 = Lag_p(T2), LA = Lag_p(AT), LB = Lag_p(BT), M = Lag_(p+1)(T1).  With the R1CS's nC constraints
+ * (A_k, B_k, C_k), nW wires and nPub public signals:
+ *   section 5 (A):   A_i  = sum_k A_k[i] L1_k  (+ L1_{nC+i} for i <= nPub)
+ *   section 6 (B1):  B1_i = sum_k B_k[i] L1_k             section 7 (B2):  B2_i = sum_k B_k[i] L2_k
+ *   K_i = sum_k A_k[i] LB_k (+ LB_{nC+i} for i <= nPub) + sum_k B_k[i] LA_k + sum_k C_k[i] L1_k
+ *   section 3 (IC):  IC_i = K_i for i <= nPub             section 8 (C):   C_{i-nPub-1} = (1 / delta) K_i for i > nPub
+ *   section 9 (H):   H_j  = (1 / delta) M_{2j+1}
+ *   header:          alpha1 = AT_0, beta1 = BT_0, beta2 = the file's section 6, gamma2 = G2, delta1 = delta G1, delta2 = delta G2
+ * Sections 4 and 10 and the section order are those of gwb_groth16_setup.  For a file whose logs are (tau, alpha, beta) the
+ * key is, byte for byte, gwb_groth16_setup's with the trapdoor (tau, alpha, beta, 1, delta).
+ *
+ * The `.ptau` file (iden3 binfile "ptau" v1; r1cs/ptau.cc has the layout).  The loader takes any bytes, an mmap'd file
+ * included, and reads only the header, the section table and the prefixes named above.  It refuses with a message: a wrong
+ * magic or version; n8 != 32 or a q that is not BN254's; power > 28; a missing, duplicate or mis-sized section 1 to 6; a
+ * coordinate >= q or a point off its curve among those it reads (naming section and index); T1_0 != G1 or T2_0 != G2; and a
+ * circuit with p + 1 > power.  snarkjs also accepts p = power, through a truncated top level of M; that case is left out
+ * here.  Like the zkey loader it does not check G2 points for subgroup membership.  The layout is restated from snarkjs's
+ * writer and has not been cross-checked against snarkjs itself (no snarkjs output is available to this project).
+ *
+ * Lagrange source.  A file that went through `powersoftau prepare phase2` carries L1, L2, LA, LB and M already (sections 12
+ * to 15).  GWB_PTAU_LAGRANGE_AUTO reads them when they are present and computes them otherwise, _FILE fails with a message
+ * when they are absent, _COMPUTE ignores them.  What the prepared sections hold is not compared with the monomial ones.
+ *
+ * Return and status conventions are those of graph_witness_r1cs.h.  gwb_groth16_setup_ptau is synchronous and runs on the
+ * current device. */
+#ifndef CWC_AMD_GRAPH_WITNESS_GROTH16_PTAU_H
+#define CWC_AMD_GRAPH_WITNESS_GROTH16_PTAU_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "graph_witness_groth16_setup.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+enum { GWB_PTAU_LAGRANGE_AUTO = 0, GWB_PTAU_LAGRANGE_FILE = 1, GWB_PTAU_LAGRANGE_COMPUTE = 2 };
+
+typedef struct {
+  uint32_t power;           /* the file holds tau^i G1 for i < 2^(power+1) - 1 */
+  uint32_t ceremony_power;  /* the power of the ceremony the file was cut from */
+  uint32_t prepared;        /* 1: sections 12 to 15 are present with their expected sizes */
+  uint32_t n_contributions; /* as section 7 states it; the records are not read */
+} gwb_ptau_info_t;
+
+/* Host only, no device: header and section table, the generators at T1_0 and T2_0. */
+int gwb_ptau_info(const void *data, size_t len, gwb_ptau_info_t *info, gw_status_t *status);
+
+/* Host only, no device: everything gwb_groth16_setup_ptau would refuse about the file for a circuit of domain
+ * 2^domain_power under lagrange_mode, with the same messages; the points are checked on the host (the setup checks them on
+ * the device). */
+int gwb_ptau_check(const void *data, size_t len, uint32_t domain_power, uint32_t lagrange_mode, gw_status_t *status);
+
+/* delta: 32 bytes canonical little-endian in [1, r), or NULL to draw it (the prover's rejection sampler over getrandom()).
+ * *zkey is released with gwb_groth16_setup_free. */
+int gwb_groth16_setup_ptau(gwb_r1cs_t *r, const void *ptau, size_t ptau_len, const uint8_t *delta, uint32_t lagrange_mode,
+                           void **zkey, size_t *zkey_len, gw_status_t *status);
+
+/* Measurement and test aid, like gwb_bn254_gen_mul_batch_device: d_points [2^log_n][64 B] (group 1) or [128 B] (group 2),
+ * canonical little-endian affine coordinates, zero bytes = infinity (the points are not checked) -> d_out, the same form:
+ * Lag_(log_n) of the sequence, in natural order.  1 <= log_n <= 27.  Asynchronous on hip_stream. */
+int gwb_bn254_point_idft_batch_device(const void *d_points, uint32_t log_n, uint32_t group, void *d_out, void *hip_stream,
+                                      gw_status_t *status);
+
+/* ms[7] of the last gwb_groth16_setup_ptau call of the process (HIP events): point_check (loading and checking the points
+ * read), idft_g1, idft_g2 (0 when the Lagrange forms came from the file), column_sums_g1, column_sums_g2, delta_scale,
+ * affine.  1 when no call has completed yet. */
+int gwb_groth16_setup_ptau_phase_ms(float *ms);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* CWC_AMD_GRAPH_WITNESS_GROTH16_PTAU_H */
