@@ -591,6 +591,11 @@ def r1cs_lib():
         L.gwb_groth16_prove_wtns.argtypes = [vp, vp, vp, sz, vp, vp, stp]
         L.gwb_groth16_time_phases.argtypes = [vp, ctypes.c_int]
         L.gwb_groth16_phase_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        L.gwb_zkey_qap_info.argtypes = [vp, ctypes.POINTER(R1csQapInfo), stp]
+        L.gwb_zkey_qap_batch_device.argtypes = [vp, vp, sz, sz, u32, vp, u32, vp, stp]
+        L.gwb_zkey_qap_batch_host.argtypes = [vp, vp, sz, sz, vp, u32, stp]
+        L.gwb_zkey_set_tile_width.argtypes = [vp, u32]
+        L.gwb_zkey_check_r1cs.argtypes = [vp, vp, stp]
         L.gwb_g16vk_from_zkey.argtypes = [vp, ctypes.POINTER(vp), stp]
         L.gwb_g16vk_load.argtypes = [vp, sz, u32, ctypes.POINTER(vp), stp]
         L.gwb_g16vk_info.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
@@ -802,11 +807,13 @@ def proof_json(proof):
 
 
 class Groth16:
-    """A circuit's Groth16 proving key (`.zkey` bytes, snarkjs's Groth16 format) with its constraint system (an R1cs of the same
-    circuit, which supplies the witness map): proofs of witness rows on the GPU, 256 bytes per row (A.x, A.y, B.x.c0, B.x.c1,
-    B.y.c0, B.y.c1, C.x, C.y, canonical little-endian)."""
+    """A circuit's Groth16 proving key (`.zkey` bytes, snarkjs's Groth16 format): proofs of witness rows on the GPU, 256 bytes
+    per row (A.x, A.y, B.x.c0, B.x.c1, B.y.c0, B.y.c1, C.x, C.y, canonical little-endian).  The witness map comes from the
+    key's own section 4 (what snarkjs and rapidsnark do), or, when an R1cs of the same circuit is given, from that.  Section 4
+    is turned into the prover's arrays at the first call that needs it; what that step refuses (a value >= r, no coefficients,
+    a domain the transform cannot take) is raised there, not here."""
 
-    def __init__(self, zkey_bytes, r1cs):
+    def __init__(self, zkey_bytes, r1cs=None):
         self._h = ctypes.c_void_p()
         self.r1cs = r1cs
         data = bytes(zkey_bytes)
@@ -824,6 +831,71 @@ class Groth16:
 
     __del__ = close
 
+    def _r1cs_handle(self):
+        return None if self.r1cs is None else self.r1cs._h
+
+    def check_r1cs(self, r1cs=None):
+        """Raises unless the key belongs to `r1cs` (default: the handle's own): section 4, summed per (matrix, constraint, signal),
+        equals the A and B combinations of the R1cs plus the nPublic + 1 public rows, and the size fields agree.  The message
+        names the smallest differing (constraint, matrix, signal).  Host only.  A zkey holds no C matrix, so the C sides are
+        not compared."""
+        r1cs = self.r1cs if r1cs is None else r1cs
+        if r1cs is None:
+            raise WitnessCalcError("check_r1cs: no R1cs given and the handle has none")
+        st = GwStatus()
+        rc = r1cs_lib().gwb_zkey_check_r1cs(self._h, r1cs._h, ctypes.byref(st))
+        _r1cs_check(rc, st)
+
+    # -- the witness map of section 4 on its own (always from the zkey, whether or not the handle has an R1cs) -----------------
+    def set_tile_width(self, t):
+        """Witness rows per wavefront of the section-4 evaluation kernel: a power of two in 1..64, or 0 = from the batch size."""
+        if r1cs_lib().gwb_zkey_set_tile_width(self._h, t) != 0:
+            raise WitnessCalcError("tile width must be 0 or a power of two in 1..64")
+
+    def qap_info(self):
+        """{n_rows, domain_power, domain_size, workspace_bytes_per_row}; n_rows = 1 + the largest constraint index in section 4."""
+        info = R1csQapInfo()
+        st = GwStatus()
+        rc = r1cs_lib().gwb_zkey_qap_info(self._h, ctypes.byref(info), ctypes.byref(st))
+        _r1cs_check(rc, st)
+        return {n: int(getattr(info, n)) for n, _ in R1csQapInfo._fields_}
+
+    def qap_batch(self, witness_rows, montgomery_out=False):
+        """Host rows uint8 [B, nVars, 32] (canonical) -> h as uint8 [B, n, 32] (canonical, or Montgomery with montgomery_out), as
+        R1cs.qap_batch.  Synchronous."""
+        if isinstance(witness_rows, tuple):
+            witness_rows = witness_rows[0]
+        w = np.ascontiguousarray(witness_rows, dtype=np.uint8)
+        assert w.ndim == 3 and w.shape[2] == 32, w.shape
+        b = w.shape[0]
+        h = np.zeros((b, self.qap_info()["domain_size"], 32), dtype=np.uint8)
+        st = GwStatus()
+        rc = r1cs_lib().gwb_zkey_qap_batch_host(self._h, w.ctypes.data, w.shape[1], b, h.ctypes.data,
+                                                FORM_MONTGOMERY if montgomery_out else FORM_CANONICAL, ctypes.byref(st))
+        _r1cs_check(rc, st)
+        return h
+
+    def qap_batch_device(self, d_witness, stream=None, montgomery=False, montgomery_out=False):
+        """Device rows (torch uint8 cuda tensor [B, nVars, 32], canonical or Montgomery form) -> h as a uint8 cuda tensor
+        [B, n, 32], as R1cs.qap_batch_device.  Asynchronous on `stream` or the current torch stream."""
+        import torch
+        assert d_witness.is_cuda and d_witness.is_contiguous() and d_witness.dtype == torch.uint8
+        assert d_witness.dim() == 3 and d_witness.shape[2] == 32, tuple(d_witness.shape)
+        b = d_witness.shape[0]
+        n = self.qap_info()["domain_size"]
+        s = stream if stream is not None else torch.cuda.current_stream(d_witness.device)
+        h = torch.empty((b, n, 32), dtype=torch.uint8, device=d_witness.device)
+        st = GwStatus()
+        with torch.cuda.device(d_witness.device):
+            rc = r1cs_lib().gwb_zkey_qap_batch_device(self._h, d_witness.data_ptr(), d_witness.shape[1], b,
+                                                      FORM_MONTGOMERY if montgomery else FORM_CANONICAL, h.data_ptr(),
+                                                      FORM_MONTGOMERY if montgomery_out else FORM_CANONICAL, s.cuda_stream,
+                                                      ctypes.byref(st))
+        _r1cs_check(rc, st)
+        if b:
+            h.record_stream(s)
+        return h
+
     def prove_batch(self, rows, rs=None):
         """Host rows uint8 [B, nVars, 32] (canonical), or the (witness, status) pair of Graph.calc_witness_batch -> uint8
         [B, 256].  rs: [B] pairs (r, s) of ints below r, or uint8 [B, 2, 32]; None draws them from getrandom().  Synchronous."""
@@ -835,7 +907,7 @@ class Groth16:
         rsa = _rs_array(rs, b)
         out = np.zeros((b, GROTH16_PROOF_BYTES), dtype=np.uint8)
         st = GwStatus()
-        rc = r1cs_lib().gwb_groth16_prove_batch_host(self._h, self.r1cs._h, w.ctypes.data, w.shape[1], b,
+        rc = r1cs_lib().gwb_groth16_prove_batch_host(self._h, self._r1cs_handle(), w.ctypes.data, w.shape[1], b,
                                                      None if rsa is None else rsa.ctypes.data, out.ctypes.data, ctypes.byref(st))
         _r1cs_check(rc, st)
         return out
@@ -852,7 +924,7 @@ class Groth16:
         out = torch.empty((b, GROTH16_PROOF_BYTES), dtype=torch.uint8, device=d_w.device)
         st = GwStatus()
         with torch.cuda.device(d_w.device):
-            rc = r1cs_lib().gwb_groth16_prove_batch_device(self._h, self.r1cs._h, d_w.data_ptr(), d_w.shape[1], b,
+            rc = r1cs_lib().gwb_groth16_prove_batch_device(self._h, self._r1cs_handle(), d_w.data_ptr(), d_w.shape[1], b,
                                                            FORM_MONTGOMERY if montgomery else FORM_CANONICAL,
                                                            None if rsa is None else rsa.ctypes.data, out.data_ptr(),
                                                            s.cuda_stream, ctypes.byref(st))
@@ -867,7 +939,7 @@ class Groth16:
         rsa = _rs_array(rs, 1)
         out = np.zeros(GROTH16_PROOF_BYTES, dtype=np.uint8)
         st = GwStatus()
-        rc = r1cs_lib().gwb_groth16_prove_wtns(self._h, self.r1cs._h, wtns, len(wtns), None if rsa is None else rsa.ctypes.data,
+        rc = r1cs_lib().gwb_groth16_prove_wtns(self._h, self._r1cs_handle(), wtns, len(wtns), None if rsa is None else rsa.ctypes.data,
                                                out.ctypes.data, ctypes.byref(st))
         _r1cs_check(rc, st)
         # the values section of the (validated) image: wire i at 32 i

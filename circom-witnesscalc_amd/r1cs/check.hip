@@ -294,7 +294,7 @@ void gwb_r1cs_free(gwb_r1cs_t* r) {
         int cur = -1;
         const bool switch_dev = hipGetDevice(&cur) == hipSuccess && cur != r->device;
         if (switch_dev) (void)hipSetDevice(r->device);
-        release_qap(r);
+        release_qap(r->qap);
         release_device(r);
         if (switch_dev) (void)hipSetDevice(cur);
     }

@@ -1,6 +1,8 @@
-// groth16-prove <circuit.r1cs> <circuit.zkey> <witness.wtns> <proof.json> <public.json>: a Groth16 proof of the witness on
-// the GPU (snarkjs `groth16 prove`), written in snarkjs's proof.json / public.json shape.  Exit status 0 on success; 2 on a
-// usage, file, format or mismatch error.
+// groth16-prove <circuit.zkey> <witness.wtns> <proof.json> <public.json>: a Groth16 proof of the witness on the GPU (snarkjs
+// `groth16 prove`, its argument order), written in snarkjs's proof.json / public.json shape; the witness map comes from the
+// zkey's section 4.  groth16-prove <circuit.r1cs> <circuit.zkey> <witness.wtns> <proof.json> <public.json> takes it from the
+// `.r1cs` instead.  Exit status 0 on success; 2 on a usage, file, format or mismatch error.  Every input is parsed before the
+// device is touched.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -66,39 +68,48 @@ static bool write_text(const char* path, const std::string& s) {
 }
 
 int main(int argc, char** argv) {
-    if (argc != 6) {
-        fprintf(stderr, "usage: %s <circuit.r1cs> <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n", argv[0]);
+    if (argc != 5 && argc != 6) {
+        fprintf(stderr,
+                "usage: %s <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n"
+                "       %s <circuit.r1cs> <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n",
+                argv[0], argv[0]);
         return 2;
     }
-    std::vector<char> files[3];
-    for (int i = 0; i < 3; ++i) {
-        if (!read_file(argv[1 + i], files[i])) {
-            fprintf(stderr, "error: cannot read %s\n", argv[1 + i]);
+    const bool with_r1cs = argc == 6;
+    char** in = argv + 1;  // inputs: [r1cs,] zkey, wtns; then the two outputs
+    const int n_in = with_r1cs ? 3 : 2;
+    std::vector<char> loaded[3];
+    for (int i = 0; i < n_in; ++i) {
+        if (!read_file(in[i], loaded[i])) {
+            fprintf(stderr, "error: cannot read %s\n", in[i]);
             return 2;
         }
     }
+    const std::vector<char>& zkey_file = loaded[n_in - 2];
+    const std::vector<char>& wtns_file = loaded[n_in - 1];
     gw_status_t st = {OK, NULL};
     gwb_r1cs_t* r = NULL;
     gwb_zkey_t* z = NULL;
-    if (gwb_r1cs_load(files[0].data(), files[0].size(), &r, &st) != 0) {
-        fprintf(stderr, "error: %s: %s\n", argv[1], st.error_msg ? st.error_msg : "load failed");
+    if (with_r1cs && gwb_r1cs_load(loaded[0].data(), loaded[0].size(), &r, &st) != 0) {
+        fprintf(stderr, "error: %s: %s\n", in[0], st.error_msg ? st.error_msg : "load failed");
         gw_free_status(&st);
         return 2;
     }
-    if (gwb_zkey_load(files[1].data(), files[1].size(), &z, &st) != 0) {
-        fprintf(stderr, "error: %s: %s\n", argv[2], st.error_msg ? st.error_msg : "load failed");
+    if (gwb_zkey_load(zkey_file.data(), zkey_file.size(), &z, &st) != 0) {
+        fprintf(stderr, "error: %s: %s\n", in[n_in - 2], st.error_msg ? st.error_msg : "load failed");
         gw_free_status(&st);
         gwb_r1cs_free(r);
         return 2;
     }
     uint8_t proof[GWB_GROTH16_PROOF_BYTES];
-    const int rc = gwb_groth16_prove_wtns(z, r, files[2].data(), files[2].size(), NULL, proof, &st);
+    // (the call parses the .wtns image and, without an .r1cs, builds the map of section 4 before it reaches the device)
+    const int rc = gwb_groth16_prove_wtns(z, r, wtns_file.data(), wtns_file.size(), NULL, proof, &st);
     gwb_zkey_info_t zi;
     gwb_zkey_info(z, &zi);
     gwb_zkey_free(z);
     gwb_r1cs_free(r);
     if (rc != 0) {
-        fprintf(stderr, "error: %s: %s\n", argv[3], st.error_msg ? st.error_msg : "prove failed");
+        fprintf(stderr, "error: %s: %s\n", in[n_in - 1], st.error_msg ? st.error_msg : "prove failed");
         gw_free_status(&st);
         return 2;
     }
@@ -112,12 +123,12 @@ int main(int argc, char** argv) {
     std::string pj = "{\n \"pi_a\": [\n  " + d(0) + ",\n  " + d(1) + ",\n  " + z1(0, 2) + "\n ],\n \"pi_b\": [\n  [\n   " + d(2) + ",\n   " + d(3) +
                      "\n  ],\n  [\n   " + d(4) + ",\n   " + d(5) + "\n  ],\n  [\n   " + z1(2, 4) + ",\n   \"0\"\n  ]\n ],\n \"pi_c\": [\n  " + d(6) +
                      ",\n  " + d(7) + ",\n  " + z1(6, 2) + "\n ],\n \"protocol\": \"groth16\",\n \"curve\": \"bn128\"\n}\n";
-    const uint8_t* w = wtns_values(files[2]);
+    const uint8_t* w = wtns_values(wtns_file);
     std::string pub = "[";
     for (uint32_t i = 1; i <= zi.n_public; ++i) pub += std::string(i > 1 ? ",\n " : "\n ") + "\"" + decimal(w + 32 * (size_t)i) + "\"";
     pub += zi.n_public ? "\n]\n" : "]\n";
-    if (!write_text(argv[4], pj) || !write_text(argv[5], pub)) {
-        fprintf(stderr, "error: cannot write %s / %s\n", argv[4], argv[5]);
+    if (!write_text(in[n_in], pj) || !write_text(in[n_in + 1], pub)) {
+        fprintf(stderr, "error: cannot write %s / %s\n", in[n_in], in[n_in + 1]);
         return 2;
     }
     return 0;

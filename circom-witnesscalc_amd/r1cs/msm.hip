@@ -535,7 +535,10 @@ bool enqueue_sub(gwb_zkey* z, gwb_r1cs* r, const Layout& L, const uint8_t* d_w, 
     const uint32_t mont = form_in == GWB_FORM_MONTGOMERY ? 1u : 0u;
     P1* g1 = S.at<P1>(L.off_g1);
     mark(z, 0, s);
-    if (!qap_enqueue(r, d_w, rows, form_in, S.at<void>(L.off_h), GWB_FORM_CANONICAL, s, err)) return false;
+    // the witness map: from the .r1cs, or with none given from the zkey's own section 4
+    if (r ? !qap_enqueue(r, d_w, rows, form_in, S.at<void>(L.off_h), GWB_FORM_CANONICAL, s, err)
+          : !zkey_qap_enqueue(z, d_w, rows, form_in, S.at<void>(L.off_h), GWB_FORM_CANONICAL, s, err))
+        return false;
     mark(z, 1, s);
     int cur = 0;
     if (!prep_sort(S, L.mw, d_w, nv, nv, mont, d_rs, cur, err)) return false;
@@ -603,7 +606,21 @@ bool make_rs(const void* rs, size_t batch, std::vector<Fr>& out, std::string& er
     return true;
 }
 
-bool check_pair(const gwb_zkey* z, gwb_r1cs* r, size_t n_witness, size_t batch, std::string& err) {
+// r == NULL: the zkey alone.  Its witness map is built here (host work), so what that refuses is refused before the device
+// is touched.
+bool check_pair(gwb_zkey* z, gwb_r1cs* r, size_t n_witness, size_t batch, std::string& err) {
+    if (!r) {
+        if (!zkey_coefs_build(z, err)) return false;
+        if (n_witness != z->info.n_vars) {
+            err = "groth16: the witness has " + std::to_string(n_witness) + " elements, the zkey nVars = " + std::to_string(z->info.n_vars);
+            return false;
+        }
+        if (batch > 0xffffffffull) {
+            err = "groth16: batch above 2^32 - 1";
+            return false;
+        }
+        return true;
+    }
     gwb_r1cs_qap_info_t qi;
     gw_status_t st{OK, nullptr};
     if (gwb_r1cs_qap_info(r, &qi, &st) != 0) {
@@ -684,7 +701,7 @@ int prove_host(gwb_zkey* z, gwb_r1cs* r, const void* witness, size_t n_witness, 
         set_ok(status);
         return 0;
     }
-    if (!ensure_device(r, err)) return fail(status, err);
+    if (r && !ensure_device(r, err)) return fail(status, err);
     void *d_w = nullptr, *d_p = nullptr;
     hipStream_t s = nullptr;
     const size_t wbytes = batch * n_witness * 32, pbytes = batch * GWB_GROTH16_PROOF_BYTES;
@@ -722,12 +739,13 @@ void gwb_zkey_free(gwb_zkey_t* z) {
     if (z->rs_done) (void)hipEventDestroy((hipEvent_t)z->rs_done);
     for (void* e : z->events)
         if (e) (void)hipEventDestroy((hipEvent_t)e);
+    release_zkey_qap(z);
     delete z;
 }
 
 int gwb_groth16_prove_batch_device(gwb_zkey_t* z, gwb_r1cs_t* r, const void* d_witness, size_t n_witness, size_t batch, uint32_t form_in,
                                    const void* rs, void* d_proofs, void* hip_stream, gw_status_t* status) {
-    if (!z || !r || (batch && (!d_witness || !d_proofs))) return fail(status, "gwb_groth16_prove_batch_device: NULL argument");
+    if (!z || (batch && (!d_witness || !d_proofs))) return fail(status, "gwb_groth16_prove_batch_device: NULL argument");
     if (form_in != GWB_FORM_CANONICAL && form_in != GWB_FORM_MONTGOMERY)
         return fail(status, "gwb_groth16_prove_batch_device: unknown form " + std::to_string(form_in));
     std::string err;
@@ -737,7 +755,7 @@ int gwb_groth16_prove_batch_device(gwb_zkey_t* z, gwb_r1cs_t* r, const void* d_w
         set_ok(status);
         return 0;
     }
-    if (!ensure_device(r, err) || !enqueue_prove(z, r, d_witness, batch, form_in, rsv, d_proofs, (hipStream_t)hip_stream, err))
+    if ((r && !ensure_device(r, err)) || !enqueue_prove(z, r, d_witness, batch, form_in, rsv, d_proofs, (hipStream_t)hip_stream, err))
         return fail(status, err);
     set_ok(status);
     return 0;
@@ -745,12 +763,12 @@ int gwb_groth16_prove_batch_device(gwb_zkey_t* z, gwb_r1cs_t* r, const void* d_w
 
 int gwb_groth16_prove_batch_host(gwb_zkey_t* z, gwb_r1cs_t* r, const void* witness, size_t n_witness, size_t batch, const void* rs, void* proofs,
                                  gw_status_t* status) {
-    if (!z || !r || (batch && (!witness || !proofs))) return fail(status, "gwb_groth16_prove_batch_host: NULL argument");
+    if (!z || (batch && (!witness || !proofs))) return fail(status, "gwb_groth16_prove_batch_host: NULL argument");
     return prove_host(z, r, witness, n_witness, batch, rs, proofs, status);
 }
 
 int gwb_groth16_prove_wtns(gwb_zkey_t* z, gwb_r1cs_t* r, const void* wtns, size_t len, const void* rs, void* proof, gw_status_t* status) {
-    if (!z || !r || !wtns || !proof) return fail(status, "gwb_groth16_prove_wtns: NULL argument");
+    if (!z || !wtns || !proof) return fail(status, "gwb_groth16_prove_wtns: NULL argument");
     const uint8_t* values = nullptr;
     uint64_t n_wit = 0;
     std::string err;

@@ -6,6 +6,11 @@
 // kernel writes a, b and c at each constraint's file index (the check's lane mapping and factor stream, lincomb.hpp); a
 // second kernel writes the input rows and the zero padding.
 //
+// The same map runs from a zkey's section 4 when a prover has no `.r1cs` (include/graph_witness_groth16.h): zkey_eval_kernel
+// reads the arrays zkey_coefs.cc builds (two row pointers per row, the public rows among the entries), qap_zero_kernel clears
+// the rows no entry names, and the NTT chain below is shared: its tables, workspace and events are a QapState, owned by
+// whichever handle the map belongs to.
+//
 // NTT layout: n = L_0 L_1 ... L_{P-1} (each L <= 2^9 for the outer passes, the innermost <= 2^11).  A pass works on blocks
 // of M = L S consecutive elements (S = L_{t+1} ... L_{P-1}): position k S + j (k < L, j < S) of a block is element k of
 // column j.  An inverse pass takes the L-point DFT (root w_L^-1) of every column and multiplies element k of column j by
@@ -130,6 +135,56 @@ __global__ __launch_bounds__(64 * EVAL_WAVES) void qap_eval_kernel(
             B[o] = b;
             C[o] = ab;
         }
+    }
+}
+
+// The same from a zkey's section 4 (zkey_coefs.cc): two row pointers per row (no C side), the public rows among the entries.
+// a, b and c = a b of rows [0, n_used) at perm[row]; the rows above n_used are qap_zero_kernel's.
+template <int T>
+__global__ __launch_bounds__(64 * EVAL_WAVES) void zkey_eval_kernel(
+    const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ fac, const uint32_t* __restrict__ cidx, const Fr* __restrict__ coef,
+    const uint32_t* __restrict__ perm, uint32_t n_used, const uint8_t* __restrict__ witness, uint32_t n_witness, uint32_t batch,
+    uint32_t montgomery, Fr* __restrict__ A, Fr* __restrict__ B, Fr* __restrict__ C, uint32_t log_n) {
+    constexpr uint32_t G = 64 / T;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t set = blockIdx.x * T + lane % T;
+    const bool set_ok = set < batch;
+    if (!set_ok) set = batch - 1;
+    const uint8_t* row = witness + (size_t)set * n_witness * 32;
+    const size_t out_row = (size_t)set << log_n;
+    const uint32_t n_groups = (n_used + G - 1) / G;
+    for (uint32_t g = blockIdx.y * EVAL_WAVES + wave; g < n_groups; g += gridDim.y * EVAL_WAVES) {
+        uint32_t c = g * G + lane / T;
+        const bool c_ok = c < n_used;
+        if (!c_ok) c = n_used - 1;
+        const uint32_t ka = rowptr[2 * c], kb = rowptr[2 * c + 1], kc = rowptr[2 * c + 2];
+        Fr a = lin_comb(fac, cidx, coef, ka, kb, row);
+        Fr b = lin_comb(fac, cidx, coef, kb, kc, row);
+        if (!montgomery) {  // canonical row: the sums are canonical
+            a = cwc::fr_to_mont(a);
+            b = cwc::fr_to_mont(b);
+        }
+        const Fr ab = cwc::fr_mul(a, b);
+        if (set_ok && c_ok) {
+            const size_t o = out_row + perm[c];
+            A[o] = a;
+            B[o] = b;
+            C[o] = ab;
+        }
+    }
+}
+
+// rows n_used .. n-1 of every set: a = b = c = 0 (n_used < n: the caller skips the launch otherwise)
+__global__ __launch_bounds__(THREADS) void qap_zero_kernel(uint32_t batch, uint32_t n_used, Fr* __restrict__ A, Fr* __restrict__ B,
+                                                           Fr* __restrict__ C, uint32_t log_n) {
+    const uint64_t per = (1ull << log_n) - n_used, total = per * batch;
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < total; k += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t set = k / per, s = k % per;
+        const size_t o = (set << log_n) + n_used + s;
+        A[o] = cwc::fr_zero();
+        B[o] = cwc::fr_zero();
+        C[o] = cwc::fr_zero();
     }
 }
 
@@ -283,6 +338,18 @@ EvalFn eval_for(uint32_t t) {
     }
 }
 
+EvalFn zkey_eval_for(uint32_t t) {
+    switch (t) {
+        case 1: return zkey_eval_kernel<1>;
+        case 2: return zkey_eval_kernel<2>;
+        case 4: return zkey_eval_kernel<4>;
+        case 8: return zkey_eval_kernel<8>;
+        case 16: return zkey_eval_kernel<16>;
+        case 32: return zkey_eval_kernel<32>;
+        default: return zkey_eval_kernel<64>;
+    }
+}
+
 struct Domain {
     uint64_t n_rows = 0;
     uint32_t p = 0;
@@ -337,8 +404,8 @@ void qap_roots(uint32_t p, Fr& wn, Fr& g) {
 namespace {
 
 // twiddle and coset tables of the handle's domain, on its device (synchronous, first call only)
-bool ensure_tables(gwb_r1cs* r, uint32_t p, std::string& err) {
-    if (r->d_qap_tw) return true;
+bool ensure_tables(QapState& st, uint32_t p, std::string& err) {
+    if (st.d_tw) return true;
     const uint64_t n = 1ull << p;
     Fr rm1 = cwc::fr_p();
     rm1.v[0] -= 1;  // r is odd
@@ -373,23 +440,23 @@ bool ensure_tables(gwb_r1cs* r, uint32_t p, std::string& err) {
         err = hip_err("building the QAP twiddle tables", e);
         return false;
     }
-    r->d_qap_tw = tw;
-    r->d_qap_coset = cs;
+    st.d_tw = tw;
+    st.d_coset = cs;
     return true;
 }
 
-bool ensure_workspace(gwb_r1cs* r, uint64_t bytes, std::string& err) {
-    if (r->qap_ws_bytes >= bytes) return true;
-    if (r->d_qap_ws) (void)hipFree(r->d_qap_ws);  // (synchronises with earlier work that used it)
-    r->d_qap_ws = nullptr;
-    r->qap_ws_bytes = 0;
-    hipError_t e = hipMalloc(&r->d_qap_ws, bytes);
+bool ensure_workspace(QapState& q, uint64_t bytes, std::string& err) {
+    if (q.ws_bytes >= bytes) return true;
+    if (q.d_ws) (void)hipFree(q.d_ws);  // (synchronises with earlier work that used it)
+    q.d_ws = nullptr;
+    q.ws_bytes = 0;
+    hipError_t e = hipMalloc(&q.d_ws, bytes);
     if (e != hipSuccess) {
-        r->d_qap_ws = nullptr;
+        q.d_ws = nullptr;
         err = hip_err("allocating the QAP workspace", e);
         return false;
     }
-    r->qap_ws_bytes = bytes;
+    q.ws_bytes = bytes;
     return true;
 }
 
@@ -413,49 +480,18 @@ bool launch_pass(int kind, PassArgs a, uint64_t rows, hipStream_t stream, std::s
     return true;
 }
 
-// h of `rows` rows: d_w rows -> A, B (workspace), C = d_h -> h in d_h
-bool enqueue_sub(gwb_r1cs* r, const Domain& dom, const uint8_t* d_w, uint64_t rows, uint32_t form_in, Fr* d_h, uint32_t form_out,
-                 hipStream_t stream, std::string& err) {
-    const uint32_t p = dom.p, nc = r->info.n_constraints, nw = r->info.n_wires;
-    const uint64_t n = 1ull << p;
-    Fr* A = (Fr*)r->d_qap_ws;
-    Fr* B = A + rows * n;
-    const uint32_t mont = form_in == GWB_FORM_MONTGOMERY ? 1u : 0u;
-    hipEvent_t* ev = (hipEvent_t*)r->qap_events;  // (ev[0] null: not timing)
-    if (ev[0]) (void)hipEventRecord(ev[0], stream);
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, r->device) != hipSuccess || cus <= 0) cus = 256;
-    if (nc) {
-        const uint32_t t = r->tile_width ? r->tile_width : pick_tile_width(rows);
-        const uint32_t g = 64 / t;
-        const uint64_t n_groups = (nc + (uint64_t)g - 1) / g, tiles = (rows + t - 1) / t;
-        const uint64_t want_y = std::max<uint64_t>(1, (uint64_t)cus * 8 / std::max<uint64_t>(tiles, 1));
-        const uint64_t gy = std::min<uint64_t>({want_y, (n_groups + EVAL_WAVES - 1) / EVAL_WAVES, 65535});
-        if (tiles > 0x7fffffffull) {
-            err = "r1cs: batch too large for one launch";
-            return false;
-        }
-        hipLaunchKernelGGL(eval_for(t), dim3((uint32_t)tiles, (uint32_t)gy), dim3(64 * EVAL_WAVES), 0, stream, (const uint32_t*)r->d_rowptr,
-                           (const uint32_t*)r->d_fac, (const uint32_t*)r->d_cidx, (const Fr*)r->d_coef, (const uint32_t*)r->d_perm, nc, d_w, nw,
-                           (uint32_t)rows, mont, A, B, d_h, p);
-    }
-    const uint64_t pad = (n - nc) * rows;
-    const uint32_t pad_blocks = (uint32_t)std::min<uint64_t>((pad + THREADS - 1) / THREADS, (uint64_t)cus * 16);
-    hipLaunchKernelGGL(qap_pad_kernel, dim3(pad_blocks), dim3(THREADS), 0, stream, d_w, nw, (uint32_t)rows, mont, nc,
-                       r->info.n_pub_out + r->info.n_pub_in, A, B, d_h, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        err = hip_err("launching the QAP evaluation", e);
-        return false;
-    }
+// The NTT chain over `rows` rows of evaluations (A, B in the workspace, C in d_h): three inverse transforms, the coset
+// shift, three forward transforms and h = A B - C into d_h.  Records the state's phase events 1 to 4.
+bool transform(QapState& q, uint32_t p, Fr* A, Fr* B, Fr* d_h, uint64_t rows, uint32_t form_out, hipStream_t stream, std::string& err) {
+    hipEvent_t* ev = (hipEvent_t*)q.events;  // (ev[0] null: not timing)
     if (ev[0]) (void)hipEventRecord(ev[1], stream);
     const Plan pl = make_plan(p);
     PassArgs a{};
     a.arr[0] = A;
     a.arr[1] = B;
     a.arr[2] = d_h;
-    a.tw = (const Fr*)r->d_qap_tw;
-    a.coset = (const Fr*)r->d_qap_coset;
+    a.tw = (const Fr*)q.d_tw;
+    a.coset = (const Fr*)q.d_coset;
     a.log_n = p;
     a.mont_out = form_out == GWB_FORM_MONTGOMERY ? 1u : 0u;
     uint32_t log_s[4], below = p;
@@ -486,16 +522,54 @@ bool enqueue_sub(gwb_r1cs* r, const Domain& dom, const uint8_t* d_w, uint64_t ro
     return true;
 }
 
+// h of `rows` rows: d_w rows -> A, B (workspace), C = d_h -> h in d_h
+bool enqueue_sub(gwb_r1cs* r, const Domain& dom, const uint8_t* d_w, uint64_t rows, uint32_t form_in, Fr* d_h, uint32_t form_out,
+                 hipStream_t stream, std::string& err) {
+    const uint32_t p = dom.p, nc = r->info.n_constraints, nw = r->info.n_wires;
+    const uint64_t n = 1ull << p;
+    Fr* A = (Fr*)r->qap.d_ws;
+    Fr* B = A + rows * n;
+    const uint32_t mont = form_in == GWB_FORM_MONTGOMERY ? 1u : 0u;
+    hipEvent_t* ev = (hipEvent_t*)r->qap.events;  // (ev[0] null: not timing)
+    if (ev[0]) (void)hipEventRecord(ev[0], stream);
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, r->device) != hipSuccess || cus <= 0) cus = 256;
+    if (nc) {
+        const uint32_t t = r->tile_width ? r->tile_width : pick_tile_width(rows);
+        const uint32_t g = 64 / t;
+        const uint64_t n_groups = (nc + (uint64_t)g - 1) / g, tiles = (rows + t - 1) / t;
+        const uint64_t want_y = std::max<uint64_t>(1, (uint64_t)cus * 8 / std::max<uint64_t>(tiles, 1));
+        const uint64_t gy = std::min<uint64_t>({want_y, (n_groups + EVAL_WAVES - 1) / EVAL_WAVES, 65535});
+        if (tiles > 0x7fffffffull) {
+            err = "r1cs: batch too large for one launch";
+            return false;
+        }
+        hipLaunchKernelGGL(eval_for(t), dim3((uint32_t)tiles, (uint32_t)gy), dim3(64 * EVAL_WAVES), 0, stream, (const uint32_t*)r->d_rowptr,
+                           (const uint32_t*)r->d_fac, (const uint32_t*)r->d_cidx, (const Fr*)r->d_coef, (const uint32_t*)r->d_perm, nc, d_w, nw,
+                           (uint32_t)rows, mont, A, B, d_h, p);
+    }
+    const uint64_t pad = (n - nc) * rows;
+    const uint32_t pad_blocks = (uint32_t)std::min<uint64_t>((pad + THREADS - 1) / THREADS, (uint64_t)cus * 16);
+    hipLaunchKernelGGL(qap_pad_kernel, dim3(pad_blocks), dim3(THREADS), 0, stream, d_w, nw, (uint32_t)rows, mont, nc,
+                       r->info.n_pub_out + r->info.n_pub_in, A, B, d_h, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        err = hip_err("launching the QAP evaluation", e);
+        return false;
+    }
+    return transform(r->qap, p, A, B, d_h, rows, form_out, stream, err);
+}
+
 bool form_ok(uint32_t f) { return f == GWB_FORM_CANONICAL || f == GWB_FORM_MONTGOMERY; }
 
 // device rows -> d_h, in sub-batches under the workspace cap
 bool enqueue_qap(gwb_r1cs* r, const void* d_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out, hipStream_t stream,
                  std::string& err) {
     Domain dom;
-    if (!domain_of(r, dom, err) || !ensure_device(r, err) || !ensure_tables(r, dom.p, err)) return false;
+    if (!domain_of(r, dom, err) || !ensure_device(r, err) || !ensure_tables(r->qap, dom.p, err)) return false;
     const uint64_t per = ws_per_row(dom.p);
     const uint64_t sub = std::min<uint64_t>(batch, std::max<uint64_t>(1, ws_cap() / per));
-    if (!ensure_workspace(r, sub * per, err)) return false;
+    if (!ensure_workspace(r->qap, sub * per, err)) return false;
     const uint64_t n = 1ull << dom.p;
     for (uint64_t s0 = 0; s0 < batch; s0 += sub) {
         const uint64_t rows = std::min<uint64_t>(sub, batch - s0);
@@ -539,6 +613,161 @@ int qap_host(gwb_r1cs* r, const void* witness, size_t n_witness, size_t batch, v
     return 0;
 }
 
+// -- the same witness map from a zkey's section 4 (groth16_internal.hpp; the host arrays are zkey_coefs.cc's)
+
+uint32_t zkey_power(const gwb_zkey* z) {  // domainSize is a power of two in 2 .. 2^27 once the map is built
+    uint32_t p = 0;
+    while ((1u << p) < z->info.domain_size) ++p;
+    return p;
+}
+
+template <class V>
+bool zkey_upload(void** d, const V& v, std::string& err) {
+    const size_t bytes = std::max<size_t>(v.size() * sizeof(v[0]), 4);
+    hipError_t e = hipMalloc(d, bytes);
+    if (e == hipSuccess && !v.empty()) e = hipMemcpy(*d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        err = hip_err("uploading the zkey's coefficient arrays", e);
+        return false;
+    }
+    return true;
+}
+
+void release_zkey_arrays(gwb_zkey* z) {
+    for (void** p : {&z->d_rowptr, &z->d_fac, &z->d_cidx, &z->d_coef, &z->d_perm}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    z->qap_device = -1;
+}
+
+// The coefficient arrays go to the current device at the first call and stay there (the device of the zkey's points, if
+// those are already uploaded).
+bool ensure_zkey_device(gwb_zkey* z, std::string& err) {
+    int dev = -1, n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+        err = "zkey: no HIP device (the witness map runs on the GPU only)";
+        return false;
+    }
+    if (hipGetDevice(&dev) != hipSuccess) {
+        err = "zkey: hipGetDevice failed";
+        return false;
+    }
+    const int home = z->qap_device >= 0 ? z->qap_device : z->device;
+    if (home >= 0 && dev != home) {
+        err = "zkey: the handle's arrays live on device " + std::to_string(home) + ", the current device is " + std::to_string(dev);
+        return false;
+    }
+    if (z->qap_device >= 0) return true;
+    if (!zkey_upload(&z->d_rowptr, z->rowptr, err) || !zkey_upload(&z->d_fac, z->fac, err) || !zkey_upload(&z->d_cidx, z->cidx, err) ||
+        !zkey_upload(&z->d_coef, z->coef, err) || !zkey_upload(&z->d_perm, z->perm, err)) {
+        release_zkey_arrays(z);
+        return false;
+    }
+    z->qap_device = dev;
+    return true;
+}
+
+bool zkey_check_args(const gwb_zkey* z, size_t n_witness, size_t batch, std::string& err) {
+    if (n_witness != z->info.n_vars) {
+        err = "zkey: the witness has " + std::to_string(n_witness) + " elements, the key nVars = " + std::to_string(z->info.n_vars);
+        return false;
+    }
+    if (batch > 0xffffffffull) {
+        err = "zkey: batch above 2^32 - 1";
+        return false;
+    }
+    return true;
+}
+
+// h of `rows` rows: d_w rows -> A, B (workspace), C = d_h -> h in d_h
+bool zkey_enqueue_sub(gwb_zkey* z, uint32_t p, const uint8_t* d_w, uint64_t rows, uint32_t form_in, Fr* d_h, uint32_t form_out,
+                      hipStream_t stream, std::string& err) {
+    const uint32_t nu = z->n_used, nw = z->info.n_vars;  // 1 <= nu <= n
+    const uint64_t n = 1ull << p;
+    Fr* A = (Fr*)z->qap.d_ws;
+    Fr* B = A + rows * n;
+    const uint32_t mont = form_in == GWB_FORM_MONTGOMERY ? 1u : 0u;
+    hipEvent_t* ev = (hipEvent_t*)z->qap.events;  // (ev[0] null: not timing)
+    if (ev[0]) (void)hipEventRecord(ev[0], stream);
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, z->qap_device) != hipSuccess || cus <= 0) cus = 256;
+    const uint32_t t = z->tile_width ? z->tile_width : pick_tile_width(rows);
+    const uint32_t g = 64 / t;
+    const uint64_t n_groups = (nu + (uint64_t)g - 1) / g, tiles = (rows + t - 1) / t;
+    const uint64_t want_y = std::max<uint64_t>(1, (uint64_t)cus * 8 / std::max<uint64_t>(tiles, 1));
+    const uint64_t gy = std::min<uint64_t>({want_y, (n_groups + EVAL_WAVES - 1) / EVAL_WAVES, 65535});
+    if (tiles > 0x7fffffffull) {
+        err = "zkey: batch too large for one launch";
+        return false;
+    }
+    hipLaunchKernelGGL(zkey_eval_for(t), dim3((uint32_t)tiles, (uint32_t)gy), dim3(64 * EVAL_WAVES), 0, stream, (const uint32_t*)z->d_rowptr,
+                       (const uint32_t*)z->d_fac, (const uint32_t*)z->d_cidx, (const Fr*)z->d_coef, (const uint32_t*)z->d_perm, nu, d_w, nw,
+                       (uint32_t)rows, mont, A, B, d_h, p);
+    const uint64_t pad = (n - nu) * rows;
+    if (pad) {  // nu == n (nC + nPublic + 1 a power of two): no row is left to clear, and a grid of 0 blocks is no launch
+        const uint32_t pad_blocks = (uint32_t)std::min<uint64_t>((pad + THREADS - 1) / THREADS, (uint64_t)cus * 16);
+        hipLaunchKernelGGL(qap_zero_kernel, dim3(pad_blocks), dim3(THREADS), 0, stream, (uint32_t)rows, nu, A, B, d_h, p);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        err = hip_err("launching the QAP evaluation of section 4", e);
+        return false;
+    }
+    return transform(z->qap, p, A, B, d_h, rows, form_out, stream, err);
+}
+
+// device rows -> d_h, in sub-batches under the workspace cap
+bool zkey_enqueue_qap(gwb_zkey* z, const void* d_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out, hipStream_t stream,
+                      std::string& err) {
+    if (!zkey_coefs_build(z, err) || !ensure_zkey_device(z, err)) return false;
+    const uint32_t p = zkey_power(z);
+    if (!ensure_tables(z->qap, p, err)) return false;
+    const uint64_t per = ws_per_row(p);
+    const uint64_t sub = std::min<uint64_t>(batch, std::max<uint64_t>(1, ws_cap() / per));
+    if (!ensure_workspace(z->qap, sub * per, err)) return false;
+    const uint64_t n = 1ull << p;
+    for (uint64_t s0 = 0; s0 < batch; s0 += sub) {
+        const uint64_t rows = std::min<uint64_t>(sub, batch - s0);
+        if (!zkey_enqueue_sub(z, p, (const uint8_t*)d_witness + s0 * z->info.n_vars * 32, rows, form_in, (Fr*)d_h + s0 * n, form_out, stream, err))
+            return false;
+    }
+    return true;
+}
+
+int zkey_qap_host(gwb_zkey* z, const void* witness, size_t n_witness, size_t batch, void* h, uint32_t form_out, gw_status_t* status) {
+    std::string err;
+    if (!zkey_coefs_build(z, err) || !zkey_check_args(z, n_witness, batch, err)) return fail(status, err);
+    if (batch == 0) {
+        set_ok(status);
+        return 0;
+    }
+    if (!ensure_zkey_device(z, err)) return fail(status, err);
+    void *d_w = nullptr, *d_h = nullptr;
+    hipStream_t s = nullptr;
+    const size_t wbytes = batch * n_witness * 32, hbytes = (batch * 32) << zkey_power(z);
+    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc(&d_w, wbytes);
+    if (e == hipSuccess) e = hipMalloc(&d_h, hbytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_w, witness, wbytes, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) err = hip_err("staging the witness rows", e);
+    bool ok = e == hipSuccess && zkey_enqueue_qap(z, d_w, batch, GWB_FORM_CANONICAL, d_h, form_out, s, err);
+    if (ok) {
+        e = hipMemcpyAsync(h, d_h, hbytes, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            err = hip_err("running the QAP witness map", e);
+            ok = false;
+        }
+    }
+    if (d_w) (void)hipFree(d_w);
+    if (d_h) (void)hipFree(d_h);
+    if (s) (void)hipStreamDestroy(s);
+    if (!ok) return fail(status, err);
+    set_ok(status);
+    return 0;
+}
+
 }  // namespace
 
 namespace cwc_r1cs {
@@ -548,13 +777,23 @@ bool qap_enqueue(gwb_r1cs* r, const void* d_witness, size_t batch, uint32_t form
     return enqueue_qap(r, d_witness, batch, form_in, d_h, form_out, (hipStream_t)stream, err);
 }
 
-void release_qap(gwb_r1cs* r) {
-    for (void** p : {&r->d_qap_tw, &r->d_qap_coset, &r->d_qap_ws}) {
+bool zkey_qap_enqueue(gwb_zkey* z, const void* d_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out, void* stream,
+                      std::string& err) {
+    return zkey_enqueue_qap(z, d_witness, batch, form_in, d_h, form_out, (hipStream_t)stream, err);
+}
+
+void release_zkey_qap(gwb_zkey* z) {
+    release_qap(z->qap);
+    release_zkey_arrays(z);
+}
+
+void release_qap(QapState& q) {
+    for (void** p : {&q.d_tw, &q.d_coset, &q.d_ws}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
-    r->qap_ws_bytes = 0;
-    for (void*& e : r->qap_events) {
+    q.ws_bytes = 0;
+    for (void*& e : q.events) {
         if (e) (void)hipEventDestroy((hipEvent_t)e);
         e = nullptr;
     }
@@ -610,14 +849,36 @@ int gwb_r1cs_qap_wtns(gwb_r1cs_t* r, const void* wtns, size_t len, void* h_out, 
     return qap_host(r, values, n_wit, 1, h_out, form_out, status);
 }
 
+int gwb_zkey_qap_batch_device(gwb_zkey_t* z, const void* d_witness, size_t n_witness, size_t batch, uint32_t form_in, void* d_h,
+                              uint32_t form_out, void* hip_stream, gw_status_t* status) {
+    if (!z || (batch && (!d_witness || !d_h))) return fail(status, "gwb_zkey_qap_batch_device: NULL argument");
+    if (!form_ok(form_in)) return fail(status, "gwb_zkey_qap_batch_device: unknown form " + std::to_string(form_in));
+    if (!form_ok(form_out)) return fail(status, "gwb_zkey_qap_batch_device: unknown form " + std::to_string(form_out));
+    std::string err;
+    if (!zkey_coefs_build(z, err) || !zkey_check_args(z, n_witness, batch, err)) return fail(status, err);
+    if (batch == 0) {
+        set_ok(status);
+        return 0;
+    }
+    if (!zkey_enqueue_qap(z, d_witness, batch, form_in, d_h, form_out, (hipStream_t)hip_stream, err)) return fail(status, err);
+    set_ok(status);
+    return 0;
+}
+
+int gwb_zkey_qap_batch_host(gwb_zkey_t* z, const void* witness, size_t n_witness, size_t batch, void* h, uint32_t form_out, gw_status_t* status) {
+    if (!z || (batch && (!witness || !h))) return fail(status, "gwb_zkey_qap_batch_host: NULL argument");
+    if (!form_ok(form_out)) return fail(status, "gwb_zkey_qap_batch_host: unknown form " + std::to_string(form_out));
+    return zkey_qap_host(z, witness, n_witness, batch, h, form_out, status);
+}
+
 int gwb_r1cs_qap_time_phases(gwb_r1cs_t* r, int on) {
     if (!r) return 1;
-    for (void*& e : r->qap_events) {
+    for (void*& e : r->qap.events) {
         if (e) (void)hipEventDestroy((hipEvent_t)e);
         e = nullptr;
     }
     if (!on) return 0;
-    for (void*& e : r->qap_events) {
+    for (void*& e : r->qap.events) {
         hipEvent_t h = nullptr;
         if (hipEventCreate(&h) != hipSuccess) {
             gwb_r1cs_qap_time_phases(r, 0);
@@ -658,8 +919,8 @@ int gwb_r1cs_modmul_rate(double* products_per_s) {
 }
 
 int gwb_r1cs_qap_phase_ms(gwb_r1cs_t* r, float* ms) {
-    if (!r || !ms || !r->qap_events[0]) return 1;
-    hipEvent_t* ev = (hipEvent_t*)r->qap_events;
+    if (!r || !ms || !r->qap.events[0]) return 1;
+    hipEvent_t* ev = (hipEvent_t*)r->qap.events;
     if (hipEventSynchronize(ev[4]) != hipSuccess) return 1;
     for (int i = 0; i < 4; ++i)
         if (hipEventElapsedTime(ms + i, ev[i], ev[i + 1]) != hipSuccess) return 1;

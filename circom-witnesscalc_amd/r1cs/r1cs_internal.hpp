@@ -37,7 +37,16 @@ bool check_args(gwb_r1cs* r, size_t n_witness, size_t batch, std::string& err);
 int fail(gw_status_t* st, const std::string& msg);      // set_status + return 1
 // A `.wtns` image as gwb_r1cs_check_wtns validates it: the witness values (elements below r) and their count.
 bool parse_wtns(const void* wtns, size_t len, const uint8_t** values, uint64_t* n_wit, std::string& err);
-void release_qap(gwb_r1cs* r);                           // qap.hip: the QAP tables and workspace
+
+// Device state of one QAP domain (qap.hip), owned by the handle whose witness map runs on it (a gwb_r1cs, or a gwb_zkey
+// proving from its section 4): twiddles w_n^e and per-position coset factors, n each, built at the first QAP call; the A / B
+// workspace, grown on demand; phase-timing events (hipEvent_t, recorded around each phase while events[0] is set).
+struct QapState {
+    void *d_tw = nullptr, *d_coset = nullptr, *d_ws = nullptr;
+    size_t ws_bytes = 0;
+    void* events[5] = {};
+};
+void release_qap(QapState& q);                           // qap.hip: the QAP tables, workspace and events
 }  // namespace cwc_r1cs
 
 struct gwb_r1cs {
@@ -51,9 +60,6 @@ struct gwb_r1cs {
     // device copies (first check call)
     int device = -1;
     void *d_rowptr = nullptr, *d_fac = nullptr, *d_cidx = nullptr, *d_coef = nullptr, *d_perm = nullptr;
-    // QAP witness map (qap.hip, first QAP call, on the same device): twiddles w_n^e and per-position coset factors, n each;
-    // the A / B workspace, grown on demand
-    void *d_qap_tw = nullptr, *d_qap_coset = nullptr, *d_qap_ws = nullptr;
-    size_t qap_ws_bytes = 0;
-    void* qap_events[5] = {};  // phase timing (gwb_r1cs_qap_time_phases): hipEvent_t, recorded around each phase
+    // QAP witness map (qap.hip, first QAP call, on the same device); its events are those of gwb_r1cs_qap_time_phases
+    cwc_r1cs::QapState qap;
 };

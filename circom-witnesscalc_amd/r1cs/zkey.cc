@@ -133,7 +133,8 @@ void load(const uint8_t* d, size_t len, gwb_zkey& z) {
     check_points("gamma2", z.gamma2, 1, true);
     check_points("delta1", z.delta1, 1, false);
     check_points("delta2", z.delta2, 1, true);
-    // -- section 4 (bounds only: the witness map comes from the .r1cs)
+    // -- section 4 (bounds only here; the entries are kept, and the witness map is built from them at its first use:
+    //    zkey_coefs.cc, which also refuses what a prover cannot use -- values >= r, no entries, a domain the NTT cannot take)
     {
         const uint64_t size = secs[4].size;
         if (size < 4) throw Fail{"zkey: section 4 (coefficients) is truncated"};
@@ -148,6 +149,7 @@ void load(const uint8_t* d, size_t len, gwb_zkey& z) {
             if (rd32(e + 4) >= in.domain_size) throw Fail{"zkey: coefficient " + std::to_string(k) + " names a constraint >= domainSize"};
             if (rd32(e + 8) >= in.n_vars) throw Fail{"zkey: coefficient " + std::to_string(k) + " names a signal >= nVars"};
         }
+        z.sec4.assign(p + 4, p + size);
     }
     // -- point sections
     struct PS {
