@@ -636,6 +636,49 @@ def modmul_rate():
     return rate.value
 
 
+# -- the Groth16 witness map, shared by R1cs (gwb_r1cs_qap_*) and Groth16 (gwb_zkey_qap_*): `src` is "r1cs" or "zkey" ----------
+def _qap_info(h, src):
+    info = R1csQapInfo()
+    st = GwStatus()
+    rc = getattr(r1cs_lib(), "gwb_%s_qap_info" % src)(h, ctypes.byref(info), ctypes.byref(st))
+    _r1cs_check(rc, st)
+    return {n: int(getattr(info, n)) for n, _ in R1csQapInfo._fields_}
+
+
+def _qap_batch(h, src, witness_rows, montgomery_out):
+    if isinstance(witness_rows, tuple):
+        witness_rows = witness_rows[0]
+    w = np.ascontiguousarray(witness_rows, dtype=np.uint8)
+    assert w.ndim == 3 and w.shape[2] == 32, w.shape
+    b = w.shape[0]
+    out = np.zeros((b, _qap_info(h, src)["domain_size"], 32), dtype=np.uint8)
+    st = GwStatus()
+    rc = getattr(r1cs_lib(), "gwb_%s_qap_batch_host" % src)(h, w.ctypes.data, w.shape[1], b, out.ctypes.data,
+                                                            FORM_MONTGOMERY if montgomery_out else FORM_CANONICAL, ctypes.byref(st))
+    _r1cs_check(rc, st)
+    return out
+
+
+def _qap_batch_device(h, src, d_witness, stream, montgomery, montgomery_out):
+    import torch
+    assert d_witness.is_cuda and d_witness.is_contiguous() and d_witness.dtype == torch.uint8
+    assert d_witness.dim() == 3 and d_witness.shape[2] == 32, tuple(d_witness.shape)
+    b = d_witness.shape[0]
+    n = _qap_info(h, src)["domain_size"]
+    s = stream if stream is not None else torch.cuda.current_stream(d_witness.device)
+    out = torch.empty((b, n, 32), dtype=torch.uint8, device=d_witness.device)
+    st = GwStatus()
+    with torch.cuda.device(d_witness.device):
+        rc = getattr(r1cs_lib(), "gwb_%s_qap_batch_device" % src)(h, d_witness.data_ptr(), d_witness.shape[1], b,
+                                                                  FORM_MONTGOMERY if montgomery else FORM_CANONICAL, out.data_ptr(),
+                                                                  FORM_MONTGOMERY if montgomery_out else FORM_CANONICAL, s.cuda_stream,
+                                                                  ctypes.byref(st))
+    _r1cs_check(rc, st)
+    if b:
+        out.record_stream(s)
+    return out
+
+
 class R1cs:
     """A circuit's constraint system (`.r1cs` bytes, iden3 binfile v1; BN254, no custom gates) for checking witness rows on the
     GPU: per row, the smallest failing constraint index (R1CS_SATISFIED if none) and the number of failing constraints."""
@@ -708,49 +751,18 @@ class R1cs:
     # -- Groth16 witness map (h, the scalars of the prover's H-point MSM; definition in include/graph_witness_r1cs.h) --------
     def qap_info(self):
         """{n_rows, domain_power, domain_size, workspace_bytes_per_row} of the QAP domain; raises for a domain above 2^27."""
-        info = R1csQapInfo()
-        st = GwStatus()
-        rc = r1cs_lib().gwb_r1cs_qap_info(self._h, ctypes.byref(info), ctypes.byref(st))
-        _r1cs_check(rc, st)
-        return {n: int(getattr(info, n)) for n, _ in R1csQapInfo._fields_}
+        return _qap_info(self._h, "r1cs")
 
     def qap_batch(self, witness_rows, montgomery_out=False):
         """Host rows uint8 [B, W, 32] (canonical), or the (witness, status) pair of Graph.calc_witness_batch -> h as uint8
         [B, n, 32] (canonical, or Montgomery with montgomery_out).  Synchronous."""
-        if isinstance(witness_rows, tuple):
-            witness_rows = witness_rows[0]
-        w = np.ascontiguousarray(witness_rows, dtype=np.uint8)
-        assert w.ndim == 3 and w.shape[2] == 32, w.shape
-        b = w.shape[0]
-        n = self.qap_info()["domain_size"]
-        h = np.zeros((b, n, 32), dtype=np.uint8)
-        st = GwStatus()
-        rc = r1cs_lib().gwb_r1cs_qap_batch_host(self._h, w.ctypes.data, w.shape[1], b, h.ctypes.data,
-                                                FORM_MONTGOMERY if montgomery_out else FORM_CANONICAL, ctypes.byref(st))
-        _r1cs_check(rc, st)
-        return h
+        return _qap_batch(self._h, "r1cs", witness_rows, montgomery_out)
 
     def qap_batch_device(self, d_witness, stream=None, montgomery=False, montgomery_out=False):
         """Device rows (torch uint8 cuda tensor [B, W, 32], canonical or Montgomery form) -> h as a uint8 cuda tensor [B, n, 32].
         Asynchronous on `stream` (torch.cuda.Stream) or the current torch stream: put it behind
         Graph.calc_witness_batch_device on the same stream."""
-        import torch
-        assert d_witness.is_cuda and d_witness.is_contiguous() and d_witness.dtype == torch.uint8
-        assert d_witness.dim() == 3 and d_witness.shape[2] == 32, tuple(d_witness.shape)
-        b = d_witness.shape[0]
-        n = self.qap_info()["domain_size"]
-        s = stream if stream is not None else torch.cuda.current_stream(d_witness.device)
-        h = torch.empty((b, n, 32), dtype=torch.uint8, device=d_witness.device)
-        st = GwStatus()
-        with torch.cuda.device(d_witness.device):
-            rc = r1cs_lib().gwb_r1cs_qap_batch_device(self._h, d_witness.data_ptr(), d_witness.shape[1], b,
-                                                      FORM_MONTGOMERY if montgomery else FORM_CANONICAL, h.data_ptr(),
-                                                      FORM_MONTGOMERY if montgomery_out else FORM_CANONICAL, s.cuda_stream,
-                                                      ctypes.byref(st))
-        _r1cs_check(rc, st)
-        if b:
-            h.record_stream(s)
-        return h
+        return _qap_batch_device(self._h, "r1cs", d_witness, stream, montgomery, montgomery_out)
 
     def qap_time_phases(self, on=True):
         """Measurement aid: record HIP events around the phases of later QAP calls (see qap_phase_ms)."""
@@ -854,47 +866,17 @@ class Groth16:
 
     def qap_info(self):
         """{n_rows, domain_power, domain_size, workspace_bytes_per_row}; n_rows = 1 + the largest constraint index in section 4."""
-        info = R1csQapInfo()
-        st = GwStatus()
-        rc = r1cs_lib().gwb_zkey_qap_info(self._h, ctypes.byref(info), ctypes.byref(st))
-        _r1cs_check(rc, st)
-        return {n: int(getattr(info, n)) for n, _ in R1csQapInfo._fields_}
+        return _qap_info(self._h, "zkey")
 
     def qap_batch(self, witness_rows, montgomery_out=False):
         """Host rows uint8 [B, nVars, 32] (canonical) -> h as uint8 [B, n, 32] (canonical, or Montgomery with montgomery_out), as
         R1cs.qap_batch.  Synchronous."""
-        if isinstance(witness_rows, tuple):
-            witness_rows = witness_rows[0]
-        w = np.ascontiguousarray(witness_rows, dtype=np.uint8)
-        assert w.ndim == 3 and w.shape[2] == 32, w.shape
-        b = w.shape[0]
-        h = np.zeros((b, self.qap_info()["domain_size"], 32), dtype=np.uint8)
-        st = GwStatus()
-        rc = r1cs_lib().gwb_zkey_qap_batch_host(self._h, w.ctypes.data, w.shape[1], b, h.ctypes.data,
-                                                FORM_MONTGOMERY if montgomery_out else FORM_CANONICAL, ctypes.byref(st))
-        _r1cs_check(rc, st)
-        return h
+        return _qap_batch(self._h, "zkey", witness_rows, montgomery_out)
 
     def qap_batch_device(self, d_witness, stream=None, montgomery=False, montgomery_out=False):
         """Device rows (torch uint8 cuda tensor [B, nVars, 32], canonical or Montgomery form) -> h as a uint8 cuda tensor
         [B, n, 32], as R1cs.qap_batch_device.  Asynchronous on `stream` or the current torch stream."""
-        import torch
-        assert d_witness.is_cuda and d_witness.is_contiguous() and d_witness.dtype == torch.uint8
-        assert d_witness.dim() == 3 and d_witness.shape[2] == 32, tuple(d_witness.shape)
-        b = d_witness.shape[0]
-        n = self.qap_info()["domain_size"]
-        s = stream if stream is not None else torch.cuda.current_stream(d_witness.device)
-        h = torch.empty((b, n, 32), dtype=torch.uint8, device=d_witness.device)
-        st = GwStatus()
-        with torch.cuda.device(d_witness.device):
-            rc = r1cs_lib().gwb_zkey_qap_batch_device(self._h, d_witness.data_ptr(), d_witness.shape[1], b,
-                                                      FORM_MONTGOMERY if montgomery else FORM_CANONICAL, h.data_ptr(),
-                                                      FORM_MONTGOMERY if montgomery_out else FORM_CANONICAL, s.cuda_stream,
-                                                      ctypes.byref(st))
-        _r1cs_check(rc, st)
-        if b:
-            h.record_stream(s)
-        return h
+        return _qap_batch_device(self._h, "zkey", d_witness, stream, montgomery, montgomery_out)
 
     def prove_batch(self, rows, rs=None):
         """Host rows uint8 [B, nVars, 32] (canonical), or the (witness, status) pair of Graph.calc_witness_batch -> uint8

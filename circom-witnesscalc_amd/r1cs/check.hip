@@ -76,17 +76,19 @@ KernelFn kernel_for(uint32_t t) {
 
 }  // namespace
 
-// Host helpers shared with qap.hip (declared in r1cs_internal.hpp).
+// Host helpers over a RowSystem, shared with qap.hip and msm.hip (declared in r1cs_internal.hpp).
 namespace cwc_r1cs {
 
 // rows per wave: the batch rounded up to a power of two, at most 64 (full waves of rows once there are 64 of them)
-uint32_t pick_tile_width(size_t batch) {
+static uint32_t pick_tile_width(size_t batch) {
     uint32_t t = 1;
     while (t < 64 && t < batch) t <<= 1;
     return t;
 }
 
 std::string hip_err(const char* what, hipError_t e) { return std::string("r1cs: ") + what + ": " + hipGetErrorString(e); }
+
+const char* prefix_of(const RowSystem& s) { return s.stride == 3 ? "r1cs: " : "zkey: "; }
 
 template <class V>
 static bool upload(void** d, const V& v, std::string& err) {
@@ -100,50 +102,70 @@ static bool upload(void** d, const V& v, std::string& err) {
     return true;
 }
 
-static void release_device(gwb_r1cs* r) {
-    for (void** p : {&r->d_rowptr, &r->d_fac, &r->d_cidx, &r->d_coef, &r->d_perm}) {
+void release_device(RowSystem& s) {
+    for (void** p : {&s.d_rowptr, &s.d_fac, &s.d_cidx, &s.d_coef, &s.d_perm}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
-    r->device = -1;
+    s.device = -1;
 }
 
-// The constraint arrays go to the current device on the first check and stay there.
-bool ensure_device(gwb_r1cs* r, std::string& err) {
+bool ensure_device(RowSystem& s, int home, std::string& err) {
+    const std::string who = prefix_of(s);
     int dev = -1, n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-        err = "r1cs: no HIP device (the check runs on the GPU only)";
+        err = who + "no HIP device (the kernels run on the GPU only)";
         return false;
     }
     if (hipGetDevice(&dev) != hipSuccess) {
-        err = "r1cs: hipGetDevice failed";
+        err = who + "hipGetDevice failed";
         return false;
     }
-    if (r->device >= 0) {
-        if (dev != r->device) {
-            err = "r1cs: the handle's constraint arrays live on device " + std::to_string(r->device) + ", the current device is " + std::to_string(dev);
-            return false;
-        }
-        return true;
-    }
-    if (!upload(&r->d_rowptr, r->rowptr, err) || !upload(&r->d_fac, r->fac, err) || !upload(&r->d_cidx, r->cidx, err) ||
-        !upload(&r->d_coef, r->coef, err) || !upload(&r->d_perm, r->perm, err)) {
-        release_device(r);
+    if (s.device >= 0) home = s.device;
+    if (home >= 0 && dev != home) {
+        err = who + "the handle's arrays live on device " + std::to_string(home) + ", the current device is " + std::to_string(dev);
         return false;
     }
-    r->device = dev;
+    if (s.device >= 0) return true;
+    if (!upload(&s.d_rowptr, s.rowptr, err) || !upload(&s.d_fac, s.fac, err) || !upload(&s.d_cidx, s.cidx, err) ||
+        !upload(&s.d_coef, s.coef, err) || !upload(&s.d_perm, s.perm, err)) {
+        release_device(s);
+        return false;
+    }
+    s.device = dev;
     return true;
 }
 
-bool check_args(gwb_r1cs* r, size_t n_witness, size_t batch, std::string& err) {
-    if (n_witness != r->info.n_wires) {
-        err = "r1cs: the witness has " + std::to_string(n_witness) + " elements, the circuit " + std::to_string(r->info.n_wires) + " wires";
+bool check_args(const RowSystem& s, size_t n_witness, size_t batch, std::string& err) {
+    if (n_witness != s.n_wires) {
+        err = s.stride == 3 ? "r1cs: the witness has " + std::to_string(n_witness) + " elements, the circuit " + std::to_string(s.n_wires) + " wires"
+                            : "zkey: the witness has " + std::to_string(n_witness) + " elements, the key nVars = " + std::to_string(s.n_wires);
         return false;
     }
     if (batch > 0xffffffffull) {
-        err = "r1cs: batch above 2^32 - 1";
+        err = std::string(prefix_of(s)) + "batch above 2^32 - 1";
         return false;
     }
+    return true;
+}
+
+int cu_count(int device) {
+    int cus = 0;
+    return hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0 ? cus : 256;
+}
+
+bool eval_grid(const RowSystem& s, uint64_t rows, int cus, int waves, EvalGrid& g, std::string& err) {
+    const uint32_t t = s.tile_width ? s.tile_width : pick_tile_width(rows);
+    const uint32_t per_wave = 64 / t;
+    const uint64_t n_groups = (s.n_rows + (uint64_t)per_wave - 1) / per_wave, tiles = (rows + t - 1) / t;
+    // about eight blocks (32 waves) per CU in all, each wave striding over the constraint groups
+    const uint64_t want_y = std::max<uint64_t>(1, (uint64_t)cus * 8 / std::max<uint64_t>(tiles, 1));
+    const uint64_t gy = std::min<uint64_t>({want_y, (n_groups + waves - 1) / waves, 65535});
+    if (tiles > 0x7fffffffull) {
+        err = std::string(prefix_of(s)) + "batch too large for one launch";
+        return false;
+    }
+    g = EvalGrid{t, (uint32_t)tiles, (uint32_t)gy};
     return true;
 }
 
@@ -221,24 +243,13 @@ bool enqueue(gwb_r1cs* r, const void* d_witness, size_t batch, uint32_t form, ui
         err = hip_err("clearing the results", e);
         return false;
     }
-    const uint32_t nc = r->info.n_constraints;
-    if (nc == 0) return true;
-    const uint32_t t = r->tile_width ? r->tile_width : pick_tile_width(batch);
-    const uint32_t g = 64 / t;
-    const uint64_t n_groups = (nc + (uint64_t)g - 1) / g;
-    const uint64_t tiles = (batch + t - 1) / t;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, r->device) != hipSuccess || cus <= 0) cus = 256;
-    // about eight blocks (32 waves) per CU in all, each wave striding over the constraint groups
-    const uint64_t want_y = std::max<uint64_t>(1, (uint64_t)cus * 8 / std::max<uint64_t>(tiles, 1));
-    const uint64_t gy = std::min<uint64_t>({want_y, (n_groups + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 65535});
-    if (tiles > 0x7fffffffull) {
-        err = "r1cs: batch too large for one launch";
-        return false;
-    }
-    hipLaunchKernelGGL(kernel_for(t), dim3((uint32_t)tiles, (uint32_t)gy), dim3(64 * WAVES_PER_BLOCK), 0, stream, (const uint32_t*)r->d_rowptr,
-                       (const uint32_t*)r->d_fac, (const uint32_t*)r->d_cidx, (const Fr*)r->d_coef, (const uint32_t*)r->d_perm, nc,
-                       (const uint8_t*)d_witness, r->info.n_wires, (uint32_t)batch, form == GWB_FORM_MONTGOMERY ? 1u : 0u, d_first, d_nfail);
+    const RowSystem& sys = r->sys;
+    if (sys.n_rows == 0) return true;
+    EvalGrid g;
+    if (!eval_grid(sys, batch, cu_count(sys.device), WAVES_PER_BLOCK, g, err)) return false;
+    hipLaunchKernelGGL(kernel_for(g.t), dim3(g.tiles, g.gy), dim3(64 * WAVES_PER_BLOCK), 0, stream, (const uint32_t*)sys.d_rowptr,
+                       (const uint32_t*)sys.d_fac, (const uint32_t*)sys.d_cidx, (const Fr*)sys.d_coef, (const uint32_t*)sys.d_perm, sys.n_rows,
+                       (const uint8_t*)d_witness, sys.n_wires, (uint32_t)batch, form == GWB_FORM_MONTGOMERY ? 1u : 0u, d_first, d_nfail);
     e = hipGetLastError();
     if (e != hipSuccess) {
         err = hip_err("launching the check kernel", e);
@@ -250,12 +261,12 @@ bool enqueue(gwb_r1cs* r, const void* d_witness, size_t batch, uint32_t form, ui
 // host rows -> device -> results back; synchronous
 int check_host(gwb_r1cs* r, const void* witness, size_t n_witness, size_t batch, uint32_t* first, uint32_t* nfail, gw_status_t* status) {
     std::string err;
-    if (!check_args(r, n_witness, batch, err)) return fail(status, err);
+    if (!check_args(r->sys, n_witness, batch, err)) return fail(status, err);
     if (batch == 0) {
         set_ok(status);
         return 0;
     }
-    if (!ensure_device(r, err)) return fail(status, err);
+    if (!ensure_device(r->sys, -1, err)) return fail(status, err);
     void *d_w = nullptr, *d_out = nullptr;
     hipStream_t s = nullptr;
     const size_t wbytes = batch * n_witness * 32;
@@ -290,12 +301,12 @@ extern "C" {
 
 void gwb_r1cs_free(gwb_r1cs_t* r) {
     if (!r) return;
-    if (r->device >= 0) {
+    if (r->sys.device >= 0) {
         int cur = -1;
-        const bool switch_dev = hipGetDevice(&cur) == hipSuccess && cur != r->device;
-        if (switch_dev) (void)hipSetDevice(r->device);
-        release_qap(r->qap);
-        release_device(r);
+        const bool switch_dev = hipGetDevice(&cur) == hipSuccess && cur != r->sys.device;
+        if (switch_dev) (void)hipSetDevice(r->sys.device);
+        release_qap(r->sys.qap);
+        release_device(r->sys);
         if (switch_dev) (void)hipSetDevice(cur);
     }
     (void)gwb_r1cs_qap_time_phases(r, 0);
@@ -307,12 +318,12 @@ int gwb_r1cs_check_batch_device(gwb_r1cs_t* r, const void* d_witness, size_t n_w
     if (!r || (batch && (!d_witness || !d_first_failed || !d_n_failed))) return fail(status, "gwb_r1cs_check_batch_device: NULL argument");
     if (form != GWB_FORM_CANONICAL && form != GWB_FORM_MONTGOMERY) return fail(status, "gwb_r1cs_check_batch_device: unknown form " + std::to_string(form));
     std::string err;
-    if (!check_args(r, n_witness, batch, err)) return fail(status, err);
+    if (!check_args(r->sys, n_witness, batch, err)) return fail(status, err);
     if (batch == 0) {
         set_ok(status);
         return 0;
     }
-    if (!ensure_device(r, err) || !enqueue(r, d_witness, batch, form, d_first_failed, d_n_failed, (hipStream_t)hip_stream, err))
+    if (!ensure_device(r->sys, -1, err) || !enqueue(r, d_witness, batch, form, d_first_failed, d_n_failed, (hipStream_t)hip_stream, err))
         return fail(status, err);
     set_ok(status);
     return 0;

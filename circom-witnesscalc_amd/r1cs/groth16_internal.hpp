@@ -1,4 +1,5 @@
-// Host representation of a loaded `.zkey` (zkey.cc), shared with the prover (msm.hip).
+// Host representation of a loaded `.zkey` (zkey.cc), shared with the prover (msm.hip) and the witness map (qap.hip), which
+// evaluates the key's section 4 through the same row system as an `.r1cs` (r1cs_internal.hpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -28,31 +29,23 @@ struct gwb_zkey {
     void* events[8] = {};  // phase timing (gwb_groth16_time_phases): recorded around each phase of the last sub-batch
     // Section 4 as stored (n_coefs x 44 B: u32 matrix, constraint, signal, then the value c R^2 mod r), bounds-checked at load.
     std::vector<uint8_t> sec4;
-    // The witness map of section 4 (zkey_coefs.cc, built at the first call that needs it), in the layout of gwb_r1cs without
-    // the C side: row k's A factors are fac[rowptr[2k] .. rowptr[2k+1]), B up to rowptr[2k+2]; perm[k] = its constraint
-    // index; rows bucketed by length.  n_used = 1 + the largest constraint index of any entry.
+    // The witness map of section 4 (zkey_coefs.cc, built at the first call that needs it): a row system without the C side, its
+    // rows [0, n_rows) those up to the largest constraint index of any entry.  Its arrays go to the device of the points above,
+    // if those are already there.
     bool coefs_built = false;
-    uint32_t n_used = 0;
-    std::vector<uint32_t> rowptr, fac, cidx, perm;
-    std::vector<cwc::Fr> coef;  // distinct general coefficients, Montgomery form c R
-    uint32_t tile_width = 0;    // 0 = from the batch size
-    // device copies of the arrays above (first zkey QAP call) and the domain's state (qap.hip)
-    int qap_device = -1;
-    void *d_rowptr = nullptr, *d_fac = nullptr, *d_cidx = nullptr, *d_coef = nullptr, *d_perm = nullptr;
-    cwc_r1cs::QapState qap;
+    cwc_r1cs::RowSystem sys;
+    gwb_zkey() { sys.stride = 2; }
 };
 
 namespace cwc_r1cs {
-// qap.hip: the witness map of device rows into d_h, as gwb_r1cs_qap_batch_device enqueues it (arguments checked by the caller)
-bool qap_enqueue(gwb_r1cs* r, const void* d_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out, void* stream,
-                 std::string& err);
 // zkey_coefs.cc: builds the witness map of section 4 (first call; later calls return at once).  Refusals start "zkey:".
 bool zkey_coefs_build(gwb_zkey* z, std::string& err);
-// qap.hip: the witness map of device rows from the zkey's section 4 into d_h (arguments checked by the caller, the map built)
-bool zkey_qap_enqueue(gwb_zkey* z, const void* d_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out, void* stream,
-                      std::string& err);
-// qap.hip: the device side of a zkey's witness map (arrays, tables, workspace)
-void release_zkey_qap(gwb_zkey* z);
+// qap.hip: the witness map of device rows into d_h, as gwb_r1cs_qap_batch_device / gwb_zkey_qap_batch_device enqueue it: from
+// the .r1cs, or from the zkey's section 4 (arguments checked by the caller, the map built)
+bool qap_enqueue(gwb_r1cs* r, const void* d_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out, void* stream,
+                 std::string& err);
+bool qap_enqueue(gwb_zkey* z, const void* d_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out, void* stream,
+                 std::string& err);
 // qap.hip: the roots of the domain of 2^p points, Montgomery form: w_n of order n, g of order 2n with g^2 = w_n
 void qap_roots(uint32_t p, cwc::Fr& wn, cwc::Fr& g);
 // msm.hip: a uniform draw from [0, r), by rejection sampling from getrandom()

@@ -127,6 +127,7 @@ void load(const uint8_t* d, size_t len, gwb_r1cs& r) {
     const Fr prime = h.fr();
     if (!fr_key_eq(prime, cwc::fr_p())) throw Fail{"r1cs: prime is not BN254's scalar field r (other fields are not supported)"};
     gwb_r1cs_info_t& in = r.info;
+    RowSystem& sys = r.sys;
     in.n_wires = h.u32();
     in.n_pub_out = h.u32();
     in.n_pub_in = h.u32();
@@ -189,9 +190,9 @@ void load(const uint8_t* d, size_t len, gwb_r1cs& r) {
                     auto it = coef_ix.find(v);
                     uint32_t ix;
                     if (it == coef_ix.end()) {
-                        ix = (uint32_t)r.coef.size();
+                        ix = (uint32_t)sys.coef.size();
                         coef_ix.emplace(v, ix);
-                        r.coef.push_back(cwc::fr_to_mont(v));
+                        sys.coef.push_back(cwc::fr_to_mont(v));
                     } else {
                         ix = it->second;
                     }
@@ -218,18 +219,20 @@ void load(const uint8_t* d, size_t len, gwb_r1cs& r) {
     for (uint32_t j = 0; j < in.n_constraints; ++j) order[j] = j;
     auto bucket = [&](uint32_t j) { return len_of[j] ? 32 - __builtin_clz(len_of[j]) : 0; };
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return bucket(a) < bucket(b); });
-    r.perm = order;
-    r.rowptr.reserve(rowptr.size());
-    r.fac.reserve(fac.size());
-    r.cidx.reserve(cidx.size());
-    r.rowptr.push_back(0);
+    sys.perm = order;
+    sys.rowptr.reserve(rowptr.size());
+    sys.fac.reserve(fac.size());
+    sys.cidx.reserve(cidx.size());
+    sys.rowptr.push_back(0);
     for (uint32_t j : order) {
         for (int k = 0; k < 3; ++k) {
-            r.fac.insert(r.fac.end(), fac.begin() + rowptr[3ull * j + k], fac.begin() + rowptr[3ull * j + k + 1]);
-            r.cidx.insert(r.cidx.end(), cidx.begin() + rowptr[3ull * j + k], cidx.begin() + rowptr[3ull * j + k + 1]);
-            r.rowptr.push_back((uint32_t)r.fac.size());
+            sys.fac.insert(sys.fac.end(), fac.begin() + rowptr[3ull * j + k], fac.begin() + rowptr[3ull * j + k + 1]);
+            sys.cidx.insert(sys.cidx.end(), cidx.begin() + rowptr[3ull * j + k], cidx.begin() + rowptr[3ull * j + k + 1]);
+            sys.rowptr.push_back((uint32_t)sys.fac.size());
         }
     }
+    sys.n_rows = in.n_constraints;
+    sys.n_wires = in.n_wires;
 }
 
 }  // namespace
@@ -270,7 +273,7 @@ int gwb_r1cs_info(const gwb_r1cs_t* r, gwb_r1cs_info_t* info) {
 
 int gwb_r1cs_set_tile_width(gwb_r1cs_t* r, uint32_t t) {
     if (!r || t > 64 || (t & (t - 1))) return 1;
-    r->tile_width = t;
+    r->sys.tile_width = t;
     return 0;
 }
 

@@ -537,7 +537,7 @@ bool enqueue_sub(gwb_zkey* z, gwb_r1cs* r, const Layout& L, const uint8_t* d_w, 
     mark(z, 0, s);
     // the witness map: from the .r1cs, or with none given from the zkey's own section 4
     if (r ? !qap_enqueue(r, d_w, rows, form_in, S.at<void>(L.off_h), GWB_FORM_CANONICAL, s, err)
-          : !zkey_qap_enqueue(z, d_w, rows, form_in, S.at<void>(L.off_h), GWB_FORM_CANONICAL, s, err))
+          : !qap_enqueue(z, d_w, rows, form_in, S.at<void>(L.off_h), GWB_FORM_CANONICAL, s, err))
         return false;
     mark(z, 1, s);
     int cur = 0;
@@ -641,7 +641,7 @@ bool check_pair(gwb_zkey* z, gwb_r1cs* r, size_t n_witness, size_t batch, std::s
         err = "groth16: zkey domainSize " + std::to_string(z->info.domain_size) + " != r1cs QAP domain " + std::to_string(qi.domain_size);
         return false;
     }
-    return check_args(r, n_witness, batch, err);
+    return check_args(r->sys, n_witness, batch, err);
 }
 
 bool enqueue_prove(gwb_zkey* z, gwb_r1cs* r, const void* d_w, size_t batch, uint32_t form_in, const std::vector<Fr>& rs, void* d_proofs,
@@ -701,7 +701,7 @@ int prove_host(gwb_zkey* z, gwb_r1cs* r, const void* witness, size_t n_witness, 
         set_ok(status);
         return 0;
     }
-    if (r && !ensure_device(r, err)) return fail(status, err);
+    if (r && !ensure_device(r->sys, -1, err)) return fail(status, err);
     void *d_w = nullptr, *d_p = nullptr;
     hipStream_t s = nullptr;
     const size_t wbytes = batch * n_witness * 32, pbytes = batch * GWB_GROTH16_PROOF_BYTES;
@@ -739,7 +739,8 @@ void gwb_zkey_free(gwb_zkey_t* z) {
     if (z->rs_done) (void)hipEventDestroy((hipEvent_t)z->rs_done);
     for (void* e : z->events)
         if (e) (void)hipEventDestroy((hipEvent_t)e);
-    release_zkey_qap(z);
+    release_qap(z->sys.qap);
+    release_device(z->sys);
     delete z;
 }
 
@@ -755,7 +756,7 @@ int gwb_groth16_prove_batch_device(gwb_zkey_t* z, gwb_r1cs_t* r, const void* d_w
         set_ok(status);
         return 0;
     }
-    if ((r && !ensure_device(r, err)) || !enqueue_prove(z, r, d_witness, batch, form_in, rsv, d_proofs, (hipStream_t)hip_stream, err))
+    if ((r && !ensure_device(r->sys, -1, err)) || !enqueue_prove(z, r, d_witness, batch, form_in, rsv, d_proofs, (hipStream_t)hip_stream, err))
         return fail(status, err);
     set_ok(status);
     return 0;

@@ -6,10 +6,11 @@
 // kernel writes a, b and c at each constraint's file index (the check's lane mapping and factor stream, lincomb.hpp); a
 // second kernel writes the input rows and the zero padding.
 //
-// The same map runs from a zkey's section 4 when a prover has no `.r1cs` (include/graph_witness_groth16.h): zkey_eval_kernel
-// reads the arrays zkey_coefs.cc builds (two row pointers per row, the public rows among the entries), qap_zero_kernel clears
-// the rows no entry names, and the NTT chain below is shared: its tables, workspace and events are a QapState, owned by
-// whichever handle the map belongs to.
+// The map runs over a RowSystem (r1cs_internal.hpp), whichever source it came from: an `.r1cs`, or a zkey's section 4 when a
+// prover has none (include/graph_witness_groth16.h; the arrays zkey_coefs.cc builds).  The sources differ in the row-pointer
+// stride, a template parameter of the evaluation kernel, and in the rows above the evaluated ones: after an `.r1cs` they are
+// the input rows taken from the witness and zeros (qap_pad_kernel), while section 4 has the public rows among its entries and
+// the rest is cleared (qap_zero_kernel).  The tables, workspace and events of the NTT chain are the row system's QapState.
 //
 // NTT layout: n = L_0 L_1 ... L_{P-1} (each L <= 2^9 for the outer passes, the innermost <= 2^11).  A pass works on blocks
 // of M = L S consecutive elements (S = L_{t+1} ... L_{P-1}): position k S + j (k < L, j < S) of a block is element k of
@@ -102,11 +103,12 @@ __device__ __forceinline__ Fr to_internal(Fr w, uint32_t montgomery) {
     return montgomery ? w : cwc::fr_to_mont(w);
 }
 
-// a and b of constraint rows (file index perm[c]) into A and B, c = a b into C; the check kernel's lane mapping
-template <int T>
+// a and b of rows [0, n_rows) (constraint index perm[c]) into A and B, c = a b into C; the check kernel's lane mapping.
+// STRIDE row pointers per row: 3 for an `.r1cs` (the C side is not read), 2 for section 4.
+template <int T, int STRIDE>
 __global__ __launch_bounds__(64 * EVAL_WAVES) void qap_eval_kernel(
     const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ fac, const uint32_t* __restrict__ cidx, const Fr* __restrict__ coef,
-    const uint32_t* __restrict__ perm, uint32_t n_constraints, const uint8_t* __restrict__ witness, uint32_t n_witness, uint32_t batch,
+    const uint32_t* __restrict__ perm, uint32_t n_rows, const uint8_t* __restrict__ witness, uint32_t n_witness, uint32_t batch,
     uint32_t montgomery, Fr* __restrict__ A, Fr* __restrict__ B, Fr* __restrict__ C, uint32_t log_n) {
     constexpr uint32_t G = 64 / T;
     const uint32_t lane = threadIdx.x & 63u;
@@ -116,12 +118,12 @@ __global__ __launch_bounds__(64 * EVAL_WAVES) void qap_eval_kernel(
     if (!set_ok) set = batch - 1;
     const uint8_t* row = witness + (size_t)set * n_witness * 32;
     const size_t out_row = (size_t)set << log_n;
-    const uint32_t n_groups = (n_constraints + G - 1) / G;
+    const uint32_t n_groups = (n_rows + G - 1) / G;
     for (uint32_t g = blockIdx.y * EVAL_WAVES + wave; g < n_groups; g += gridDim.y * EVAL_WAVES) {
         uint32_t c = g * G + lane / T;
-        const bool c_ok = c < n_constraints;
-        if (!c_ok) c = n_constraints - 1;
-        const uint32_t ka = rowptr[3 * c], kb = rowptr[3 * c + 1], kc = rowptr[3 * c + 2];
+        const bool c_ok = c < n_rows;
+        if (!c_ok) c = n_rows - 1;  // (n_rows >= 1: the host launches nothing for a system without rows)
+        const uint32_t ka = rowptr[STRIDE * c], kb = rowptr[STRIDE * c + 1], kc = rowptr[STRIDE * c + 2];
         Fr a = lin_comb(fac, cidx, coef, ka, kb, row);
         Fr b = lin_comb(fac, cidx, coef, kb, kc, row);
         if (!montgomery) {  // canonical row: the sums are canonical
@@ -138,44 +140,7 @@ __global__ __launch_bounds__(64 * EVAL_WAVES) void qap_eval_kernel(
     }
 }
 
-// The same from a zkey's section 4 (zkey_coefs.cc): two row pointers per row (no C side), the public rows among the entries.
-// a, b and c = a b of rows [0, n_used) at perm[row]; the rows above n_used are qap_zero_kernel's.
-template <int T>
-__global__ __launch_bounds__(64 * EVAL_WAVES) void zkey_eval_kernel(
-    const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ fac, const uint32_t* __restrict__ cidx, const Fr* __restrict__ coef,
-    const uint32_t* __restrict__ perm, uint32_t n_used, const uint8_t* __restrict__ witness, uint32_t n_witness, uint32_t batch,
-    uint32_t montgomery, Fr* __restrict__ A, Fr* __restrict__ B, Fr* __restrict__ C, uint32_t log_n) {
-    constexpr uint32_t G = 64 / T;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint32_t set = blockIdx.x * T + lane % T;
-    const bool set_ok = set < batch;
-    if (!set_ok) set = batch - 1;
-    const uint8_t* row = witness + (size_t)set * n_witness * 32;
-    const size_t out_row = (size_t)set << log_n;
-    const uint32_t n_groups = (n_used + G - 1) / G;
-    for (uint32_t g = blockIdx.y * EVAL_WAVES + wave; g < n_groups; g += gridDim.y * EVAL_WAVES) {
-        uint32_t c = g * G + lane / T;
-        const bool c_ok = c < n_used;
-        if (!c_ok) c = n_used - 1;
-        const uint32_t ka = rowptr[2 * c], kb = rowptr[2 * c + 1], kc = rowptr[2 * c + 2];
-        Fr a = lin_comb(fac, cidx, coef, ka, kb, row);
-        Fr b = lin_comb(fac, cidx, coef, kb, kc, row);
-        if (!montgomery) {  // canonical row: the sums are canonical
-            a = cwc::fr_to_mont(a);
-            b = cwc::fr_to_mont(b);
-        }
-        const Fr ab = cwc::fr_mul(a, b);
-        if (set_ok && c_ok) {
-            const size_t o = out_row + perm[c];
-            A[o] = a;
-            B[o] = b;
-            C[o] = ab;
-        }
-    }
-}
-
-// rows n_used .. n-1 of every set: a = b = c = 0 (n_used < n: the caller skips the launch otherwise)
+// section 4: rows n_used .. n-1 of every set: a = b = c = 0 (n_used < n: the caller skips the launch otherwise)
 __global__ __launch_bounds__(THREADS) void qap_zero_kernel(uint32_t batch, uint32_t n_used, Fr* __restrict__ A, Fr* __restrict__ B,
                                                            Fr* __restrict__ C, uint32_t log_n) {
     const uint64_t per = (1ull << log_n) - n_used, total = per * batch;
@@ -188,7 +153,7 @@ __global__ __launch_bounds__(THREADS) void qap_zero_kernel(uint32_t batch, uint3
     }
 }
 
-// rows nC .. n-1 of every set: a = w[i - nC] for i - nC <= nPub, else 0; b = c = 0
+// `.r1cs`: rows nC .. n-1 of every set: a = w[i - nC] for i - nC <= nPub, else 0; b = c = 0
 __global__ __launch_bounds__(THREADS) void qap_pad_kernel(const uint8_t* __restrict__ witness, uint32_t n_witness, uint32_t batch,
                                                           uint32_t montgomery, uint32_t n_constraints, uint32_t n_pub, Fr* __restrict__ A,
                                                           Fr* __restrict__ B, Fr* __restrict__ C, uint32_t log_n) {
@@ -326,29 +291,20 @@ __global__ __launch_bounds__(THREADS) void modmul_probe_kernel(Fr* __restrict__ 
 typedef void (*EvalFn)(const uint32_t*, const uint32_t*, const uint32_t*, const Fr*, const uint32_t*, uint32_t, const uint8_t*, uint32_t,
                        uint32_t, uint32_t, Fr*, Fr*, Fr*, uint32_t);
 
-EvalFn eval_for(uint32_t t) {
+template <int STRIDE>
+EvalFn eval_of(uint32_t t) {
     switch (t) {
-        case 1: return qap_eval_kernel<1>;
-        case 2: return qap_eval_kernel<2>;
-        case 4: return qap_eval_kernel<4>;
-        case 8: return qap_eval_kernel<8>;
-        case 16: return qap_eval_kernel<16>;
-        case 32: return qap_eval_kernel<32>;
-        default: return qap_eval_kernel<64>;
+        case 1: return qap_eval_kernel<1, STRIDE>;
+        case 2: return qap_eval_kernel<2, STRIDE>;
+        case 4: return qap_eval_kernel<4, STRIDE>;
+        case 8: return qap_eval_kernel<8, STRIDE>;
+        case 16: return qap_eval_kernel<16, STRIDE>;
+        case 32: return qap_eval_kernel<32, STRIDE>;
+        default: return qap_eval_kernel<64, STRIDE>;
     }
 }
 
-EvalFn zkey_eval_for(uint32_t t) {
-    switch (t) {
-        case 1: return zkey_eval_kernel<1>;
-        case 2: return zkey_eval_kernel<2>;
-        case 4: return zkey_eval_kernel<4>;
-        case 8: return zkey_eval_kernel<8>;
-        case 16: return zkey_eval_kernel<16>;
-        case 32: return zkey_eval_kernel<32>;
-        default: return zkey_eval_kernel<64>;
-    }
-}
+EvalFn eval_for(uint32_t t, uint32_t stride) { return stride == 3 ? eval_of<3>(t) : eval_of<2>(t); }
 
 struct Domain {
     uint64_t n_rows = 0;
@@ -522,81 +478,100 @@ bool transform(QapState& q, uint32_t p, Fr* A, Fr* B, Fr* d_h, uint64_t rows, ui
     return true;
 }
 
+// One witness map: the rows, the domain of 2^p points, and what else the sources differ in
+struct Map {
+    RowSystem* sys = nullptr;
+    uint32_t p = 0;
+    uint32_t n_pub = 0;  // `.r1cs`: rows n_rows .. n_rows + n_pub are the first witness elements (qap_pad_kernel)
+    int home = -1;       // the device the arrays have to share (ensure_device)
+};
+
+bool map_of(gwb_r1cs* r, Map& m, std::string& err) {
+    Domain d;
+    if (!domain_of(r, d, err)) return false;
+    m = Map{&r->sys, d.p, r->info.n_pub_out + r->info.n_pub_in, -1};
+    return true;
+}
+
+// (domainSize is a power of two in 2 .. 2^27 once the map is built; the arrays go where the zkey's points are, if uploaded)
+bool map_of(gwb_zkey* z, Map& m, std::string& err) {
+    if (!zkey_coefs_build(z, err)) return false;
+    uint32_t p = 0;
+    while ((1u << p) < z->info.domain_size) ++p;
+    m = Map{&z->sys, p, 0, z->device};
+    return true;
+}
+
 // h of `rows` rows: d_w rows -> A, B (workspace), C = d_h -> h in d_h
-bool enqueue_sub(gwb_r1cs* r, const Domain& dom, const uint8_t* d_w, uint64_t rows, uint32_t form_in, Fr* d_h, uint32_t form_out,
-                 hipStream_t stream, std::string& err) {
-    const uint32_t p = dom.p, nc = r->info.n_constraints, nw = r->info.n_wires;
+bool enqueue_sub(const Map& m, const uint8_t* d_w, uint64_t rows, uint32_t form_in, Fr* d_h, uint32_t form_out, hipStream_t stream,
+                 std::string& err) {
+    RowSystem& s = *m.sys;
+    const uint32_t p = m.p, nr = s.n_rows, nw = s.n_wires;
     const uint64_t n = 1ull << p;
-    Fr* A = (Fr*)r->qap.d_ws;
+    Fr* A = (Fr*)s.qap.d_ws;
     Fr* B = A + rows * n;
     const uint32_t mont = form_in == GWB_FORM_MONTGOMERY ? 1u : 0u;
-    hipEvent_t* ev = (hipEvent_t*)r->qap.events;  // (ev[0] null: not timing)
+    hipEvent_t* ev = (hipEvent_t*)s.qap.events;  // (ev[0] null: not timing)
     if (ev[0]) (void)hipEventRecord(ev[0], stream);
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, r->device) != hipSuccess || cus <= 0) cus = 256;
-    if (nc) {
-        const uint32_t t = r->tile_width ? r->tile_width : pick_tile_width(rows);
-        const uint32_t g = 64 / t;
-        const uint64_t n_groups = (nc + (uint64_t)g - 1) / g, tiles = (rows + t - 1) / t;
-        const uint64_t want_y = std::max<uint64_t>(1, (uint64_t)cus * 8 / std::max<uint64_t>(tiles, 1));
-        const uint64_t gy = std::min<uint64_t>({want_y, (n_groups + EVAL_WAVES - 1) / EVAL_WAVES, 65535});
-        if (tiles > 0x7fffffffull) {
-            err = "r1cs: batch too large for one launch";
-            return false;
-        }
-        hipLaunchKernelGGL(eval_for(t), dim3((uint32_t)tiles, (uint32_t)gy), dim3(64 * EVAL_WAVES), 0, stream, (const uint32_t*)r->d_rowptr,
-                           (const uint32_t*)r->d_fac, (const uint32_t*)r->d_cidx, (const Fr*)r->d_coef, (const uint32_t*)r->d_perm, nc, d_w, nw,
+    const int cus = cu_count(s.device);
+    if (nr) {  // (an `.r1cs` may have no constraints; section 4 has at least one row)
+        EvalGrid g;
+        if (!eval_grid(s, rows, cus, EVAL_WAVES, g, err)) return false;
+        hipLaunchKernelGGL(eval_for(g.t, s.stride), dim3(g.tiles, g.gy), dim3(64 * EVAL_WAVES), 0, stream, (const uint32_t*)s.d_rowptr,
+                           (const uint32_t*)s.d_fac, (const uint32_t*)s.d_cidx, (const Fr*)s.d_coef, (const uint32_t*)s.d_perm, nr, d_w, nw,
                            (uint32_t)rows, mont, A, B, d_h, p);
     }
-    const uint64_t pad = (n - nc) * rows;
+    // the rows above: the one difference between the sources
+    const uint64_t pad = (n - nr) * rows;
     const uint32_t pad_blocks = (uint32_t)std::min<uint64_t>((pad + THREADS - 1) / THREADS, (uint64_t)cus * 16);
-    hipLaunchKernelGGL(qap_pad_kernel, dim3(pad_blocks), dim3(THREADS), 0, stream, d_w, nw, (uint32_t)rows, mont, nc,
-                       r->info.n_pub_out + r->info.n_pub_in, A, B, d_h, p);
-    hipError_t e = hipGetLastError();
+    if (s.stride == 3)  // (never empty: the row of wire 0 follows the constraints)
+        hipLaunchKernelGGL(qap_pad_kernel, dim3(pad_blocks), dim3(THREADS), 0, stream, d_w, nw, (uint32_t)rows, mont, nr, m.n_pub, A, B, d_h, p);
+    else if (pad)  // n_used == n (nC + nPublic + 1 a power of two): no row is left to clear, and a grid of 0 blocks is no launch
+        hipLaunchKernelGGL(qap_zero_kernel, dim3(pad_blocks), dim3(THREADS), 0, stream, (uint32_t)rows, nr, A, B, d_h, p);
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         err = hip_err("launching the QAP evaluation", e);
         return false;
     }
-    return transform(r->qap, p, A, B, d_h, rows, form_out, stream, err);
+    return transform(s.qap, p, A, B, d_h, rows, form_out, stream, err);
 }
 
 bool form_ok(uint32_t f) { return f == GWB_FORM_CANONICAL || f == GWB_FORM_MONTGOMERY; }
 
 // device rows -> d_h, in sub-batches under the workspace cap
-bool enqueue_qap(gwb_r1cs* r, const void* d_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out, hipStream_t stream,
+bool enqueue_qap(const Map& m, const void* d_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out, hipStream_t stream,
                  std::string& err) {
-    Domain dom;
-    if (!domain_of(r, dom, err) || !ensure_device(r, err) || !ensure_tables(r->qap, dom.p, err)) return false;
-    const uint64_t per = ws_per_row(dom.p);
+    RowSystem& s = *m.sys;
+    if (!ensure_device(s, m.home, err) || !ensure_tables(s.qap, m.p, err)) return false;
+    const uint64_t per = ws_per_row(m.p);
     const uint64_t sub = std::min<uint64_t>(batch, std::max<uint64_t>(1, ws_cap() / per));
-    if (!ensure_workspace(r->qap, sub * per, err)) return false;
-    const uint64_t n = 1ull << dom.p;
+    if (!ensure_workspace(s.qap, sub * per, err)) return false;
+    const uint64_t n = 1ull << m.p;
     for (uint64_t s0 = 0; s0 < batch; s0 += sub) {
         const uint64_t rows = std::min<uint64_t>(sub, batch - s0);
-        if (!enqueue_sub(r, dom, (const uint8_t*)d_witness + s0 * r->info.n_wires * 32, rows, form_in, (Fr*)d_h + s0 * n, form_out, stream, err))
-            return false;
+        if (!enqueue_sub(m, (const uint8_t*)d_witness + s0 * s.n_wires * 32, rows, form_in, (Fr*)d_h + s0 * n, form_out, stream, err)) return false;
     }
     return true;
 }
 
-int qap_host(gwb_r1cs* r, const void* witness, size_t n_witness, size_t batch, void* h, uint32_t form_out, gw_status_t* status) {
+// host rows -> device -> h back; synchronous
+int qap_host(const Map& m, const void* witness, size_t n_witness, size_t batch, void* h, uint32_t form_out, gw_status_t* status) {
     std::string err;
-    Domain dom;
-    if (!domain_of(r, dom, err) || !check_args(r, n_witness, batch, err)) return fail(status, err);
+    if (!check_args(*m.sys, n_witness, batch, err)) return fail(status, err);
     if (batch == 0) {
         set_ok(status);
         return 0;
     }
-    if (!ensure_device(r, err)) return fail(status, err);
+    if (!ensure_device(*m.sys, m.home, err)) return fail(status, err);
     void *d_w = nullptr, *d_h = nullptr;
     hipStream_t s = nullptr;
-    const size_t wbytes = batch * n_witness * 32, hbytes = (batch * 32) << dom.p;
+    const size_t wbytes = batch * n_witness * 32, hbytes = (batch * 32) << m.p;
     hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipMalloc(&d_w, wbytes);
     if (e == hipSuccess) e = hipMalloc(&d_h, hbytes);
     if (e == hipSuccess) e = hipMemcpyAsync(d_w, witness, wbytes, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) err = hip_err("staging the witness rows", e);
-    bool ok = e == hipSuccess && enqueue_qap(r, d_w, batch, GWB_FORM_CANONICAL, d_h, form_out, s, err);
+    bool ok = e == hipSuccess && enqueue_qap(m, d_w, batch, GWB_FORM_CANONICAL, d_h, form_out, s, err);
     if (ok) {
         e = hipMemcpyAsync(h, d_h, hbytes, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -613,159 +588,33 @@ int qap_host(gwb_r1cs* r, const void* witness, size_t n_witness, size_t batch, v
     return 0;
 }
 
-// -- the same witness map from a zkey's section 4 (groth16_internal.hpp; the host arrays are zkey_coefs.cc's)
-
-uint32_t zkey_power(const gwb_zkey* z) {  // domainSize is a power of two in 2 .. 2^27 once the map is built
-    uint32_t p = 0;
-    while ((1u << p) < z->info.domain_size) ++p;
-    return p;
-}
-
-template <class V>
-bool zkey_upload(void** d, const V& v, std::string& err) {
-    const size_t bytes = std::max<size_t>(v.size() * sizeof(v[0]), 4);
-    hipError_t e = hipMalloc(d, bytes);
-    if (e == hipSuccess && !v.empty()) e = hipMemcpy(*d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        err = hip_err("uploading the zkey's coefficient arrays", e);
-        return false;
-    }
-    return true;
-}
-
-void release_zkey_arrays(gwb_zkey* z) {
-    for (void** p : {&z->d_rowptr, &z->d_fac, &z->d_cidx, &z->d_coef, &z->d_perm}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    z->qap_device = -1;
-}
-
-// The coefficient arrays go to the current device at the first call and stay there (the device of the zkey's points, if
-// those are already uploaded).
-bool ensure_zkey_device(gwb_zkey* z, std::string& err) {
-    int dev = -1, n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-        err = "zkey: no HIP device (the witness map runs on the GPU only)";
-        return false;
-    }
-    if (hipGetDevice(&dev) != hipSuccess) {
-        err = "zkey: hipGetDevice failed";
-        return false;
-    }
-    const int home = z->qap_device >= 0 ? z->qap_device : z->device;
-    if (home >= 0 && dev != home) {
-        err = "zkey: the handle's arrays live on device " + std::to_string(home) + ", the current device is " + std::to_string(dev);
-        return false;
-    }
-    if (z->qap_device >= 0) return true;
-    if (!zkey_upload(&z->d_rowptr, z->rowptr, err) || !zkey_upload(&z->d_fac, z->fac, err) || !zkey_upload(&z->d_cidx, z->cidx, err) ||
-        !zkey_upload(&z->d_coef, z->coef, err) || !zkey_upload(&z->d_perm, z->perm, err)) {
-        release_zkey_arrays(z);
-        return false;
-    }
-    z->qap_device = dev;
-    return true;
-}
-
-bool zkey_check_args(const gwb_zkey* z, size_t n_witness, size_t batch, std::string& err) {
-    if (n_witness != z->info.n_vars) {
-        err = "zkey: the witness has " + std::to_string(n_witness) + " elements, the key nVars = " + std::to_string(z->info.n_vars);
-        return false;
-    }
-    if (batch > 0xffffffffull) {
-        err = "zkey: batch above 2^32 - 1";
-        return false;
-    }
-    return true;
-}
-
-// h of `rows` rows: d_w rows -> A, B (workspace), C = d_h -> h in d_h
-bool zkey_enqueue_sub(gwb_zkey* z, uint32_t p, const uint8_t* d_w, uint64_t rows, uint32_t form_in, Fr* d_h, uint32_t form_out,
-                      hipStream_t stream, std::string& err) {
-    const uint32_t nu = z->n_used, nw = z->info.n_vars;  // 1 <= nu <= n
-    const uint64_t n = 1ull << p;
-    Fr* A = (Fr*)z->qap.d_ws;
-    Fr* B = A + rows * n;
-    const uint32_t mont = form_in == GWB_FORM_MONTGOMERY ? 1u : 0u;
-    hipEvent_t* ev = (hipEvent_t*)z->qap.events;  // (ev[0] null: not timing)
-    if (ev[0]) (void)hipEventRecord(ev[0], stream);
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, z->qap_device) != hipSuccess || cus <= 0) cus = 256;
-    const uint32_t t = z->tile_width ? z->tile_width : pick_tile_width(rows);
-    const uint32_t g = 64 / t;
-    const uint64_t n_groups = (nu + (uint64_t)g - 1) / g, tiles = (rows + t - 1) / t;
-    const uint64_t want_y = std::max<uint64_t>(1, (uint64_t)cus * 8 / std::max<uint64_t>(tiles, 1));
-    const uint64_t gy = std::min<uint64_t>({want_y, (n_groups + EVAL_WAVES - 1) / EVAL_WAVES, 65535});
-    if (tiles > 0x7fffffffull) {
-        err = "zkey: batch too large for one launch";
-        return false;
-    }
-    hipLaunchKernelGGL(zkey_eval_for(t), dim3((uint32_t)tiles, (uint32_t)gy), dim3(64 * EVAL_WAVES), 0, stream, (const uint32_t*)z->d_rowptr,
-                       (const uint32_t*)z->d_fac, (const uint32_t*)z->d_cidx, (const Fr*)z->d_coef, (const uint32_t*)z->d_perm, nu, d_w, nw,
-                       (uint32_t)rows, mont, A, B, d_h, p);
-    const uint64_t pad = (n - nu) * rows;
-    if (pad) {  // nu == n (nC + nPublic + 1 a power of two): no row is left to clear, and a grid of 0 blocks is no launch
-        const uint32_t pad_blocks = (uint32_t)std::min<uint64_t>((pad + THREADS - 1) / THREADS, (uint64_t)cus * 16);
-        hipLaunchKernelGGL(qap_zero_kernel, dim3(pad_blocks), dim3(THREADS), 0, stream, (uint32_t)rows, nu, A, B, d_h, p);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        err = hip_err("launching the QAP evaluation of section 4", e);
-        return false;
-    }
-    return transform(z->qap, p, A, B, d_h, rows, form_out, stream, err);
-}
-
-// device rows -> d_h, in sub-batches under the workspace cap
-bool zkey_enqueue_qap(gwb_zkey* z, const void* d_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out, hipStream_t stream,
-                      std::string& err) {
-    if (!zkey_coefs_build(z, err) || !ensure_zkey_device(z, err)) return false;
-    const uint32_t p = zkey_power(z);
-    if (!ensure_tables(z->qap, p, err)) return false;
-    const uint64_t per = ws_per_row(p);
-    const uint64_t sub = std::min<uint64_t>(batch, std::max<uint64_t>(1, ws_cap() / per));
-    if (!ensure_workspace(z->qap, sub * per, err)) return false;
-    const uint64_t n = 1ull << p;
-    for (uint64_t s0 = 0; s0 < batch; s0 += sub) {
-        const uint64_t rows = std::min<uint64_t>(sub, batch - s0);
-        if (!zkey_enqueue_sub(z, p, (const uint8_t*)d_witness + s0 * z->info.n_vars * 32, rows, form_in, (Fr*)d_h + s0 * n, form_out, stream, err))
-            return false;
-    }
-    return true;
-}
-
-int zkey_qap_host(gwb_zkey* z, const void* witness, size_t n_witness, size_t batch, void* h, uint32_t form_out, gw_status_t* status) {
+// The bodies of gwb_r1cs_qap_batch_* and gwb_zkey_qap_batch_*; `fn` is the entry point's name
+template <class H>
+int batch_device(const char* fn, H* h, const void* d_witness, size_t n_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out,
+                 void* hip_stream, gw_status_t* status) {
+    if (!h || (batch && (!d_witness || !d_h))) return fail(status, std::string(fn) + ": NULL argument");
+    if (!form_ok(form_in)) return fail(status, std::string(fn) + ": unknown form " + std::to_string(form_in));
+    if (!form_ok(form_out)) return fail(status, std::string(fn) + ": unknown form " + std::to_string(form_out));
     std::string err;
-    if (!zkey_coefs_build(z, err) || !zkey_check_args(z, n_witness, batch, err)) return fail(status, err);
+    Map m;
+    if (!map_of(h, m, err) || !check_args(*m.sys, n_witness, batch, err)) return fail(status, err);
     if (batch == 0) {
         set_ok(status);
         return 0;
     }
-    if (!ensure_zkey_device(z, err)) return fail(status, err);
-    void *d_w = nullptr, *d_h = nullptr;
-    hipStream_t s = nullptr;
-    const size_t wbytes = batch * n_witness * 32, hbytes = (batch * 32) << zkey_power(z);
-    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&d_w, wbytes);
-    if (e == hipSuccess) e = hipMalloc(&d_h, hbytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_w, witness, wbytes, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) err = hip_err("staging the witness rows", e);
-    bool ok = e == hipSuccess && zkey_enqueue_qap(z, d_w, batch, GWB_FORM_CANONICAL, d_h, form_out, s, err);
-    if (ok) {
-        e = hipMemcpyAsync(h, d_h, hbytes, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            err = hip_err("running the QAP witness map", e);
-            ok = false;
-        }
-    }
-    if (d_w) (void)hipFree(d_w);
-    if (d_h) (void)hipFree(d_h);
-    if (s) (void)hipStreamDestroy(s);
-    if (!ok) return fail(status, err);
+    if (!enqueue_qap(m, d_witness, batch, form_in, d_h, form_out, (hipStream_t)hip_stream, err)) return fail(status, err);
     set_ok(status);
     return 0;
+}
+
+template <class H>
+int batch_host(const char* fn, H* handle, const void* witness, size_t n_witness, size_t batch, void* h, uint32_t form_out, gw_status_t* status) {
+    if (!handle || (batch && (!witness || !h))) return fail(status, std::string(fn) + ": NULL argument");
+    if (!form_ok(form_out)) return fail(status, std::string(fn) + ": unknown form " + std::to_string(form_out));
+    std::string err;
+    Map m;
+    if (!map_of(handle, m, err)) return fail(status, err);
+    return qap_host(m, witness, n_witness, batch, h, form_out, status);
 }
 
 }  // namespace
@@ -774,17 +623,14 @@ namespace cwc_r1cs {
 
 bool qap_enqueue(gwb_r1cs* r, const void* d_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out, void* stream,
                  std::string& err) {
-    return enqueue_qap(r, d_witness, batch, form_in, d_h, form_out, (hipStream_t)stream, err);
+    Map m;
+    return map_of(r, m, err) && enqueue_qap(m, d_witness, batch, form_in, d_h, form_out, (hipStream_t)stream, err);
 }
 
-bool zkey_qap_enqueue(gwb_zkey* z, const void* d_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out, void* stream,
-                      std::string& err) {
-    return zkey_enqueue_qap(z, d_witness, batch, form_in, d_h, form_out, (hipStream_t)stream, err);
-}
-
-void release_zkey_qap(gwb_zkey* z) {
-    release_qap(z->qap);
-    release_zkey_arrays(z);
+bool qap_enqueue(gwb_zkey* z, const void* d_witness, size_t batch, uint32_t form_in, void* d_h, uint32_t form_out, void* stream,
+                 std::string& err) {
+    Map m;
+    return map_of(z, m, err) && enqueue_qap(m, d_witness, batch, form_in, d_h, form_out, (hipStream_t)stream, err);
 }
 
 void release_qap(QapState& q) {
@@ -818,25 +664,11 @@ int gwb_r1cs_qap_info(const gwb_r1cs_t* r, gwb_r1cs_qap_info_t* info, gw_status_
 
 int gwb_r1cs_qap_batch_device(gwb_r1cs_t* r, const void* d_witness, size_t n_witness, size_t batch, uint32_t form_in, void* d_h,
                               uint32_t form_out, void* hip_stream, gw_status_t* status) {
-    if (!r || (batch && (!d_witness || !d_h))) return fail(status, "gwb_r1cs_qap_batch_device: NULL argument");
-    if (!form_ok(form_in)) return fail(status, "gwb_r1cs_qap_batch_device: unknown form " + std::to_string(form_in));
-    if (!form_ok(form_out)) return fail(status, "gwb_r1cs_qap_batch_device: unknown form " + std::to_string(form_out));
-    std::string err;
-    Domain dom;
-    if (!domain_of(r, dom, err) || !check_args(r, n_witness, batch, err)) return fail(status, err);
-    if (batch == 0) {
-        set_ok(status);
-        return 0;
-    }
-    if (!enqueue_qap(r, d_witness, batch, form_in, d_h, form_out, (hipStream_t)hip_stream, err)) return fail(status, err);
-    set_ok(status);
-    return 0;
+    return batch_device("gwb_r1cs_qap_batch_device", r, d_witness, n_witness, batch, form_in, d_h, form_out, hip_stream, status);
 }
 
 int gwb_r1cs_qap_batch_host(gwb_r1cs_t* r, const void* witness, size_t n_witness, size_t batch, void* h, uint32_t form_out, gw_status_t* status) {
-    if (!r || (batch && (!witness || !h))) return fail(status, "gwb_r1cs_qap_batch_host: NULL argument");
-    if (!form_ok(form_out)) return fail(status, "gwb_r1cs_qap_batch_host: unknown form " + std::to_string(form_out));
-    return qap_host(r, witness, n_witness, batch, h, form_out, status);
+    return batch_host("gwb_r1cs_qap_batch_host", r, witness, n_witness, batch, h, form_out, status);
 }
 
 int gwb_r1cs_qap_wtns(gwb_r1cs_t* r, const void* wtns, size_t len, void* h_out, uint32_t form_out, gw_status_t* status) {
@@ -845,40 +677,28 @@ int gwb_r1cs_qap_wtns(gwb_r1cs_t* r, const void* wtns, size_t len, void* h_out, 
     const uint8_t* values = nullptr;
     uint64_t n_wit = 0;
     std::string err;
-    if (!parse_wtns(wtns, len, &values, &n_wit, err)) return fail(status, err);
-    return qap_host(r, values, n_wit, 1, h_out, form_out, status);
+    Map m;
+    if (!parse_wtns(wtns, len, &values, &n_wit, err) || !map_of(r, m, err)) return fail(status, err);
+    return qap_host(m, values, n_wit, 1, h_out, form_out, status);
 }
 
 int gwb_zkey_qap_batch_device(gwb_zkey_t* z, const void* d_witness, size_t n_witness, size_t batch, uint32_t form_in, void* d_h,
                               uint32_t form_out, void* hip_stream, gw_status_t* status) {
-    if (!z || (batch && (!d_witness || !d_h))) return fail(status, "gwb_zkey_qap_batch_device: NULL argument");
-    if (!form_ok(form_in)) return fail(status, "gwb_zkey_qap_batch_device: unknown form " + std::to_string(form_in));
-    if (!form_ok(form_out)) return fail(status, "gwb_zkey_qap_batch_device: unknown form " + std::to_string(form_out));
-    std::string err;
-    if (!zkey_coefs_build(z, err) || !zkey_check_args(z, n_witness, batch, err)) return fail(status, err);
-    if (batch == 0) {
-        set_ok(status);
-        return 0;
-    }
-    if (!zkey_enqueue_qap(z, d_witness, batch, form_in, d_h, form_out, (hipStream_t)hip_stream, err)) return fail(status, err);
-    set_ok(status);
-    return 0;
+    return batch_device("gwb_zkey_qap_batch_device", z, d_witness, n_witness, batch, form_in, d_h, form_out, hip_stream, status);
 }
 
 int gwb_zkey_qap_batch_host(gwb_zkey_t* z, const void* witness, size_t n_witness, size_t batch, void* h, uint32_t form_out, gw_status_t* status) {
-    if (!z || (batch && (!witness || !h))) return fail(status, "gwb_zkey_qap_batch_host: NULL argument");
-    if (!form_ok(form_out)) return fail(status, "gwb_zkey_qap_batch_host: unknown form " + std::to_string(form_out));
-    return zkey_qap_host(z, witness, n_witness, batch, h, form_out, status);
+    return batch_host("gwb_zkey_qap_batch_host", z, witness, n_witness, batch, h, form_out, status);
 }
 
 int gwb_r1cs_qap_time_phases(gwb_r1cs_t* r, int on) {
     if (!r) return 1;
-    for (void*& e : r->qap.events) {
+    for (void*& e : r->sys.qap.events) {
         if (e) (void)hipEventDestroy((hipEvent_t)e);
         e = nullptr;
     }
     if (!on) return 0;
-    for (void*& e : r->qap.events) {
+    for (void*& e : r->sys.qap.events) {
         hipEvent_t h = nullptr;
         if (hipEventCreate(&h) != hipSuccess) {
             gwb_r1cs_qap_time_phases(r, 0);
@@ -919,8 +739,8 @@ int gwb_r1cs_modmul_rate(double* products_per_s) {
 }
 
 int gwb_r1cs_qap_phase_ms(gwb_r1cs_t* r, float* ms) {
-    if (!r || !ms || !r->qap.events[0]) return 1;
-    hipEvent_t* ev = (hipEvent_t*)r->qap.events;
+    if (!r || !ms || !r->sys.qap.events[0]) return 1;
+    hipEvent_t* ev = (hipEvent_t*)r->sys.qap.events;
     if (hipEventSynchronize(ev[4]) != hipSuccess) return 1;
     for (int i = 0; i < 4; ++i)
         if (hipEventElapsedTime(ms + i, ev[i], ev[i + 1]) != hipSuccess) return 1;

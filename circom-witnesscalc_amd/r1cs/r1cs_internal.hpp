@@ -1,5 +1,5 @@
 // Host representation of a loaded `.r1cs` file, shared by the loader (loader.cc), the device check (check.hip) and the QAP
-// witness map (qap.hip).
+// witness map (qap.hip), and the row system both it and a zkey's section 4 (groth16_internal.hpp) are evaluated through.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -27,39 +27,58 @@ void set_ok(gw_status_t* st);
 
 }  // namespace cwc_r1cs
 
-struct gwb_r1cs;
-
-// Host helpers of check.hip, shared with qap.hip.
+// Host helpers of check.hip, shared with qap.hip and msm.hip.
 namespace cwc_r1cs {
-uint32_t pick_tile_width(size_t batch);                  // rows per wave for a batch
-bool ensure_device(gwb_r1cs* r, std::string& err);       // constraint arrays on the current device (first call)
-bool check_args(gwb_r1cs* r, size_t n_witness, size_t batch, std::string& err);
 int fail(gw_status_t* st, const std::string& msg);      // set_status + return 1
 // A `.wtns` image as gwb_r1cs_check_wtns validates it: the witness values (elements below r) and their count.
 bool parse_wtns(const void* wtns, size_t len, const uint8_t** values, uint64_t* n_wit, std::string& err);
 
-// Device state of one QAP domain (qap.hip), owned by the handle whose witness map runs on it (a gwb_r1cs, or a gwb_zkey
-// proving from its section 4): twiddles w_n^e and per-position coset factors, n each, built at the first QAP call; the A / B
-// workspace, grown on demand; phase-timing events (hipEvent_t, recorded around each phase while events[0] is set).
+// Device state of one QAP domain (qap.hip), owned by the row system whose witness map runs on it: twiddles w_n^e and
+// per-position coset factors, n each, built at the first QAP call; the A / B workspace, grown on demand; phase-timing events
+// (hipEvent_t, recorded around each phase while events[0] is set).
 struct QapState {
     void *d_tw = nullptr, *d_coset = nullptr, *d_ws = nullptr;
     size_t ws_bytes = 0;
     void* events[5] = {};
 };
 void release_qap(QapState& q);                           // qap.hip: the QAP tables, workspace and events
+
+// Rows of linear combinations over a witness, as the check and evaluation kernels read them (lincomb.hpp): an `.r1cs`
+// (loader.cc; stride 3: sides A, B, C) or section 4 of a zkey (zkey_coefs.cc; stride 2: A, B, the public rows among them).
+// Rows are in device order (bucketed by length, stable inside a bucket): side m of row k is fac[rowptr[stride k + m] ..
+// rowptr[stride k + m + 1]), and perm[k] is the row's constraint index.  The stride also tells the two sources apart where
+// they differ: the prefix of a refusal ("r1cs: " / "zkey: ") and the kernel that fills the rows above n_rows (qap.hip).
+struct RowSystem {
+    std::vector<uint32_t> rowptr, fac, cidx, perm;
+    std::vector<cwc::Fr> coef;  // distinct general coefficients, Montgomery form c R
+    uint32_t stride = 3;        // row pointers per row
+    uint32_t n_rows = 0;        // evaluated rows: n_constraints, or 1 + the largest constraint index of section 4
+    uint32_t n_wires = 0;       // elements per witness row: n_wires, or nVars
+    uint32_t tile_width = 0;    // witness rows per wave, 0 = from the batch size
+    // device copies (first call that needs them) and the QAP domain's state, on the same device
+    int device = -1;
+    void *d_rowptr = nullptr, *d_fac = nullptr, *d_cidx = nullptr, *d_coef = nullptr, *d_perm = nullptr;
+    QapState qap;
+};
+
+const char* prefix_of(const RowSystem& s);               // "r1cs: " or "zkey: "
+// The arrays go to the current device at the first call and stay there; `home` >= 0 names the device they have to share
+// (a zkey's uploaded points), -1 leaves the choice to the current device.
+bool ensure_device(RowSystem& s, int home, std::string& err);
+void release_device(RowSystem& s);
+bool check_args(const RowSystem& s, size_t n_witness, size_t batch, std::string& err);
+
+// Grid of a kernel with the check's lane mapping: a wave covers t rows x 64 / t constraints, blockIdx.x walks the `tiles`
+// groups of t rows, and gy blocks of `waves` waves stride over the constraint groups: about eight blocks per CU in all.
+struct EvalGrid {
+    uint32_t t, tiles, gy;
+};
+int cu_count(int device);                                // 256 where the device does not say
+bool eval_grid(const RowSystem& s, uint64_t rows, int cus, int waves, EvalGrid& g, std::string& err);
 }  // namespace cwc_r1cs
 
 struct gwb_r1cs {
     gwb_r1cs_info_t info{};
-    // Constraints in device order (bucketed by length, stable inside a bucket): constraint k's A factors are
-    // fac[rowptr[3k] .. rowptr[3k+1]), B up to rowptr[3k+2], C up to rowptr[3k+3]; perm[k] = its index in the file.
-    std::vector<uint32_t> rowptr, fac, cidx, perm;
-    std::vector<cwc::Fr> coef;        // distinct general coefficients, Montgomery form
+    cwc_r1cs::RowSystem sys;          // the constraints, stride 3; the QAP events are those of gwb_r1cs_qap_time_phases
     std::vector<uint64_t> wire_label; // section 3 (kept for info, unused by the check)
-    uint32_t tile_width = 0;          // 0 = from the batch size
-    // device copies (first check call)
-    int device = -1;
-    void *d_rowptr = nullptr, *d_fac = nullptr, *d_cidx = nullptr, *d_coef = nullptr, *d_perm = nullptr;
-    // QAP witness map (qap.hip, first QAP call, on the same device); its events are those of gwb_r1cs_qap_time_phases
-    cwc_r1cs::QapState qap;
 };

@@ -350,22 +350,22 @@ uint32_t segment_terms() {  // CWC_GROTH16_SETUP_SEGMENT: terms per segment of a
 // The by-wire transpose of the handle's matrices (Columns: ptau_internal.hpp)
 void transpose(const gwb_r1cs* r, uint32_t segment, Columns& c) {
     const uint32_t nw = r->info.n_wires, nc = r->info.n_constraints;
-    const size_t n_terms = r->fac.size();
+    const size_t n_terms = r->sys.fac.size();
     std::vector<uint32_t> start(3 * (size_t)nw + 1, 0);
     for (uint32_t k = 0; k < nc; ++k)
         for (uint32_t m = 0; m < 3; ++m)
-            for (uint32_t j = r->rowptr[3 * (size_t)k + m]; j < r->rowptr[3 * (size_t)k + m + 1]; ++j)
-                ++start[3 * (size_t)(r->fac[j] & WIRE_MASK) + m + 1];
+            for (uint32_t j = r->sys.rowptr[3 * (size_t)k + m]; j < r->sys.rowptr[3 * (size_t)k + m + 1]; ++j)
+                ++start[3 * (size_t)(r->sys.fac[j] & WIRE_MASK) + m + 1];
     for (size_t i = 1; i < start.size(); ++i) start[i] += start[i - 1];
     c.ent.resize(n_terms);
     c.cidx.resize(n_terms);
     std::vector<uint32_t> fill(start.begin(), start.end() - 1);
     for (uint32_t k = 0; k < nc; ++k)
         for (uint32_t m = 0; m < 3; ++m)
-            for (uint32_t j = r->rowptr[3 * (size_t)k + m]; j < r->rowptr[3 * (size_t)k + m + 1]; ++j) {
-                const uint32_t f = r->fac[j], at = fill[3 * (size_t)(f & WIRE_MASK) + m]++;
-                c.ent[at] = r->perm[k] | (f & ~WIRE_MASK);
-                c.cidx[at] = r->cidx[j];
+            for (uint32_t j = r->sys.rowptr[3 * (size_t)k + m]; j < r->sys.rowptr[3 * (size_t)k + m + 1]; ++j) {
+                const uint32_t f = r->sys.fac[j], at = fill[3 * (size_t)(f & WIRE_MASK) + m]++;
+                c.ent[at] = r->sys.perm[k] | (f & ~WIRE_MASK);
+                c.cidx[at] = r->sys.cidx[j];
             }
     c.wire_seg.assign((size_t)nw + 1, 0);
     for (uint32_t i = 0; i < nw; ++i) {
@@ -516,20 +516,20 @@ bool cwc_setup::coefficients_section(const gwb_r1cs* r, std::vector<uint8_t>& ou
         return false;
     }
     const Fr one_rr = cwc::fr_r2(), minus_rr = cwc::fr_neg(one_rr);
-    std::vector<Fr> coef_rr(r->coef.size());
-    for (size_t i = 0; i < coef_rr.size(); ++i) coef_rr[i] = cwc::fr_to_mont(r->coef[i]);  // c R -> c R^2
+    std::vector<Fr> coef_rr(r->sys.coef.size());
+    for (size_t i = 0; i < coef_rr.size(); ++i) coef_rr[i] = cwc::fr_to_mont(r->sys.coef[i]);  // c R -> c R^2
     std::vector<uint32_t> pos(nc);  // file index -> position in the handle's order
-    for (uint32_t k = 0; k < nc; ++k) pos[r->perm[k]] = k;
+    for (uint32_t k = 0; k < nc; ++k) pos[r->sys.perm[k]] = k;
     out.reserve(4 + count * 44);
     put32(out, (uint32_t)count);
     for (uint32_t k = 0; k < nc; ++k)
         for (uint32_t m = 0; m < 2; ++m)
-            for (uint32_t j = r->rowptr[3 * (size_t)pos[k] + m]; j < r->rowptr[3 * (size_t)pos[k] + m + 1]; ++j) {
-                const uint32_t f = r->fac[j], kind = f >> 30;
+            for (uint32_t j = r->sys.rowptr[3 * (size_t)pos[k] + m]; j < r->sys.rowptr[3 * (size_t)pos[k] + m + 1]; ++j) {
+                const uint32_t f = r->sys.fac[j], kind = f >> 30;
                 put32(out, m);
                 put32(out, k);
                 put32(out, f & WIRE_MASK);
-                put_fr(out, kind == KIND_PLUS ? one_rr : kind == KIND_MINUS ? minus_rr : coef_rr[r->cidx[j]]);
+                put_fr(out, kind == KIND_PLUS ? one_rr : kind == KIND_MINUS ? minus_rr : coef_rr[r->sys.cidx[j]]);
             }
     for (uint32_t s = 0; s <= n_pub; ++s) {
         put32(out, 0);
@@ -620,7 +620,7 @@ int setup(gwb_r1cs* r, const gwb_groth16_trapdoor_t* trapdoor, void** zkey, size
     Carve cs, cw;
     const size_t o_lag = cs.take(2ull * n * 32), o_pref = cs.take(2ull * n * 32), o_part = cs.take((size_t)n_seg * 32),
                  o_uvw = cs.take(3ull * nw * 32), o_s1 = cs.take(n1 * 32), o_s2 = cs.take(n2 * 32);
-    const size_t o_ent = cw.take(n_terms * 4), o_cidx = cw.take(n_terms * 4), o_coef = cw.take(r->coef.size() * 32),
+    const size_t o_ent = cw.take(n_terms * 4), o_cidx = cw.take(n_terms * 4), o_coef = cw.take(r->sys.coef.size() * 32),
                  o_soff = cw.take(((size_t)n_seg + 1) * 4), o_skey = cw.take((size_t)n_seg * 4), o_wseg = cw.take(((size_t)nw + 1) * 4),
                  o_x1 = cw.take(n1 * sizeof(Xyzz<G1>)), o_x2 = cw.take(n2 * sizeof(Xyzz<G2>)), o_p1 = cw.take(n1 * G1_BYTES),
                  o_p2 = cw.take(n2 * G2_BYTES);
@@ -637,7 +637,7 @@ int setup(gwb_r1cs* r, const gwb_groth16_trapdoor_t* trapdoor, void** zkey, size
     };
     up(o_ent, col.ent.data(), n_terms * 4);
     up(o_cidx, col.cidx.data(), n_terms * 4);
-    up(o_coef, r->coef.data(), r->coef.size() * 32);
+    up(o_coef, r->sys.coef.data(), r->sys.coef.size() * 32);
     up(o_soff, col.seg_off.data(), ((size_t)n_seg + 1) * 4);
     up(o_skey, col.seg_key.data(), (size_t)n_seg * 4);
     up(o_wseg, col.wire_seg.data(), ((size_t)nw + 1) * 4);

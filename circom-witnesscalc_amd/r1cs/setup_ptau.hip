@@ -423,7 +423,7 @@ int setup(gwb_r1cs* r, const uint8_t* ptau, size_t ptau_len, const uint8_t* delt
 
     Device D;
     Carve cw;
-    const size_t o_ent = cw.take(n_terms * 4), o_cidx = cw.take(n_terms * 4), o_coef = cw.take(r->coef.size() * 32),
+    const size_t o_ent = cw.take(n_terms * 4), o_cidx = cw.take(n_terms * 4), o_coef = cw.take(r->sys.coef.size() * 32),
                  o_soff = cw.take(((size_t)n_seg + 1) * 4), o_skey = cw.take((size_t)n_seg * 4), o_wseg = cw.take(((size_t)nw + 1) * 4),
                  o_raw1 = cw.take(5ull * n * G1_BYTES),  // compute: T1 (2n), AT, BT; file: L1, LA, LB, M (2n)
                  o_raw2 = cw.take((size_t)n * G2_BYTES), o_lag1 = cw.take(4ull * n * X1),  // L1, LA, LB and (compute) D
@@ -444,7 +444,7 @@ int setup(gwb_r1cs* r, const uint8_t* ptau, size_t ptau_len, const uint8_t* delt
     };
     up(o_ent, col.ent.data(), n_terms * 4);
     up(o_cidx, col.cidx.data(), n_terms * 4);
-    up(o_coef, r->coef.data(), r->coef.size() * 32);
+    up(o_coef, r->sys.coef.data(), r->sys.coef.size() * 32);
     up(o_soff, col.seg_off.data(), ((size_t)n_seg + 1) * 4);
     up(o_skey, col.seg_key.data(), (size_t)n_seg * 4);
     up(o_wseg, col.wire_seg.data(), ((size_t)nw + 1) * 4);

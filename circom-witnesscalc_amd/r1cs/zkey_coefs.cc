@@ -6,7 +6,7 @@
 // with the same (m, c, s) add up, a zero value contributes nothing, and a row without entries is zero.
 //
 // zkey_coefs_build turns the entries the loader kept (zkey.cc: matrix, constraint and signal already in range) into the arrays
-// the evaluation kernels read (r1cs_internal.hpp): the factor stream wire | kind << 30 with KIND_PLUS / KIND_MINUS for v = +-R^2,
+// the evaluation kernel reads (a RowSystem, r1cs_internal.hpp): the factor stream wire | kind << 30 with KIND_PLUS / KIND_MINUS for v = +-R^2,
 // the distinct other values as c R (one fr_from_mont of the file value), rows bucketed by length with perm back to the
 // constraint index, and two row pointers per row.  Entries with the same (m, c, s) stay separate factors: the kernel's sum adds them.
 #include <string.h>
@@ -136,12 +136,14 @@ bool build(gwb_zkey* z, std::string& err) {
             cidx[o] = ix;
         }
     }
-    z->n_used = n_used;
-    z->rowptr.swap(rowptr);
-    z->fac.swap(fac);
-    z->cidx.swap(cidx);
-    z->perm.swap(order);
-    z->coef.swap(coef);
+    RowSystem& sys = z->sys;  // (stride 2 since the handle was made)
+    sys.n_rows = n_used;
+    sys.n_wires = in.n_vars;
+    sys.rowptr.swap(rowptr);
+    sys.fac.swap(fac);
+    sys.cidx.swap(cidx);
+    sys.perm.swap(order);
+    sys.coef.swap(coef);
     z->coefs_built = true;
     return true;
 }
@@ -191,6 +193,7 @@ int check_r1cs(const gwb_zkey* z, const gwb_r1cs* r, gw_status_t* status) {
     normalise(zt, [](const Fr& v) { return cwc::fr_from_mont(cwc::fr_from_mont(v)); });
     // the .r1cs: A and B of every constraint at its file index (values c R), then the public rows
     const gwb_r1cs_info_t& ri = r->info;
+    const RowSystem& rs = r->sys;
     const uint32_t nc = ri.n_constraints;
     const uint64_t n_pub = (uint64_t)ri.n_pub_out + ri.n_pub_in;
     std::vector<Term> rt;
@@ -198,9 +201,9 @@ int check_r1cs(const gwb_zkey* z, const gwb_r1cs* r, gw_status_t* status) {
     const Fr one = cwc::fr_one(), minus_one = cwc::fr_neg(one);
     for (uint32_t k = 0; k < nc; ++k)
         for (uint32_t m = 0; m < 2; ++m)
-            for (uint32_t j = r->rowptr[3ull * k + m]; j < r->rowptr[3ull * k + m + 1]; ++j) {
-                const uint32_t f = r->fac[j], kind = f >> 30;
-                rt.push_back(Term{r->perm[k], m, f & WIRE_MASK, kind == KIND_PLUS ? one : kind == KIND_MINUS ? minus_one : r->coef[r->cidx[j]]});
+            for (uint32_t j = rs.rowptr[3ull * k + m]; j < rs.rowptr[3ull * k + m + 1]; ++j) {
+                const uint32_t f = rs.fac[j], kind = f >> 30;
+                rt.push_back(Term{rs.perm[k], m, f & WIRE_MASK, kind == KIND_PLUS ? one : kind == KIND_MINUS ? minus_one : rs.coef[rs.cidx[j]]});
             }
     for (uint64_t s = 0; s <= n_pub; ++s) rt.push_back(Term{(uint64_t)nc + s, 0, (uint32_t)s, one});
     normalise(rt, [](const Fr& v) { return cwc::fr_from_mont(v); });
@@ -250,7 +253,7 @@ extern "C" {
 
 int gwb_zkey_set_tile_width(gwb_zkey_t* z, uint32_t t) {
     if (!z || t > 64 || (t & (t - 1))) return 1;
-    z->tile_width = t;
+    z->sys.tile_width = t;
     return 0;
 }
 
@@ -260,7 +263,7 @@ int gwb_zkey_qap_info(gwb_zkey_t* z, gwb_r1cs_qap_info_t* info, gw_status_t* sta
     if (!zkey_coefs_build(z, err)) return refuse(status, err);
     uint32_t p = 0;
     while ((1u << p) < z->info.domain_size) ++p;
-    info->n_rows = z->n_used;
+    info->n_rows = z->sys.n_rows;
     info->domain_power = p;
     info->domain_size = z->info.domain_size;
     info->workspace_bytes_per_row = 2ull * 32 << p;

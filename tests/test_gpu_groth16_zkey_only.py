@@ -1,4 +1,4 @@
-"""Proving from the zkey alone on an MI355X: the witness map of section 4 (r1cs/qap.hip zkey_eval_kernel, gwb_zkey_qap_*) against
+"""Proving from the zkey alone on an MI355X: the witness map of section 4 (r1cs/qap.hip, gwb_zkey_qap_*) against
 the `.r1cs` path and the big-integer reference (tests/qap_reference.py), and zkey-only proofs against known discrete logs and the
 `.r1cs` path's bytes.  Section 4 is written from plain integers by tests/zkey_coefs_fixtures.py (c R^2 mod r), independent of
 r1cs/setup.hip; one test reads a key that setup.hip wrote instead.  Witness-map tests use zkeys whose points are all at infinity

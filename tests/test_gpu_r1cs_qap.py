@@ -1,8 +1,8 @@
 """The Groth16 witness map (r1cs/qap.hip, gwb_r1cs_qap_*) on an MI355X, compared exactly with the plain-Python restatement
 (tests/qap_reference.py): planted systems with public signals at every domain power through 2^13 (the in-LDS sizes and the
 first four-step sizes), a 2^17 domain on sampled points, every tile width, both row and output forms, rows above r,
-unsatisfied witnesses, batches 0 and 1, sub-batches under a small workspace cap, every entry point on the same rows, the
-refusals, and the whole chain behind the witness calculator on the authV2-class graph."""
+unsatisfied witnesses, batches 0 and 1, a system without constraints, sub-batches under a small workspace cap, every entry
+point on the same rows, the refusals, and the whole chain behind the witness calculator on the authV2-class graph."""
 import os
 import random
 import struct
@@ -141,6 +141,27 @@ def test_batch_zero_and_one(pkg):
     assert tuple(r.qap_batch_device(torch.from_numpy(empty).cuda()).shape) == (0, n, 32)
     rows = [pl.complete(rnd)]
     _assert_h(_device(r, F.rows_array(rows)), _want(pl.constraints, n_pub, rows), "batch 1")
+
+
+def test_no_constraints(pkg):
+    """an `.r1cs` without constraints: the evaluation launch is skipped (its clamp to the last row has no row to clamp to), the
+    input rows come from the witness, b is zero at every point, so h = A B - C is zero whatever the row holds"""
+    rnd = random.Random(450)
+    n_wires = 7  # wire 0, one public output, one public input, four free wires
+    r = PKG.R1cs(F.write_r1cs(n_wires, [], n_pub_out=1, n_pub_in=1, n_prv_in=0))
+    info = r.qap_info()
+    assert info["n_rows"] == 3 and info["domain_size"] == 4, info
+    rows = [[1] + [rnd.randrange(R) for _ in range(n_wires - 1)] for _ in range(3)]
+    want = _want([], 2, rows)
+    assert want.shape == (3, 4, 32) and not want.any()
+    canon = F.rows_array(rows)
+    mont = F.rows_array([[F.to_montgomery(x) for x in row] for row in rows])
+    for out in (False, True):  # (zero is zero in both forms)
+        _assert_h(r.qap_batch(canon, montgomery_out=out), want, "host, montgomery_out=%s" % out)
+        for t in (0, 64):
+            r.set_tile_width(t)
+            _assert_h(_device(r, canon, montgomery_out=out), want, "t=%d canonical, montgomery_out=%s" % (t, out))
+            _assert_h(_device(r, mont, montgomery=True, montgomery_out=out), want, "t=%d montgomery in, montgomery_out=%s" % (t, out))
 
 
 def test_sub_batches_under_a_small_cap(pkg):
