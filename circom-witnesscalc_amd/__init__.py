@@ -616,6 +616,10 @@ def r1cs_lib():
         L.gwb_groth16_setup_ptau.argtypes = [vp, vp, sz, vp, u32, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
         L.gwb_bn254_point_idft_batch_device.argtypes = [vp, u32, u32, vp, vp, stp]
         L.gwb_groth16_setup_ptau_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_float)]
+        L.gwb_bn254_g2_check_batch_device.argtypes = [vp, sz, u32, u32, vp, vp, stp]
+        L.gwb_zkey_check_g2.argtypes = [vp, stp]
+        L.gwb_zkey_check_wtns.argtypes = [vp, vp, sz, stp]
+        L.gwb_ptau_check_g2.argtypes = [vp, sz, u32, u32, stp]
         _r1cs_lib = L
     return _r1cs_lib
 
@@ -823,9 +827,10 @@ class Groth16:
     per row (A.x, A.y, B.x.c0, B.x.c1, B.y.c0, B.y.c1, C.x, C.y, canonical little-endian).  The witness map comes from the
     key's own section 4 (what snarkjs and rapidsnark do), or, when an R1cs of the same circuit is given, from that.  Section 4
     is turned into the prover's arrays at the first call that needs it; what that step refuses (a value >= r, no coefficients,
-    a domain the transform cannot take) is raised there, not here."""
+    a domain the transform cannot take) is raised there, not here.  check_g2=True also runs check_g2() on the loaded key (on
+    the GPU); by default the key's G2 points are checked for the curve equation alone, as before."""
 
-    def __init__(self, zkey_bytes, r1cs=None):
+    def __init__(self, zkey_bytes, r1cs=None, check_g2=False):
         self._h = ctypes.c_void_p()
         self.r1cs = r1cs
         data = bytes(zkey_bytes)
@@ -835,6 +840,8 @@ class Groth16:
         info = ZkeyInfo()
         r1cs_lib().gwb_zkey_info(self._h, ctypes.byref(info))
         self.info = {n: int(getattr(info, n)) for n, _ in ZkeyInfo._fields_}
+        if check_g2:
+            self.check_g2()
 
     def close(self):
         if getattr(self, "_h", None) and _r1cs_lib is not None:
@@ -856,6 +863,15 @@ class Groth16:
             raise WitnessCalcError("check_r1cs: no R1cs given and the handle has none")
         st = GwStatus()
         rc = r1cs_lib().gwb_zkey_check_r1cs(self._h, r1cs._h, ctypes.byref(st))
+        _r1cs_check(rc, st)
+
+    def check_g2(self):
+        """Raises unless beta2, gamma2, delta2 and every B2 point (section 7) lie in G2's order-r subgroup; checked on the
+        current GPU (synchronous).  The message names the first offender: "zkey: beta2 is not in the order-r subgroup of G2", or
+        "zkey: section 7 (B2) point 12 is not in the order-r subgroup of G2 (3 of 70 points are not)".  A proof made with a
+        B2 point outside the subgroup is refused by every verifier (VERIFY_SUBGROUP)."""
+        st = GwStatus()
+        rc = r1cs_lib().gwb_zkey_check_g2(self._h, ctypes.byref(st))
         _r1cs_check(rc, st)
 
     # -- the witness map of section 4 on its own (always from the zkey, whether or not the handle has an R1cs) -----------------
@@ -941,10 +957,10 @@ class Groth16:
         return cls(groth16_setup(r1cs, trapdoor), r1cs)
 
     @classmethod
-    def setup_ptau(cls, r1cs, ptau, delta=None, lagrange="auto"):
+    def setup_ptau(cls, r1cs, ptau, delta=None, lagrange="auto", check_g2=False):
         """A proving key made for `r1cs` from a powers-of-tau file by groth16_setup_ptau (see its trust statement), loaded
-        against it."""
-        return cls(groth16_setup_ptau(r1cs, ptau, delta, lagrange), r1cs)
+        against it.  check_g2: as groth16_setup_ptau's."""
+        return cls(groth16_setup_ptau(r1cs, ptau, delta, lagrange, check_g2=check_g2), r1cs)
 
     def verifying_key(self):
         """The zkey's verifying key (Groth16VerifyingKey)."""
@@ -1065,14 +1081,31 @@ def ptau_check(ptau, domain_power, lagrange="auto"):
     del keep
 
 
-def groth16_setup_ptau(r1cs, ptau, delta=None, lagrange="auto"):
+def ptau_check_g2(ptau, domain_power, lagrange="auto"):
+    """Raises WitnessCalcError unless the G2 points that groth16_setup_ptau reads from this file for a circuit of domain
+    2^domain_power lie in G2's order-r subgroup: betaG2 and tauG2[0 .. n) when the Lagrange forms are computed, tauG2[0] and level
+    domain_power of section 13 when they are read.  The header, the plan and alpha1, beta1, beta2 are checked first, on the host,
+    with ptau_check's messages; the points are then checked on the current GPU in bounded pieces (synchronous).  The message
+    names section and index: "ptau: section 3 (tauG2) point 5 is not in the order-r subgroup of G2"."""
+    keep, addr, n = _ptau_buffer(ptau)
+    st = GwStatus()
+    rc = r1cs_lib().gwb_ptau_check_g2(addr, n, int(domain_power), _lagrange_mode(lagrange), ctypes.byref(st))
+    _r1cs_check(rc, st)
+    del keep
+
+
+def groth16_setup_ptau(r1cs, ptau, delta=None, lagrange="auto", check_g2=False):
     """The Groth16 proving key of an R1cs as `.zkey` bytes, made on the GPU from a powers-of-tau file (what snarkjs
     `groth16 setup` does; synchronous).  tau, alpha and beta are the ceremony's; gamma = 1.  delta: an int in [1, r), or None:
     drawn, applied and discarded, after which soundness rests on the ceremony behind the file and on this call's runner
     having discarded delta (a single-party phase 2; knowing delta alone is enough to forge).  delta = 1 is the state of
     snarkjs `zkey new`: a key to hand to a phase-2 ceremony, not to use.  lagrange: "auto" reads the file's prepared sections
-    when it has them, "file" requires them, "compute" ignores them."""
+    when it has them, "file" requires them, "compute" ignores them.  check_g2=True first runs ptau_check_g2 for the circuit's
+    domain: without it the file's G2 points are checked for the curve equation alone, and a point outside the order-r subgroup
+    ends up in a key whose proofs every verifier refuses."""
     mode = _lagrange_mode(lagrange)
+    if check_g2:
+        ptau_check_g2(ptau, r1cs.qap_info()["domain_power"], lagrange)
     buf = None
     if delta is not None:
         d = int(delta)
@@ -1334,6 +1367,33 @@ def bn254_pairing_batch_device(d_g1, d_g2, stream=None):
         rc = r1cs_lib().gwb_bn254_pairing_batch_device(d_g1.data_ptr(), d_g2.data_ptr(), n, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
     _r1cs_check(rc, st)
     if n:
+        out.record_stream(s)
+    return out
+
+
+G2_CHECK_METHODS = {"fast": 0, "order": 1}
+
+
+def bn254_g2_check_batch_device(d_points, montgomery=False, method="fast", stream=None):
+    """Measurement and test aid, and the kernel behind Groth16.check_g2 and ptau_check_g2: device G2 points (uint8 cuda [n, 128]:
+    x.c0, x.c1, y.c0, y.c1, canonical little-endian or, with montgomery, as the files store them; zero bytes = infinity) -> a
+    uint32 cuda tensor [n]: VERIFY_VALID (in the order-r subgroup, infinity included), VERIFY_POINT (a coordinate >= q, or not on
+    the twist) or VERIFY_SUBGROUP (on the twist, outside the subgroup).  method "fast" is the psi criterion
+    [x + 1] P + psi([x] P) + psi^2([x] P) = psi^3([2x] P), "order" is [r] P = O.  Asynchronous on `stream` or the current stream."""
+    import torch
+    if method not in G2_CHECK_METHODS:
+        raise WitnessCalcError("method must be one of %s" % ", ".join(G2_CHECK_METHODS))
+    n = d_points.shape[0]
+    assert tuple(d_points.shape) == (n, 128) and d_points.is_cuda and d_points.is_contiguous() and d_points.dtype == torch.uint8
+    s = stream if stream is not None else torch.cuda.current_stream(d_points.device)
+    out = torch.empty(n, dtype=torch.uint32, device=d_points.device)
+    st = GwStatus()
+    with torch.cuda.device(d_points.device):
+        rc = r1cs_lib().gwb_bn254_g2_check_batch_device(d_points.data_ptr() if n else None, n, FORM_MONTGOMERY if montgomery else FORM_CANONICAL,
+                                                        G2_CHECK_METHODS[method], out.data_ptr() if n else None, s.cuda_stream, ctypes.byref(st))
+    _r1cs_check(rc, st)
+    if n:
+        d_points.record_stream(s)
         out.record_stream(s)
     return out
 

@@ -1,7 +1,9 @@
 // groth16-prove <circuit.zkey> <witness.wtns> <proof.json> <public.json>: a Groth16 proof of the witness on the GPU (snarkjs
 // `groth16 prove`, its argument order), written in snarkjs's proof.json / public.json shape; the witness map comes from the
 // zkey's section 4.  groth16-prove <circuit.r1cs> <circuit.zkey> <witness.wtns> <proof.json> <public.json> takes it from the
-// `.r1cs` instead.  Exit status 0 on success; 2 on a usage, file, format or mismatch error.  Every input is parsed before the
+// `.r1cs` instead.  --check-g2 (anywhere among the arguments, either form) first checks the key's G2 points (beta2, gamma2,
+// delta2, section 7) for membership in the order-r subgroup, on the GPU, and refuses the key before proving if one is outside
+// it.  Exit status 0 on success; 2 on a usage, file, format, mismatch or subgroup error.  Every input is parsed before the
 // device is touched.
 #include <stdio.h>
 #include <stdlib.h>
@@ -68,15 +70,26 @@ static bool write_text(const char* path, const std::string& s) {
 }
 
 int main(int argc, char** argv) {
-    if (argc != 5 && argc != 6) {
+    bool check_g2 = false, usage = false;
+    std::vector<char*> pos;
+    for (int i = 1; i < argc; ++i) {
+        if (strcmp(argv[i], "--check-g2") == 0) {
+            usage = usage || check_g2;
+            check_g2 = true;
+        } else {
+            pos.push_back(argv[i]);
+        }
+    }
+    if (usage || (pos.size() != 4 && pos.size() != 5)) {
         fprintf(stderr,
-                "usage: %s <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n"
-                "       %s <circuit.r1cs> <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n",
+                "usage: %s [--check-g2] <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n"
+                "       %s [--check-g2] <circuit.r1cs> <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n"
+                "  --check-g2  refuse a key whose G2 points are not all in the order-r subgroup (checked on the GPU before proving)\n",
                 argv[0], argv[0]);
         return 2;
     }
-    const bool with_r1cs = argc == 6;
-    char** in = argv + 1;  // inputs: [r1cs,] zkey, wtns; then the two outputs
+    const bool with_r1cs = pos.size() == 5;
+    char** in = pos.data();  // inputs: [r1cs,] zkey, wtns; then the two outputs
     const int n_in = with_r1cs ? 3 : 2;
     std::vector<char> loaded[3];
     for (int i = 0; i < n_in; ++i) {
@@ -100,6 +113,16 @@ int main(int argc, char** argv) {
         gw_free_status(&st);
         gwb_r1cs_free(r);
         return 2;
+    }
+    if (check_g2) {  // the witness is parsed first, so that the subgroup check is not the first to find a broken image
+        const bool parsed = gwb_zkey_check_wtns(z, wtns_file.data(), wtns_file.size(), &st) == 0;
+        if (!parsed || gwb_zkey_check_g2(z, &st) != 0) {
+            fprintf(stderr, "error: %s: %s\n", in[parsed ? n_in - 2 : n_in - 1], st.error_msg ? st.error_msg : "check failed");
+            gw_free_status(&st);
+            gwb_zkey_free(z);
+            gwb_r1cs_free(r);
+            return 2;
+        }
     }
     uint8_t proof[GWB_GROTH16_PROOF_BYTES];
     // (the call parses the .wtns image and, without an .r1cs, builds the map of section 4 before it reaches the device)

@@ -5,7 +5,9 @@
 // groth16-setup --ptau FILE [--delta FILE] [--lagrange auto|file|compute] <circuit.r1cs> <circuit.zkey> [verification_key.json]:
 // the key from a powers-of-tau file, which is mapped into memory, not read (include/graph_witness_groth16_ptau.h): tau, alpha
 // and beta are the ceremony's, gamma is 1, and delta is drawn and discarded or read from FILE (one decimal integer in [1, r);
-// 1 gives the state of snarkjs `zkey new`).  --ptau and --trapdoor exclude each other.  With a third path the verifying key is written too, in snarkjs's
+// 1 gives the state of snarkjs `zkey new`).  --check-g2 (with --ptau only) first checks the G2 points the setup reads from
+// the file for membership in the order-r subgroup, on the GPU, and refuses the file before a key is made if one is outside it.
+// --ptau and --trapdoor exclude each other.  With a third path the verifying key is written too, in snarkjs's
 // verification_key.json shape with vk_alphabeta_12.  Exit status 0 on success; 2 on a usage, file or format error.  Every
 // input is parsed before the device is touched.
 #include <stdio.h>
@@ -213,8 +215,13 @@ static bool vk_json(const void* zkey, size_t len, std::string& out, std::string&
 int main(int argc, char** argv) {
     const char *trapdoor_path = NULL, *ptau_path = NULL, *delta_path = NULL, *lagrange = NULL;
     std::vector<const char*> pos;
-    bool usage = false;
+    bool usage = false, check_g2 = false;
     for (int i = 1; i < argc && !usage; ++i) {
+        if (strcmp(argv[i], "--check-g2") == 0) {
+            usage = check_g2;
+            check_g2 = true;
+            continue;
+        }
         const char** opt = strcmp(argv[i], "--trapdoor") == 0 ? &trapdoor_path
                            : strcmp(argv[i], "--ptau") == 0   ? &ptau_path
                            : strcmp(argv[i], "--delta") == 0  ? &delta_path
@@ -236,12 +243,13 @@ int main(int argc, char** argv) {
         else if (strcmp(lagrange, "auto") != 0)
             usage = true;
     }
-    // --ptau and --trapdoor exclude each other; --delta and --lagrange belong to --ptau
-    if ((ptau_path && trapdoor_path) || (!ptau_path && (delta_path || lagrange))) usage = true;
+    // --ptau and --trapdoor exclude each other; --delta, --lagrange and --check-g2 belong to --ptau
+    if ((ptau_path && trapdoor_path) || (!ptau_path && (delta_path || lagrange || check_g2))) usage = true;
     if (usage || (pos.size() != 2 && pos.size() != 3)) {
         fprintf(stderr,
                 "usage: %s [--trapdoor FILE] <circuit.r1cs> <circuit.zkey> [verification_key.json]\n"
-                "       %s --ptau FILE [--delta FILE] [--lagrange auto|file|compute] <circuit.r1cs> <circuit.zkey> [verification_key.json]\n",
+                "       %s --ptau FILE [--delta FILE] [--lagrange auto|file|compute] [--check-g2] <circuit.r1cs> <circuit.zkey> [verification_key.json]\n"
+                "  --check-g2  refuse a file whose G2 points, as far as this setup reads them, are not all in the order-r subgroup\n",
                 argv[0], argv[0]);
         return 2;
     }
@@ -278,6 +286,16 @@ int main(int argc, char** argv) {
             return 2;
         }
         if (delta_path && !parse_delta(delta_path, delta)) {
+            gwb_r1cs_free(r);
+            return 2;
+        }
+    }
+    if (check_g2) {
+        gwb_r1cs_qap_info_t qi;
+        if (gwb_r1cs_qap_info(r, &qi, &st) != 0 || gwb_ptau_check_g2(ptau.data, ptau.len, qi.domain_power, mode, &st) != 0) {
+            fprintf(stderr, "error: %s: %s\n", ptau_path, st.error_msg ? st.error_msg : "check failed");
+            gw_free_status(&st);
+            explicit_bzero(delta, sizeof delta);
             gwb_r1cs_free(r);
             return 2;
         }

@@ -10,7 +10,8 @@
 //   Lag_m of the first 2^m monomial points) starts at point offset 2^m - 1; levels 0 .. power, and in section 12 also power + 1.
 // The loader reads the header, the section table, and of the points only what a setup for one domain needs (Plan): it never
 // walks a whole section, so a file of gigabytes that is mapped into memory is touched in a few places.  G2 points are not
-// checked for subgroup membership.  The layout is restated from snarkjs's writer; no snarkjs output was available to check it.
+// checked for subgroup membership here; gwb_ptau_check_g2 (subgroup.hip) checks those a setup reads, on the device, when asked
+// (groth16_setup_ptau(..., check_g2=True), groth16-setup --ptau FILE --check-g2).  The layout is restated from snarkjs's writer; no snarkjs output was available to check it.
 #include <string.h>
 
 #include <string>
@@ -81,6 +82,7 @@ bool check_points(uint32_t section, const uint8_t* p, uint64_t base_index, uint6
 
 std::string point_message(uint32_t section, uint64_t index, uint32_t fault, bool g2) {
     std::string m = "ptau: section " + std::to_string(section) + " (" + section_name(section) + ") point " + std::to_string(index);
+    if (fault == SUBGROUP) return m + " is not in the order-r subgroup of G2";
     return m + (fault == COORDINATE ? " has a coordinate >= q" : std::string(" is not on the ") + (g2 ? "G2" : "G1") + " curve");
 }
 

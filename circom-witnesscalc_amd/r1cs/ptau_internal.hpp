@@ -32,7 +32,7 @@ struct Plan {
     const uint8_t *l1 = nullptr, *l2 = nullptr, *la = nullptr, *lb = nullptr, *m = nullptr;
 };
 
-enum PointFault : uint32_t { COORDINATE = 0, CURVE = 1 };
+enum PointFault : uint32_t { COORDINATE = 0, CURVE = 1, SUBGROUP = 2 };
 
 // header, section table, sizes of the required sections, T1_0 = G1, T2_0 = G2, section 6's point
 bool parse(const uint8_t* d, size_t len, View& v, std::string& err);
@@ -42,7 +42,7 @@ bool plan(const View& v, uint32_t p, uint32_t mode, Plan& pl, std::string& err);
 bool check_header_points(const Plan& pl, std::string& err);
 // the bulk arrays, on the host (gwb_ptau_check; the setup checks them on the device)
 bool check_bulk_points(const Plan& pl, std::string& err);
-// "ptau: section 2 (tauG1) point 5 is not on the G1 curve"
+// "ptau: section 2 (tauG1) point 5 is not on the G1 curve"; SUBGROUP (subgroup.hip, G2 only): "... is not in the order-r subgroup of G2"
 std::string point_message(uint32_t section, uint64_t index, uint32_t fault, bool g2);
 
 }  // namespace cwc_ptau

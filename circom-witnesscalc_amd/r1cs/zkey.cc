@@ -8,7 +8,9 @@
 //   section 5:  A, nVars G1               section 6: B1, nVars G1            section 7: B2, nVars G2
 //   section 8:  C, nVars - nPublic - 1 G1 section 9: H, domainSize G1         section 10: contributions (ignored)
 // Every coordinate must be below q and every point other than infinity on its curve (G1: y^2 = x^3 + 3, G2: y^2 = x^3 +
-// 3 / (9 + u)); G2 points are not checked for subgroup membership.  The curve check uses the host build of fq_gfx950.hpp.
+// 3 / (9 + u)).  G2 points are not checked for subgroup membership here; gwb_zkey_check_g2 (subgroup.hip) checks beta2, gamma2,
+// delta2 and section 7 on the device when asked (Groth16(zkey, check_g2=True), groth16-prove --check-g2).  The curve check uses
+// the host build of fq_gfx950.hpp.
 #include <string.h>
 
 #include <map>
@@ -195,6 +197,18 @@ int gwb_zkey_load(const void* data, size_t len, gwb_zkey_t** out, gw_status_t* s
         return 1;
     }
     *out = z;
+    cwc_r1cs::set_ok(status);
+    return 0;
+}
+
+int gwb_zkey_check_wtns(const gwb_zkey_t* z, const void* wtns, size_t wtns_len, gw_status_t* status) {
+    if (!z || (!wtns && wtns_len)) return cwc_r1cs::fail(status, "gwb_zkey_check_wtns: NULL argument");
+    const uint8_t* values = nullptr;
+    uint64_t n_wit = 0;
+    std::string err;
+    if (!cwc_r1cs::parse_wtns(wtns, wtns_len, &values, &n_wit, err)) return cwc_r1cs::fail(status, err);
+    if (n_wit != z->info.n_vars)
+        return cwc_r1cs::fail(status, "groth16: the witness has " + std::to_string(n_wit) + " elements, the zkey nVars = " + std::to_string(z->info.n_vars));
     cwc_r1cs::set_ok(status);
     return 0;
 }

@@ -12,7 +12,8 @@
  * zero bytes.
  *
  * The `.zkey` (iden3 binfile "zkey" v1, Groth16) is validated when loaded: BN254's q and r, section sizes against its header,
- * coordinates below q, every point other than infinity on its curve.  G2 points are not checked for subgroup membership.
+ * coordinates below q, every point other than infinity on its curve.  G2 points are not checked for subgroup membership by
+ * the loader; gwb_zkey_check_g2 checks them on the device when asked.
  * Section 4 (the coefficients) is bounds-checked at load: matrix 0 or 1, constraint < domainSize, signal < nVars.
  *
  * The witness map h comes from one of two places.  With an `.r1cs` handle the prover takes it from there, as before, and the
@@ -98,6 +99,16 @@ int gwb_zkey_set_tile_width(gwb_zkey_t *z, uint32_t tile_width);
  * r1cs at constraint 12, matrix B, signal 7" -- or, where the terms agree, the size field that does not.  A zkey does not hold
  * the C matrix, so the C sides of the `.r1cs` are not compared: two circuits that differ only there pass. */
 int gwb_zkey_check_r1cs(const gwb_zkey_t *z, const gwb_r1cs_t *r, gw_status_t *status);
+/* Are the key's G2 points in the order-r subgroup?  (The twist has order r (2q - r), so a point on the curve can carry a
+ * component of small order; a proof made with such a B2 point is refused by every verifier.)  Checks beta2, gamma2, delta2 and
+ * the nVars points of section 7 on the current device (gwb_bn254_g2_check_batch_device's method 0; synchronous; the upload is
+ * temporary and does not touch the prover's copies).  Returns 0, or 1 with the first offender in this order:
+ * "zkey: beta2 is not in the order-r subgroup of G2" (likewise gamma2, delta2), then "zkey: section 7 (B2) point 12 is not in the
+ * order-r subgroup of G2 (3 of 70 points are not)" with the smallest index. */
+int gwb_zkey_check_g2(gwb_zkey_t *z, gw_status_t *status);
+/* Host only: the `.wtns` image as gwb_groth16_prove_wtns validates it before it reaches the device, and nWitness == nVars
+ * (for a caller that wants every input parsed before a device call other than the prove call, as groth16-prove --check-g2). */
+int gwb_zkey_check_wtns(const gwb_zkey_t *z, const void *wtns, size_t wtns_len, gw_status_t *status);
 
 #ifdef __cplusplus
 }

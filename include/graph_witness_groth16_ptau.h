@@ -32,7 +32,8 @@
  * magic or version; n8 != 32 or a q that is not BN254's; power > 28; a missing, duplicate or mis-sized section 1 to 6; a
  * coordinate >= q or a point off its curve among those it reads (naming section and index); T1_0 != G1 or T2_0 != G2; and a
  * circuit with p + 1 > power.  snarkjs also accepts p = power, through a truncated top level of M; that case is left out
- * here.  Like the zkey loader it does not check G2 points for subgroup membership.  The layout is restated from snarkjs's
+ * here.  Like the zkey loader it does not check G2 points for subgroup membership; gwb_ptau_check_g2 does, on the device,
+ * when asked.  The layout is restated from snarkjs's
  * writer and has not been cross-checked against snarkjs itself (no snarkjs output is available to this project).
  *
  * Lagrange source.  A file that went through `powersoftau prepare phase2` carries L1, L2, LA, LB and M already (sections 12
@@ -69,6 +70,15 @@ int gwb_ptau_info(const void *data, size_t len, gwb_ptau_info_t *info, gw_status
  * 2^domain_power under lagrange_mode, with the same messages; the points are checked on the host (the setup checks them on
  * the device). */
 int gwb_ptau_check(const void *data, size_t len, uint32_t domain_power, uint32_t lagrange_mode, gw_status_t *status);
+
+/* G2 subgroup membership of the G2 points a setup for the domain 2^domain_power reads under lagrange_mode: beta2 (section 6)
+ * and tauG2[0 .. n) (section 3) when the Lagrange forms are computed, or tauG2[0] and the n points of level domain_power of
+ * section 13 when they come from the file.  First everything gwb_ptau_check refuses about the header, the section table, the
+ * plan and alpha1, beta1, beta2, on the host and with its messages; then the points go to the current device in bounded pieces
+ * (gwb_bn254_g2_check_batch_device's method 0; synchronous).  Returns 0, or 1 with the first offender, section 6 before 3 before
+ * 13: "ptau: section 3 (tauG2) point 5 is not in the order-r subgroup of G2" (a coordinate >= q or a point off the curve among
+ * them is named as gwb_ptau_check names it). */
+int gwb_ptau_check_g2(const void *data, size_t len, uint32_t domain_power, uint32_t lagrange_mode, gw_status_t *status);
 
 /* delta: 32 bytes canonical little-endian in [1, r), or NULL to draw it (the prover's rejection sampler over getrandom()).
  * *zkey is released with gwb_groth16_setup_free. */

@@ -73,6 +73,16 @@ int gwb_groth16_verify_batch_host(gwb_g16vk_t *vk, const void *proofs, const voi
  * the points are not validated: they must lie on their curves, in G1 and G2), by the general path with a changing Q.
  * Asynchronous on hip_stream (its workspace is allocated and freed in stream order). */
 int gwb_bn254_pairing_batch_device(const void *d_g1, const void *d_g2, size_t n, void *d_gt, void *hip_stream, gw_status_t *status);
+/* Measurement and test aid, and what gwb_zkey_check_g2 and gwb_ptau_check_g2 run: d_status[i] (uint32) for n device G2 points
+ * (128 B each: x.c0, x.c1, y.c0, y.c1 in form GWB_FORM_CANONICAL or GWB_FORM_MONTGOMERY) is
+ *   GWB_G16V_VALID     the point is in G2's order-r subgroup (infinity, all zero bytes, included)
+ *   GWB_G16V_POINT     a coordinate >= q, or the point is not on the twist
+ *   GWB_G16V_SUBGROUP  on the twist, outside the subgroup
+ * method 0 decides by [x + 1] P + psi([x] P) + psi^2([x] P) = psi^3([2x] P) (x the BN parameter, psi the untwist-Frobenius-twist
+ * endomorphism; r1cs/g2_subgroup_gfx950.hpp), method 1 by [r] P = O, the verifier's rule (cross-check and baseline).  An unknown
+ * form or method returns 1 before any device work; n = 0 does nothing.  Asynchronous on hip_stream. */
+int gwb_bn254_g2_check_batch_device(const void *d_points, size_t n, uint32_t form, uint32_t method, void *d_status, void *hip_stream,
+                                    gw_status_t *status);
 
 #ifdef __cplusplus
 }
