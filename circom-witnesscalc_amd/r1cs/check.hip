@@ -18,6 +18,7 @@
 
 #include <string>
 
+#include "hip_util.hpp"
 #include "lincomb.hpp"
 #include "r1cs_internal.hpp"
 

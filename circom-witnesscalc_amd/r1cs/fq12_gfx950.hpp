@@ -15,11 +15,9 @@
 // (q^4 - q^2 + 1) / r by Scott et al.'s addition chain in f^x, f^(x^2), f^(x^3) (x = 4965661367192848881), which computes
 // that exponent itself and not a multiple of it.
 #pragma once
-#include "fq_gfx950.hpp"
+#include "bn254_points_gfx950.hpp"  // and with it the generated constants (fq12_consts_gfx950.inc)
 
 namespace cwc_g16 {
-
-#include "fq12_consts_gfx950.inc"
 
 constexpr uint64_t BN_X = 4965661367192848881ull;  // the BN parameter x (63 bits)
 // 6x + 2 = 2^64 + ATE_LOW: 65 bits; the Miller loop starts at T = Q for the top bit and walks bits 63 .. 0

@@ -241,6 +241,25 @@ FRD Xyzz<T> xyzz_mul(const Xyzz<T>& p, const cwc::Fr& k) {
     return acc;
 }
 
+// k p for a canonical k: double and add from the top nonzero word of k (inside it the doublings of infinity return at once)
+template <class T>
+FRD Xyzz<T> xyzz_mul_short(const Xyzz<T>& p, const cwc::Fr& k) {
+    Xyzz<T> acc = xyzz_inf<T>();
+    cwc::Fr kk = k;  // words move up into kk.v[7] (constant indices: no stack copy of k)
+    for (int w = 0; w < 8; ++w) {
+        const uint32_t word = kk.v[7];
+        if (word != 0 || !xyzz_is_inf(acc)) {
+            for (int b = 31; b >= 0; --b) {
+                acc = xyzz_dbl(acc);
+                if ((word >> b) & 1u) acc = xyzz_add(acc, p);
+            }
+        }
+#pragma unroll
+        for (int i = 7; i > 0; --i) kk.v[i] = kk.v[i - 1];
+    }
+    return acc;
+}
+
 // y^2 == x^3 + b (Montgomery coordinates; b in Montgomery form)
 template <class T>
 FRD bool on_curve(const Affine<T>& p, const typename T::E& b) {

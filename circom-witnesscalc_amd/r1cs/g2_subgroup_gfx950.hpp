@@ -58,7 +58,7 @@ FRD bool g2_in_subgroup(const Affine<Fq2T>& p) {
 // the rule this replaces where it is used, and its cross-check: [r] P = O by the 254-bit double-and-add
 FRD bool g2_in_subgroup_by_order(const Affine<Fq2T>& p) {
     if (affine_is_inf(p)) return true;
-    return xyzz_is_inf(xyzz_mul(Xyzz<Fq2T>{p.x, p.y, fq2_one(), fq2_one()}, cwc::fr_p()));
+    return xyzz_is_inf(xyzz_mul(from_affine(p), cwc::fr_p()));
 }
 
 }  // namespace cwc_g16

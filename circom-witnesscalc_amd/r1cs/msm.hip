@@ -34,24 +34,16 @@
 #include <string>
 #include <vector>
 
-#include "fq_gfx950.hpp"
+#include "bn254_points_gfx950.hpp"
 #include "groth16_internal.hpp"
+#include "hip_util.hpp"
 #include "lincomb.hpp"
-
-namespace cwc_r1cs {
-std::string hip_err(const char* what, hipError_t e);  // check.hip
-}
 
 using namespace cwc_r1cs;
 using namespace cwc_g16;
 using cwc::Fr;
 
 namespace {
-
-using G1 = FqT;
-using G2 = Fq2T;
-using P1 = Xyzz<G1>;
-using P2 = Xyzz<G2>;
 
 constexpr uint32_t K = 32;           // entries per accumulation chunk
 constexpr uint32_t THREADS = 256;
@@ -233,11 +225,6 @@ __global__ __launch_bounds__(THREADS) void windows_kernel(const Xyzz<T>* __restr
     out[(size_t)row * stride] = acc;
 }
 
-template <class T>
-__device__ __forceinline__ Xyzz<T> from_affine(const Affine<T>& a) {
-    return affine_is_inf(a) ? xyzz_inf<T>() : Xyzz<T>{a.x, a.y, T::one(), T::one()};
-}
-
 struct Consts {
     Affine<G1> alpha1, beta1, delta1;
     Affine<G2> beta2;
@@ -262,24 +249,11 @@ __global__ __launch_bounds__(THREADS) void assemble_kernel(const P1* __restrict_
     tmp[t] = x;
 }
 
+// p -> canonical affine bytes
 template <class T>
-__device__ void put_affine(uint8_t* out, const Xyzz<T>& p);
-
-template <>
-__device__ void put_affine<G1>(uint8_t* out, const P1& p) {
-    const Affine<G1> a = xyzz_to_affine(p);
-    Fq* o = reinterpret_cast<Fq*>(out);
-    o[0] = fq_from_mont(a.x);
-    o[1] = fq_from_mont(a.y);
-}
-template <>
-__device__ void put_affine<G2>(uint8_t* out, const P2& p) {
-    const Affine<G2> a = xyzz_to_affine(p);
-    Fq* o = reinterpret_cast<Fq*>(out);
-    o[0] = fq_from_mont(a.x.c0);
-    o[1] = fq_from_mont(a.x.c1);
-    o[2] = fq_from_mont(a.y.c0);
-    o[3] = fq_from_mont(a.y.c1);
+__device__ void put_affine(uint8_t* out, const Xyzz<T>& p) {
+    const Affine<T> a = xyzz_to_affine(p);
+    put_coords<T>(out, a.x, a.y, true);
 }
 
 // job 0: pi_A, 1: pi_B, 2: pi_C -> canonical affine bytes
@@ -310,8 +284,6 @@ uint64_t ws_cap() {  // CWC_GROTH16_WORKSPACE_MB, read once per process
     }();
     return cap;
 }
-
-uint64_t up(uint64_t x) { return (x + 255) & ~255ull; }
 
 uint32_t bits_for(uint64_t x) {  // smallest b with 2^b > x
     uint32_t b = 0;
@@ -355,31 +327,26 @@ bool plan(const gwb_zkey* z, uint64_t rows, Layout& L, std::string& err) {
     }
     L.sort_tmp = s1;
     L.sel_tmp = s2;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += up(bytes);
-        return at;
-    };
-    L.off_h = take(rows * n * 32);
-    for (int i = 0; i < 2; ++i) L.off_keys[i] = take(L.m0 * 4);
-    for (int i = 0; i < 2; ++i) L.off_vals[i] = take(L.m0 * 4);
-    L.off_buckets = take(n_keys * sizeof(P2));
+    Carve cw;
+    L.off_h = cw.take(rows * n * 32);
+    for (int i = 0; i < 2; ++i) L.off_keys[i] = cw.take(L.m0 * 4);
+    for (int i = 0; i < 2; ++i) L.off_vals[i] = cw.take(L.m0 * 4);
+    L.off_buckets = cw.take(n_keys * sizeof(P2));
     for (int i = 0; i < 2; ++i) {
         const uint64_t s = i ? L.slots1 : L.slots0;
-        L.off_slot_keys[i] = take(s * 4);
-        L.off_slot_pts[i] = take(s * sizeof(P2));
-        L.off_flags[i] = take(s * 4);
-        L.off_sel[i] = take(s * 4);
+        L.off_slot_keys[i] = cw.take(s * 4);
+        L.off_slot_pts[i] = cw.take(s * sizeof(P2));
+        L.off_flags[i] = cw.take(s * 4);
+        L.off_sel[i] = cw.take(s * 4);
     }
-    L.off_count = take(8);
-    L.off_win = take(rows * std::max(L.mw.n_win, L.mh.n_win) * sizeof(P2));
-    L.off_g1 = take(rows * 4 * sizeof(P1));
-    L.off_g2 = take(rows * sizeof(P2));
-    L.off_tmp = take(rows * 3 * sizeof(P1));
-    L.off_sort_tmp = take(L.sort_tmp);
-    L.off_sel_tmp = take(L.sel_tmp);
-    L.total = o;
+    L.off_count = cw.take(8);
+    L.off_win = cw.take(rows * std::max(L.mw.n_win, L.mh.n_win) * sizeof(P2));
+    L.off_g1 = cw.take(rows * 4 * sizeof(P1));
+    L.off_g2 = cw.take(rows * sizeof(P2));
+    L.off_tmp = cw.take(rows * 3 * sizeof(P1));
+    L.off_sort_tmp = cw.take(L.sort_tmp);
+    L.off_sel_tmp = cw.take(L.sel_tmp);
+    L.total = cw.o;
     return true;
 }
 
@@ -661,7 +628,7 @@ bool enqueue_prove(gwb_zkey* z, gwb_r1cs* r, const void* d_w, size_t batch, uint
         if (L.total + batch * 64 <= ws_cap() || sub == 1) break;
         sub = std::max<uint64_t>(1, sub * ws_cap() / (L.total + batch * 64 + 1));
     }
-    const size_t rs_off = up(L.total);
+    const size_t rs_off = L.total;  // a multiple of 256
     if (!ensure_ws(z, rs_off + batch * 64, err)) return false;
     Fr* d_rs = (Fr*)((uint8_t*)z->d_ws + rs_off);
     // r, s go through a pinned buffer of the handle; the previous call's copy out of it is waited for first

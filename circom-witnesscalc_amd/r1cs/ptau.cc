@@ -17,33 +17,16 @@
 #include <string>
 
 #include "../../include/graph_witness_groth16_ptau.h"
-#include "fq_gfx950.hpp"
+#include "binfile.hpp"
+#include "bn254_points_gfx950.hpp"
 #include "ptau_internal.hpp"
 
 using namespace cwc_g16;
+using cwc_r1cs::rd32;
 
 namespace cwc_ptau {
 
 namespace {
-
-uint32_t rd32(const uint8_t* p) {
-    uint32_t v;
-    memcpy(&v, p, 4);
-    return v;
-}
-
-Fq rd_fq(const uint8_t* p) {
-    Fq v;
-    memcpy(v.v, p, 32);
-    return v;
-}
-
-Fq2 g2_b() {  // 3 / (9 + u), Montgomery form
-    const Fq2 t{fq_to_mont(Fq{{9, 0, 0, 0, 0, 0, 0, 0}}), fq_one()};
-    const Fq three = fq_to_mont(Fq{{3, 0, 0, 0, 0, 0, 0, 0}});
-    const Fq2 i = fq2_inv(t);
-    return Fq2{fq_mul(i.c0, three), fq_mul(i.c1, three)};
-}
 
 const char* section_name(uint32_t id) {
     static const char* names[MAX_SECTION + 1] = {"", "header", "tauG1", "tauG2", "alphaTauG1", "betaTauG1", "betaG2", "contributions",
@@ -53,101 +36,53 @@ const char* section_name(uint32_t id) {
 
 // n points at p, every `stride`-th from `first`: coordinates below q, on the curve unless all zero
 bool check_points(uint32_t section, const uint8_t* p, uint64_t base_index, uint64_t n, uint64_t first, uint64_t stride, bool g2, std::string& err) {
-    const Fq b1 = fq_to_mont(Fq{{3, 0, 0, 0, 0, 0, 0, 0}});
-    static const Fq2 b2 = g2_b();
-    const uint32_t words = g2 ? 4 : 2;
     for (uint64_t i = first; i < n; i += stride) {
-        const uint8_t* pt = p + i * words * 32;
-        bool zero = true;
-        for (uint32_t k = 0; k < words; ++k) {
-            const Fq c = rd_fq(pt + 32 * k);
-            if (!cwc::u256_lt(c, fq_p())) {
-                err = point_message(section, base_index + i, COORDINATE, g2);
-                return false;
-            }
-            zero = zero && cwc::u256_is_zero(c);
-        }
-        if (zero) continue;
-        const bool ok = g2 ? on_curve<Fq2T>(Affine<Fq2T>{Fq2{rd_fq(pt), rd_fq(pt + 32)}, Fq2{rd_fq(pt + 64), rd_fq(pt + 96)}}, b2)
-                           : on_curve<FqT>(Affine<FqT>{rd_fq(pt), rd_fq(pt + 32)}, b1);
-        if (!ok) {
-            err = point_message(section, base_index + i, CURVE, g2);
-            return false;
-        }
+        const PointFault f = g2 ? point_fault<G2>(p + i * G2_BYTES, false) : point_fault<G1>(p + i * G1_BYTES, false);
+        if (f == PointFault::NONE) continue;
+        err = point_message(section, base_index + i, f, g2);
+        return false;
     }
     return true;
 }
 
 }  // namespace
 
-std::string point_message(uint32_t section, uint64_t index, uint32_t fault, bool g2) {
+std::string point_message(uint32_t section, uint64_t index, PointFault fault, bool g2) {
     std::string m = "ptau: section " + std::to_string(section) + " (" + section_name(section) + ") point " + std::to_string(index);
-    if (fault == SUBGROUP) return m + " is not in the order-r subgroup of G2";
-    return m + (fault == COORDINATE ? " has a coordinate >= q" : std::string(" is not on the ") + (g2 ? "G2" : "G1") + " curve");
+    switch (fault) {
+        case PointFault::COORDINATE: return m + " has a coordinate >= q";
+        case PointFault::CURVE: return m + " is not on the " + (g2 ? "G2" : "G1") + " curve";
+        case PointFault::SUBGROUP: return m + " is not in the order-r subgroup of G2";
+        case PointFault::NONE: break;
+    }
+    return m + " was refused by the device, and the host finds no fault in it";
 }
 
 bool parse(const uint8_t* d, size_t len, View& v, std::string& err) {
-    if (len < 12 || memcmp(d, "ptau", 4) != 0) {
-        err = "ptau: bad magic (not a .ptau file)";
-        return false;
-    }
-    const uint32_t version = rd32(d + 4), n_sections = rd32(d + 8);
-    if (version != 1) {
-        err = "ptau: unsupported version " + std::to_string(version) + " (1 expected)";
-        return false;
-    }
-    uint64_t off = 12;
-    for (uint32_t i = 0; i < n_sections; ++i) {
-        if (len - off < 12) {
-            err = "ptau: truncated section header";
-            return false;
-        }
-        const uint32_t id = rd32(d + off);
-        uint64_t size;
-        memcpy(&size, d + off + 4, 8);
-        off += 12;
-        if (size > len - off) {
-            err = "ptau: truncated section " + std::to_string(id) + " (declares " + std::to_string(size) + " bytes, " + std::to_string(len - off) +
-                  " left)";
-            return false;
-        }
-        if ((id >= 1 && id <= 7) || (id >= 12 && id <= 15)) {
-            if (v.sec[id]) {
-                err = "ptau: duplicate section " + std::to_string(id);
-                return false;
-            }
-            v.sec[id] = d + off;
-            v.size[id] = size;
-        }
-        off += size;
-    }
-    if (off != len) {
-        err = "ptau: " + std::to_string(len - off) + " trailing bytes after the last section";
-        return false;
-    }
+    if (!cwc_r1cs::binfile_sections(d, len, "ptau", 0xf0feu, v.sec, err)) return false;  // sections 1 to 7 and 12 to 15
     for (uint32_t id = 1; id <= 6; ++id)
-        if (!v.sec[id]) {
+        if (!v.sec[id].p) {
             err = "ptau: missing section " + std::to_string(id) + " (" + section_name(id) + ")";
             return false;
         }
     // -- section 1
-    if (v.size[1] < 4 || rd32(v.sec[1]) != 32) {
+    if (v.sec[1].size < 4 || rd32(v.sec[1].p) != 32) {
         err = "ptau: n8 is not 32 (only BN254 is supported)";
         return false;
     }
     auto sized = [&](uint32_t id, uint64_t want) {
-        if (v.size[id] == want) return true;
-        err = "ptau: section " + std::to_string(id) + " (" + section_name(id) + ") has " + std::to_string(v.size[id]) + " bytes, " +
+        if (v.sec[id].size == want) return true;
+        err = "ptau: section " + std::to_string(id) + " (" + section_name(id) + ") has " + std::to_string(v.sec[id].size) + " bytes, " +
               std::to_string(want) + " expected";
         return false;
     };
     if (!sized(1, 44)) return false;
-    if (!cwc::u256_eq(rd_fq(v.sec[1] + 4), fq_p())) {
+    if (!cwc::u256_eq(rd_fq(v.sec[1].p + 4), fq_p())) {
         err = "ptau: base field q is not BN254's";
         return false;
     }
-    v.power = rd32(v.sec[1] + 36);
-    v.ceremony_power = rd32(v.sec[1] + 40);
+    v.power = rd32(v.sec[1].p + 36);
+    v.ceremony_power = rd32(v.sec[1].p + 40);
     if (v.power > MAX_POWER) {
         err = "ptau: power " + std::to_string(v.power) + " is above " + std::to_string(MAX_POWER);
         return false;
@@ -156,17 +91,18 @@ bool parse(const uint8_t* d, size_t len, View& v, std::string& err) {
     if (!sized(2, (2 * np - 1) * G1_BYTES) || !sized(3, np * G2_BYTES) || !sized(4, np * G1_BYTES) || !sized(5, np * G1_BYTES) ||
         !sized(6, G2_BYTES))
         return false;
-    v.n_contributions = v.sec[7] && v.size[7] >= 4 ? rd32(v.sec[7]) : 0;
-    v.prepared = v.sec[12] && v.sec[13] && v.sec[14] && v.sec[15] && v.size[12] == (4 * np - 1) * G1_BYTES &&
-                 v.size[13] == (2 * np - 1) * G2_BYTES && v.size[14] == (2 * np - 1) * G1_BYTES && v.size[15] == (2 * np - 1) * G1_BYTES;
+    v.n_contributions = v.sec[7].p && v.sec[7].size >= 4 ? rd32(v.sec[7].p) : 0;
+    v.prepared = v.sec[12].p && v.sec[13].p && v.sec[14].p && v.sec[15].p && v.sec[12].size == (4 * np - 1) * G1_BYTES &&
+                 v.sec[13].size == (2 * np - 1) * G2_BYTES && v.sec[14].size == (2 * np - 1) * G1_BYTES && v.sec[15].size == (2 * np - 1) * G1_BYTES;
     // -- the generators
     uint8_t g1[G1_BYTES], g2[G2_BYTES];
-    cwc_setup::generator_bytes(g1, g2);
-    if (memcmp(v.sec[2], g1, G1_BYTES) != 0) {
+    put_coords<G1>(g1, g1_generator().x, g1_generator().y, false);
+    put_coords<G2>(g2, g2_generator().x, g2_generator().y, false);
+    if (memcmp(v.sec[2].p, g1, G1_BYTES) != 0) {
         err = "ptau: section 2 (tauG1) point 0 is not the G1 generator";
         return false;
     }
-    if (memcmp(v.sec[3], g2, G2_BYTES) != 0) {
+    if (memcmp(v.sec[3].p, g2, G2_BYTES) != 0) {
         err = "ptau: section 3 (tauG2) point 0 is not the G2 generator";
         return false;
     }
@@ -189,18 +125,18 @@ bool plan(const View& v, uint32_t p, uint32_t mode, Plan& pl, std::string& err) 
     }
     pl.p = p;
     pl.from_file = mode == GWB_PTAU_LAGRANGE_FILE || (mode == GWB_PTAU_LAGRANGE_AUTO && v.prepared);
-    pl.t1 = v.sec[2];
-    pl.t2 = v.sec[3];
-    pl.at = v.sec[4];
-    pl.bt = v.sec[5];
-    pl.beta2 = v.sec[6];
+    pl.t1 = v.sec[2].p;
+    pl.t2 = v.sec[3].p;
+    pl.at = v.sec[4].p;
+    pl.bt = v.sec[5].p;
+    pl.beta2 = v.sec[6].p;
     if (pl.from_file) {
         const uint64_t n = 1ull << p, lvl = n - 1, lvl2 = 2 * n - 1;
-        pl.l1 = v.sec[12] + lvl * G1_BYTES;
-        pl.l2 = v.sec[13] + lvl * G2_BYTES;
-        pl.la = v.sec[14] + lvl * G1_BYTES;
-        pl.lb = v.sec[15] + lvl * G1_BYTES;
-        pl.m = v.sec[12] + lvl2 * G1_BYTES;
+        pl.l1 = v.sec[12].p + lvl * G1_BYTES;
+        pl.l2 = v.sec[13].p + lvl * G2_BYTES;
+        pl.la = v.sec[14].p + lvl * G1_BYTES;
+        pl.lb = v.sec[15].p + lvl * G1_BYTES;
+        pl.m = v.sec[12].p + lvl2 * G1_BYTES;
     }
     return true;
 }

@@ -35,18 +35,15 @@
 
 #include "lincomb.hpp"
 #include "groth16_internal.hpp"
+#include "hip_util.hpp"
 #include "r1cs_internal.hpp"
-
-namespace cwc_r1cs {
-std::string hip_err(const char* what, hipError_t e);  // check.hip
-}
 
 using namespace cwc_r1cs;
 using cwc::Fr;
 
 namespace {
 
-constexpr uint32_t MAX_POWER = 27;     // 2-adicity of r is 28; the coset needs a 2n-th root
+constexpr uint32_t MAX_POWER = MAX_DOMAIN_POWER;
 constexpr uint32_t LOG_TILE = 11;      // elements per block (LDS: 2^11 x 32 B = 64 KiB)
 constexpr uint32_t LOG_OUTER_MAX = 9;  // outer passes: L <= 2^9, 4 columns
 constexpr uint32_t LOG_COLS = 2;
@@ -70,10 +67,6 @@ Plan make_plan(uint32_t p) {
     pl.n_pass = m + 1;
     return pl;
 }
-
-struct Pows {
-    Fr v[MAX_POWER + 1];  // x^(2^b), Montgomery form
-};
 
 // tw[e] = w_n^e; coset[pos] = g^i / n for the coefficient i the inverse passes leave at pos (digits of pos reversed)
 __global__ __launch_bounds__(THREADS) void qap_tables_kernel(Fr* __restrict__ tw, Fr* __restrict__ coset, uint32_t log_n, Pows w_pows,
@@ -367,13 +360,6 @@ bool ensure_tables(QapState& st, uint32_t p, std::string& err) {
     rm1.v[0] -= 1;  // r is odd
     Fr wn, g;
     qap_roots(p, wn, g);
-    Pows wp, gp;
-    wp.v[0] = wn;
-    gp.v[0] = g;
-    for (uint32_t b = 1; b <= MAX_POWER; ++b) {
-        wp.v[b] = cwc::fr_mul(wp.v[b - 1], wp.v[b - 1]);
-        gp.v[b] = cwc::fr_mul(gp.v[b - 1], gp.v[b - 1]);
-    }
     // 1/n = r - (r-1)/n, since n divides r - 1
     Fr q = cwc::u256_shr(rm1, p), n_inv;
     cwc::u256_sub(n_inv, cwc::fr_p(), q);
@@ -385,7 +371,7 @@ bool ensure_tables(QapState& st, uint32_t p, std::string& err) {
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
     if (e == hipSuccess) {
         const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + THREADS - 1) / THREADS, 4096);
-        hipLaunchKernelGGL(qap_tables_kernel, dim3(blocks), dim3(THREADS), 0, s, (Fr*)tw, (Fr*)cs, p, wp, gp, n_inv, make_plan(p));
+        hipLaunchKernelGGL(qap_tables_kernel, dim3(blocks), dim3(THREADS), 0, s, (Fr*)tw, (Fr*)cs, p, powers_of(wn), powers_of(g), n_inv, make_plan(p));
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }

@@ -46,35 +46,24 @@
 #include <vector>
 
 #include "../../include/graph_witness_groth16_setup.h"
-#include "fq_gfx950.hpp"
+#include "bn254_points_gfx950.hpp"
 #include "groth16_internal.hpp"
 #include "lincomb.hpp"
-#include "ptau_internal.hpp"
-
-namespace cwc_r1cs {
-std::string hip_err(const char* what, hipError_t e);  // check.hip
-}
+#include "setup_internal.hpp"
 
 using namespace cwc_r1cs;
 using namespace cwc_g16;
 using cwc::Fr;
 using cwc_setup::Columns;
+using cwc_setup::KeyLayout;
 
 namespace {
-
-using G1 = FqT;
-using G2 = Fq2T;
 
 constexpr uint32_t THREADS = 256;
 constexpr uint32_t INV_CHUNK = 16;    // values per shared inversion
 constexpr uint32_t N_WIN = 32;        // 8-bit windows of a 256-bit scalar
 constexpr uint32_t TABLE_POINTS = N_WIN * 256;
 constexpr uint32_t SEGMENT_DEFAULT = 64;
-constexpr uint32_t MAX_DOMAIN_POWER = 27;
-
-struct Pows {
-    Fr v[MAX_DOMAIN_POWER + 1];  // w^(2^b), Montgomery form
-};
 
 // lag[e] = z x / (tau - x): e < n: x = w^e, z = zf (L_e); e >= n: x = g w^(e - n), z = zf2 (M_{e-n}).  pref is a work array.
 __global__ __launch_bounds__(THREADS) void setup_lagrange_kernel(Fr* __restrict__ lag, Fr* __restrict__ pref, uint32_t log_n, Pows wp, Fr g,
@@ -153,22 +142,22 @@ struct KeyConsts {
 // three trapdoor values at the end of each)
 __global__ __launch_bounds__(THREADS) void setup_scalars_kernel(const Fr* __restrict__ uvw, const Fr* __restrict__ lag, uint32_t n_wires,
                                                                 uint32_t n_pub, uint32_t n, KeyConsts k, Fr* __restrict__ s1, Fr* __restrict__ s2) {
-    const size_t off_b1 = n_wires, off_c = 2 * (size_t)n_wires, off_h = off_c + (n_wires - n_pub - 1), off_ic = off_h + n;
+    const KeyLayout at{n_wires, n_pub, n};
     const uint32_t total = n_wires > n ? n_wires : n;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
         if (i < n_wires) {
             const Fr u = uvw[i], v = uvw[(size_t)n_wires + i], w = uvw[2 * (size_t)n_wires + i];
             const Fr vc = cwc::fr_from_mont(v);
             s1[i] = cwc::fr_from_mont(u);
-            s1[off_b1 + i] = vc;
+            s1[at.b1() + i] = vc;
             s2[i] = vc;
             const Fr t = cwc::fr_add(cwc::fr_add(cwc::fr_mul(k.beta_m, u), cwc::fr_mul(k.alpha_m, v)), w);
             if (i <= n_pub)
-                s1[off_ic + i] = cwc::fr_from_mont(cwc::fr_mul(t, k.gamma_inv_m));
+                s1[at.ic() + i] = cwc::fr_from_mont(cwc::fr_mul(t, k.gamma_inv_m));
             else
-                s1[off_c + (i - n_pub - 1)] = cwc::fr_from_mont(cwc::fr_mul(t, k.delta_inv_m));
+                s1[at.c() + (i - n_pub - 1)] = cwc::fr_from_mont(cwc::fr_mul(t, k.delta_inv_m));
         }
-        if (i < n) s1[off_h + i] = cwc::fr_from_mont(cwc::fr_mul(lag[(size_t)n + i], k.delta_inv_m));
+        if (i < n) s1[at.h() + i] = cwc::fr_from_mont(cwc::fr_mul(lag[(size_t)n + i], k.delta_inv_m));
     }
 }
 
@@ -220,23 +209,6 @@ __global__ __launch_bounds__(THREADS) void gen_mul_kernel(const Fr* __restrict__
     out[t] = acc;
 }
 
-template <class T>
-__device__ __forceinline__ void put_coords(uint8_t* out, const typename T::E& x, const typename T::E& y, bool canonical);
-template <>
-__device__ __forceinline__ void put_coords<G1>(uint8_t* out, const Fq& x, const Fq& y, bool canonical) {
-    Fq* o = reinterpret_cast<Fq*>(out);
-    o[0] = canonical ? fq_from_mont(x) : x;
-    o[1] = canonical ? fq_from_mont(y) : y;
-}
-template <>
-__device__ __forceinline__ void put_coords<G2>(uint8_t* out, const Fq2& x, const Fq2& y, bool canonical) {
-    Fq* o = reinterpret_cast<Fq*>(out);
-    o[0] = canonical ? fq_from_mont(x.c0) : x.c0;
-    o[1] = canonical ? fq_from_mont(x.c1) : x.c1;
-    o[2] = canonical ? fq_from_mont(y.c0) : y.c0;
-    o[3] = canonical ? fq_from_mont(y.c1) : y.c1;
-}
-
 // pts -> affine coordinates (x, y; Montgomery bytes as the zkey stores them, or canonical), infinity = zero bytes
 template <class T>
 __global__ __launch_bounds__(THREADS) void affine_kernel(const Xyzz<T>* __restrict__ pts, uint32_t n, uint8_t* __restrict__ out, uint32_t canonical) {
@@ -267,17 +239,6 @@ __global__ __launch_bounds__(THREADS) void affine_kernel(const Xyzz<T>* __restri
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
 
-uint32_t blocks_for(uint64_t threads) { return (uint32_t)std::max<uint64_t>(1, (threads + THREADS - 1) / THREADS); }
-
-Affine<G1> g1_generator() { return Affine<G1>{fq_one(), fq_add(fq_one(), fq_one())}; }  // (1, 2)
-Affine<G2> g2_generator() {
-    const Fq c[4] = {{{0xd992f6edu, 0x46debd5cu, 0xf75edaddu, 0x674322d4u, 0x5e5c4479u, 0x426a0066u, 0x121f1e76u, 0x1800deefu}},
-                     {{0xaef312c2u, 0x97e485b7u, 0x35a9e712u, 0xf1aa4933u, 0x31fb5d25u, 0x7260bfb7u, 0x920d483au, 0x198e9393u}},
-                     {{0x66fa7daau, 0x4ce6cc01u, 0x0c43d37bu, 0xe3d1e769u, 0x8dcb408fu, 0x4aab7180u, 0xdb8c6debu, 0x12c85ea5u}},
-                     {{0xd122975bu, 0x55acdadcu, 0x70b38ef3u, 0xbc4b3133u, 0x690c3395u, 0xec9e99adu, 0x585ff075u, 0x090689d0u}}};
-    return Affine<G2>{Fq2{fq_to_mont(c[0]), fq_to_mont(c[1])}, Fq2{fq_to_mont(c[2]), fq_to_mont(c[3])}};
-}
-
 // The tables of one device: built at the first use in the process and kept until it ends.
 struct Tables {
     void *g1 = nullptr, *g2 = nullptr;
@@ -293,7 +254,7 @@ hipError_t build_table(const Affine<T>& gen, void** out, hipStream_t s) {
     if (e == hipSuccess) e = hipMalloc(&table, TABLE_POINTS * sizeof(Affine<T>));
     if (e == hipSuccess) {
         hipLaunchKernelGGL(table_bases_kernel<T>, dim3(1), dim3(64), 0, s, gen, (Affine<T>*)bases);
-        hipLaunchKernelGGL(table_fill_kernel<T>, dim3(blocks_for(TABLE_POINTS)), dim3(THREADS), 0, s, (const Affine<T>*)bases, (Affine<T>*)table);
+        hipLaunchKernelGGL(table_fill_kernel<T>, dim3(blocks_for(TABLE_POINTS, THREADS)), dim3(THREADS), 0, s, (const Affine<T>*)bases, (Affine<T>*)table);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }
@@ -332,7 +293,7 @@ bool ensure_tables(Tables& t, std::string& err) {
 
 template <class T>
 void enqueue_affine(const void* d_xyzz, uint32_t n, uint8_t* d_out, bool canonical, hipStream_t s) {
-    hipLaunchKernelGGL(affine_kernel<T>, dim3(blocks_for(((uint64_t)n + INV_CHUNK - 1) / INV_CHUNK)), dim3(THREADS), 0, s, (const Xyzz<T>*)d_xyzz, n,
+    hipLaunchKernelGGL(affine_kernel<T>, dim3(blocks_for(((uint64_t)n + INV_CHUNK - 1) / INV_CHUNK, THREADS)), dim3(THREADS), 0, s, (const Xyzz<T>*)d_xyzz, n,
                        d_out, canonical ? 1u : 0u);
 }
 
@@ -347,7 +308,7 @@ uint32_t segment_terms() {  // CWC_GROTH16_SETUP_SEGMENT: terms per segment of a
     return v == 0 || v > 0xffffffffull ? 0xffffffffu : (uint32_t)v;
 }
 
-// The by-wire transpose of the handle's matrices (Columns: ptau_internal.hpp)
+// The by-wire transpose of the handle's matrices (Columns: setup_internal.hpp)
 void transpose(const gwb_r1cs* r, uint32_t segment, Columns& c) {
     const uint32_t nw = r->info.n_wires, nc = r->info.n_constraints;
     const size_t n_terms = r->sys.fac.size();
@@ -383,11 +344,29 @@ void transpose(const gwb_r1cs* r, uint32_t segment, Columns& c) {
     c.seg_off.push_back((uint32_t)n_terms);
 }
 
-void generator_bytes(uint8_t* g1, uint8_t* g2) {
-    const Affine<G1> a = g1_generator();
-    const Affine<G2> b = g2_generator();
-    memcpy(g1, &a, G1_BYTES);
-    memcpy(g2, &b, G2_BYTES);
+size_t columns_bytes(const Columns& c, size_t n_coef) {
+    Carve cw;
+    for (size_t bytes : {c.ent.size() * 4, c.cidx.size() * 4, n_coef * 32, c.seg_off.size() * 4, c.seg_key.size() * 4, c.wire_seg.size() * 4}) cw.take(bytes);
+    return cw.o;
+}
+
+// the arrays in columns_bytes' order
+DeviceColumns upload_columns(const Columns& c, const std::vector<Fr>& coef, uint8_t* at, hipStream_t s, hipError_t& e) {
+    Carve cw;
+    auto up = [&](const void* src, size_t bytes) {
+        uint8_t* dst = at + cw.take(bytes);
+        if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
+        return dst;
+    };
+    DeviceColumns d;
+    d.ent = (const uint32_t*)up(c.ent.data(), c.ent.size() * 4);
+    d.cidx = (const uint32_t*)up(c.cidx.data(), c.cidx.size() * 4);
+    d.coef = (const Fr*)up(coef.data(), coef.size() * 32);
+    d.seg_off = (const uint32_t*)up(c.seg_off.data(), c.seg_off.size() * 4);
+    d.seg_key = (const uint32_t*)up(c.seg_key.data(), c.seg_key.size() * 4);
+    d.wire_seg = (const uint32_t*)up(c.wire_seg.data(), c.wire_seg.size() * 4);
+    d.n_seg = (uint32_t)c.seg_key.size();
+    return d;
 }
 
 void enqueue_affine_g1(const void* d_xyzz, uint32_t n, uint8_t* d_out, bool canonical, void* stream) {
@@ -469,37 +448,7 @@ void derive(Secrets& s, uint32_t p) {
     s.k.delta_inv_m = cwc::fr_inv_fermat(cwc::fr_to_mont(s.delta));
 }
 
-// The device side of one call.  `secret` holds everything derived from the trapdoor and is zeroed before it is released.
-struct Device {
-    hipStream_t s = nullptr;
-    void *secret = nullptr, *work = nullptr;
-    size_t secret_bytes = 0;
-    hipEvent_t ev[6] = {};
-    ~Device() {
-        if (secret) {
-            (void)hipMemsetAsync(secret, 0, secret_bytes, s);
-            (void)hipStreamSynchronize(s);
-            (void)hipFree(secret);
-        }
-        if (work) (void)hipFree(work);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (s) (void)hipStreamDestroy(s);
-    }
-};
-
-struct Carve {
-    size_t o = 0;
-    size_t take(size_t bytes) {
-        const size_t at = o;
-        o += (bytes + 255) & ~(size_t)255;
-        return at;
-    }
-};
-
-std::mutex g_phase_mutex;
-float g_phase_ms[5];
-bool g_phase_valid = false;
+PhaseTimes<5> g_phases;
 
 void put32(std::vector<uint8_t>& v, uint32_t x) { v.insert(v.end(), (const uint8_t*)&x, (const uint8_t*)&x + 4); }
 void put64(std::vector<uint8_t>& v, uint64_t x) { v.insert(v.end(), (const uint8_t*)&x, (const uint8_t*)&x + 8); }
@@ -605,42 +554,27 @@ int setup(gwb_r1cs* r, const gwb_groth16_trapdoor_t* trapdoor, void** zkey, size
     Secrets sec;
     if (!take_trapdoor(trapdoor, p, sec, err)) return fail(status, err);
     derive(sec, p);
-    const uint64_t n1 = 3ull * nw - n_pub - 1 + (n_pub + 1) + n + 3, n2 = (uint64_t)nw + 3;
+    const KeyLayout at{nw, n_pub, n};
+    const uint64_t n1 = at.n1() + 3, n2 = (uint64_t)nw + 3;  // the header's scalars at the end of both lists
     if (n1 > 0x7fffffffull) return fail(status, "groth16 setup: more than 2^31 - 1 points");
     std::vector<uint8_t> sec4;
     if (!coefficients_section(r, sec4, err)) return fail(status, err);
     Columns col;
     transpose(r, segment_terms(), col);
     const uint32_t n_seg = (uint32_t)col.seg_key.size();
-    const size_t n_terms = col.ent.size();
 
     Tables tab;
     if (!ensure_tables(tab, err)) return fail(status, err);
-    Device D;
+    SetupDevice<6> D;
     Carve cs, cw;
     const size_t o_lag = cs.take(2ull * n * 32), o_pref = cs.take(2ull * n * 32), o_part = cs.take((size_t)n_seg * 32),
                  o_uvw = cs.take(3ull * nw * 32), o_s1 = cs.take(n1 * 32), o_s2 = cs.take(n2 * 32);
-    const size_t o_ent = cw.take(n_terms * 4), o_cidx = cw.take(n_terms * 4), o_coef = cw.take(r->sys.coef.size() * 32),
-                 o_soff = cw.take(((size_t)n_seg + 1) * 4), o_skey = cw.take((size_t)n_seg * 4), o_wseg = cw.take(((size_t)nw + 1) * 4),
-                 o_x1 = cw.take(n1 * sizeof(Xyzz<G1>)), o_x2 = cw.take(n2 * sizeof(Xyzz<G2>)), o_p1 = cw.take(n1 * G1_BYTES),
-                 o_p2 = cw.take(n2 * G2_BYTES);
-    D.secret_bytes = cs.o;
-    hipError_t e = hipStreamCreateWithFlags(&D.s, hipStreamNonBlocking);
-    for (hipEvent_t& ev : D.ev)
-        if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e == hipSuccess) e = hipMalloc(&D.secret, cs.o);
-    if (e == hipSuccess) e = hipMalloc(&D.work, std::max<size_t>(cw.o, 256));
+    const size_t o_col = cw.take(columns_bytes(col, r->sys.coef.size())), o_x1 = cw.take(n1 * sizeof(Xyzz<G1>)),
+                 o_x2 = cw.take(n2 * sizeof(Xyzz<G2>)), o_p1 = cw.take(n1 * G1_BYTES), o_p2 = cw.take(n2 * G2_BYTES);
+    hipError_t e = D.open(cs.o, std::max<size_t>(cw.o, 256));
     if (e != hipSuccess) return fail(status, hip_err("allocating the setup workspace", e));
     uint8_t *S = (uint8_t*)D.secret, *W = (uint8_t*)D.work;
-    auto up = [&](size_t off, const void* src, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpyAsync(W + off, src, bytes, hipMemcpyHostToDevice, D.s);
-    };
-    up(o_ent, col.ent.data(), n_terms * 4);
-    up(o_cidx, col.cidx.data(), n_terms * 4);
-    up(o_coef, r->sys.coef.data(), r->sys.coef.size() * 32);
-    up(o_soff, col.seg_off.data(), ((size_t)n_seg + 1) * 4);
-    up(o_skey, col.seg_key.data(), (size_t)n_seg * 4);
-    up(o_wseg, col.wire_seg.data(), ((size_t)nw + 1) * 4);
+    const DeviceColumns dc = upload_columns(col, r->sys.coef, W + o_col, D.s, e);
     // the header's scalars, at the end of the two scalar lists
     Fr *lag = (Fr*)(S + o_lag), *s1 = (Fr*)(S + o_s1), *s2 = (Fr*)(S + o_s2);
     Fr k1s[3] = {sec.alpha, sec.beta, sec.delta}, k2s[3] = {sec.beta, sec.gamma, sec.delta};
@@ -651,28 +585,25 @@ int setup(gwb_r1cs* r, const gwb_groth16_trapdoor_t* trapdoor, void** zkey, size
     explicit_bzero(k2s, sizeof k2s);
     if (e != hipSuccess) return fail(status, hip_err("uploading the transposed constraint matrices", e));
 
-    Pows wp;
-    Fr g;
-    qap_roots(p, wp.v[0], g);
-    for (uint32_t b = 1; b <= MAX_DOMAIN_POWER; ++b) wp.v[b] = cwc::fr_mul(wp.v[b - 1], wp.v[b - 1]);
+    Fr wn, g;
+    qap_roots(p, wn, g);
     (void)hipEventRecord(D.ev[0], D.s);
-    hipLaunchKernelGGL(setup_lagrange_kernel, dim3(blocks_for((2ull * n + INV_CHUNK - 1) / INV_CHUNK)), dim3(THREADS), 0, D.s, lag,
-                       (Fr*)(S + o_pref), p, wp, g, sec.tau_m, sec.zf, sec.zf2);
+    hipLaunchKernelGGL(setup_lagrange_kernel, dim3(blocks_for((2ull * n + INV_CHUNK - 1) / INV_CHUNK, THREADS)), dim3(THREADS), 0, D.s, lag,
+                       (Fr*)(S + o_pref), p, powers_of(wn), g, sec.tau_m, sec.zf, sec.zf2);
     (void)hipEventRecord(D.ev[1], D.s);
     if (n_seg)
-        hipLaunchKernelGGL(setup_segments_kernel, dim3(blocks_for(n_seg)), dim3(THREADS), 0, D.s, (const uint32_t*)(W + o_ent),
-                           (const uint32_t*)(W + o_cidx), (const Fr*)(W + o_coef), (const Fr*)lag, (const uint32_t*)(W + o_soff), n_seg,
-                           (Fr*)(S + o_part));
-    hipLaunchKernelGGL(setup_wires_kernel, dim3(blocks_for(nw)), dim3(THREADS), 0, D.s, (const Fr*)(S + o_part), (const uint32_t*)(W + o_skey),
-                       (const uint32_t*)(W + o_wseg), (const Fr*)lag, nw, nc, n_pub, (Fr*)(S + o_uvw));
+        hipLaunchKernelGGL(setup_segments_kernel, dim3(blocks_for(n_seg, THREADS)), dim3(THREADS), 0, D.s, dc.ent, dc.cidx, dc.coef, (const Fr*)lag, dc.seg_off,
+                           n_seg, (Fr*)(S + o_part));
+    hipLaunchKernelGGL(setup_wires_kernel, dim3(blocks_for(nw, THREADS)), dim3(THREADS), 0, D.s, (const Fr*)(S + o_part), dc.seg_key, dc.wire_seg,
+                       (const Fr*)lag, nw, nc, n_pub, (Fr*)(S + o_uvw));
     (void)hipEventRecord(D.ev[2], D.s);
-    hipLaunchKernelGGL(setup_scalars_kernel, dim3(std::min<uint32_t>(blocks_for(std::max(nw, n)), 4096)), dim3(THREADS), 0, D.s,
+    hipLaunchKernelGGL(setup_scalars_kernel, dim3(std::min<uint32_t>(blocks_for(std::max(nw, n), THREADS), 4096)), dim3(THREADS), 0, D.s,
                        (const Fr*)(S + o_uvw), (const Fr*)lag, nw, n_pub, n, sec.k, s1, s2);
     (void)hipEventRecord(D.ev[3], D.s);
-    hipLaunchKernelGGL(gen_mul_kernel<G1>, dim3(blocks_for(n1)), dim3(THREADS), 0, D.s, (const Fr*)s1, (uint32_t)n1, (const Affine<G1>*)tab.g1,
+    hipLaunchKernelGGL(gen_mul_kernel<G1>, dim3(blocks_for(n1, THREADS)), dim3(THREADS), 0, D.s, (const Fr*)s1, (uint32_t)n1, (const Affine<G1>*)tab.g1,
                        (Xyzz<G1>*)(W + o_x1));
     (void)hipEventRecord(D.ev[4], D.s);
-    hipLaunchKernelGGL(gen_mul_kernel<G2>, dim3(blocks_for(n2)), dim3(THREADS), 0, D.s, (const Fr*)s2, (uint32_t)n2, (const Affine<G2>*)tab.g2,
+    hipLaunchKernelGGL(gen_mul_kernel<G2>, dim3(blocks_for(n2, THREADS)), dim3(THREADS), 0, D.s, (const Fr*)s2, (uint32_t)n2, (const Affine<G2>*)tab.g2,
                        (Xyzz<G2>*)(W + o_x2));
     enqueue_affine<G1>(W + o_x1, (uint32_t)n1, W + o_p1, false, D.s);
     enqueue_affine<G2>(W + o_x2, (uint32_t)n2, W + o_p2, false, D.s);
@@ -685,17 +616,10 @@ int setup(gwb_r1cs* r, const gwb_groth16_trapdoor_t* trapdoor, void** zkey, size
     if (e == hipSuccess) e = hipMemsetAsync(D.secret, 0, D.secret_bytes, D.s);
     if (e == hipSuccess) e = hipStreamSynchronize(D.s);
     if (e != hipSuccess) return fail(status, hip_err("running the setup", e));
-    {
-        float ms[5];
-        bool ok = true;
-        for (int i = 0; i < 5; ++i) ok = ok && hipEventElapsedTime(ms + i, D.ev[i], D.ev[i + 1]) == hipSuccess;
-        std::lock_guard<std::mutex> lock(g_phase_mutex);
-        if (ok) memcpy(g_phase_ms, ms, sizeof ms);
-        g_phase_valid = ok;
-    }
+    g_phases.record(D.ev);
 
-    const uint8_t *a = p1.data(), *b1 = a + (size_t)nw * G1_BYTES, *c = b1 + (size_t)nw * G1_BYTES,
-                  *h = c + (size_t)(nw - n_pub - 1) * G1_BYTES, *ic = h + (size_t)n * G1_BYTES, *k1 = ic + (size_t)(n_pub + 1) * G1_BYTES;
+    const uint8_t *a = p1.data(), *b1 = a + at.b1() * G1_BYTES, *c = a + at.c() * G1_BYTES, *h = a + at.h() * G1_BYTES,
+                  *ic = a + at.ic() * G1_BYTES, *k1 = a + at.n1() * G1_BYTES;
     const uint8_t *b2 = p2.data(), *k2 = b2 + (size_t)nw * G2_BYTES;
     const KeyPoints kp{nw, n_pub, n, k1, k1 + G1_BYTES, k2, k2 + G2_BYTES, k1 + 2 * G1_BYTES, k2 + 2 * G2_BYTES, ic, a, b1, b2, c, h};
     return write_zkey(kp, sec4, zkey, zkey_len, status);
@@ -734,11 +658,11 @@ int gwb_bn254_gen_mul_batch_device(const void* d_scalars, size_t n, uint32_t gro
     hipError_t e = hipMallocAsync(&ws, n * (group == 1 ? sizeof(Xyzz<G1>) : sizeof(Xyzz<G2>)), s);
     if (e != hipSuccess) return fail(status, hip_err("allocating the multiplication workspace", e));
     if (group == 1) {
-        hipLaunchKernelGGL(gen_mul_kernel<G1>, dim3(blocks_for(n)), dim3(THREADS), 0, s, (const Fr*)d_scalars, (uint32_t)n,
+        hipLaunchKernelGGL(gen_mul_kernel<G1>, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, (const Fr*)d_scalars, (uint32_t)n,
                            (const Affine<G1>*)tab.g1, (Xyzz<G1>*)ws);
         enqueue_affine<G1>(ws, (uint32_t)n, (uint8_t*)d_points, true, s);
     } else {
-        hipLaunchKernelGGL(gen_mul_kernel<G2>, dim3(blocks_for(n)), dim3(THREADS), 0, s, (const Fr*)d_scalars, (uint32_t)n,
+        hipLaunchKernelGGL(gen_mul_kernel<G2>, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, (const Fr*)d_scalars, (uint32_t)n,
                            (const Affine<G2>*)tab.g2, (Xyzz<G2>*)ws);
         enqueue_affine<G2>(ws, (uint32_t)n, (uint8_t*)d_points, true, s);
     }
@@ -750,12 +674,6 @@ int gwb_bn254_gen_mul_batch_device(const void* d_scalars, size_t n, uint32_t gro
     return 0;
 }
 
-int gwb_groth16_setup_phase_ms(float* ms) {
-    if (!ms) return 1;
-    std::lock_guard<std::mutex> lock(g_phase_mutex);
-    if (!g_phase_valid) return 1;
-    memcpy(ms, g_phase_ms, sizeof g_phase_ms);
-    return 0;
-}
+int gwb_groth16_setup_phase_ms(float* ms) { return g_phases.read(ms); }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // Groth16 setup from a powers-of-tau file on gfx950 (include/graph_witness_groth16_ptau.h has the definition): no trapdoor, so no
 // scalars to multiply generators by; every key point is a linear combination of the ceremony's points.  The host side that
 // does not depend on where the points come from (column transpose and segments, section 4, conversion to affine, the zkey
-// image) is setup.hip's (ptau_internal.hpp); the `.ptau` itself is read by ptau.cc.
+// image) is setup.hip's (setup_internal.hpp); the `.ptau` itself is read by ptau.cc (ptau_internal.hpp).
 //
 // Loading.  The prefixes that are read are uploaded as stored; one thread per point checks the coordinate ranges and the curve
 // equation and writes the point in XYZZ form (ZZ = ZZZ = 1, or 0 for infinity).  The first fault of an array goes to a flag
@@ -10,7 +10,7 @@
 // Group inverse DFT.  Radix 2, decimation in time, in place on XYZZ points in global memory: the load writes point i to slot
 // bitrev(i); stage s (half = 2^s) takes, for k < half and every group of 2 half slots, a = x[j], c = w_N^(-k N / (2 half))
 // x[j + half] and writes a + c, a - c; the output is in natural order.  A twiddle is a 254-bit scalar, so a butterfly is one
-// variable-base multiplication (xyzz_mul_short: double and add from the scalar's top word) and two additions; k = 0 has no
+// variable-base multiplication (fq_gfx950.hpp's xyzz_mul_short: double and add from the scalar's top word) and two additions; k = 0 has no
 // multiplication (all of stage 0, and one butterfly per group after it).  The twiddles w_N^(-k), k < N / 2, are computed once
 // per call into a table of canonical values.  While a stage has 64 or more groups, a wave's lanes take the same k in 64
 // groups: the scalar is the same in every lane, so the wave skips the additions of the scalar's zero bits together instead
@@ -33,7 +33,7 @@
 // that is zeroed before it is released.
 //
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage for gfx950; every kernel: 0 bytes of scratch; VGPRs + AGPRs, waves / SIMD):
-//   load_kernel<G1> 69, 7           load_kernel<G2> 121, 4            twiddle_kernel 36, 8        put_fr_kernel 10, 8
+//   load_kernel<G1> 53, 8           load_kernel<G2> 110, 4            twiddle_kernel 36, 8        put_fr_kernel 10, 8
 //   idft_stage_kernel<G1> 188, 2    idft_stage_kernel<G2> 256 + 170, 1     odd_half_kernel<G1> 152, 3
 //   scale_kernel<G1> 114, 4         scale_kernel<G2> 256 + 1, 1
 //   segments_kernel<G1> 186, 2      segments_kernel<G2> 256 + 151, 1
@@ -45,19 +45,15 @@
 #include <string.h>
 
 #include <algorithm>
-#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/graph_witness_groth16_ptau.h"
-#include "fq_gfx950.hpp"
+#include "bn254_points_gfx950.hpp"
 #include "groth16_internal.hpp"
 #include "ptau_internal.hpp"
-
-namespace cwc_r1cs {
-std::string hip_err(const char* what, hipError_t e);  // check.hip
-}
+#include "setup_internal.hpp"
 
 using namespace cwc_r1cs;
 using namespace cwc_g16;
@@ -66,76 +62,26 @@ using cwc::Fr;
 
 namespace {
 
-using G1 = FqT;
-using G2 = Fq2T;
-
 constexpr uint32_t THREADS = 256;
-constexpr uint32_t MAX_LOG_N = 27;
+constexpr uint32_t MAX_LOG_N = MAX_DOMAIN_POWER;
 constexpr unsigned long long NO_FAULT = ~0ull;
-
-struct Pows {
-    Fr v[MAX_LOG_N + 1];  // base^(2^b), Montgomery form
-};
-
-// k p for a canonical k: double and add from the top nonzero word of k (inside it the doublings of infinity return at once)
-template <class T>
-__device__ __forceinline__ Xyzz<T> xyzz_mul_short(const Xyzz<T>& p, const Fr& k) {
-    Xyzz<T> acc = xyzz_inf<T>();
-    Fr kk = k;  // words move up into kk.v[7] (constant indices: no stack copy of k)
-    for (int w = 0; w < 8; ++w) {
-        const uint32_t word = kk.v[7];
-        if (word != 0 || !xyzz_is_inf(acc)) {
-            for (int b = 31; b >= 0; --b) {
-                acc = xyzz_dbl(acc);
-                if ((word >> b) & 1u) acc = xyzz_add(acc, p);
-            }
-        }
-#pragma unroll
-        for (int i = 7; i > 0; --i) kk.v[i] = kk.v[i - 1];
-    }
-    return acc;
-}
-
-template <class T>
-__device__ __forceinline__ bool get_coords(const uint8_t* in, typename T::E& x, typename T::E& y, bool canonical);
-template <>
-__device__ __forceinline__ bool get_coords<G1>(const uint8_t* in, Fq& x, Fq& y, bool canonical) {
-    const Fq* c = reinterpret_cast<const Fq*>(in);
-    const Fq a = c[0], b = c[1];
-    const bool ok = cwc::both(cwc::u256_lt(a, fq_p()), cwc::u256_lt(b, fq_p()));
-    x = canonical ? fq_to_mont(a) : a;
-    y = canonical ? fq_to_mont(b) : b;
-    return ok;
-}
-template <>
-__device__ __forceinline__ bool get_coords<G2>(const uint8_t* in, Fq2& x, Fq2& y, bool canonical) {
-    const Fq* c = reinterpret_cast<const Fq*>(in);
-    const Fq a = c[0], b = c[1], d = c[2], e = c[3];
-    const bool ok = cwc::both(cwc::both(cwc::u256_lt(a, fq_p()), cwc::u256_lt(b, fq_p())), cwc::both(cwc::u256_lt(d, fq_p()), cwc::u256_lt(e, fq_p())));
-    x = Fq2{canonical ? fq_to_mont(a) : a, canonical ? fq_to_mont(b) : b};
-    y = Fq2{canonical ? fq_to_mont(d) : d, canonical ? fq_to_mont(e) : e};
-    return ok;
-}
 
 // out[slot(i)] = the affine point in[first + i stride] in XYZZ form, slot(i) = i or, for rev_bits != 0, i's rev_bits bits
 // reversed.  flag != nullptr: the point is checked, and the smallest 2 i + fault of the array is left in *flag.
 template <class T>
 __global__ __launch_bounds__(THREADS) void load_kernel(const uint8_t* __restrict__ in, uint32_t n, uint32_t first, uint32_t stride, uint32_t canonical,
-                                                       uint32_t rev_bits, typename T::E curve_b, Xyzz<T>* __restrict__ out,
-                                                       unsigned long long* __restrict__ flag) {
-    using E = typename T::E;
+                                                       uint32_t rev_bits, Xyzz<T>* __restrict__ out, unsigned long long* __restrict__ flag) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    E x, y;
-    const bool in_range = get_coords<T>(in + ((size_t)first + (size_t)i * stride) * (2 * sizeof(E)), x, y, canonical != 0);
-    Xyzz<T> p = xyzz_inf<T>();
-    if (!cwc::both(T::is_zero(x), T::is_zero(y))) p = Xyzz<T>{x, y, T::one(), T::one()};
+    Affine<T> a;
+    const bool in_range = get_coords<T>(in + ((size_t)first + (size_t)i * stride) * sizeof a, canonical != 0, a.x, a.y);
+    Xyzz<T> p = from_affine(a);
     if (flag) {
         if (!in_range) {
-            atomicMin(flag, 2ull * i + cwc_ptau::COORDINATE);
+            atomicMin(flag, 2ull * i + (uint32_t)PointFault::COORDINATE);
             p = xyzz_inf<T>();
-        } else if (!xyzz_is_inf(p) && !on_curve(Affine<T>{x, y}, curve_b)) {
-            atomicMin(flag, 2ull * i + cwc_ptau::CURVE);
+        } else if (!xyzz_is_inf(p) && !on_curve(a, curve_b<T>())) {
+            atomicMin(flag, 2ull * i + (uint32_t)PointFault::CURVE);
             p = xyzz_inf<T>();
         }
     }
@@ -260,10 +206,10 @@ __global__ __launch_bounds__(THREADS) void wires_g1_kernel(const Xyzz<G1>* __res
         a = xyzz_add(a, l1[n_constraints + i]);
         k = xyzz_add(k, lb[n_constraints + i]);
     }
-    const size_t off_c = 2 * (size_t)n_wires, off_ic = off_c + (n_wires - n_pub - 1) + n;
+    const KeyLayout at{n_wires, n_pub, n};
     list[i] = a;
-    list[(size_t)n_wires + i] = b;
-    list[i <= n_pub ? off_ic + i : off_c + (i - n_pub - 1)] = k;
+    list[at.b1() + i] = b;
+    list[i <= n_pub ? at.ic() + i : at.c() + (i - n_pub - 1)] = k;
 }
 
 // out[i] = the sum of wire i's segments of matrix m
@@ -281,29 +227,6 @@ __global__ __launch_bounds__(THREADS) void wires_one_kernel(const Xyzz<T>* __res
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
 
-uint32_t blocks_for(uint64_t threads) { return (uint32_t)std::max<uint64_t>(1, (threads + THREADS - 1) / THREADS); }
-
-Fq g1_b() { return fq_to_mont(Fq{{3, 0, 0, 0, 0, 0, 0, 0}}); }
-Fq2 g2_b() {  // 3 / (9 + u), Montgomery form
-    const Fq2 t{fq_to_mont(Fq{{9, 0, 0, 0, 0, 0, 0, 0}}), fq_one()};
-    const Fq three = fq_to_mont(Fq{{3, 0, 0, 0, 0, 0, 0, 0}});
-    const Fq2 i = fq2_inv(t);
-    return Fq2{fq_mul(i.c0, three), fq_mul(i.c1, three)};
-}
-template <class T>
-typename T::E curve_b();
-template <>
-Fq curve_b<G1>() { return g1_b(); }
-template <>
-Fq2 curve_b<G2>() { return g2_b(); }
-
-Pows powers_of(Fr base) {  // Montgomery form
-    Pows p;
-    p.v[0] = base;
-    for (uint32_t b = 1; b <= MAX_LOG_N; ++b) p.v[b] = cwc::fr_mul(p.v[b - 1], p.v[b - 1]);
-    return p;
-}
-
 Fr inverse_of_u32(uint32_t x) {  // canonical 1 / x mod r
     return cwc::fr_from_mont(cwc::fr_inv_fermat(cwc::fr_to_mont(Fr{{x, 0, 0, 0, 0, 0, 0, 0}})));
 }
@@ -313,14 +236,13 @@ void enqueue_twiddles(Fr* tw, uint32_t log_n, hipStream_t s) {
     Fr wn, g;
     qap_roots(log_n, wn, g);
     const uint32_t count = 1u << (log_n - 1);
-    hipLaunchKernelGGL(twiddle_kernel, dim3(blocks_for(count)), dim3(THREADS), 0, s, tw, count, powers_of(cwc::fr_inv_fermat(wn)));
+    hipLaunchKernelGGL(twiddle_kernel, dim3(blocks_for(count, THREADS)), dim3(THREADS), 0, s, tw, count, powers_of(cwc::fr_inv_fermat(wn)));
 }
 
 template <class T>
 void enqueue_load(const uint8_t* d_in, uint32_t n, uint32_t first, uint32_t stride, bool canonical, uint32_t rev_bits, Xyzz<T>* out,
                   unsigned long long* flag, hipStream_t s) {
-    hipLaunchKernelGGL(load_kernel<T>, dim3(blocks_for(n)), dim3(THREADS), 0, s, d_in, n, first, stride, canonical ? 1u : 0u, rev_bits, curve_b<T>(), out,
-                       flag);
+    hipLaunchKernelGGL(load_kernel<T>, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, d_in, n, first, stride, canonical ? 1u : 0u, rev_bits, out, flag);
 }
 
 // the stages of `batch` transforms in x (inputs in bit-reversed slots), without the factor 1 / N
@@ -328,41 +250,13 @@ template <class T>
 void enqueue_stages(Xyzz<T>* x, uint32_t log_n, uint32_t batch, const Fr* tw, hipStream_t s) {
     const uint64_t threads = (uint64_t)batch << (log_n - 1);
     for (uint32_t st = 0; st < log_n; ++st)
-        hipLaunchKernelGGL(idft_stage_kernel<T>, dim3(blocks_for(threads)), dim3(THREADS), 0, s, x, log_n, st, batch, tw);
+        hipLaunchKernelGGL(idft_stage_kernel<T>, dim3(blocks_for(threads, THREADS)), dim3(THREADS), 0, s, x, log_n, st, batch, tw);
 }
 
 template <class T>
 void enqueue_scale(Xyzz<T>* x, uint32_t count, const Fr* d_k, hipStream_t s) {
-    if (count) hipLaunchKernelGGL(scale_kernel<T>, dim3(blocks_for(count)), dim3(THREADS), 0, s, x, count, d_k);
+    if (count) hipLaunchKernelGGL(scale_kernel<T>, dim3(blocks_for(count, THREADS)), dim3(THREADS), 0, s, x, count, d_k);
 }
-
-struct Carve {
-    size_t o = 0;
-    size_t take(size_t bytes) {
-        const size_t at = o;
-        o += (bytes + 255) & ~(size_t)255;
-        return at;
-    }
-};
-
-// The device side of one call.  `secret` holds delta and 1 / delta and is zeroed before it is released.
-struct Device {
-    hipStream_t s = nullptr;
-    void *secret = nullptr, *work = nullptr;
-    size_t secret_bytes = 0;
-    hipEvent_t ev[8] = {};
-    ~Device() {
-        if (secret) {
-            (void)hipMemsetAsync(secret, 0, secret_bytes, s);
-            (void)hipStreamSynchronize(s);
-            (void)hipFree(secret);
-        }
-        if (work) (void)hipFree(work);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (s) (void)hipStreamDestroy(s);
-    }
-};
 
 struct Delta {
     Fr delta, delta_inv;  // canonical
@@ -385,9 +279,7 @@ bool take_delta(const uint8_t* given, Delta& d, std::string& err) {
     return true;
 }
 
-std::mutex g_phase_mutex;
-float g_phase_ms[7];
-bool g_phase_valid = false;
+PhaseTimes<7> g_phases;
 
 // an array of points that the device loads and checks: where its indices lie in the file, for the message
 struct Checked {
@@ -410,44 +302,33 @@ int setup(gwb_r1cs* r, const uint8_t* ptau, size_t ptau_len, const uint8_t* delt
     Delta dl;
     if (!take_delta(delta, dl, err)) return fail(status, err);
     const bool delta_is_one = cwc::u256_eq(dl.delta, Fr{{1, 0, 0, 0, 0, 0, 0, 0}});
-    const uint64_t n1 = 3ull * nw + n + 1, n2 = (uint64_t)nw + 1;  // [A][B1][C][H][IC][delta1], [B2][delta2]
+    const KeyLayout at{nw, n_pub, n};
+    const uint64_t n1 = at.n1() + 1, n2 = (uint64_t)nw + 1;  // [A][B1][C][H][IC][delta1], [B2][delta2]
     if (n1 > 0x7fffffffull) return fail(status, "groth16 setup: more than 2^31 - 1 points");
     std::vector<uint8_t> sec4;
     if (!coefficients_section(r, sec4, err)) return fail(status, err);
     Columns col;
     transpose(r, segment_terms(), col);
     const uint32_t n_seg = (uint32_t)col.seg_key.size();
-    const size_t n_terms = col.ent.size();
     const size_t X1 = sizeof(Xyzz<G1>), X2 = sizeof(Xyzz<G2>);
-    const size_t off_c = 2 * (size_t)nw, off_h = off_c + (nw - n_pub - 1);
+    const size_t off_c = at.c(), off_h = at.h();
 
-    Device D;
+    SetupDevice<8> D;
     Carve cw;
-    const size_t o_ent = cw.take(n_terms * 4), o_cidx = cw.take(n_terms * 4), o_coef = cw.take(r->sys.coef.size() * 32),
-                 o_soff = cw.take(((size_t)n_seg + 1) * 4), o_skey = cw.take((size_t)n_seg * 4), o_wseg = cw.take(((size_t)nw + 1) * 4),
+    const size_t o_col = cw.take(columns_bytes(col, r->sys.coef.size())),
                  o_raw1 = cw.take(5ull * n * G1_BYTES),  // compute: T1 (2n), AT, BT; file: L1, LA, LB, M (2n)
                  o_raw2 = cw.take((size_t)n * G2_BYTES), o_lag1 = cw.take(4ull * n * X1),  // L1, LA, LB and (compute) D
                  o_t1 = cw.take(pl.from_file ? 0 : 2ull * n * X1), o_lag2 = cw.take((size_t)n * X2), o_tw = cw.take((size_t)n / 2 * 32),
                  o_twg = cw.take((size_t)n * 32), o_pa = cw.take((size_t)n_seg * X1), o_pk = cw.take((size_t)n_seg * X1),
                  o_pq = cw.take((size_t)n_seg * X2), o_x1 = cw.take(n1 * X1), o_x2 = cw.take(n2 * X2), o_p1 = cw.take(n1 * G1_BYTES),
                  o_p2 = cw.take(n2 * G2_BYTES), o_flag = cw.take(8 * sizeof(unsigned long long)), o_pub = cw.take(2 * 32);
-    D.secret_bytes = 256;
-    hipError_t e = hipStreamCreateWithFlags(&D.s, hipStreamNonBlocking);
-    for (hipEvent_t& ev : D.ev)
-        if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e == hipSuccess) e = hipMalloc(&D.secret, D.secret_bytes);
-    if (e == hipSuccess) e = hipMalloc(&D.work, cw.o);
+    hipError_t e = D.open(256, cw.o);
     if (e != hipSuccess) return fail(status, hip_err("allocating the setup workspace", e));
     uint8_t* W = (uint8_t*)D.work;
     auto up = [&](size_t off, const void* src, size_t bytes) {
         if (e == hipSuccess && bytes) e = hipMemcpyAsync(W + off, src, bytes, hipMemcpyHostToDevice, D.s);
     };
-    up(o_ent, col.ent.data(), n_terms * 4);
-    up(o_cidx, col.cidx.data(), n_terms * 4);
-    up(o_coef, r->sys.coef.data(), r->sys.coef.size() * 32);
-    up(o_soff, col.seg_off.data(), ((size_t)n_seg + 1) * 4);
-    up(o_skey, col.seg_key.data(), (size_t)n_seg * 4);
-    up(o_wseg, col.wire_seg.data(), ((size_t)nw + 1) * 4);
+    const DeviceColumns dc = upload_columns(col, r->sys.coef, W + o_col, D.s, e);
     const size_t nb1 = (size_t)n * G1_BYTES;
     if (pl.from_file) {
         up(o_raw1, pl.l1, nb1);
@@ -462,12 +343,10 @@ int setup(gwb_r1cs* r, const uint8_t* ptau, size_t ptau_len, const uint8_t* delt
         up(o_raw2, pl.t2, (size_t)n * G2_BYTES);
     }
     // the generators, which delta1 and delta2 are multiples of, at the end of the two lists
-    Xyzz<G1> gen1{fq_zero(), fq_zero(), fq_one(), fq_one()};
-    Xyzz<G2> gen2{Fq2T::zero(), Fq2T::zero(), Fq2T::one(), Fq2T::one()};
-    uint8_t gb1[G1_BYTES], gb2[G2_BYTES];
-    generator_bytes(gb1, gb2);
-    memcpy(&gen1, gb1, G1_BYTES);
-    memcpy(&gen2, gb2, G2_BYTES);
+    const Xyzz<G1> gen1 = from_affine(g1_generator());
+    const Xyzz<G2> gen2 = from_affine(g2_generator());
+    uint8_t gb2[G2_BYTES];  // gamma2 of a key without a trapdoor
+    put_coords<G2>(gb2, gen2.X, gen2.Y, false);
     up(o_x1 + (n1 - 1) * X1, &gen1, X1);
     up(o_x2 + (n2 - 1) * X2, &gen2, X2);
     const Fr pub[2] = {inverse_of_u32(n), inverse_of_u32(2 * n)};
@@ -506,8 +385,8 @@ int setup(gwb_r1cs* r, const uint8_t* ptau, size_t ptau_len, const uint8_t* delt
         Fr wn, g;
         qap_roots(p, wn, g);
         enqueue_twiddles(tw, p, D.s);
-        hipLaunchKernelGGL(twiddle_kernel, dim3(blocks_for(n)), dim3(THREADS), 0, D.s, twg, n, powers_of(cwc::fr_inv_fermat(g)));
-        hipLaunchKernelGGL(odd_half_kernel<G1>, dim3(blocks_for(n)), dim3(THREADS), 0, D.s, (const Xyzz<G1>*)t1, p, (const Fr*)twg, dd);
+        hipLaunchKernelGGL(twiddle_kernel, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, D.s, twg, n, powers_of(cwc::fr_inv_fermat(g)));
+        hipLaunchKernelGGL(odd_half_kernel<G1>, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, D.s, (const Xyzz<G1>*)t1, p, (const Fr*)twg, dd);
         enqueue_stages<G1>(lag1, p, 4, tw, D.s);
         enqueue_scale<G1>(lag1, 3 * n, d_inv_n, D.s);
         enqueue_scale<G1>(dd, n, d_inv_2n, D.s);
@@ -520,26 +399,23 @@ int setup(gwb_r1cs* r, const uint8_t* ptau, size_t ptau_len, const uint8_t* delt
         enqueue_scale<G2>(l2, n, d_inv_n, D.s);
     }
     (void)hipEventRecord(D.ev[3], D.s);
-    const uint32_t *d_ent = (const uint32_t*)(W + o_ent), *d_cidx = (const uint32_t*)(W + o_cidx), *d_soff = (const uint32_t*)(W + o_soff),
-                   *d_skey = (const uint32_t*)(W + o_skey), *d_wseg = (const uint32_t*)(W + o_wseg);
-    const Fr* d_coef = (const Fr*)(W + o_coef);
     Xyzz<G1>*pa = (Xyzz<G1>*)(W + o_pa), *pk = (Xyzz<G1>*)(W + o_pk);
     Xyzz<G2>* pq = (Xyzz<G2>*)(W + o_pq);
     const Xyzz<G1>* none1 = nullptr;
     const Xyzz<G2>* none2 = nullptr;
     if (n_seg) {
-        hipLaunchKernelGGL(segments_kernel<G1>, dim3(blocks_for(n_seg)), dim3(THREADS), 0, D.s, d_ent, d_cidx, d_coef, d_soff, d_skey, n_seg,
+        hipLaunchKernelGGL(segments_kernel<G1>, dim3(blocks_for(n_seg, THREADS)), dim3(THREADS), 0, D.s, dc.ent, dc.cidx, dc.coef, dc.seg_off, dc.seg_key, n_seg,
                            (const Xyzz<G1>*)l1, (const Xyzz<G1>*)l1, (const Xyzz<G1>*)l1, pa);
-        hipLaunchKernelGGL(segments_kernel<G1>, dim3(blocks_for(n_seg)), dim3(THREADS), 0, D.s, d_ent, d_cidx, d_coef, d_soff, d_skey, n_seg,
+        hipLaunchKernelGGL(segments_kernel<G1>, dim3(blocks_for(n_seg, THREADS)), dim3(THREADS), 0, D.s, dc.ent, dc.cidx, dc.coef, dc.seg_off, dc.seg_key, n_seg,
                            (const Xyzz<G1>*)lb, (const Xyzz<G1>*)la, none1, pk);
     }
-    hipLaunchKernelGGL(wires_g1_kernel, dim3(blocks_for(nw)), dim3(THREADS), 0, D.s, (const Xyzz<G1>*)pa, (const Xyzz<G1>*)pk, d_skey, d_wseg,
+    hipLaunchKernelGGL(wires_g1_kernel, dim3(blocks_for(nw, THREADS)), dim3(THREADS), 0, D.s, (const Xyzz<G1>*)pa, (const Xyzz<G1>*)pk, dc.seg_key, dc.wire_seg,
                        (const Xyzz<G1>*)l1, (const Xyzz<G1>*)lb, nw, nc, n_pub, n, x1);
     (void)hipEventRecord(D.ev[4], D.s);
     if (n_seg)
-        hipLaunchKernelGGL(segments_kernel<G2>, dim3(blocks_for(n_seg)), dim3(THREADS), 0, D.s, d_ent, d_cidx, d_coef, d_soff, d_skey, n_seg, none2,
+        hipLaunchKernelGGL(segments_kernel<G2>, dim3(blocks_for(n_seg, THREADS)), dim3(THREADS), 0, D.s, dc.ent, dc.cidx, dc.coef, dc.seg_off, dc.seg_key, n_seg, none2,
                            (const Xyzz<G2>*)l2, none2, pq);
-    hipLaunchKernelGGL(wires_one_kernel<G2>, dim3(blocks_for(nw)), dim3(THREADS), 0, D.s, (const Xyzz<G2>*)pq, d_skey, d_wseg, nw, 1u, x2);
+    hipLaunchKernelGGL(wires_one_kernel<G2>, dim3(blocks_for(nw, THREADS)), dim3(THREADS), 0, D.s, (const Xyzz<G2>*)pq, dc.seg_key, dc.wire_seg, nw, 1u, x2);
     (void)hipEventRecord(D.ev[5], D.s);
     if (!delta_is_one) enqueue_scale<G1>(x1 + off_c, (nw - n_pub - 1) + n, d_delta_inv, D.s);  // C and H
     enqueue_scale<G1>(x1 + (n1 - 1), 1, d_delta, D.s);
@@ -561,19 +437,11 @@ int setup(gwb_r1cs* r, const uint8_t* ptau, size_t ptau_len, const uint8_t* delt
     for (size_t a = 0; a < checked.size(); ++a)
         if (faults[a] != NO_FAULT) {
             const Checked& c = checked[a];
-            return fail(status, cwc_ptau::point_message(c.section, c.base + c.first + (faults[a] >> 1) * c.stride, (uint32_t)(faults[a] & 1), c.g2));
+            return fail(status, cwc_ptau::point_message(c.section, c.base + c.first + (faults[a] >> 1) * c.stride, (PointFault)(faults[a] & 1), c.g2));
         }
-    {
-        float ms[7];
-        bool ok = true;
-        for (int i = 0; i < 7; ++i) ok = ok && hipEventElapsedTime(ms + i, D.ev[i], D.ev[i + 1]) == hipSuccess;
-        if (pl.from_file) ms[1] = ms[2] = 0.0f;  // nothing was enqueued between those events
-        std::lock_guard<std::mutex> lock(g_phase_mutex);
-        if (ok) memcpy(g_phase_ms, ms, sizeof ms);
-        g_phase_valid = ok;
-    }
-    const uint8_t *a = p1.data(), *b1 = a + (size_t)nw * G1_BYTES, *c = a + off_c * G1_BYTES, *h = a + off_h * G1_BYTES,
-                  *ic = h + (size_t)n * G1_BYTES, *delta1 = a + (n1 - 1) * G1_BYTES;
+    g_phases.record(D.ev, pl.from_file ? 6u : 0u);  // from a file, nothing lies between the events of the two transforms
+    const uint8_t *a = p1.data(), *b1 = a + at.b1() * G1_BYTES, *c = a + off_c * G1_BYTES, *h = a + off_h * G1_BYTES,
+                  *ic = a + at.ic() * G1_BYTES, *delta1 = a + at.n1() * G1_BYTES;
     const uint8_t *b2 = p2.data(), *delta2 = b2 + (size_t)nw * G2_BYTES;
     const KeyPoints kp{nw, n_pub, n, pl.at, pl.bt, pl.beta2, gb2, delta1, delta2, ic, a, b1, b2, c, h};
     return write_zkey(kp, sec4, zkey, zkey_len, status);
@@ -632,12 +500,6 @@ int gwb_bn254_point_idft_batch_device(const void* d_points, uint32_t log_n, uint
                       : idft_aid<G2>(d_points, log_n, d_out, (hipStream_t)hip_stream, status);
 }
 
-int gwb_groth16_setup_ptau_phase_ms(float* ms) {
-    if (!ms) return 1;
-    std::lock_guard<std::mutex> lock(g_phase_mutex);
-    if (!g_phase_valid) return 1;
-    memcpy(ms, g_phase_ms, sizeof g_phase_ms);
-    return 0;
-}
+int gwb_groth16_setup_ptau_phase_ms(float* ms) { return g_phases.read(ms); }
 
 }  // extern "C"

@@ -13,8 +13,8 @@
 // on a stream of their own, and free everything before they return.
 //
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage for gfx950; every kernel: 0 bytes of scratch, 0 bytes of LDS):
-//   g2_check_kernel<0>  50 SGPRs, 256 VGPRs + 125 AGPRs, 1 wave / SIMD
-//   g2_check_kernel<1>  50 SGPRs, 256 VGPRs + 33 AGPRs, 1 wave / SIMD
+//   g2_check_kernel<0>  106 SGPRs, 256 VGPRs + 125 AGPRs, 1 wave / SIMD
+//   g2_check_kernel<1>  103 SGPRs, 256 VGPRs + 33 AGPRs, 1 wave / SIMD
 //   first_bad_kernel    19 SGPRs, 4 VGPRs, 8 waves / SIMD
 // The chain keeps the running left side and psi^k([x] P) (Xyzz<Fq2T>: 64 registers each) across an inlined addition with its
 // own temporaries, which does not fit 256 registers: capped there (__launch_bounds__(64, 2)) the compiler spills 504 and 136
@@ -33,18 +33,13 @@
 #include "../../include/graph_witness_groth16_verify.h"
 #include "g2_subgroup_gfx950.hpp"
 #include "groth16_internal.hpp"
+#include "hip_util.hpp"
 #include "ptau_internal.hpp"
-
-namespace cwc_r1cs {
-std::string hip_err(const char* what, hipError_t e);  // check.hip
-}
 
 using namespace cwc_r1cs;
 using namespace cwc_g16;
 
 namespace {
-
-using A2 = Affine<Fq2T>;
 
 constexpr uint32_t THREADS = 64;
 constexpr uint32_t REDUCE_THREADS = 256;
@@ -56,15 +51,13 @@ __global__ __launch_bounds__(THREADS) void g2_check_kernel(const uint8_t* __rest
                                                            uint32_t* __restrict__ status) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const Fq* c = reinterpret_cast<const Fq*>(in + (size_t)i * G2_BYTES);
-    const Fq a = c[0], b = c[1], d = c[2], e = c[3];
-    const bool in_range = cwc::both(cwc::both(cwc::u256_lt(a, fq_p()), cwc::u256_lt(b, fq_p())), cwc::both(cwc::u256_lt(d, fq_p()), cwc::u256_lt(e, fq_p())));
-    const A2 p{Fq2{canonical ? fq_to_mont(a) : a, canonical ? fq_to_mont(b) : b}, Fq2{canonical ? fq_to_mont(d) : d, canonical ? fq_to_mont(e) : e}};
+    A2 p;
+    const bool in_range = get_coords<G2>(in + (size_t)i * G2_BYTES, canonical != 0, p.x, p.y);
     uint32_t st = GWB_G16V_VALID;
     if (!in_range) {
         st = GWB_G16V_POINT;
     } else if (!affine_is_inf(p)) {
-        if (!on_curve<Fq2T>(p, twist_b()))
+        if (!on_curve<G2>(p, curve_b<G2>()))
             st = GWB_G16V_POINT;
         else if (!(METHOD == 0 ? g2_in_subgroup(p) : g2_in_subgroup_by_order(p)))
             st = GWB_G16V_SUBGROUP;
@@ -84,13 +77,11 @@ __global__ __launch_bounds__(REDUCE_THREADS) void first_bad_kernel(const uint32_
     }
 }
 
-uint32_t blocks_of(uint64_t n, uint32_t threads) { return (uint32_t)std::max<uint64_t>(1, (n + threads - 1) / threads); }
-
 bool enqueue_check(const uint8_t* d_points, uint32_t n, bool canonical, uint32_t method, uint32_t* d_status, hipStream_t s, std::string& err) {
     if (method == 0)
-        hipLaunchKernelGGL(g2_check_kernel<0>, dim3(blocks_of(n, THREADS)), dim3(THREADS), 0, s, d_points, n, canonical ? 1u : 0u, d_status);
+        hipLaunchKernelGGL(g2_check_kernel<0>, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, d_points, n, canonical ? 1u : 0u, d_status);
     else
-        hipLaunchKernelGGL(g2_check_kernel<1>, dim3(blocks_of(n, THREADS)), dim3(THREADS), 0, s, d_points, n, canonical ? 1u : 0u, d_status);
+        hipLaunchKernelGGL(g2_check_kernel<1>, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, d_points, n, canonical ? 1u : 0u, d_status);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         err = hip_err("launching the G2 subgroup check", e);
@@ -144,7 +135,7 @@ struct Checker {
                 return false;
             }
             if (!enqueue_check(d_pts, m, false, 0, d_status, s, err)) return false;
-            hipLaunchKernelGGL(first_bad_kernel, dim3(blocks_of(m, REDUCE_THREADS)), dim3(REDUCE_THREADS), 0, s, (const uint32_t*)d_status, m, d_res,
+            hipLaunchKernelGGL(first_bad_kernel, dim3(blocks_for(m, REDUCE_THREADS)), dim3(REDUCE_THREADS), 0, s, (const uint32_t*)d_status, m, d_res,
                                (uint32_t*)(d_res + 1));
             e = hipGetLastError();
             if (e == hipSuccess) e = hipMemcpyAsync(res, d_res, sizeof res, hipMemcpyDeviceToHost, s);
@@ -163,16 +154,6 @@ struct Checker {
         return true;
     }
 };
-
-// why the device called a stored point GWB_G16V_POINT: the loaders' own two faults
-uint32_t point_fault(const uint8_t* pt) {
-    for (uint32_t k = 0; k < 4; ++k) {
-        Fq c;
-        memcpy(c.v, pt + 32 * k, 32);
-        if (!cwc::u256_lt(c, fq_p())) return cwc_ptau::COORDINATE;
-    }
-    return cwc_ptau::CURVE;
-}
 
 int check_zkey(gwb_zkey* z, gw_status_t* status) {
     const uint64_t n = z->info.n_vars;
@@ -220,7 +201,8 @@ int check_ptau(const uint8_t* data, size_t len, uint32_t domain_power, uint32_t 
         uint32_t st;
         if (!c.run(a.p, a.n, first, st, count, nullptr, err)) return fail(status, err);
         if (first == NONE_BAD) continue;
-        const uint32_t fault = st == GWB_G16V_SUBGROUP ? (uint32_t)cwc_ptau::SUBGROUP : point_fault(a.p + first * G2_BYTES);
+        // GWB_G16V_POINT: which of the loaders' two faults
+        const PointFault fault = st == GWB_G16V_SUBGROUP ? PointFault::SUBGROUP : point_fault<G2>(a.p + first * G2_BYTES, false);
         return fail(status, cwc_ptau::point_message(a.section, a.base + first, fault, true));
     }
     set_ok(status);

@@ -19,28 +19,19 @@
 
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/graph_witness_groth16_verify.h"
 #include "fq12_gfx950.hpp"
 #include "groth16_internal.hpp"
-
-namespace cwc_r1cs {
-std::string hip_err(const char* what, hipError_t e);  // check.hip
-}
+#include "hip_util.hpp"
 
 using namespace cwc_r1cs;
 using namespace cwc_g16;
 using cwc::Fr;
 
 namespace {
-
-using G1 = FqT;
-using G2 = Fq2T;
-using A1 = Affine<G1>;
-using A2 = Affine<G2>;
-using P1 = Xyzz<G1>;
-using P2 = Xyzz<G2>;
 
 constexpr uint32_t THREADS = 64;
 constexpr uint32_t VKX_GROUP = 8;   // signals per vk_x thread
@@ -54,21 +45,6 @@ struct RowPts {
 };
 
 // ---- device ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ Fq ld_fq(const uint8_t* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 lo = q[0], hi = q[1];
-    return Fq{{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}};
-}
-
-// canonical coordinate -> Montgomery; ok cleared when it is not below q
-__device__ __forceinline__ Fq coord(const uint8_t* p, bool& ok) {
-    const Fq v = ld_fq(p);
-    ok = cwc::both(ok, cwc::u256_lt(v, fq_p()));
-    return fq_to_mont(v);
-}
-
-__device__ __forceinline__ Fq g1_b() { return fq_to_mont(Fq{{3, 0, 0, 0, 0, 0, 0, 0}}); }  // G1: y^2 = x^3 + 3
-
 __constant__ MillerSched c_sched = miller_sched();
 __constant__ FxProg c_fx = fx_prog();
 
@@ -111,22 +87,21 @@ __global__ __launch_bounds__(THREADS) void check_kernel(const uint8_t* __restric
     uint32_t st = GWB_G16V_VALID;
     const uint8_t* s = pub + (size_t)row * npub * 32;
     for (uint32_t i = 0; i < npub; ++i)
-        if (!cwc::u256_lt(ld_fq(s + (size_t)i * 32), cwc::fr_p())) st = GWB_G16V_PUBLIC;
+        if (!cwc::u256_lt(rd_fq(s + (size_t)i * 32), cwc::fr_p())) st = GWB_G16V_PUBLIC;
     const uint8_t* p = proofs + (size_t)row * GWB_GROTH16_PROOF_BYTES;
-    bool ok = true;
     RowPts r;
-    r.a = A1{coord(p, ok), coord(p + 32, ok)};
-    r.b = A2{Fq2{coord(p + 64, ok), coord(p + 96, ok)}, Fq2{coord(p + 128, ok), coord(p + 160, ok)}};
-    r.c = A1{coord(p + 192, ok), coord(p + 224, ok)};
+    bool ok = get_coords<G1>(p, true, r.a.x, r.a.y);
+    ok = cwc::both(ok, get_coords<G2>(p + 64, true, r.b.x, r.b.y));
+    ok = cwc::both(ok, get_coords<G1>(p + 192, true, r.c.x, r.c.y));
     const bool a_inf = affine_is_inf(r.a), b_inf = affine_is_inf(r.b), c_inf = affine_is_inf(r.c);
-    ok = cwc::both(ok, cwc::either(a_inf, on_curve<G1>(r.a, g1_b())));
-    ok = cwc::both(ok, cwc::either(c_inf, on_curve<G1>(r.c, g1_b())));
-    ok = cwc::both(ok, cwc::either(b_inf, on_curve<G2>(r.b, twist_b())));
+    ok = cwc::both(ok, cwc::either(a_inf, on_curve<G1>(r.a, curve_b<G1>())));
+    ok = cwc::both(ok, cwc::either(c_inf, on_curve<G1>(r.c, curve_b<G1>())));
+    ok = cwc::both(ok, cwc::either(b_inf, on_curve<G2>(r.b, curve_b<G2>())));
     if (st == GWB_G16V_VALID && !ok) st = GWB_G16V_POINT;
-    if (st == GWB_G16V_VALID && !b_inf && !xyzz_is_inf(xyzz_mul(Xyzz<G2>{r.b.x, r.b.y, fq2_one(), fq2_one()}, cwc::fr_p())))
+    if (st == GWB_G16V_VALID && !b_inf && !xyzz_is_inf(xyzz_mul(from_affine(r.b), cwc::fr_p())))
         st = GWB_G16V_SUBGROUP;
     if (st == GWB_G16V_VALID) {
-        P1 vx = affine_is_inf(ic0) ? xyzz_inf<G1>() : P1{ic0.x, ic0.y, fq_one(), fq_one()};
+        P1 vx = from_affine(ic0);
         for (uint32_t g = 0; g < n_groups; ++g) vx = xyzz_add(vx, part[(size_t)row * n_groups + g]);
         r.vx = xyzz_to_affine(vx);
         r.vx.y = fq_neg(r.vx.y);  // (0, 0) stays (0, 0)
@@ -226,27 +201,22 @@ __global__ __launch_bounds__(THREADS) void pairs_kernel(const uint8_t* __restric
                                                         RowPts* __restrict__ pts) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    bool ok = true;
-    const uint8_t* p = g1 + (size_t)i * 64;
-    const uint8_t* q = g2 + (size_t)i * 128;
-    RowPts r;
-    r.a = A1{coord(p, ok), coord(p + 32, ok)};
-    r.b = A2{Fq2{coord(q, ok), coord(q + 32, ok)}, Fq2{coord(q + 64, ok), coord(q + 96, ok)}};
+    RowPts r;  // coordinates that are not below q are taken as they reduce
+    get_coords<G1>(g1 + (size_t)i * G1_BYTES, true, r.a.x, r.a.y);
+    get_coords<G2>(g2 + (size_t)i * G2_BYTES, true, r.b.x, r.b.y);
     r.vx = r.c = A1{fq_zero(), fq_zero()};
     pts[i] = r;
 }
-
-uint32_t blocks(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + THREADS - 1) / THREADS); }
 
 // pairing aid path on a workspace of n RowPts, n Fq12 and FX_SLOTS n spill slots
 bool enqueue_pairing(const uint8_t* g1, const uint8_t* g2, uint32_t n, uint8_t* gt, void* ws, hipStream_t s, std::string& err) {
     RowPts* pts = (RowPts*)ws;
     Fq12* f = (Fq12*)(pts + n);
     uint32_t* sp = (uint32_t*)(f + n);
-    hipLaunchKernelGGL(pairs_kernel, dim3(blocks(n)), dim3(THREADS), 0, s, g1, g2, n, pts);
-    hipLaunchKernelGGL(miller_kernel, dim3(blocks(n)), dim3(THREADS), 0, s, pts, n, (const uint32_t*)nullptr, (const Line*)nullptr, 0u, f);
-    hipLaunchKernelGGL(easy_kernel, dim3(blocks(n)), dim3(THREADS), 0, s, f, n, (const uint32_t*)nullptr);
-    hipLaunchKernelGGL(final_kernel, dim3(blocks(n)), dim3(THREADS), 0, s, f, n, (const Fq12*)nullptr, (uint32_t*)nullptr, sp, gt);
+    hipLaunchKernelGGL(pairs_kernel, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, g1, g2, n, pts);
+    hipLaunchKernelGGL(miller_kernel, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, pts, n, (const uint32_t*)nullptr, (const Line*)nullptr, 0u, f);
+    hipLaunchKernelGGL(easy_kernel, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, f, n, (const uint32_t*)nullptr);
+    hipLaunchKernelGGL(final_kernel, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, f, n, (const Fq12*)nullptr, (uint32_t*)nullptr, sp, gt);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         err = hip_err("launching the pairing kernels", e);
@@ -282,37 +252,19 @@ struct Fail {
     std::string msg;
 };
 
-Fq rd_fq(const uint8_t* p) {
-    Fq v;
-    memcpy(v.v, p, 32);
-    return v;
-}
-
 // a canonical point at p -> Montgomery affine; refusals name the point
 template <class T>
-Affine<T> key_point(const uint8_t* p, const std::string& what);
-
-Fq key_coord(const uint8_t* p, const std::string& what) {
-    const Fq v = rd_fq(p);
-    if (!cwc::u256_lt(v, fq_p())) throw Fail{"verifying key: " + what + " has a coordinate >= q"};
-    return fq_to_mont(v);
-}
-
-template <>
-A1 key_point<G1>(const uint8_t* p, const std::string& what) {
-    const A1 a{key_coord(p, what), key_coord(p + 32, what)};
-    if (!affine_is_inf(a) && !on_curve<G1>(a, fq_to_mont(Fq{{3, 0, 0, 0, 0, 0, 0, 0}})))
-        throw Fail{"verifying key: " + what + " is not on the G1 curve"};
+Affine<T> key_point(const uint8_t* p, const std::string& what) {
+    Affine<T> a;
+    const PointFault f = get_point<T>(p, true, a);
+    if (f == PointFault::COORDINATE) throw Fail{"verifying key: " + what + " has a coordinate >= q"};
+    if (f == PointFault::CURVE) throw Fail{"verifying key: " + what + (std::is_same<T, G2>::value ? " is not on the G2 twist curve" : " is not on the G1 curve")};
     return a;
 }
-
-template <>
-A2 key_point<G2>(const uint8_t* p, const std::string& what) {
-    const A2 a{Fq2{key_coord(p, what), key_coord(p + 32, what)}, Fq2{key_coord(p + 64, what), key_coord(p + 96, what)}};
-    if (affine_is_inf(a)) return a;
-    if (!on_curve<G2>(a, twist_b())) throw Fail{"verifying key: " + what + " is not on the G2 twist curve"};
-    if (!xyzz_is_inf(xyzz_mul(P2{a.x, a.y, fq2_one(), fq2_one()}, cwc::fr_p())))
-        throw Fail{"verifying key: " + what + " is not in the order-r subgroup of G2"};
+// a G2 point of the key must also have order r: [r] P = O
+A2 key_point_g2(const uint8_t* p, const std::string& what) {
+    const A2 a = key_point<G2>(p, what);
+    if (!xyzz_is_inf(xyzz_mul(from_affine(a), cwc::fr_p()))) throw Fail{"verifying key: " + what + " is not in the order-r subgroup of G2"};
     return a;
 }
 
@@ -327,9 +279,9 @@ void load_key(const uint8_t* d, size_t len, uint32_t n_public, gwb_g16vk& k) {
     k.n_public = n_public;
     k.points.assign(d, d + len);
     key_point<G1>(d, "alpha1");
-    key_point<G2>(d + 64, "beta2");
-    k.gamma2 = key_point<G2>(d + 192, "gamma2");
-    k.delta2 = key_point<G2>(d + 320, "delta2");
+    key_point_g2(d + 64, "beta2");
+    k.gamma2 = key_point_g2(d + 192, "gamma2");
+    k.delta2 = key_point_g2(d + 320, "delta2");
     k.ic0 = key_point<G1>(d + KEY_BYTES, "IC[0]");
     k.tab.resize((size_t)n_public * TAB);
     for (uint32_t i = 0; i < n_public; ++i) {
@@ -432,12 +384,12 @@ bool enqueue_verify(gwb_g16vk* k, const uint8_t* d_proofs, const uint8_t* d_pub,
     Fq12* f = (Fq12*)(pts + batch);
     uint32_t* sp = (uint32_t*)(f + batch);
     if (n_groups)
-        hipLaunchKernelGGL(vkx_kernel, dim3(blocks((uint64_t)n * n_groups)), dim3(THREADS), 0, s, d_pub, npub, n, n_groups, k->d_tab, part);
-    hipLaunchKernelGGL(check_kernel, dim3(blocks(n)), dim3(THREADS), 0, s, d_proofs, d_pub, npub, n, k->ic0, part, n_groups, pts, d_status);
+        hipLaunchKernelGGL(vkx_kernel, dim3(blocks_for((uint64_t)n * n_groups, THREADS)), dim3(THREADS), 0, s, d_pub, npub, n, n_groups, k->d_tab, part);
+    hipLaunchKernelGGL(check_kernel, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, d_proofs, d_pub, npub, n, k->ic0, part, n_groups, pts, d_status);
     const uint32_t fixed_inf = (affine_is_inf(k->gamma2) ? 1u : 0u) | (affine_is_inf(k->delta2) ? 2u : 0u);
-    hipLaunchKernelGGL(miller_kernel, dim3(blocks(n)), dim3(THREADS), 0, s, pts, n, d_status, k->d_lines, fixed_inf, f);
-    hipLaunchKernelGGL(easy_kernel, dim3(blocks(n)), dim3(THREADS), 0, s, f, n, (const uint32_t*)d_status);
-    hipLaunchKernelGGL(final_kernel, dim3(blocks(n)), dim3(THREADS), 0, s, f, n, k->d_ab, d_status, sp, (uint8_t*)nullptr);
+    hipLaunchKernelGGL(miller_kernel, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, pts, n, d_status, k->d_lines, fixed_inf, f);
+    hipLaunchKernelGGL(easy_kernel, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, f, n, (const uint32_t*)d_status);
+    hipLaunchKernelGGL(final_kernel, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, f, n, k->d_ab, d_status, sp, (uint8_t*)nullptr);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         err = hip_err("launching the verifier kernels", e);

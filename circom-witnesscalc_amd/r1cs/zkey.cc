@@ -9,17 +9,20 @@
 //   section 8:  C, nVars - nPublic - 1 G1 section 9: H, domainSize G1         section 10: contributions (ignored)
 // Every coordinate must be below q and every point other than infinity on its curve (G1: y^2 = x^3 + 3, G2: y^2 = x^3 +
 // 3 / (9 + u)).  G2 points are not checked for subgroup membership here; gwb_zkey_check_g2 (subgroup.hip) checks beta2, gamma2,
-// delta2 and section 7 on the device when asked (Groth16(zkey, check_g2=True), groth16-prove --check-g2).  The curve check uses
-// the host build of fq_gfx950.hpp.
+// delta2 and section 7 on the device when asked (Groth16(zkey, check_g2=True), groth16-prove --check-g2).  The section table is
+// read by binfile.hpp, the points are checked by the host build of bn254_points_gfx950.hpp.
 #include <string.h>
 
-#include <map>
 #include <string>
 
-#include "fq_gfx950.hpp"
+#include "binfile.hpp"
+#include "bn254_points_gfx950.hpp"
 #include "groth16_internal.hpp"
 
 using namespace cwc_g16;
+using cwc_r1cs::BinSection;
+using cwc_r1cs::binfile_sections;
+using cwc_r1cs::rd32;
 
 namespace {
 
@@ -29,78 +32,26 @@ struct Fail {
 
 constexpr uint32_t SEC_HEADER_BYTES = 4 + 32 + 4 + 32 + 12 + 3 * G1_BYTES + 3 * G2_BYTES;  // 660
 
-uint32_t rd32(const uint8_t* p) {
-    uint32_t v;
-    memcpy(&v, p, 4);
-    return v;
-}
-
-Fq rd_fq(const uint8_t* p) {
-    Fq v;
-    memcpy(v.v, p, 32);
-    return v;
-}
-
-Fq2 g2_b() {  // 3 / (9 + u), Montgomery form
-    const Fq2 t{fq_to_mont(Fq{{9, 0, 0, 0, 0, 0, 0, 0}}), fq_one()};
-    const Fq three = fq_to_mont(Fq{{3, 0, 0, 0, 0, 0, 0, 0}});
-    const Fq2 i = fq2_inv(t);
-    return Fq2{fq_mul(i.c0, three), fq_mul(i.c1, three)};
-}
-
-// n points of `words` coordinates each at p: coordinates below q, on the curve unless all zero
-void check_points(const char* what, const uint8_t* p, uint64_t n, bool g2) {
-    const Fq b1 = fq_to_mont(Fq{{3, 0, 0, 0, 0, 0, 0, 0}});
-    static const Fq2 b2 = g2_b();
-    const uint32_t words = g2 ? 4 : 2;
+// n points at p: coordinates below q, on the curve unless all zero (bn254_points_gfx950.hpp's point_fault)
+void require_points(const char* what, const uint8_t* p, uint64_t n, bool g2) {
     for (uint64_t i = 0; i < n; ++i) {
-        const uint8_t* pt = p + i * words * 32;
-        bool zero = true;
-        for (uint32_t k = 0; k < words; ++k) {
-            const Fq c = rd_fq(pt + 32 * k);
-            if (!cwc::u256_lt(c, fq_p()))
-                throw Fail{std::string("zkey: ") + what + " point " + std::to_string(i) + " has a coordinate >= q"};
-            zero = zero && cwc::u256_is_zero(c);
-        }
-        if (zero) continue;
-        const bool ok = g2 ? on_curve<Fq2T>(Affine<Fq2T>{Fq2{rd_fq(pt), rd_fq(pt + 32)}, Fq2{rd_fq(pt + 64), rd_fq(pt + 96)}}, b2)
-                           : on_curve<FqT>(Affine<FqT>{rd_fq(pt), rd_fq(pt + 32)}, b1);
-        if (!ok) throw Fail{std::string("zkey: ") + what + " point " + std::to_string(i) + " is not on the " + (g2 ? "G2" : "G1") + " curve"};
+        const PointFault f = g2 ? point_fault<G2>(p + i * G2_BYTES, false) : point_fault<G1>(p + i * G1_BYTES, false);
+        if (f == PointFault::COORDINATE) throw Fail{std::string("zkey: ") + what + " point " + std::to_string(i) + " has a coordinate >= q"};
+        if (f == PointFault::CURVE) throw Fail{std::string("zkey: ") + what + " point " + std::to_string(i) + " is not on the " + (g2 ? "G2" : "G1") + " curve"};
     }
 }
 
 void load(const uint8_t* d, size_t len, gwb_zkey& z) {
-    if (len < 12 || memcmp(d, "zkey", 4) != 0) throw Fail{"zkey: bad magic (not a .zkey file)"};
-    const uint32_t version = rd32(d + 4), n_sections = rd32(d + 8);
-    if (version != 1) throw Fail{"zkey: unsupported version " + std::to_string(version) + " (1 expected)"};
-    struct Sec {
-        uint64_t off, size;
-    };
-    std::map<uint32_t, Sec> secs;
-    uint64_t off = 12;
-    for (uint32_t i = 0; i < n_sections; ++i) {
-        if (len - off < 12) throw Fail{"zkey: truncated section header"};
-        const uint32_t id = rd32(d + off);
-        uint64_t size;
-        memcpy(&size, d + off + 4, 8);
-        off += 12;
-        if (size > len - off)
-            throw Fail{"zkey: truncated section " + std::to_string(id) + " (declares " + std::to_string(size) + " bytes, " +
-                       std::to_string(len - off) + " left)"};
-        if (id >= 1 && id <= 10) {
-            if (secs.count(id)) throw Fail{"zkey: duplicate section " + std::to_string(id)};
-            secs[id] = Sec{off, size};
-        }
-        off += size;
-    }
-    if (off != len) throw Fail{"zkey: " + std::to_string(len - off) + " trailing bytes after the last section"};
+    BinSection secs[11];
+    std::string err;
+    if (!binfile_sections(d, len, "zkey", 0x7feu, secs, err)) throw Fail{err};  // sections 1 to 10
     for (uint32_t id = 1; id <= 9; ++id)
-        if (!secs.count(id)) throw Fail{"zkey: missing section " + std::to_string(id)};
+        if (!secs[id].p) throw Fail{"zkey: missing section " + std::to_string(id)};
     auto sized = [&](uint32_t id, uint64_t want, const char* what) {
         if (secs[id].size != want)
             throw Fail{"zkey: section " + std::to_string(id) + " (" + what + ") has " + std::to_string(secs[id].size) + " bytes, " +
                        std::to_string(want) + " expected"};
-        return d + secs[id].off;
+        return secs[id].p;
     };
     // -- section 1
     const uint32_t protocol = rd32(sized(1, 4, "protocol"));
@@ -108,9 +59,9 @@ void load(const uint8_t* d, size_t len, gwb_zkey& z) {
     if (protocol == 10) throw Fail{"zkey: fflonk keys (protocol 10) are not supported: Groth16 only"};
     if (protocol != 1) throw Fail{"zkey: unknown protocol " + std::to_string(protocol) + " (1 = Groth16 expected)"};
     // -- section 2
-    if (secs[2].size < 4 || rd32(d + secs[2].off) != 32)
+    if (secs[2].size < 4 || rd32(secs[2].p) != 32)
         throw Fail{"zkey: n8q is not 32 (only BN254 is supported)"};
-    if (secs[2].size < 72 || rd32(d + secs[2].off + 36) != 32) throw Fail{"zkey: n8r is not 32 (only BN254 is supported)"};
+    if (secs[2].size < 72 || rd32(secs[2].p + 36) != 32) throw Fail{"zkey: n8r is not 32 (only BN254 is supported)"};
     const uint8_t* h = sized(2, SEC_HEADER_BYTES, "header");
     if (!cwc::u256_eq(rd_fq(h + 4), fq_p())) throw Fail{"zkey: base field q is not BN254's"};
     if (!cwc::u256_eq(rd_fq(h + 40), cwc::fr_p())) throw Fail{"zkey: scalar field r is not BN254's"};
@@ -129,18 +80,18 @@ void load(const uint8_t* d, size_t len, gwb_zkey& z) {
     memcpy(z.gamma2, pts + 256, G2_BYTES);
     memcpy(z.delta1, pts + 384, G1_BYTES);
     memcpy(z.delta2, pts + 448, G2_BYTES);
-    check_points("alpha1", z.alpha1, 1, false);
-    check_points("beta1", z.beta1, 1, false);
-    check_points("beta2", z.beta2, 1, true);
-    check_points("gamma2", z.gamma2, 1, true);
-    check_points("delta1", z.delta1, 1, false);
-    check_points("delta2", z.delta2, 1, true);
+    require_points("alpha1", z.alpha1, 1, false);
+    require_points("beta1", z.beta1, 1, false);
+    require_points("beta2", z.beta2, 1, true);
+    require_points("gamma2", z.gamma2, 1, true);
+    require_points("delta1", z.delta1, 1, false);
+    require_points("delta2", z.delta2, 1, true);
     // -- section 4 (bounds only here; the entries are kept, and the witness map is built from them at its first use:
     //    zkey_coefs.cc, which also refuses what a prover cannot use -- values >= r, no entries, a domain the NTT cannot take)
     {
         const uint64_t size = secs[4].size;
         if (size < 4) throw Fail{"zkey: section 4 (coefficients) is truncated"};
-        const uint8_t* p = d + secs[4].off;
+        const uint8_t* p = secs[4].p;
         in.n_coefs = rd32(p);
         if (size != 4 + in.n_coefs * 44)
             throw Fail{"zkey: section 4 (coefficients) has " + std::to_string(size) + " bytes, " + std::to_string(4 + in.n_coefs * 44) +
@@ -169,7 +120,7 @@ void load(const uint8_t* d, size_t len, gwb_zkey& z) {
                      {9, in.domain_size, false, "H", &z.h}};
     for (const PS& s : ps) {
         const uint8_t* p = sized(s.id, s.n * (s.g2 ? G2_BYTES : G1_BYTES), s.what);
-        check_points(s.what, p, s.n, s.g2);
+        require_points(s.what, p, s.n, s.g2);
         s.dst->assign(p, p + secs[s.id].size);
     }
 }

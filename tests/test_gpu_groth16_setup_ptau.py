@@ -283,11 +283,13 @@ def test_mode_and_domain_refusals():
                                                  (5, 64, 1, "compute"), (12, 64, 15, "file"), (12, 64, 30, "file"), (12, 64, 32, "file"),
                                                  (13, 128, 20, "file"), (14, 64, 22, "file"), (15, 64, 17, "file")))
 def test_point_faults_found_on_the_device(sid, unit, index, mode):
-    """p = 4: a point off its curve and a coordinate >= q among the points read, named as the host check names them"""
+    """p = 4: a point off its curve and, in each coordinate slot in turn, a coordinate >= q among the points read, named as the
+    host check names them"""
     _, _, _, _, r1 = system("p4")
     secs = dict(ptau_sections(5, True))
     off = GF.lem(1) + GF.lem(3) if unit == 64 else GF.lem(1) + GF.lem(0) + GF.lem(1) + GF.lem(0)
-    for fault, pattern in ((off, r"is not on the G%d curve" % (unit // 64)), (bytes(unit - 32) + Q.to_bytes(32, "little"), "has a coordinate >= q")):
+    at_q = [bytes(32 * k) + Q.to_bytes(32, "little") + bytes(unit - 32 * k - 32) for k in range(unit // 32)]
+    for fault, pattern in [(off, r"is not on the G%d curve" % (unit // 64))] + [(f, "has a coordinate >= q") for f in at_q]:
         body = secs[sid]
         bad = dict(secs)
         bad[sid] = body[:unit * index] + fault + body[unit * index + unit:]

@@ -161,9 +161,9 @@ def test_batch_zero_and_one():
 def test_negative_rows_and_mixed_batch():
     key = Key(2, 40)
     rnd = key.rnd
-    pubs = _signals(rnd, 2, 12)
+    pubs = _signals(rnd, 2, 19)
     rows = _proof_rows(key.forge(pubs))
-    want = [VALID] * 12
+    want = [VALID] * 19
     # 0: a public signal + 1 -> EQUATION
     pubs[0] = [(pubs[0][0] + 1) % R, pubs[0][1]]
     want[0] = EQUATION
@@ -192,6 +192,11 @@ def test_negative_rows_and_mixed_batch():
     # 10: A at infinity with a c that does not fit -> EQUATION; 11 stays valid
     rows[10] = _proof_rows([(0, rnd.randrange(1, R), rnd.randrange(R))])[0]
     want[10] = EQUATION
+    # 12 .. 18: as row 2, in each of the other seven coordinate slots (A.y, B's four, C's two) -> POINT
+    for i, off in enumerate(range(32, 256, 32), 12):
+        v = int.from_bytes(bytes(rows[i, off:off + 32]), "little") + Q
+        rows[i, off:off + 32] = np.frombuffer(v.to_bytes(32, "little"), np.uint8)
+        want[i] = POINT
     assert list(_verify_both(key, rows, pubs)) == want
 
 
