@@ -87,28 +87,13 @@ static uint32_t pick_tile_width(size_t batch) {
     return t;
 }
 
-std::string hip_err(const char* what, hipError_t e) { return std::string("r1cs: ") + what + ": " + hipGetErrorString(e); }
-
 const char* prefix_of(const RowSystem& s) { return s.stride == 3 ? "r1cs: " : "zkey: "; }
 
 template <class V>
-static bool upload(void** d, const V& v, std::string& err) {
-    const size_t bytes = std::max<size_t>(v.size() * sizeof(v[0]), 4);
-    hipError_t e = hipMalloc(d, bytes);
-    if (e == hipSuccess && !v.empty()) e = hipMemcpy(*d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        err = hip_err("uploading the constraint arrays", e);
-        return false;
-    }
-    return true;
-}
-
-void release_device(RowSystem& s) {
-    for (void** p : {&s.d_rowptr, &s.d_fac, &s.d_cidx, &s.d_coef, &s.d_perm}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    s.device = -1;
+static bool upload(DeviceBuf& d, const V& v, std::string& err) {
+    const hipError_t e = d.upload(v.data(), v.size() * sizeof(v[0]));
+    if (e != hipSuccess) err = hip_err("uploading the constraint arrays", e);
+    return e == hipSuccess;
 }
 
 bool ensure_device(RowSystem& s, int home, std::string& err) {
@@ -128,11 +113,12 @@ bool ensure_device(RowSystem& s, int home, std::string& err) {
         return false;
     }
     if (s.device >= 0) return true;
-    if (!upload(&s.d_rowptr, s.rowptr, err) || !upload(&s.d_fac, s.fac, err) || !upload(&s.d_cidx, s.cidx, err) ||
-        !upload(&s.d_coef, s.coef, err) || !upload(&s.d_perm, s.perm, err)) {
-        release_device(s);
+    DeviceBuf up[5];  // the row system gets all five or none
+    if (!upload(up[0], s.rowptr, err) || !upload(up[1], s.fac, err) || !upload(up[2], s.cidx, err) || !upload(up[3], s.coef, err) ||
+        !upload(up[4], s.perm, err))
         return false;
-    }
+    DeviceBuf* dst[5] = {&s.d_rowptr, &s.d_fac, &s.d_cidx, &s.d_coef, &s.d_perm};
+    for (int i = 0; i < 5; ++i) *dst[i] = std::move(up[i]);
     s.device = dev;
     return true;
 }
@@ -248,8 +234,8 @@ bool enqueue(gwb_r1cs* r, const void* d_witness, size_t batch, uint32_t form, ui
     if (sys.n_rows == 0) return true;
     EvalGrid g;
     if (!eval_grid(sys, batch, cu_count(sys.device), WAVES_PER_BLOCK, g, err)) return false;
-    hipLaunchKernelGGL(kernel_for(g.t), dim3(g.tiles, g.gy), dim3(64 * WAVES_PER_BLOCK), 0, stream, (const uint32_t*)sys.d_rowptr,
-                       (const uint32_t*)sys.d_fac, (const uint32_t*)sys.d_cidx, (const Fr*)sys.d_coef, (const uint32_t*)sys.d_perm, sys.n_rows,
+    hipLaunchKernelGGL(kernel_for(g.t), dim3(g.tiles, g.gy), dim3(64 * WAVES_PER_BLOCK), 0, stream, sys.d_rowptr.as<const uint32_t>(),
+                       sys.d_fac.as<const uint32_t>(), sys.d_cidx.as<const uint32_t>(), sys.d_coef.as<const Fr>(), sys.d_perm.as<const uint32_t>(), sys.n_rows,
                        (const uint8_t*)d_witness, sys.n_wires, (uint32_t)batch, form == GWB_FORM_MONTGOMERY ? 1u : 0u, d_first, d_nfail);
     e = hipGetLastError();
     if (e != hipSuccess) {
@@ -268,30 +254,13 @@ int check_host(gwb_r1cs* r, const void* witness, size_t n_witness, size_t batch,
         return 0;
     }
     if (!ensure_device(r->sys, -1, err)) return fail(status, err);
-    void *d_w = nullptr, *d_out = nullptr;
-    hipStream_t s = nullptr;
     const size_t wbytes = batch * n_witness * 32;
-    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&d_w, wbytes);
-    if (e == hipSuccess) e = hipMalloc(&d_out, batch * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_w, witness, wbytes, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) err = hip_err("staging the witness rows", e);
-    uint32_t* d_first = (uint32_t*)d_out;
-    uint32_t* d_nfail = d_first + batch;
-    bool ok = e == hipSuccess && enqueue(r, d_w, batch, GWB_FORM_CANONICAL, d_first, d_nfail, s, err);
-    if (ok) {
-        e = hipMemcpyAsync(first, d_first, batch * 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(nfail, d_nfail, batch * 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            err = hip_err("running the check", e);
-            ok = false;
-        }
-    }
-    if (d_w) (void)hipFree(d_w);
-    if (d_out) (void)hipFree(d_out);
-    if (s) (void)hipStreamDestroy(s);
-    if (!ok) return fail(status, err);
+    auto run = [&](unsigned char* const* d, hipStream_t s, std::string& err) {  // d[1]: first_failed, n_failed
+        return enqueue(r, d[0], batch, GWB_FORM_CANONICAL, (uint32_t*)d[1], (uint32_t*)d[1] + batch, s, err);
+    };
+    if (!run_staged({wbytes, batch * 8}, {{witness, wbytes, 0, 0}}, {{first, batch * 4, 1, 0}, {nfail, batch * 4, 1, batch * 4}}, "staging the witness rows",
+                    "running the check", run, err))
+        return fail(status, err);
     set_ok(status);
     return 0;
 }
@@ -300,19 +269,7 @@ int check_host(gwb_r1cs* r, const void* witness, size_t n_witness, size_t batch,
 
 extern "C" {
 
-void gwb_r1cs_free(gwb_r1cs_t* r) {
-    if (!r) return;
-    if (r->sys.device >= 0) {
-        int cur = -1;
-        const bool switch_dev = hipGetDevice(&cur) == hipSuccess && cur != r->sys.device;
-        if (switch_dev) (void)hipSetDevice(r->sys.device);
-        release_qap(r->sys.qap);
-        release_device(r->sys);
-        if (switch_dev) (void)hipSetDevice(cur);
-    }
-    (void)gwb_r1cs_qap_time_phases(r, 0);
-    delete r;
-}
+void gwb_r1cs_free(gwb_r1cs_t* r) { delete r; }  // (the owners in it free what is on the device, with that device current)
 
 int gwb_r1cs_check_batch_device(gwb_r1cs_t* r, const void* d_witness, size_t n_witness, size_t batch, uint32_t form, uint32_t* d_first_failed,
                                 uint32_t* d_n_failed, void* hip_stream, gw_status_t* status) {

@@ -20,13 +20,10 @@ struct gwb_zkey {
     // device copies (first prove call): A, B1, B2 with two more points each, the bases of the scalars r and s
     // (A: delta1, O; B1: O, delta1; B2: O, delta2), then C and H as stored
     int device = -1;
-    void *d_a = nullptr, *d_b1 = nullptr, *d_b2 = nullptr, *d_c = nullptr, *d_h = nullptr;
-    void* d_ws = nullptr;
-    size_t ws_bytes = 0;
-    void* h_rs = nullptr;  // pinned staging of r, s (h_rs_bytes), and the event after its last copy
-    size_t h_rs_bytes = 0;
-    void* rs_done = nullptr;
-    void* events[8] = {};  // phase timing (gwb_groth16_time_phases): recorded around each phase of the last sub-batch
+    cwc_r1cs::DeviceBuf d_a, d_b1, d_b2, d_c, d_h;
+    cwc_r1cs::Workspace ws;
+    cwc_r1cs::PinnedStage rs_stage;    // pinned staging of r, s
+    cwc_r1cs::PhaseEvents<8> events;  // phase timing (gwb_groth16_time_phases): recorded around each phase of the last sub-batch
     // Section 4 as stored (n_coefs x 44 B: u32 matrix, constraint, signal, then the value c R^2 mod r), bounds-checked at load.
     std::vector<uint8_t> sec4;
     // The witness map of section 4 (zkey_coefs.cc, built at the first call that needs it): a row system without the C side, its

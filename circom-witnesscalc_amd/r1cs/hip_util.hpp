@@ -1,5 +1,6 @@
-// Host-side plumbing that the library's .hip files share: the error text, the launch grid, the workspace carver, the table of
-// squarings that the kernels build powers from, and the device side of a key setup with its phase timer.
+// Host-side plumbing that the library's .hip files share: the owners of device memory, streams and events (device_owners.hpp,
+// with the error text), the launch grid, the workspace carver, the table of squarings that the kernels build powers from, and
+// the device side of a key setup with its phase timer.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -9,10 +10,9 @@
 #include <string>
 
 #include "../csrc/fr_gfx950.hpp"
+#include "device_owners.hpp"
 
 namespace cwc_r1cs {
-
-std::string hip_err(const char* what, hipError_t e);  // check.hip: "r1cs: <what>: <the runtime's text>"
 
 // blocks of `block` threads for n threads, at least one
 inline uint32_t blocks_for(uint64_t n, uint32_t block) { return (uint32_t)std::max<uint64_t>(1, (n + block - 1) / block); }
@@ -40,32 +40,28 @@ inline Pows powers_of(const cwc::Fr& base) {  // Montgomery form
 }
 
 // The device side of one setup call: a stream, N_EVENTS events around its phases, the workspace, and `secret`, which holds what
-// derives from the trapdoor and is zeroed before it is released.
+// derives from the trapdoor and is zeroed before it is released.  The destructor's body does that, and it runs while every
+// member is alive; the members then go in reverse order: `secret` (zeroed by now), `work`, the events, and the stream last,
+// after the buffers, whose release waits for what was enqueued on it.
 template <int N_EVENTS>
 struct SetupDevice {
-    hipStream_t s = nullptr;
-    void *secret = nullptr, *work = nullptr;
+    Stream s;
+    PhaseEvents<N_EVENTS> ev;
+    DeviceBuf work, secret;
     size_t secret_bytes = 0;
-    hipEvent_t ev[N_EVENTS] = {};
     hipError_t open(size_t secret_size, size_t work_size) {
         secret_bytes = secret_size;
-        hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-        for (hipEvent_t& v : ev)
-            if (e == hipSuccess) e = hipEventCreate(&v);
-        if (e == hipSuccess) e = hipMalloc(&secret, secret_bytes);
-        if (e == hipSuccess) e = hipMalloc(&work, work_size);
+        hipError_t e = s.create();
+        if (e == hipSuccess) e = ev.on();
+        if (e == hipSuccess) e = secret.alloc(secret_bytes);
+        if (e == hipSuccess) e = work.alloc(work_size);
         return e;
     }
     ~SetupDevice() {
         if (secret) {
-            (void)hipMemsetAsync(secret, 0, secret_bytes, s);
+            (void)hipMemsetAsync(secret.as(), 0, secret_bytes, s);
             (void)hipStreamSynchronize(s);
-            (void)hipFree(secret);
         }
-        if (work) (void)hipFree(work);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (s) (void)hipStreamDestroy(s);
     }
 };
 
@@ -75,14 +71,12 @@ struct PhaseTimes {
     std::mutex mutex;
     float ms[N];
     bool valid = false;
-    // phase i lies between ev[i] and ev[i + 1] (all completed); a phase whose bit of `idle` is set enqueued nothing: 0 ms
-    void record(const hipEvent_t* ev, uint32_t idle = 0) {
+    // phase i lies between events i and i + 1 (all completed); a phase whose bit of `idle` is set enqueued nothing: 0 ms
+    void record(const PhaseEvents<N + 1>& ev, uint32_t idle = 0) {
         float t[N];
-        bool ok = true;
-        for (int i = 0; i < N; ++i) {
-            ok = ok && hipEventElapsedTime(t + i, ev[i], ev[i + 1]) == hipSuccess;
+        const bool ok = ev.elapsed(t) == hipSuccess;
+        for (int i = 0; i < N; ++i)
             if ((idle >> i) & 1u) t[i] = 0.0f;
-        }
         std::lock_guard<std::mutex> lock(mutex);
         if (ok) memcpy(ms, t, sizeof t);
         valid = ok;

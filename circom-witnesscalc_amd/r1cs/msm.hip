@@ -354,7 +354,6 @@ bool ensure_bases(gwb_zkey* z, std::string& err) {
     if (z->d_a) return true;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
-    const uint64_t nv = z->info.n_vars;
     std::vector<uint8_t> a(z->a), b1(z->b1), b2(z->b2);
     a.insert(a.end(), z->delta1, z->delta1 + G1_BYTES);
     a.insert(a.end(), G1_BYTES, 0);
@@ -362,41 +361,16 @@ bool ensure_bases(gwb_zkey* z, std::string& err) {
     b1.insert(b1.end(), z->delta1, z->delta1 + G1_BYTES);
     b2.insert(b2.end(), G2_BYTES, 0);
     b2.insert(b2.end(), z->delta2, z->delta2 + G2_BYTES);
-    struct Up {
-        void** dst;
-        const std::vector<uint8_t>* src;
-    };
-    const Up ups[] = {{&z->d_a, &a}, {&z->d_b1, &b1}, {&z->d_b2, &b2}, {&z->d_c, &z->c}, {&z->d_h, &z->h}};
-    for (const Up& u : ups) {
-        if (e != hipSuccess) break;
-        e = hipMalloc(u.dst, std::max<size_t>(u.src->size(), 1));
-        if (e == hipSuccess && !u.src->empty()) e = hipMemcpy(*u.dst, u.src->data(), u.src->size(), hipMemcpyHostToDevice);
-    }
-    (void)nv;
+    const std::vector<uint8_t>* src[5] = {&a, &b1, &b2, &z->c, &z->h};
+    DeviceBuf* dst[5] = {&z->d_a, &z->d_b1, &z->d_b2, &z->d_c, &z->d_h};
+    DeviceBuf up[5];  // the key gets all five or none
+    for (int i = 0; i < 5 && e == hipSuccess; ++i) e = up[i].upload(src[i]->data(), src[i]->size());
     if (e != hipSuccess) {
-        for (const Up& u : ups) {
-            if (*u.dst) (void)hipFree(*u.dst);
-            *u.dst = nullptr;
-        }
         err = hip_err("uploading the zkey points", e);
         return false;
     }
+    for (int i = 0; i < 5; ++i) *dst[i] = std::move(up[i]);
     z->device = dev;
-    return true;
-}
-
-bool ensure_ws(gwb_zkey* z, size_t bytes, std::string& err) {
-    if (z->ws_bytes >= bytes) return true;
-    if (z->d_ws) (void)hipFree(z->d_ws);
-    z->d_ws = nullptr;
-    z->ws_bytes = 0;
-    const hipError_t e = hipMalloc(&z->d_ws, bytes);
-    if (e != hipSuccess) {
-        z->d_ws = nullptr;
-        err = hip_err("allocating the prover workspace", e);
-        return false;
-    }
-    z->ws_bytes = bytes;
     return true;
 }
 
@@ -491,13 +465,11 @@ Consts consts_of(const gwb_zkey* z) {
     return k;
 }
 
-void mark(gwb_zkey* z, int i, hipStream_t s) {
-    if (z->events[0]) (void)hipEventRecord((hipEvent_t)z->events[i], s);
-}
+void mark(gwb_zkey* z, int i, hipStream_t s) { z->events.record(i, s); }
 
 bool enqueue_sub(gwb_zkey* z, gwb_r1cs* r, const Layout& L, const uint8_t* d_w, uint64_t rows, uint32_t form_in, const Fr* d_rs,
                  uint8_t* d_proofs, hipStream_t s, std::string& err) {
-    Sub S{(uint8_t*)z->d_ws, &L, rows, s};
+    Sub S{z->ws.as<uint8_t>(), &L, rows, s};
     const uint32_t nv = z->info.n_vars, n = z->info.domain_size, npub = z->info.n_public;
     const uint32_t mont = form_in == GWB_FORM_MONTGOMERY ? 1u : 0u;
     P1* g1 = S.at<P1>(L.off_g1);
@@ -510,15 +482,15 @@ bool enqueue_sub(gwb_zkey* z, gwb_r1cs* r, const Layout& L, const uint8_t* d_w, 
     int cur = 0;
     if (!prep_sort(S, L.mw, d_w, nv, nv, mont, d_rs, cur, err)) return false;
     mark(z, 2, s);
-    if (!run_msm<G1>(S, L.mw, cur, z->d_a, 0, nv + 2, g1 + 0, 4, err) || !run_msm<G1>(S, L.mw, cur, z->d_b1, 0, nv + 2, g1 + 1, 4, err) ||
-        !run_msm<G1>(S, L.mw, cur, z->d_c, npub + 1, nv, g1 + 2, 4, err))
+    if (!run_msm<G1>(S, L.mw, cur, z->d_a.as(), 0, nv + 2, g1 + 0, 4, err) || !run_msm<G1>(S, L.mw, cur, z->d_b1.as(), 0, nv + 2, g1 + 1, 4, err) ||
+        !run_msm<G1>(S, L.mw, cur, z->d_c.as(), npub + 1, nv, g1 + 2, 4, err))
         return false;
     mark(z, 3, s);
-    if (!run_msm<G2>(S, L.mw, cur, z->d_b2, 0, nv + 2, S.at<P2>(L.off_g2), 1, err)) return false;
+    if (!run_msm<G2>(S, L.mw, cur, z->d_b2.as(), 0, nv + 2, S.at<P2>(L.off_g2), 1, err)) return false;
     mark(z, 4, s);
     if (!prep_sort(S, L.mh, S.at<uint8_t>(L.off_h), n, n, 0, nullptr, cur, err)) return false;
     mark(z, 5, s);
-    if (!run_msm<G1>(S, L.mh, cur, z->d_h, 0, n, g1 + 3, 4, err)) return false;
+    if (!run_msm<G1>(S, L.mh, cur, z->d_h.as(), 0, n, g1 + 3, 4, err)) return false;
     mark(z, 6, s);
     const Consts k = consts_of(z);
     hipLaunchKernelGGL(assemble_kernel, dim3(grid_for(rows * 3)), dim3(THREADS), 0, s, g1, d_rs, k, (uint32_t)rows, S.at<P1>(L.off_tmp));
@@ -629,22 +601,10 @@ bool enqueue_prove(gwb_zkey* z, gwb_r1cs* r, const void* d_w, size_t batch, uint
         sub = std::max<uint64_t>(1, sub * ws_cap() / (L.total + batch * 64 + 1));
     }
     const size_t rs_off = L.total;  // a multiple of 256
-    if (!ensure_ws(z, rs_off + batch * 64, err)) return false;
-    Fr* d_rs = (Fr*)((uint8_t*)z->d_ws + rs_off);
+    if (!z->ws.ensure(rs_off + batch * 64, "allocating the prover workspace", err)) return false;
+    Fr* d_rs = (Fr*)(z->ws.as<uint8_t>() + rs_off);
     // r, s go through a pinned buffer of the handle; the previous call's copy out of it is waited for first
-    hipError_t e = z->rs_done ? hipEventSynchronize((hipEvent_t)z->rs_done) : hipEventCreateWithFlags((hipEvent_t*)&z->rs_done, hipEventDisableTiming);
-    if (e == hipSuccess && z->h_rs_bytes < batch * 64) {
-        if (z->h_rs) (void)hipHostFree(z->h_rs);
-        z->h_rs = nullptr;
-        z->h_rs_bytes = 0;
-        e = hipHostMalloc(&z->h_rs, batch * 64, hipHostMallocDefault);
-        if (e == hipSuccess) z->h_rs_bytes = batch * 64;
-    }
-    if (e == hipSuccess) {
-        memcpy(z->h_rs, rs.data(), batch * 64);
-        e = hipMemcpyAsync(d_rs, z->h_rs, batch * 64, hipMemcpyHostToDevice, s);
-    }
-    if (e == hipSuccess) e = hipEventRecord((hipEvent_t)z->rs_done, s);
+    const hipError_t e = z->rs_stage.send(d_rs, rs.data(), batch * 64, s);
     if (e != hipSuccess) {
         err = hip_err("copying r, s", e);
         return false;
@@ -669,27 +629,12 @@ int prove_host(gwb_zkey* z, gwb_r1cs* r, const void* witness, size_t n_witness, 
         return 0;
     }
     if (r && !ensure_device(r->sys, -1, err)) return fail(status, err);
-    void *d_w = nullptr, *d_p = nullptr;
-    hipStream_t s = nullptr;
     const size_t wbytes = batch * n_witness * 32, pbytes = batch * GWB_GROTH16_PROOF_BYTES;
-    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&d_w, wbytes);
-    if (e == hipSuccess) e = hipMalloc(&d_p, pbytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_w, witness, wbytes, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) err = hip_err("staging the witness rows", e);
-    bool ok = e == hipSuccess && enqueue_prove(z, r, d_w, batch, GWB_FORM_CANONICAL, rsv, d_p, s, err);
-    if (ok) {
-        e = hipMemcpyAsync(proofs, d_p, pbytes, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            err = hip_err("running the prover", e);
-            ok = false;
-        }
-    }
-    if (d_w) (void)hipFree(d_w);
-    if (d_p) (void)hipFree(d_p);
-    if (s) (void)hipStreamDestroy(s);
-    if (!ok) return fail(status, err);
+    auto run = [&](unsigned char* const* d, hipStream_t s, std::string& err) {
+        return enqueue_prove(z, r, d[0], batch, GWB_FORM_CANONICAL, rsv, d[1], s, err);
+    };
+    if (!run_staged({wbytes, pbytes}, {{witness, wbytes, 0, 0}}, {{proofs, pbytes, 1, 0}}, "staging the witness rows", "running the prover", run, err))
+        return fail(status, err);
     set_ok(status);
     return 0;
 }
@@ -698,18 +643,7 @@ int prove_host(gwb_zkey* z, gwb_r1cs* r, const void* witness, size_t n_witness, 
 
 extern "C" {
 
-void gwb_zkey_free(gwb_zkey_t* z) {
-    if (!z) return;
-    for (void* p : {z->d_a, z->d_b1, z->d_b2, z->d_c, z->d_h, z->d_ws})
-        if (p) (void)hipFree(p);
-    if (z->h_rs) (void)hipHostFree(z->h_rs);
-    if (z->rs_done) (void)hipEventDestroy((hipEvent_t)z->rs_done);
-    for (void* e : z->events)
-        if (e) (void)hipEventDestroy((hipEvent_t)e);
-    release_qap(z->sys.qap);
-    release_device(z->sys);
-    delete z;
-}
+void gwb_zkey_free(gwb_zkey_t* z) { delete z; }
 
 int gwb_groth16_prove_batch_device(gwb_zkey_t* z, gwb_r1cs_t* r, const void* d_witness, size_t n_witness, size_t batch, uint32_t form_in,
                                    const void* rs, void* d_proofs, void* hip_stream, gw_status_t* status) {
@@ -746,29 +680,13 @@ int gwb_groth16_prove_wtns(gwb_zkey_t* z, gwb_r1cs_t* r, const void* wtns, size_
 
 int gwb_groth16_time_phases(gwb_zkey_t* z, int on) {
     if (!z) return 1;
-    for (void*& e : z->events) {
-        if (e) (void)hipEventDestroy((hipEvent_t)e);
-        e = nullptr;
-    }
-    if (!on) return 0;
-    for (void*& e : z->events) {
-        hipEvent_t h = nullptr;
-        if (hipEventCreate(&h) != hipSuccess) {
-            gwb_groth16_time_phases(z, 0);
-            return 1;
-        }
-        e = h;
-    }
-    return 0;
+    if (!on) z->events.off();
+    return on && z->events.on() != hipSuccess ? 1 : 0;
 }
 
 int gwb_groth16_phase_ms(gwb_zkey_t* z, float* ms) {
-    if (!z || !ms || !z->events[0]) return 1;
-    hipEvent_t* ev = (hipEvent_t*)z->events;
-    if (hipEventSynchronize(ev[7]) != hipSuccess) return 1;
     float d[7];
-    for (int i = 0; i < 7; ++i)
-        if (hipEventElapsedTime(d + i, ev[i], ev[i + 1]) != hipSuccess) return 1;
+    if (!z || !ms || z->events.elapsed(d) != hipSuccess) return 1;
     ms[0] = d[0];         // witness map
     ms[1] = d[1] + d[4];  // scalar preparation and sort (w, h)
     ms[2] = d[2] + d[5];  // G1 MSMs (A, B1, C; H)

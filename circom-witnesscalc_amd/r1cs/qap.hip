@@ -354,7 +354,7 @@ namespace {
 
 // twiddle and coset tables of the handle's domain, on its device (synchronous, first call only)
 bool ensure_tables(QapState& st, uint32_t p, std::string& err) {
-    if (st.d_tw) return true;
+    if (st.tw) return true;
     const uint64_t n = 1ull << p;
     Fr rm1 = cwc::fr_p();
     rm1.v[0] -= 1;  // r is odd
@@ -364,41 +364,23 @@ bool ensure_tables(QapState& st, uint32_t p, std::string& err) {
     Fr q = cwc::u256_shr(rm1, p), n_inv;
     cwc::u256_sub(n_inv, cwc::fr_p(), q);
     n_inv = cwc::fr_to_mont(n_inv);
-    void *tw = nullptr, *cs = nullptr;
-    hipStream_t s = nullptr;
-    hipError_t e = hipMalloc(&tw, n * 32);
-    if (e == hipSuccess) e = hipMalloc(&cs, n * 32);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    DeviceBuf tw, cs;
+    Stream s;
+    hipError_t e = tw.alloc(n * 32);
+    if (e == hipSuccess) e = cs.alloc(n * 32);
+    if (e == hipSuccess) e = s.create();
     if (e == hipSuccess) {
         const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + THREADS - 1) / THREADS, 4096);
-        hipLaunchKernelGGL(qap_tables_kernel, dim3(blocks), dim3(THREADS), 0, s, (Fr*)tw, (Fr*)cs, p, powers_of(wn), powers_of(g), n_inv, make_plan(p));
+        hipLaunchKernelGGL(qap_tables_kernel, dim3(blocks), dim3(THREADS), 0, s, tw.as<Fr>(), cs.as<Fr>(), p, powers_of(wn), powers_of(g), n_inv, make_plan(p));
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }
-    if (s) (void)hipStreamDestroy(s);
     if (e != hipSuccess) {
-        if (tw) (void)hipFree(tw);
-        if (cs) (void)hipFree(cs);
         err = hip_err("building the QAP twiddle tables", e);
         return false;
     }
-    st.d_tw = tw;
-    st.d_coset = cs;
-    return true;
-}
-
-bool ensure_workspace(QapState& q, uint64_t bytes, std::string& err) {
-    if (q.ws_bytes >= bytes) return true;
-    if (q.d_ws) (void)hipFree(q.d_ws);  // (synchronises with earlier work that used it)
-    q.d_ws = nullptr;
-    q.ws_bytes = 0;
-    hipError_t e = hipMalloc(&q.d_ws, bytes);
-    if (e != hipSuccess) {
-        q.d_ws = nullptr;
-        err = hip_err("allocating the QAP workspace", e);
-        return false;
-    }
-    q.ws_bytes = bytes;
+    st.tw = std::move(tw);
+    st.coset = std::move(cs);
     return true;
 }
 
@@ -425,15 +407,14 @@ bool launch_pass(int kind, PassArgs a, uint64_t rows, hipStream_t stream, std::s
 // The NTT chain over `rows` rows of evaluations (A, B in the workspace, C in d_h): three inverse transforms, the coset
 // shift, three forward transforms and h = A B - C into d_h.  Records the state's phase events 1 to 4.
 bool transform(QapState& q, uint32_t p, Fr* A, Fr* B, Fr* d_h, uint64_t rows, uint32_t form_out, hipStream_t stream, std::string& err) {
-    hipEvent_t* ev = (hipEvent_t*)q.events;  // (ev[0] null: not timing)
-    if (ev[0]) (void)hipEventRecord(ev[1], stream);
+    q.events.record(1, stream);
     const Plan pl = make_plan(p);
     PassArgs a{};
     a.arr[0] = A;
     a.arr[1] = B;
     a.arr[2] = d_h;
-    a.tw = (const Fr*)q.d_tw;
-    a.coset = (const Fr*)q.d_coset;
+    a.tw = q.tw.as<const Fr>();
+    a.coset = q.coset.as<const Fr>();
     a.log_n = p;
     a.mont_out = form_out == GWB_FORM_MONTGOMERY ? 1u : 0u;
     uint32_t log_s[4], below = p;
@@ -446,13 +427,13 @@ bool transform(QapState& q, uint32_t p, Fr* A, Fr* B, Fr* d_h, uint64_t rows, ui
         a.combine = 0;
         if (!launch_pass(PASS_INV, a, rows, stream, err)) return false;
     }
-    if (ev[0]) (void)hipEventRecord(ev[2], stream);
+    q.events.record(2, stream);
     a.log_l = pl.logl[outer];
     a.log_s = 0;
     a.log_cc = 0;
     a.combine = outer == 0;
     if (!launch_pass(PASS_MID, a, rows, stream, err)) return false;
-    if (ev[0]) (void)hipEventRecord(ev[3], stream);
+    q.events.record(3, stream);
     for (uint32_t t = outer; t-- > 0;) {
         a.log_l = pl.logl[t];
         a.log_s = log_s[t];
@@ -460,7 +441,7 @@ bool transform(QapState& q, uint32_t p, Fr* A, Fr* B, Fr* d_h, uint64_t rows, ui
         a.combine = t == 0;
         if (!launch_pass(PASS_FWD, a, rows, stream, err)) return false;
     }
-    if (ev[0]) (void)hipEventRecord(ev[4], stream);
+    q.events.record(4, stream);
     return true;
 }
 
@@ -494,17 +475,16 @@ bool enqueue_sub(const Map& m, const uint8_t* d_w, uint64_t rows, uint32_t form_
     RowSystem& s = *m.sys;
     const uint32_t p = m.p, nr = s.n_rows, nw = s.n_wires;
     const uint64_t n = 1ull << p;
-    Fr* A = (Fr*)s.qap.d_ws;
+    Fr* A = s.qap.ws.as<Fr>();
     Fr* B = A + rows * n;
     const uint32_t mont = form_in == GWB_FORM_MONTGOMERY ? 1u : 0u;
-    hipEvent_t* ev = (hipEvent_t*)s.qap.events;  // (ev[0] null: not timing)
-    if (ev[0]) (void)hipEventRecord(ev[0], stream);
+    s.qap.events.record(0, stream);
     const int cus = cu_count(s.device);
     if (nr) {  // (an `.r1cs` may have no constraints; section 4 has at least one row)
         EvalGrid g;
         if (!eval_grid(s, rows, cus, EVAL_WAVES, g, err)) return false;
-        hipLaunchKernelGGL(eval_for(g.t, s.stride), dim3(g.tiles, g.gy), dim3(64 * EVAL_WAVES), 0, stream, (const uint32_t*)s.d_rowptr,
-                           (const uint32_t*)s.d_fac, (const uint32_t*)s.d_cidx, (const Fr*)s.d_coef, (const uint32_t*)s.d_perm, nr, d_w, nw,
+        hipLaunchKernelGGL(eval_for(g.t, s.stride), dim3(g.tiles, g.gy), dim3(64 * EVAL_WAVES), 0, stream, s.d_rowptr.as<const uint32_t>(),
+                           s.d_fac.as<const uint32_t>(), s.d_cidx.as<const uint32_t>(), s.d_coef.as<const Fr>(), s.d_perm.as<const uint32_t>(), nr, d_w, nw,
                            (uint32_t)rows, mont, A, B, d_h, p);
     }
     // the rows above: the one difference between the sources
@@ -531,7 +511,7 @@ bool enqueue_qap(const Map& m, const void* d_witness, size_t batch, uint32_t for
     if (!ensure_device(s, m.home, err) || !ensure_tables(s.qap, m.p, err)) return false;
     const uint64_t per = ws_per_row(m.p);
     const uint64_t sub = std::min<uint64_t>(batch, std::max<uint64_t>(1, ws_cap() / per));
-    if (!ensure_workspace(s.qap, sub * per, err)) return false;
+    if (!s.qap.ws.ensure(sub * per, "allocating the QAP workspace", err)) return false;
     const uint64_t n = 1ull << m.p;
     for (uint64_t s0 = 0; s0 < batch; s0 += sub) {
         const uint64_t rows = std::min<uint64_t>(sub, batch - s0);
@@ -549,27 +529,12 @@ int qap_host(const Map& m, const void* witness, size_t n_witness, size_t batch, 
         return 0;
     }
     if (!ensure_device(*m.sys, m.home, err)) return fail(status, err);
-    void *d_w = nullptr, *d_h = nullptr;
-    hipStream_t s = nullptr;
     const size_t wbytes = batch * n_witness * 32, hbytes = (batch * 32) << m.p;
-    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&d_w, wbytes);
-    if (e == hipSuccess) e = hipMalloc(&d_h, hbytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_w, witness, wbytes, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) err = hip_err("staging the witness rows", e);
-    bool ok = e == hipSuccess && enqueue_qap(m, d_w, batch, GWB_FORM_CANONICAL, d_h, form_out, s, err);
-    if (ok) {
-        e = hipMemcpyAsync(h, d_h, hbytes, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            err = hip_err("running the QAP witness map", e);
-            ok = false;
-        }
-    }
-    if (d_w) (void)hipFree(d_w);
-    if (d_h) (void)hipFree(d_h);
-    if (s) (void)hipStreamDestroy(s);
-    if (!ok) return fail(status, err);
+    auto run = [&](unsigned char* const* d, hipStream_t s, std::string& err) {
+        return enqueue_qap(m, d[0], batch, GWB_FORM_CANONICAL, d[1], form_out, s, err);
+    };
+    if (!run_staged({wbytes, hbytes}, {{witness, wbytes, 0, 0}}, {{h, hbytes, 1, 0}}, "staging the witness rows", "running the QAP witness map", run, err))
+        return fail(status, err);
     set_ok(status);
     return 0;
 }
@@ -617,18 +582,6 @@ bool qap_enqueue(gwb_zkey* z, const void* d_witness, size_t batch, uint32_t form
                  std::string& err) {
     Map m;
     return map_of(z, m, err) && enqueue_qap(m, d_witness, batch, form_in, d_h, form_out, (hipStream_t)stream, err);
-}
-
-void release_qap(QapState& q) {
-    for (void** p : {&q.d_tw, &q.d_coset, &q.d_ws}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    q.ws_bytes = 0;
-    for (void*& e : q.events) {
-        if (e) (void)hipEventDestroy((hipEvent_t)e);
-        e = nullptr;
-    }
 }
 
 }  // namespace cwc_r1cs
@@ -679,20 +632,8 @@ int gwb_zkey_qap_batch_host(gwb_zkey_t* z, const void* witness, size_t n_witness
 
 int gwb_r1cs_qap_time_phases(gwb_r1cs_t* r, int on) {
     if (!r) return 1;
-    for (void*& e : r->sys.qap.events) {
-        if (e) (void)hipEventDestroy((hipEvent_t)e);
-        e = nullptr;
-    }
-    if (!on) return 0;
-    for (void*& e : r->sys.qap.events) {
-        hipEvent_t h = nullptr;
-        if (hipEventCreate(&h) != hipSuccess) {
-            gwb_r1cs_qap_time_phases(r, 0);
-            return 1;
-        }
-        e = h;
-    }
-    return 0;
+    if (!on) r->sys.qap.events.off();
+    return on && r->sys.qap.events.on() != hipSuccess ? 1 : 0;
 }
 
 int gwb_r1cs_modmul_rate(double* products_per_s) {
@@ -701,35 +642,28 @@ int gwb_r1cs_modmul_rate(double* products_per_s) {
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
         return 1;
     const uint32_t blocks = (uint32_t)cus * 8, iters = 4096;  // 8 waves per SIMD
-    void* out = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipMalloc(&out, (size_t)blocks * THREADS * 32);
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    float ms = 0;
+    DeviceBuf out;
+    PhaseEvents<2> ev;
+    hipError_t e = out.alloc((size_t)blocks * THREADS * 32);
+    if (e == hipSuccess) e = ev.on();
+    float ms[1] = {0};
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(modmul_probe_kernel, dim3(blocks), dim3(THREADS), 0, nullptr, (Fr*)out, 16u);  // warm-up
-        (void)hipEventRecord(e0, nullptr);
-        hipLaunchKernelGGL(modmul_probe_kernel, dim3(blocks), dim3(THREADS), 0, nullptr, (Fr*)out, iters);
-        (void)hipEventRecord(e1, nullptr);
+        hipLaunchKernelGGL(modmul_probe_kernel, dim3(blocks), dim3(THREADS), 0, nullptr, out.as<Fr>(), 16u);  // warm-up
+        ev.record(0, nullptr);
+        hipLaunchKernelGGL(modmul_probe_kernel, dim3(blocks), dim3(THREADS), 0, nullptr, out.as<Fr>(), iters);
+        ev.record(1, nullptr);
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        if (e == hipSuccess) e = ev.elapsed(ms);
     }
-    if (out) (void)hipFree(out);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess || ms <= 0) return 1;
-    *products_per_s = (double)blocks * THREADS * 4 * iters / (ms * 1e-3);
+    if (e != hipSuccess || ms[0] <= 0) return 1;
+    *products_per_s = (double)blocks * THREADS * 4 * iters / (ms[0] * 1e-3);
     return 0;
 }
 
 int gwb_r1cs_qap_phase_ms(gwb_r1cs_t* r, float* ms) {
-    if (!r || !ms || !r->sys.qap.events[0]) return 1;
-    hipEvent_t* ev = (hipEvent_t*)r->sys.qap.events;
-    if (hipEventSynchronize(ev[4]) != hipSuccess) return 1;
-    for (int i = 0; i < 4; ++i)
-        if (hipEventElapsedTime(ms + i, ev[i], ev[i + 1]) != hipSuccess) return 1;
+    float t[4];
+    if (!r || !ms || r->sys.qap.events.elapsed(t) != hipSuccess) return 1;
+    memcpy(ms, t, sizeof t);
     return 0;
 }
 

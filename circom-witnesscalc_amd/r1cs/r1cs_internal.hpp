@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../csrc/fr_gfx950.hpp"
+#include "device_owners.hpp"
 #include "../../include/graph_witness_r1cs.h"
 
 namespace cwc_r1cs {
@@ -35,13 +36,12 @@ bool parse_wtns(const void* wtns, size_t len, const uint8_t** values, uint64_t* 
 
 // Device state of one QAP domain (qap.hip), owned by the row system whose witness map runs on it: twiddles w_n^e and
 // per-position coset factors, n each, built at the first QAP call; the A / B workspace, grown on demand; phase-timing events
-// (hipEvent_t, recorded around each phase while events[0] is set).
+// (recorded around each phase while timing is on).
 struct QapState {
-    void *d_tw = nullptr, *d_coset = nullptr, *d_ws = nullptr;
-    size_t ws_bytes = 0;
-    void* events[5] = {};
+    DeviceBuf tw, coset;
+    Workspace ws;
+    PhaseEvents<5> events;
 };
-void release_qap(QapState& q);                           // qap.hip: the QAP tables, workspace and events
 
 // Rows of linear combinations over a witness, as the check and evaluation kernels read them (lincomb.hpp): an `.r1cs`
 // (loader.cc; stride 3: sides A, B, C) or section 4 of a zkey (zkey_coefs.cc; stride 2: A, B, the public rows among them).
@@ -55,9 +55,9 @@ struct RowSystem {
     uint32_t n_rows = 0;        // evaluated rows: n_constraints, or 1 + the largest constraint index of section 4
     uint32_t n_wires = 0;       // elements per witness row: n_wires, or nVars
     uint32_t tile_width = 0;    // witness rows per wave, 0 = from the batch size
-    // device copies (first call that needs them) and the QAP domain's state, on the same device
+    // device copies (first call that needs them; all five or none) and the QAP domain's state, on the same device
     int device = -1;
-    void *d_rowptr = nullptr, *d_fac = nullptr, *d_cidx = nullptr, *d_coef = nullptr, *d_perm = nullptr;
+    DeviceBuf d_rowptr, d_fac, d_cidx, d_coef, d_perm;
     QapState qap;
 };
 
@@ -65,7 +65,6 @@ const char* prefix_of(const RowSystem& s);               // "r1cs: " or "zkey: "
 // The arrays go to the current device at the first call and stay there; `home` >= 0 names the device they have to share
 // (a zkey's uploaded points), -1 leaves the choice to the current device.
 bool ensure_device(RowSystem& s, int home, std::string& err);
-void release_device(RowSystem& s);
 bool check_args(const RowSystem& s, size_t n_witness, size_t batch, std::string& err);
 
 // Grid of a kernel with the check's lane mapping: a wave covers t rows x 64 / t constraints, blockIdx.x walks the `tiles`

@@ -249,21 +249,18 @@ Tables g_tables[MAX_DEVICES];
 
 template <class T>
 hipError_t build_table(const Affine<T>& gen, void** out, hipStream_t s) {
-    void *bases = nullptr, *table = nullptr;
-    hipError_t e = hipMalloc(&bases, N_WIN * sizeof(Affine<T>));
-    if (e == hipSuccess) e = hipMalloc(&table, TABLE_POINTS * sizeof(Affine<T>));
+    DeviceBuf bases, table;
+    hipError_t e = bases.alloc(N_WIN * sizeof(Affine<T>));
+    if (e == hipSuccess) e = table.alloc(TABLE_POINTS * sizeof(Affine<T>));
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(table_bases_kernel<T>, dim3(1), dim3(64), 0, s, gen, (Affine<T>*)bases);
-        hipLaunchKernelGGL(table_fill_kernel<T>, dim3(blocks_for(TABLE_POINTS, THREADS)), dim3(THREADS), 0, s, (const Affine<T>*)bases, (Affine<T>*)table);
+        hipLaunchKernelGGL(table_bases_kernel<T>, dim3(1), dim3(64), 0, s, gen, bases.as<Affine<T>>());
+        hipLaunchKernelGGL(table_fill_kernel<T>, dim3(blocks_for(TABLE_POINTS, THREADS)), dim3(THREADS), 0, s, bases.as<const Affine<T>>(),
+                           table.as<Affine<T>>());
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }
-    if (bases) (void)hipFree(bases);
-    if (e != hipSuccess) {
-        if (table) (void)hipFree(table);
-        return e;
-    }
-    *out = table;
+    if (e != hipSuccess) return e;
+    *out = table.release();  // kept until the process ends, by design: the table leaves its owner here
     return hipSuccess;
 }
 
@@ -277,11 +274,10 @@ bool ensure_tables(Tables& t, std::string& err) {
     std::lock_guard<std::mutex> lock(g_tables_mutex);
     Tables& g = g_tables[dev];
     if (!g.g2) {
-        hipStream_t s = nullptr;
-        e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+        Stream s;
+        e = s.create();
         if (e == hipSuccess && !g.g1) e = build_table<G1>(g1_generator(), &g.g1, s);
         if (e == hipSuccess) e = build_table<G2>(g2_generator(), &g.g2, s);
-        if (s) (void)hipStreamDestroy(s);
         if (e != hipSuccess) {
             err = hip_err("building the tables of generator multiples", e);
             return false;
@@ -573,7 +569,7 @@ int setup(gwb_r1cs* r, const gwb_groth16_trapdoor_t* trapdoor, void** zkey, size
                  o_x2 = cw.take(n2 * sizeof(Xyzz<G2>)), o_p1 = cw.take(n1 * G1_BYTES), o_p2 = cw.take(n2 * G2_BYTES);
     hipError_t e = D.open(cs.o, std::max<size_t>(cw.o, 256));
     if (e != hipSuccess) return fail(status, hip_err("allocating the setup workspace", e));
-    uint8_t *S = (uint8_t*)D.secret, *W = (uint8_t*)D.work;
+    uint8_t *S = D.secret.as<uint8_t>(), *W = D.work.as<uint8_t>();
     const DeviceColumns dc = upload_columns(col, r->sys.coef, W + o_col, D.s, e);
     // the header's scalars, at the end of the two scalar lists
     Fr *lag = (Fr*)(S + o_lag), *s1 = (Fr*)(S + o_s1), *s2 = (Fr*)(S + o_s2);
@@ -587,33 +583,33 @@ int setup(gwb_r1cs* r, const gwb_groth16_trapdoor_t* trapdoor, void** zkey, size
 
     Fr wn, g;
     qap_roots(p, wn, g);
-    (void)hipEventRecord(D.ev[0], D.s);
+    D.ev.record(0, D.s);
     hipLaunchKernelGGL(setup_lagrange_kernel, dim3(blocks_for((2ull * n + INV_CHUNK - 1) / INV_CHUNK, THREADS)), dim3(THREADS), 0, D.s, lag,
                        (Fr*)(S + o_pref), p, powers_of(wn), g, sec.tau_m, sec.zf, sec.zf2);
-    (void)hipEventRecord(D.ev[1], D.s);
+    D.ev.record(1, D.s);
     if (n_seg)
         hipLaunchKernelGGL(setup_segments_kernel, dim3(blocks_for(n_seg, THREADS)), dim3(THREADS), 0, D.s, dc.ent, dc.cidx, dc.coef, (const Fr*)lag, dc.seg_off,
                            n_seg, (Fr*)(S + o_part));
     hipLaunchKernelGGL(setup_wires_kernel, dim3(blocks_for(nw, THREADS)), dim3(THREADS), 0, D.s, (const Fr*)(S + o_part), dc.seg_key, dc.wire_seg,
                        (const Fr*)lag, nw, nc, n_pub, (Fr*)(S + o_uvw));
-    (void)hipEventRecord(D.ev[2], D.s);
+    D.ev.record(2, D.s);
     hipLaunchKernelGGL(setup_scalars_kernel, dim3(std::min<uint32_t>(blocks_for(std::max(nw, n), THREADS), 4096)), dim3(THREADS), 0, D.s,
                        (const Fr*)(S + o_uvw), (const Fr*)lag, nw, n_pub, n, sec.k, s1, s2);
-    (void)hipEventRecord(D.ev[3], D.s);
+    D.ev.record(3, D.s);
     hipLaunchKernelGGL(gen_mul_kernel<G1>, dim3(blocks_for(n1, THREADS)), dim3(THREADS), 0, D.s, (const Fr*)s1, (uint32_t)n1, (const Affine<G1>*)tab.g1,
                        (Xyzz<G1>*)(W + o_x1));
-    (void)hipEventRecord(D.ev[4], D.s);
+    D.ev.record(4, D.s);
     hipLaunchKernelGGL(gen_mul_kernel<G2>, dim3(blocks_for(n2, THREADS)), dim3(THREADS), 0, D.s, (const Fr*)s2, (uint32_t)n2, (const Affine<G2>*)tab.g2,
                        (Xyzz<G2>*)(W + o_x2));
     enqueue_affine<G1>(W + o_x1, (uint32_t)n1, W + o_p1, false, D.s);
     enqueue_affine<G2>(W + o_x2, (uint32_t)n2, W + o_p2, false, D.s);
-    (void)hipEventRecord(D.ev[5], D.s);
+    D.ev.record(5, D.s);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(status, hip_err("launching the setup kernels", e));
     std::vector<uint8_t> p1(n1 * G1_BYTES), p2(n2 * G2_BYTES);
     e = hipMemcpyAsync(p1.data(), W + o_p1, p1.size(), hipMemcpyDeviceToHost, D.s);
     if (e == hipSuccess) e = hipMemcpyAsync(p2.data(), W + o_p2, p2.size(), hipMemcpyDeviceToHost, D.s);
-    if (e == hipSuccess) e = hipMemsetAsync(D.secret, 0, D.secret_bytes, D.s);
+    if (e == hipSuccess) e = hipMemsetAsync(D.secret.as(), 0, D.secret_bytes, D.s);
     if (e == hipSuccess) e = hipStreamSynchronize(D.s);
     if (e != hipSuccess) return fail(status, hip_err("running the setup", e));
     g_phases.record(D.ev);

@@ -324,7 +324,7 @@ int setup(gwb_r1cs* r, const uint8_t* ptau, size_t ptau_len, const uint8_t* delt
                  o_p2 = cw.take(n2 * G2_BYTES), o_flag = cw.take(8 * sizeof(unsigned long long)), o_pub = cw.take(2 * 32);
     hipError_t e = D.open(256, cw.o);
     if (e != hipSuccess) return fail(status, hip_err("allocating the setup workspace", e));
-    uint8_t* W = (uint8_t*)D.work;
+    uint8_t* W = D.work.as<uint8_t>();
     auto up = [&](size_t off, const void* src, size_t bytes) {
         if (e == hipSuccess && bytes) e = hipMemcpyAsync(W + off, src, bytes, hipMemcpyHostToDevice, D.s);
     };
@@ -352,10 +352,10 @@ int setup(gwb_r1cs* r, const uint8_t* ptau, size_t ptau_len, const uint8_t* delt
     const Fr pub[2] = {inverse_of_u32(n), inverse_of_u32(2 * n)};
     up(o_pub, pub, sizeof pub);
     if (e == hipSuccess) e = hipMemsetAsync(W + o_flag, 0xff, 8 * sizeof(unsigned long long), D.s);
-    if (e == hipSuccess) e = hipMemcpyAsync(D.secret, &dl, sizeof dl, hipMemcpyHostToDevice, D.s);
+    if (e == hipSuccess) e = hipMemcpyAsync(D.secret.as(), &dl, sizeof dl, hipMemcpyHostToDevice, D.s);
     if (e == hipSuccess) e = hipStreamSynchronize(D.s);  // the copies have left the host arrays
     if (e != hipSuccess) return fail(status, hip_err("uploading the ceremony points and the transposed constraint matrices", e));
-    const Fr *d_delta = (const Fr*)D.secret, *d_delta_inv = d_delta + 1, *d_inv_n = (const Fr*)(W + o_pub), *d_inv_2n = d_inv_n + 1;
+    const Fr *d_delta = D.secret.as<const Fr>(), *d_delta_inv = d_delta + 1, *d_inv_n = (const Fr*)(W + o_pub), *d_inv_2n = d_inv_n + 1;
 
     Xyzz<G1>*lag1 = (Xyzz<G1>*)(W + o_lag1), *l1 = lag1, *la = lag1 + n, *lb = lag1 + 2 * (size_t)n, *dd = lag1 + 3 * (size_t)n;
     Xyzz<G1>*t1 = (Xyzz<G1>*)(W + o_t1), *x1 = (Xyzz<G1>*)(W + o_x1);
@@ -363,7 +363,7 @@ int setup(gwb_r1cs* r, const uint8_t* ptau, size_t ptau_len, const uint8_t* delt
     unsigned long long* flag = (unsigned long long*)(W + o_flag);
     Fr *tw = (Fr*)(W + o_tw), *twg = (Fr*)(W + o_twg);
     std::vector<Checked> checked;
-    (void)hipEventRecord(D.ev[0], D.s);
+    D.ev.record(0, D.s);
     if (pl.from_file) {
         const uint64_t lvl = (uint64_t)n - 1;
         checked = {{12, lvl, 0, 1, false}, {14, lvl, 0, 1, false}, {15, lvl, 0, 1, false}, {12, 2 * (uint64_t)n - 1, 1, 2, false}, {13, lvl, 0, 1, true}};
@@ -380,7 +380,7 @@ int setup(gwb_r1cs* r, const uint8_t* ptau, size_t ptau_len, const uint8_t* delt
         enqueue_load<G1>(W + o_raw1 + 3 * nb1, n, 0, 1, false, p, lb, flag + 2, D.s);
         enqueue_load<G2>(W + o_raw2, n, 0, 1, false, p, l2, flag + 3, D.s);
     }
-    (void)hipEventRecord(D.ev[1], D.s);
+    D.ev.record(1, D.s);
     if (!pl.from_file) {
         Fr wn, g;
         qap_roots(p, wn, g);
@@ -393,12 +393,12 @@ int setup(gwb_r1cs* r, const uint8_t* ptau, size_t ptau_len, const uint8_t* delt
         e = hipMemcpyAsync(x1 + off_h, dd, (size_t)n * X1, hipMemcpyDeviceToDevice, D.s);
         if (e != hipSuccess) return fail(status, hip_err("placing H", e));
     }
-    (void)hipEventRecord(D.ev[2], D.s);
+    D.ev.record(2, D.s);
     if (!pl.from_file) {
         enqueue_stages<G2>(l2, p, 1, tw, D.s);
         enqueue_scale<G2>(l2, n, d_inv_n, D.s);
     }
-    (void)hipEventRecord(D.ev[3], D.s);
+    D.ev.record(3, D.s);
     Xyzz<G1>*pa = (Xyzz<G1>*)(W + o_pa), *pk = (Xyzz<G1>*)(W + o_pk);
     Xyzz<G2>* pq = (Xyzz<G2>*)(W + o_pq);
     const Xyzz<G1>* none1 = nullptr;
@@ -411,19 +411,19 @@ int setup(gwb_r1cs* r, const uint8_t* ptau, size_t ptau_len, const uint8_t* delt
     }
     hipLaunchKernelGGL(wires_g1_kernel, dim3(blocks_for(nw, THREADS)), dim3(THREADS), 0, D.s, (const Xyzz<G1>*)pa, (const Xyzz<G1>*)pk, dc.seg_key, dc.wire_seg,
                        (const Xyzz<G1>*)l1, (const Xyzz<G1>*)lb, nw, nc, n_pub, n, x1);
-    (void)hipEventRecord(D.ev[4], D.s);
+    D.ev.record(4, D.s);
     if (n_seg)
         hipLaunchKernelGGL(segments_kernel<G2>, dim3(blocks_for(n_seg, THREADS)), dim3(THREADS), 0, D.s, dc.ent, dc.cidx, dc.coef, dc.seg_off, dc.seg_key, n_seg, none2,
                            (const Xyzz<G2>*)l2, none2, pq);
     hipLaunchKernelGGL(wires_one_kernel<G2>, dim3(blocks_for(nw, THREADS)), dim3(THREADS), 0, D.s, (const Xyzz<G2>*)pq, dc.seg_key, dc.wire_seg, nw, 1u, x2);
-    (void)hipEventRecord(D.ev[5], D.s);
+    D.ev.record(5, D.s);
     if (!delta_is_one) enqueue_scale<G1>(x1 + off_c, (nw - n_pub - 1) + n, d_delta_inv, D.s);  // C and H
     enqueue_scale<G1>(x1 + (n1 - 1), 1, d_delta, D.s);
     enqueue_scale<G2>(x2 + (n2 - 1), 1, d_delta, D.s);
-    (void)hipEventRecord(D.ev[6], D.s);
+    D.ev.record(6, D.s);
     enqueue_affine_g1(x1, (uint32_t)n1, W + o_p1, false, D.s);
     enqueue_affine_g2(x2, (uint32_t)n2, W + o_p2, false, D.s);
-    (void)hipEventRecord(D.ev[7], D.s);
+    D.ev.record(7, D.s);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(status, hip_err("launching the setup kernels", e));
     std::vector<uint8_t> p1(n1 * G1_BYTES), p2(n2 * G2_BYTES);
@@ -431,7 +431,7 @@ int setup(gwb_r1cs* r, const uint8_t* ptau, size_t ptau_len, const uint8_t* delt
     e = hipMemcpyAsync(p1.data(), W + o_p1, p1.size(), hipMemcpyDeviceToHost, D.s);
     if (e == hipSuccess) e = hipMemcpyAsync(p2.data(), W + o_p2, p2.size(), hipMemcpyDeviceToHost, D.s);
     if (e == hipSuccess) e = hipMemcpyAsync(faults, flag, sizeof faults, hipMemcpyDeviceToHost, D.s);
-    if (e == hipSuccess) e = hipMemsetAsync(D.secret, 0, D.secret_bytes, D.s);
+    if (e == hipSuccess) e = hipMemsetAsync(D.secret.as(), 0, D.secret_bytes, D.s);
     if (e == hipSuccess) e = hipStreamSynchronize(D.s);
     if (e != hipSuccess) return fail(status, hip_err("running the setup", e));
     for (size_t a = 0; a < checked.size(); ++a)

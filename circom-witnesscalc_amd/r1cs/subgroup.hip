@@ -99,22 +99,15 @@ uint64_t chunk_points() {
 
 // The device side of one file check: a stream and the buffers of one piece, released with the object.
 struct Checker {
-    hipStream_t s = nullptr;
-    uint8_t* d_pts = nullptr;
-    uint32_t* d_status = nullptr;
-    unsigned long long* d_res = nullptr;  // [0] the smallest 4 i + status, [1]'s low word the count
+    Stream s;
+    DeviceBuf pts, status, res;  // res: [0] the smallest 4 i + status, [1]'s low word the count
     uint64_t chunk = 0;
-    ~Checker() {
-        for (void* p : {(void*)d_pts, (void*)d_status, (void*)d_res})
-            if (p) (void)hipFree(p);
-        if (s) (void)hipStreamDestroy(s);
-    }
     bool open(uint64_t largest, std::string& err) {
         chunk = std::max<uint64_t>(1, std::min(chunk_points(), largest));
-        hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipMalloc((void**)&d_pts, chunk * G2_BYTES);
-        if (e == hipSuccess) e = hipMalloc((void**)&d_status, chunk * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&d_res, 2 * sizeof(unsigned long long));
+        hipError_t e = s.create();
+        if (e == hipSuccess) e = pts.alloc(chunk * G2_BYTES);
+        if (e == hipSuccess) e = status.alloc(chunk * sizeof(uint32_t));
+        if (e == hipSuccess) e = res.alloc(2 * sizeof(unsigned long long));
         if (e != hipSuccess) err = hip_err("allocating the G2 subgroup check's buffers", e);
         return e == hipSuccess;
     }
@@ -122,6 +115,9 @@ struct Checker {
     // status, and the number of such points (all pieces are checked, so the count is the array's).  statuses != nullptr: every
     // status, for a short array.
     bool run(const uint8_t* p, uint64_t n, uint64_t& first, uint32_t& first_status, uint64_t& count, uint32_t* statuses, std::string& err) {
+        uint8_t* d_pts = pts.as<uint8_t>();
+        uint32_t* d_status = status.as<uint32_t>();
+        unsigned long long* d_res = res.as<unsigned long long>();
         first = NONE_BAD;
         first_status = GWB_G16V_VALID;
         count = 0;

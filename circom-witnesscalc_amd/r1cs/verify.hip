@@ -239,11 +239,8 @@ struct gwb_g16vk {
     bool ab_ready = false;
     uint8_t ab[GWB_GT_BYTES] = {};
     int device = -1;
-    Line* d_lines = nullptr;
-    A1* d_tab = nullptr;
-    Fq12* d_ab = nullptr;
-    void* d_ws = nullptr;
-    size_t ws_bytes = 0;
+    DeviceBuf d_lines, d_tab, d_ab;  // Line[2 N_LINES], A1[tab.size()], one Fq12: all three (ensure_key) or none
+    Workspace ws;
 };
 
 namespace {
@@ -294,31 +291,6 @@ void load_key(const uint8_t* d, size_t len, uint32_t n_public, gwb_g16vk& k) {
     }
 }
 
-void release_device(gwb_g16vk* k) {
-    for (void* p : {(void*)k->d_lines, (void*)k->d_tab, (void*)k->d_ab, k->d_ws})
-        if (p) (void)hipFree(p);
-    k->d_lines = nullptr;
-    k->d_tab = nullptr;
-    k->d_ab = nullptr;
-    k->d_ws = nullptr;
-    k->ws_bytes = 0;
-}
-
-bool ensure_ws(gwb_g16vk* k, size_t bytes, std::string& err) {
-    if (k->ws_bytes >= bytes) return true;
-    if (k->d_ws) (void)hipFree(k->d_ws);
-    k->d_ws = nullptr;
-    k->ws_bytes = 0;
-    const hipError_t e = hipMalloc(&k->d_ws, bytes);
-    if (e != hipSuccess) {
-        k->d_ws = nullptr;
-        err = hip_err("allocating the verifier workspace", e);
-        return false;
-    }
-    k->ws_bytes = bytes;
-    return true;
-}
-
 // the key's device data on the current device (first call; synchronous): lines of gamma2 and delta2, the IC tables,
 // e(alpha1, beta2) (through the pairing path) in canonical bytes and in Montgomery form
 bool ensure_key(gwb_g16vk* k, std::string& err) {
@@ -329,28 +301,23 @@ bool ensure_key(gwb_g16vk* k, std::string& err) {
         err = "groth16 verify: the key's data live on device " + std::to_string(k->device) + ", the current device is " + std::to_string(dev);
         return false;
     }
-    hipStream_t s = nullptr;
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&k->d_lines, 2 * N_LINES * sizeof(Line));
-    if (e == hipSuccess) e = hipMalloc(&k->d_tab, std::max<size_t>(1, k->tab.size() * sizeof(A1)));
-    if (e == hipSuccess) e = hipMalloc(&k->d_ab, sizeof(Fq12));
-    if (e == hipSuccess && !k->tab.empty()) e = hipMemcpyAsync(k->d_tab, k->tab.data(), k->tab.size() * sizeof(A1), hipMemcpyHostToDevice, s);
+    Stream s;
+    DeviceBuf lines, tab, ab;  // the key gets all three or none
+    if (e == hipSuccess) e = s.create();
+    if (e == hipSuccess) e = lines.alloc(2 * N_LINES * sizeof(Line));
+    if (e == hipSuccess) e = tab.alloc(k->tab.size() * sizeof(A1));
+    if (e == hipSuccess) e = ab.alloc(sizeof(Fq12));
+    if (e == hipSuccess && !k->tab.empty()) e = hipMemcpyAsync(tab.as(), k->tab.data(), k->tab.size() * sizeof(A1), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(lines_kernel, dim3(1), dim3(THREADS), 0, s, k->gamma2, k->delta2, k->d_lines);
+        hipLaunchKernelGGL(lines_kernel, dim3(1), dim3(THREADS), 0, s, k->gamma2, k->delta2, lines.as<Line>());
         e = hipGetLastError();
     }
-    if (e == hipSuccess && !ensure_ws(k, 64 + 128 + GWB_GT_BYTES + pairing_ws(1), err)) {
-        if (s) (void)hipStreamDestroy(s);
-        release_device(k);
-        return false;
-    }
-    uint8_t* ws = (uint8_t*)k->d_ws;
+    if (e == hipSuccess && !k->ws.ensure(64 + 128 + GWB_GT_BYTES + pairing_ws(1), "allocating the verifier workspace", err)) return false;
+    uint8_t* ws = k->ws.as<uint8_t>();
     if (e == hipSuccess) e = hipMemcpyAsync(ws, k->points.data(), 64, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(ws + 64, k->points.data() + 64, 128, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && !enqueue_pairing(ws, ws + 64, 1, ws + 192, ws + 192 + GWB_GT_BYTES, s, err)) {
         (void)hipStreamSynchronize(s);
-        (void)hipStreamDestroy(s);
-        release_device(k);
         return false;
     }
     if (e == hipSuccess) e = hipMemcpyAsync(k->ab, ws + 192, GWB_GT_BYTES, hipMemcpyDeviceToHost, s);
@@ -359,14 +326,15 @@ bool ensure_key(gwb_g16vk* k, std::string& err) {
         Fq12 m;
         Fq* c = reinterpret_cast<Fq*>(&m);
         for (int i = 0; i < 12; ++i) c[i] = fq_to_mont(rd_fq(k->ab + 32 * i));
-        e = hipMemcpy(k->d_ab, &m, sizeof m, hipMemcpyHostToDevice);
+        e = hipMemcpy(ab.as(), &m, sizeof m, hipMemcpyHostToDevice);
     }
-    if (s) (void)hipStreamDestroy(s);
     if (e != hipSuccess) {
-        release_device(k);
         err = hip_err("preparing the verifying key on the device", e);
         return false;
     }
+    k->d_lines = std::move(lines);
+    k->d_tab = std::move(tab);
+    k->d_ab = std::move(ab);
     k->device = dev;
     k->ab_ready = true;
     return true;
@@ -378,18 +346,18 @@ bool enqueue_verify(gwb_g16vk* k, const uint8_t* d_proofs, const uint8_t* d_pub,
     const uint32_t n = (uint32_t)batch, npub = k->n_public, n_groups = (npub + VKX_GROUP - 1) / VKX_GROUP;
     const size_t part_bytes = (size_t)batch * n_groups * sizeof(P1);
     const size_t bytes = part_bytes + batch * (sizeof(RowPts) + sizeof(Fq12) + FX_SLOTS * sizeof(Fq12)) + 256;
-    if (!ensure_ws(k, bytes, err)) return false;
-    P1* part = (P1*)k->d_ws;
-    RowPts* pts = (RowPts*)((uint8_t*)k->d_ws + ((part_bytes + 255) & ~(size_t)255));
+    if (!k->ws.ensure(bytes, "allocating the verifier workspace", err)) return false;
+    P1* part = k->ws.as<P1>();
+    RowPts* pts = (RowPts*)(k->ws.as<uint8_t>() + ((part_bytes + 255) & ~(size_t)255));
     Fq12* f = (Fq12*)(pts + batch);
     uint32_t* sp = (uint32_t*)(f + batch);
     if (n_groups)
-        hipLaunchKernelGGL(vkx_kernel, dim3(blocks_for((uint64_t)n * n_groups, THREADS)), dim3(THREADS), 0, s, d_pub, npub, n, n_groups, k->d_tab, part);
+        hipLaunchKernelGGL(vkx_kernel, dim3(blocks_for((uint64_t)n * n_groups, THREADS)), dim3(THREADS), 0, s, d_pub, npub, n, n_groups, k->d_tab.as<const A1>(), part);
     hipLaunchKernelGGL(check_kernel, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, d_proofs, d_pub, npub, n, k->ic0, part, n_groups, pts, d_status);
     const uint32_t fixed_inf = (affine_is_inf(k->gamma2) ? 1u : 0u) | (affine_is_inf(k->delta2) ? 2u : 0u);
-    hipLaunchKernelGGL(miller_kernel, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, pts, n, d_status, k->d_lines, fixed_inf, f);
+    hipLaunchKernelGGL(miller_kernel, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, pts, n, d_status, k->d_lines.as<const Line>(), fixed_inf, f);
     hipLaunchKernelGGL(easy_kernel, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, f, n, (const uint32_t*)d_status);
-    hipLaunchKernelGGL(final_kernel, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, f, n, k->d_ab, d_status, sp, (uint8_t*)nullptr);
+    hipLaunchKernelGGL(final_kernel, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, f, n, k->d_ab.as<const Fq12>(), d_status, sp, (uint8_t*)nullptr);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         err = hip_err("launching the verifier kernels", e);
@@ -462,11 +430,7 @@ int gwb_g16vk_alphabeta(gwb_g16vk_t* vk, void* gt, gw_status_t* status) {
     return 0;
 }
 
-void gwb_g16vk_free(gwb_g16vk_t* vk) {
-    if (!vk) return;
-    release_device(vk);
-    delete vk;
-}
+void gwb_g16vk_free(gwb_g16vk_t* vk) { delete vk; }
 
 int gwb_groth16_verify_batch_device(gwb_g16vk_t* vk, const void* d_proofs, const void* d_public, size_t n_public, size_t batch, void* d_status,
                                     void* hip_stream, gw_status_t* status) {
@@ -496,28 +460,15 @@ int gwb_groth16_verify_batch_host(gwb_g16vk_t* vk, const void* proofs, const voi
         return 0;
     }
     std::string err;
-    void* d_p = nullptr;
-    hipStream_t s = nullptr;
     const size_t pb = batch * GWB_GROTH16_PROOF_BYTES, sb = batch * n_public * 32;
-    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&d_p, pb + ((sb + 255) & ~(size_t)255) + batch * 4);
-    uint8_t* d_pub = (uint8_t*)d_p + pb;
-    uint32_t* d_st = (uint32_t*)(d_pub + ((sb + 255) & ~(size_t)255));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_p, proofs, pb, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && sb) e = hipMemcpyAsync(d_pub, pub, sb, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) err = hip_err("staging the proofs", e);
-    bool ok = e == hipSuccess && enqueue_verify(vk, (const uint8_t*)d_p, d_pub, batch, d_st, s, err);
-    if (ok) {
-        e = hipMemcpyAsync(status_out, d_st, batch * 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            err = hip_err("running the verifier", e);
-            ok = false;
-        }
-    }
-    if (d_p) (void)hipFree(d_p);
-    if (s) (void)hipStreamDestroy(s);
-    if (!ok) return fail(status, err);
+    Carve c;  // one allocation: the proofs, the public signals, the statuses
+    const size_t o_proofs = c.take(pb), o_pub = c.take(sb), o_st = c.take(batch * 4);
+    auto run = [&](unsigned char* const* d, hipStream_t s, std::string& err) {
+        return enqueue_verify(vk, d[0] + o_proofs, d[0] + o_pub, batch, (uint32_t*)(d[0] + o_st), s, err);
+    };
+    if (!run_staged({c.o}, {{proofs, pb, 0, o_proofs}, {pub, sb, 0, o_pub}}, {{status_out, batch * 4, 0, o_st}}, "staging the proofs", "running the verifier",
+                    run, err))
+        return fail(status, err);
     set_ok(status);
     return 0;
 }
