@@ -620,6 +620,17 @@ def r1cs_lib():
         L.gwb_zkey_check_g2.argtypes = [vp, stp]
         L.gwb_zkey_check_wtns.argtypes = [vp, vp, sz, stp]
         L.gwb_ptau_check_g2.argtypes = [vp, sz, u32, u32, stp]
+        L.gwb_groth16_contribute.argtypes = [vp, sz, ctypes.c_char_p, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), vp, stp]
+        L.gwb_groth16_contribute_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_float)]
+        L.gwb_zkey_verify_contributions.argtypes = [vp, sz, vp, ctypes.POINTER(sz), stp]
+        L.gwb_zkey_verify_step.argtypes = [vp, sz, vp, sz, vp, stp]
+        L.gwb_zkey_contributions.argtypes = [vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
+        L.gwb_blake2b512.restype = None
+        L.gwb_blake2b512.argtypes = [vp, sz, vp]
+        L.gwb_zkey_contribution_challenge.restype = None
+        L.gwb_zkey_contribution_challenge.argtypes = [vp, vp]
+        L.gwb_bn254_g1_scale_batch_device.argtypes = [vp, sz, vp, vp, vp, stp]
+        L.gwb_bn254_g1_lincomb128_device.argtypes = [vp, vp, sz, vp, vp, stp]
         _r1cs_lib = L
     return _r1cs_lib
 
@@ -1158,6 +1169,145 @@ def groth16_setup_ptau_phase_ms():
     if r1cs_lib().gwb_groth16_setup_ptau_phase_ms(ms) != 0:
         raise WitnessCalcError("no setup phase times (no groth16_setup_ptau call yet)")
     return dict(zip(GROTH16_SETUP_PTAU_PHASES, (float(x) for x in ms)))
+
+
+# -- Groth16 phase-2 contributions (include/graph_witness_groth16_contribute.h, libcwc_r1cs.so) ---------------------------------
+GROTH16_CONTRIBUTE_PHASES = ("load", "scale", "affine")
+CONTRIBUTION_HASH_BYTES = 64
+
+
+def groth16_contribute(zkey, name="", delta=None):
+    """One phase-2 contribution to a Groth16 key on the GPU (synchronous): `.zkey` bytes -> (new `.zkey` bytes, the 64-byte
+    contribution hash to publish).  delta1 and delta2 are multiplied by the secret, sections 8 (C) and 9 (H) by its inverse, a
+    record with a proof of knowledge is appended to section 10, everything else stays byte for byte.  delta: an int in
+    [1, r) for reproducible keys, or None: drawn, applied and discarded.  name: at most 255 bytes of UTF-8.  The records are
+    this library's own (BLAKE2b transcript, its own challenge derivation): `snarkjs zkey verify` does not accept them, while
+    sections 1 to 9 are ordinary and every Groth16 prover and verifier works with the key."""
+    nm = name.encode("utf-8") if isinstance(name, str) else bytes(name)
+    if b"\0" in nm:
+        raise WitnessCalcError("the name holds a zero byte")
+    buf = None
+    if delta is not None:
+        d = int(delta)
+        if not 0 <= d < (1 << 256):
+            raise WitnessCalcError("delta is not in [0, 2^256)")
+        buf = ctypes.create_string_buffer(d.to_bytes(32, "little"), 32)
+    data = bytes(zkey)
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    digest = ctypes.create_string_buffer(CONTRIBUTION_HASH_BYTES)
+    st = GwStatus()
+    try:
+        rc = r1cs_lib().gwb_groth16_contribute(data, len(data), nm, buf, ctypes.byref(out), ctypes.byref(n), digest, ctypes.byref(st))
+    finally:
+        if buf is not None:
+            ctypes.memset(buf, 0, 32)
+    _r1cs_check(rc, st)
+    try:
+        return ctypes.string_at(out, n.value), digest.raw
+    finally:
+        r1cs_lib().gwb_groth16_setup_free(out)
+
+
+def groth16_contribute_phase_ms():
+    """{load, scale, affine} in ms of the process's last groth16_contribute call, summed over its pieces."""
+    ms = (ctypes.c_float * 3)()
+    if r1cs_lib().gwb_groth16_contribute_phase_ms(ms) != 0:
+        raise WitnessCalcError("no contribution phase times (no groth16_contribute call yet)")
+    return dict(zip(GROTH16_CONTRIBUTE_PHASES, (float(x) for x in ms)))
+
+
+def zkey_contributions(zkey):
+    """Section 10 of a `.zkey` (host only): {"cs_hash", "contributions": [{"name", "type", "delta_after", "g1_s", "g1_sx",
+    "g2_spx", "transcript", "hash"}]}.  Points are canonical little-endian bytes (64 for G1, 128 for G2: x.c0, x.c1, y.c0,
+    y.c1), type is 0 (contribution) or 1 (beacon), hash is what the participant published.  Nothing is verified beyond the
+    section's form; a malformed section raises with a message starting "zkey: section 10"."""
+    data = bytes(zkey)
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    st = GwStatus()
+    rc = r1cs_lib().gwb_zkey_contributions(data, len(data), ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
+    _r1cs_check(rc, st)
+    try:
+        img = ctypes.string_at(out, n.value)
+    finally:
+        r1cs_lib().gwb_groth16_setup_free(out)
+    count = int.from_bytes(img[64:68], "little")
+    off, recs = 68, []
+    for _ in range(count):
+        fixed = img[off:off + 448]
+        typ, name_len = (int.from_bytes(img[off + 448 + 4 * i:off + 452 + 4 * i], "little") for i in range(2))
+        off += 456
+        recs.append({"name": img[off:off + name_len].decode("utf-8", "replace"), "type": typ, "delta_after": fixed[:64], "g1_s": fixed[64:128],
+                     "g1_sx": fixed[128:192], "g2_spx": fixed[192:320], "transcript": fixed[320:384], "hash": fixed[384:448]})
+        off += name_len
+    return {"cs_hash": img[:64], "contributions": recs}
+
+
+def groth16_verify_contributions(zkey):
+    """Checks every contribution record of a key on the GPU and returns their hashes, oldest first ([] for a key without
+    records, whose delta must then be the generator).  Raises WitnessCalcError naming the first failing record and rule, for
+    example "zkey: contribution 2: deltaAfter is not deltaPrev times the proven secret".  This checks the chain of deltas; it does not compare the key with its circuit or
+    its powers-of-tau file."""
+    data = bytes(zkey)
+    room = len(zkey_contributions(data)["contributions"])
+    hashes = ctypes.create_string_buffer(max(1, room * CONTRIBUTION_HASH_BYTES))
+    n = ctypes.c_size_t(room)
+    st = GwStatus()
+    rc = r1cs_lib().gwb_zkey_verify_contributions(data, len(data), hashes, ctypes.byref(n), ctypes.byref(st))
+    _r1cs_check(rc, st)
+    return [hashes.raw[64 * k:64 * k + 64] for k in range(n.value)]
+
+
+def groth16_verify_contribution_step(prev, next, seed=None):
+    """Checks on the GPU that the key `next` is the key `prev` after exactly one contribution: the new record, the delta
+    points, the untouched sections byte for byte, and sections 8 and 9 through random linear combinations of their points
+    (a wrong point passes with probability about 2^-128 over the seed).  seed: 32 bytes for a reproducible check, or None to
+    draw them.  Raises WitnessCalcError naming what differs."""
+    a, b = bytes(prev), bytes(next)
+    if seed is not None and len(seed) != 32:
+        raise WitnessCalcError("seed: 32 bytes expected")
+    st = GwStatus()
+    rc = r1cs_lib().gwb_zkey_verify_step(a, len(a), b, len(b), bytes(seed) if seed is not None else None, ctypes.byref(st))
+    _r1cs_check(rc, st)
+
+
+def bn254_g1_scale_batch_device(d_points, k, stream=None):
+    """Measurement and test aid of the contribution's kernel: device G1 points (uint8 cuda [n, 64], canonical affine, zero
+    bytes for infinity, not validated) -> k times each, the same form, for one int k in [0, 2^256).  Asynchronous on `stream`
+    or the current stream."""
+    import torch
+    n = d_points.shape[0]
+    assert tuple(d_points.shape) == (n, 64) and d_points.is_cuda and d_points.is_contiguous() and d_points.dtype == torch.uint8
+    s = stream if stream is not None else torch.cuda.current_stream(d_points.device)
+    out = torch.empty_like(d_points)
+    st = GwStatus()
+    with torch.cuda.device(d_points.device):
+        rc = r1cs_lib().gwb_bn254_g1_scale_batch_device(d_points.data_ptr(), n, int(k).to_bytes(32, "little"), out.data_ptr(), s.cuda_stream,
+                                                        ctypes.byref(st))
+    _r1cs_check(rc, st)
+    if n:
+        d_points.record_stream(s)
+        out.record_stream(s)
+    return out
+
+
+def bn254_g1_lincomb128_device(d_points, d_rho, stream=None):
+    """Measurement and test aid of the step check's kernels: device G1 points (uint8 cuda [n, 64], canonical affine) and
+    128-bit little-endian scalars (uint8 cuda [n, 16]) -> sum_i rho_i P_i as uint8 cuda [64].  Asynchronous on `stream` or the
+    current stream."""
+    import torch
+    n = d_points.shape[0]
+    assert tuple(d_points.shape) == (n, 64) and d_points.is_cuda and d_points.is_contiguous() and d_points.dtype == torch.uint8
+    assert tuple(d_rho.shape) == (n, 16) and d_rho.is_cuda and d_rho.is_contiguous() and d_rho.dtype == torch.uint8
+    s = stream if stream is not None else torch.cuda.current_stream(d_points.device)
+    out = torch.empty((64,), dtype=torch.uint8, device=d_points.device)
+    st = GwStatus()
+    with torch.cuda.device(d_points.device):
+        rc = r1cs_lib().gwb_bn254_g1_lincomb128_device(d_points.data_ptr(), d_rho.data_ptr(), n, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
+    _r1cs_check(rc, st)
+    d_points.record_stream(s)
+    d_rho.record_stream(s)
+    out.record_stream(s)
+    return out
 
 
 # -- Groth16 verifier (include/graph_witness_groth16_verify.h, libcwc_r1cs.so) ------------------------------------------------

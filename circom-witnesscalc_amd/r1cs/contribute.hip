@@ -1,0 +1,661 @@
+// Groth16 phase-2 contributions on gfx950 (include/graph_witness_groth16_contribute.h has the definitions): the contribution
+// itself, the check of a key's records and the check of one step between two keys.  Section 10, BLAKE2b, the transcript and
+// the challenge point are contributions.cc's (contribute_internal.hpp); the pairing is verify.hip's and the conversion to
+// affine bytes setup.hip's, both through their enqueue functions.
+//
+// Contribute.  The few single points (g1_s, g1_sx, g2_spx, delta1, delta2) are multiplied on the host.  Sections 8 and 9 are one
+// list of stored G1 points that goes through the device in pieces of CWC_CONTRIBUTE_CHUNK points: scale_points_kernel decodes
+// a point and multiplies it by 1 / delta (fq_gfx950.hpp's xyzz_mul_short; the scalar is read through one uniform address, so
+// a wave takes the additions of the scalar's one bits together), then the shared-inversion kernel writes the stored bytes, zero
+// bytes for infinity.  1 / delta lives in a device buffer that is zeroed before it is released.
+//
+// Step check.  R = sum rho_i P_i over a section of the previous key and R' over the same section of the next key, rho_i of 128
+// bits, the same for both: lincomb_kernel takes one point per thread (blockIdx.y picks the list), multiplies it by its rho
+// (four words of double-and-add) and the workgroup adds its 256 products through LDS, halving the active threads each round;
+// lincomb_sum_kernel, one workgroup per list, adds the per-group sums to the running sum of the list.  The bucket method of
+// msm.hip was not reused: it is built around the prover's resident bases and 254-bit scalars, and this sum is a small part
+// of a step check next to its pairings.
+//
+// Registers (hipcc -Rpass-analysis=kernel-resource-usage for gfx950; every kernel: 0 bytes of scratch, no AGPRs; VGPRs, waves / SIMD):
+//   scale_points_kernel 156, 3      lincomb_kernel 164, 3 (32 KB LDS)      lincomb_sum_kernel 119, 4 (32 KB LDS)      put_scalar_kernel 10, 8
+#include <hip/hip_runtime.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/random.h>
+
+#include <algorithm>
+#include <memory>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/graph_witness_groth16_contribute.h"
+#include "../../include/graph_witness_groth16_setup.h"
+#include "../../include/graph_witness_groth16_verify.h"
+#include "binfile.hpp"
+#include "bn254_points_gfx950.hpp"
+#include "contribute_internal.hpp"
+#include "groth16_internal.hpp"
+#include "setup_internal.hpp"
+
+using namespace cwc_r1cs;
+using namespace cwc_g16;
+using namespace cwc_contrib;
+using cwc::Fr;
+using cwc_setup::enqueue_affine_g1;
+
+namespace {
+
+constexpr uint32_t THREADS = 256;
+constexpr uint64_t DEFAULT_CHUNK = 1ull << 18;
+constexpr size_t RHO_BYTES = 16;
+
+// out[i] = k in[i] for the stored points in[0 .. n) (Montgomery, or canonical), XYZZ
+__global__ __launch_bounds__(THREADS) void scale_points_kernel(const uint8_t* __restrict__ in, uint32_t n, uint32_t canonical, const Fr* __restrict__ k,
+                                                               Xyzz<G1>* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    A1 a;
+    get_coords<G1>(in + (size_t)i * G1_BYTES, canonical != 0, a.x, a.y);
+    out[i] = xyzz_mul_short(from_affine(a), *k);
+}
+
+// *out = v (a scalar for scale_points_kernel without a copy from host memory)
+__global__ __launch_bounds__(64) void put_scalar_kernel(Fr* __restrict__ out, Fr v) {
+    if (threadIdx.x == 0) *out = v;
+}
+
+// the sum of sh[0 .. THREADS) into sh[0]
+__device__ __forceinline__ void block_sum(Xyzz<G1>* sh) {
+    __syncthreads();
+    for (uint32_t stride = THREADS / 2; stride > 0; stride >>= 1) {
+        if (threadIdx.x < stride) sh[threadIdx.x] = xyzz_add(sh[threadIdx.x], sh[threadIdx.x + stride]);
+        __syncthreads();
+    }
+}
+
+// part[blockIdx.y gridDim.x + blockIdx.x] = sum over the workgroup's i of rho[i] P_i, P = in0 or (blockIdx.y = 1) in1
+__global__ __launch_bounds__(THREADS) void lincomb_kernel(const uint8_t* __restrict__ in0, const uint8_t* __restrict__ in1, uint32_t n, uint32_t canonical,
+                                                          const uint32_t* __restrict__ rho, Xyzz<G1>* __restrict__ part) {
+    __shared__ Xyzz<G1> sh[THREADS];
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    Xyzz<G1> acc = xyzz_inf<G1>();
+    if (i < n) {
+        const uint8_t* in = blockIdx.y ? in1 : in0;
+        A1 a;
+        get_coords<G1>(in + (size_t)i * G1_BYTES, canonical != 0, a.x, a.y);
+        const uint32_t* r = rho + 4 * (size_t)i;
+        acc = xyzz_mul_short(from_affine(a), Fr{{r[0], r[1], r[2], r[3], 0, 0, 0, 0}});
+    }
+    sh[threadIdx.x] = acc;
+    block_sum(sh);
+    if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = sh[0];
+}
+
+// acc[blockIdx.x] += sum of part[blockIdx.x n_part .. + n_part)
+__global__ __launch_bounds__(THREADS) void lincomb_sum_kernel(const Xyzz<G1>* __restrict__ part, uint32_t n_part, Xyzz<G1>* __restrict__ acc) {
+    __shared__ Xyzz<G1> sh[THREADS];
+    Xyzz<G1> s = xyzz_inf<G1>();
+    for (uint32_t j = threadIdx.x; j < n_part; j += THREADS) s = xyzz_add(s, part[(size_t)blockIdx.x * n_part + j]);
+    sh[threadIdx.x] = s;
+    block_sum(sh);
+    if (threadIdx.x == 0) acc[blockIdx.x] = xyzz_add(acc[blockIdx.x], sh[0]);
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------------
+
+int fail2(gw_status_t* status, const std::string& msg) {  // a failure that is not a verdict about the key
+    set_status(status, msg);
+    return 2;
+}
+
+uint64_t chunk_points() {
+    const char* v = getenv("CWC_CONTRIBUTE_CHUNK");
+    if (!v || !*v) return DEFAULT_CHUNK;
+    const unsigned long long c = strtoull(v, nullptr, 10);
+    return c >= 1 && c <= (1ull << 24) ? c : DEFAULT_CHUNK;
+}
+
+struct ZkeyFree {
+    void operator()(gwb_zkey_t* z) const { gwb_zkey_free(z); }
+};
+using ZkeyPtr = std::unique_ptr<gwb_zkey_t, ZkeyFree>;
+
+// A key as the three functions read it: checked by the loader, its section table and its section 10.
+struct Key {
+    ZkeyPtr z;
+    BinSection secs[11];
+    Section10 s10;
+};
+
+bool read_key(const void* data, size_t len, Key& k, std::string& err) {
+    gw_status_t st{};
+    gwb_zkey_t* z = nullptr;
+    if (gwb_zkey_load(data, len, &z, &st) != 0) {
+        err = st.error_msg ? st.error_msg : "zkey: not loaded";
+        free(st.error_msg);
+        return false;
+    }
+    k.z.reset(z);
+    if (!binfile_sections((const uint8_t*)data, len, "zkey", 0x7feu, k.secs, err)) return false;
+    if (!k.secs[10].p) {
+        err = "zkey: section 10 is missing";
+        return false;
+    }
+    return parse_section10(k.secs[10].p, k.secs[10].size, k.s10, err);
+}
+
+// H(the bodies of sections 1 to 9 in id order)
+void sections_hash(const BinSection* secs, uint8_t out[HASH_BYTES]) {
+    Blake2b h;
+    for (uint32_t id = 1; id <= 9; ++id) h.update(secs[id].p, secs[id].size);
+    h.final(out);
+}
+
+bool is_zero_bytes(const uint8_t* p, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (p[i]) return false;
+    return true;
+}
+
+struct Secrets {
+    Fr delta, delta_inv, s;  // canonical
+    ~Secrets() { explicit_bzero(this, sizeof *this); }
+};
+
+bool draw_nonzero(Fr& x, std::string& err) {
+    do {
+        if (!draw_fr(x, err)) return false;
+    } while (cwc::u256_is_zero(x));
+    return true;
+}
+
+PhaseTimes<3> g_phases;
+
+// out = k in for the n stored points at `in`, in pieces; d_k is the device address of the canonical scalar
+bool scale_list(const uint8_t* in, uint64_t n, const Fr* d_k, SetupDevice<4>& D, uint64_t chunk, uint8_t* out, std::string& err) {
+    uint8_t* W = D.work.as<uint8_t>();
+    Carve cw;
+    const size_t o_in = cw.take(chunk * G1_BYTES), o_x = cw.take(chunk * sizeof(Xyzz<G1>)), o_out = cw.take(chunk * G1_BYTES);
+    float total[3] = {0, 0, 0};
+    bool timed = true;
+    for (uint64_t at = 0; at < n; at += chunk) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - at);
+        D.ev.record(0, D.s);
+        hipError_t e = hipMemcpyAsync(W + o_in, in + at * G1_BYTES, (size_t)m * G1_BYTES, hipMemcpyHostToDevice, D.s);
+        if (e != hipSuccess) {
+            err = hip_err("uploading the points of sections 8 and 9", e);
+            return false;
+        }
+        D.ev.record(1, D.s);
+        hipLaunchKernelGGL(scale_points_kernel, dim3(blocks_for(m, THREADS)), dim3(THREADS), 0, D.s, (const uint8_t*)(W + o_in), m, 0u, d_k, (Xyzz<G1>*)(W + o_x));
+        D.ev.record(2, D.s);
+        enqueue_affine_g1(W + o_x, m, W + o_out, false, D.s);
+        D.ev.record(3, D.s);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(out + at * G1_BYTES, W + o_out, (size_t)m * G1_BYTES, hipMemcpyDeviceToHost, D.s);
+        if (e == hipSuccess) e = hipStreamSynchronize(D.s);
+        if (e != hipSuccess) {
+            err = hip_err("scaling the points of sections 8 and 9", e);
+            return false;
+        }
+        float t[3];
+        if (D.ev.elapsed(t) == hipSuccess)
+            for (int i = 0; i < 3; ++i) total[i] += t[i];
+        else
+            timed = false;
+    }
+    g_phases.store(total, timed);
+    return true;
+}
+
+void put32(std::vector<uint8_t>& v, uint32_t x) { v.insert(v.end(), (const uint8_t*)&x, (const uint8_t*)&x + 4); }
+void put_section(std::vector<uint8_t>& v, uint32_t id, const uint8_t* p, size_t n) {
+    const uint64_t size = n;
+    put32(v, id);
+    v.insert(v.end(), (const uint8_t*)&size, (const uint8_t*)&size + 8);
+    v.insert(v.end(), p, p + n);
+}
+
+constexpr size_t HDR_DELTA1 = 84 + 2 * G1_BYTES + 2 * G2_BYTES, HDR_DELTA2 = HDR_DELTA1 + G1_BYTES;  // in section 2
+
+int contribute(const uint8_t* zkey, size_t len, const char* name, const uint8_t* delta, void** out, size_t* out_len, uint8_t* hash64,
+               gw_status_t* status) {
+    std::string err;
+    Key key;
+    if (!read_key(zkey, len, key, err)) return fail(status, err);
+    const std::string nm = name ? name : "";
+    if (nm.size() > GWB_CONTRIBUTION_NAME_MAX)
+        return fail(status, "groth16 contribute: the name has " + std::to_string(nm.size()) + " bytes, 255 at the most");
+    Secrets sec;
+    if (delta) {
+        memcpy(sec.delta.v, delta, 32);
+        if (cwc::u256_is_zero(sec.delta) || !cwc::u256_lt(sec.delta, cwc::fr_p())) return fail(status, "groth16 contribute: delta is not in [1, r)");
+    } else if (!draw_nonzero(sec.delta, err)) {
+        return fail(status, err);
+    }
+    sec.delta_inv = cwc::fr_from_mont(cwc::fr_inv_fermat(cwc::fr_to_mont(sec.delta)));
+    if (!draw_nonzero(sec.s, err)) return fail(status, err);
+
+    const gwb_zkey& z = *key.z;
+    Section10 s10 = key.s10;
+    if (s10.blank()) sections_hash(key.secs, s10.cs_hash);
+    Record rec;
+    uint8_t gen1[G1_BYTES], g2_sp[G2_BYTES];
+    put_stored(gen1, g1_generator());
+    g1_mul_stored(gen1, sec.s, rec.g1_s);
+    g1_mul_stored(rec.g1_s, sec.delta, rec.g1_sx);
+    transcript_of(s10, s10.recs.size(), rec.g1_s, rec.g1_sx, rec.transcript);
+    put_stored(g2_sp, hash_to_g2(rec.transcript));
+    g2_mul_stored(g2_sp, sec.delta, rec.g2_spx);
+    uint8_t delta2[G2_BYTES];
+    g1_mul_stored(z.delta1, sec.delta, rec.delta_after);
+    g2_mul_stored(z.delta2, sec.delta, delta2);
+    rec.type = 0;
+    rec.params = name_params(nm);
+    rec.name = nm;
+    record_hash(rec, hash64);
+    s10.recs.push_back(rec);
+
+    // sections 8 and 9 as one list
+    const uint64_t n_c = z.c.size() / G1_BYTES, n_h = z.h.size() / G1_BYTES, n = n_c + n_h;
+    std::vector<uint8_t> pts(n * G1_BYTES), scaled(n * G1_BYTES);
+    memcpy(pts.data(), z.c.data(), z.c.size());
+    memcpy(pts.data() + z.c.size(), z.h.data(), z.h.size());
+    {
+        SetupDevice<4> D;
+        const uint64_t chunk = std::max<uint64_t>(1, std::min(chunk_points(), n));
+        Carve cw;
+        cw.take(chunk * G1_BYTES);
+        cw.take(chunk * sizeof(Xyzz<G1>));
+        cw.take(chunk * G1_BYTES);
+        hipError_t e = D.open(256, cw.o);
+        if (e != hipSuccess) return fail(status, hip_err("allocating the contribution's workspace", e));
+        e = hipMemcpyAsync(D.secret.as(), &sec.delta_inv, sizeof(Fr), hipMemcpyHostToDevice, D.s);
+        if (e == hipSuccess) e = hipStreamSynchronize(D.s);  // the copy has left the host value
+        if (e != hipSuccess) return fail(status, hip_err("uploading the contribution's scalar", e));
+        if (!scale_list(pts.data(), n, D.secret.as<const Fr>(), D, chunk, scaled.data(), err)) return fail(status, err);
+        e = hipMemsetAsync(D.secret.as(), 0, D.secret_bytes, D.s);
+        if (e == hipSuccess) e = hipStreamSynchronize(D.s);
+        if (e != hipSuccess) return fail(status, hip_err("clearing the contribution's scalar", e));
+    }
+
+    std::vector<uint8_t> hdr(key.secs[2].p, key.secs[2].p + key.secs[2].size), sec10, file;
+    memcpy(hdr.data() + HDR_DELTA1, rec.delta_after, G1_BYTES);
+    memcpy(hdr.data() + HDR_DELTA2, delta2, G2_BYTES);
+    write_section10(s10, sec10);
+    file.reserve(len + sec10.size() + 64);
+    file.insert(file.end(), {'z', 'k', 'e', 'y'});
+    put32(file, 1);
+    put32(file, 10);
+    for (uint32_t id = 1; id <= 10; ++id) {
+        if (id == 2)
+            put_section(file, id, hdr.data(), hdr.size());
+        else if (id == 8)
+            put_section(file, id, scaled.data(), n_c * G1_BYTES);
+        else if (id == 9)
+            put_section(file, id, scaled.data() + n_c * G1_BYTES, n_h * G1_BYTES);
+        else if (id == 10)
+            put_section(file, id, sec10.data(), sec10.size());
+        else
+            put_section(file, id, key.secs[id].p, key.secs[id].size);
+    }
+    void* buf = malloc(file.size());
+    if (!buf) return fail(status, "groth16 contribute: out of host memory");
+    memcpy(buf, file.data(), file.size());
+    *out = buf;
+    *out_len = file.size();
+    set_ok(status);
+    return 0;
+}
+
+// ---- verification -----------------------------------------------------------------------------------------------------------
+
+// e(a1, a2) = e(b1, b2)?  Stored points; `msg` is what the failure says.
+struct PairCheck {
+    const uint8_t *a1, *a2, *b1, *b2;
+    std::string msg;
+};
+
+// The host rules of record k of s (its transcript, no infinity, g2_spx in the subgroup); "" or what fails.  The record's two
+// pairing rules go to `checks`; g2_sp (stored) gets the record's challenge point and has to outlive the checks.
+std::string record_rules(const Section10& s, size_t k, const uint8_t* delta_prev, uint8_t* g2_sp, std::vector<PairCheck>& checks) {
+    const Record& r = s.recs[k];
+    const std::string who = "zkey: contribution " + std::to_string(k + 1) + ": ";
+    uint8_t t[HASH_BYTES];
+    transcript_of(s, k, r.g1_s, r.g1_sx, t);
+    if (memcmp(t, r.transcript, HASH_BYTES) != 0) return who + "the transcript is not that of the csHash, the records before it and g1_s, g1_sx";
+    const struct {
+        const char* name;
+        const uint8_t* at;
+        size_t bytes;
+    } pts[4] = {{"deltaAfter", r.delta_after, G1_BYTES}, {"g1_s", r.g1_s, G1_BYTES}, {"g1_sx", r.g1_sx, G1_BYTES}, {"g2_spx", r.g2_spx, G2_BYTES}};
+    for (const auto& p : pts)
+        if (is_zero_bytes(p.at, p.bytes)) return who + p.name + " is the point at infinity";
+    if (!g2_stored_in_subgroup(r.g2_spx)) return who + "g2_spx is not in the order-r subgroup of G2";
+    put_stored(g2_sp, hash_to_g2(t));
+    checks.push_back({r.g1_s, r.g2_spx, r.g1_sx, g2_sp, who + "g1_sx is not g1_s times the secret that g2_spx proves"});
+    checks.push_back({delta_prev, r.g2_spx, r.delta_after, g2_sp, who + "deltaAfter is not deltaPrev times the proven secret"});
+    return "";
+}
+
+// The rules about the header's delta points after the last record (`last`: its deltaAfter, or nullptr without records).
+std::string delta_rules(const gwb_zkey& z, const uint8_t* last, const uint8_t* gen1, const uint8_t* gen2, std::vector<PairCheck>& checks) {
+    if (!last && memcmp(z.delta1, gen1, G1_BYTES) != 0) return "zkey: delta is not the generator and no contribution accounts for it";
+    if (last && memcmp(z.delta1, last, G1_BYTES) != 0) return "zkey: delta1 is not the deltaAfter of the last contribution";
+    if (is_zero_bytes(z.delta2, G2_BYTES)) return "zkey: delta2 is the point at infinity";
+    if (!g2_stored_in_subgroup(z.delta2)) return "zkey: delta2 is not in the order-r subgroup of G2";
+    checks.push_back({z.delta1, gen2, gen1, z.delta2, "zkey: delta2 is not the G2 generator times delta1's scalar"});
+    return "";
+}
+
+// Runs the pairings of `checks` in one batched launch; verdict = the message of the first check that fails, "" if none does.
+bool run_checks(const std::vector<PairCheck>& checks, std::string& verdict, std::string& err) {
+    verdict.clear();
+    const size_t n = 2 * checks.size();
+    if (n == 0) return true;
+    std::vector<uint8_t> g1(n * G1_BYTES), g2(n * G2_BYTES), gt(n * GWB_GT_BYTES);
+    for (size_t i = 0; i < checks.size(); ++i) {
+        canonical_g1(checks[i].a1, g1.data() + 2 * i * G1_BYTES);
+        canonical_g2(checks[i].a2, g2.data() + 2 * i * G2_BYTES);
+        canonical_g1(checks[i].b1, g1.data() + (2 * i + 1) * G1_BYTES);
+        canonical_g2(checks[i].b2, g2.data() + (2 * i + 1) * G2_BYTES);
+    }
+    auto run = [&](unsigned char** d, hipStream_t s, std::string& e) {
+        gw_status_t st{};
+        if (gwb_bn254_pairing_batch_device(d[0], d[1], n, d[2], s, &st) != 0) {
+            e = st.error_msg ? st.error_msg : "pairing failed";
+            free(st.error_msg);
+            return false;
+        }
+        return true;
+    };
+    if (!run_staged({g1.size(), g2.size(), gt.size()}, {{g1.data(), g1.size(), 0, 0}, {g2.data(), g2.size(), 1, 0}}, {{gt.data(), gt.size(), 2, 0}},
+                    "staging the pairings of the contribution check", "running the pairings of the contribution check", run, err))
+        return false;
+    for (size_t i = 0; i < checks.size(); ++i)
+        if (memcmp(gt.data() + 2 * i * GWB_GT_BYTES, gt.data() + (2 * i + 1) * GWB_GT_BYTES, GWB_GT_BYTES) != 0) {
+            verdict = checks[i].msg;
+            return true;
+        }
+    return true;
+}
+
+struct Generators {
+    uint8_t g1[G1_BYTES], g2[G2_BYTES];
+    Generators() {
+        put_stored(g1, g1_generator());
+        put_stored(g2, g2_generator());
+    }
+};
+
+int verify_contributions(const uint8_t* zkey, size_t len, uint8_t* hashes_out, size_t* n_io, gw_status_t* status) {
+    std::string err;
+    Key key;
+    if (!read_key(zkey, len, key, err)) return fail2(status, err);
+    const Section10& s = key.s10;
+    const size_t n = s.recs.size();
+    const Generators gen;
+    std::vector<PairCheck> checks;
+    std::vector<uint8_t> sp(std::max<size_t>(n, 1) * G2_BYTES);
+    std::string host_verdict;  // the first host rule that fails; the pairing rules of the records before it come first
+    for (size_t k = 0; k < n && host_verdict.empty(); ++k)
+        host_verdict = record_rules(s, k, k ? s.recs[k - 1].delta_after : gen.g1, sp.data() + k * G2_BYTES, checks);
+    if (host_verdict.empty()) host_verdict = delta_rules(*key.z, n ? s.recs[n - 1].delta_after : nullptr, gen.g1, gen.g2, checks);
+    std::string verdict;
+    if (!run_checks(checks, verdict, err)) return fail2(status, err);
+    if (verdict.empty()) verdict = host_verdict;
+    if (!verdict.empty()) return fail(status, verdict);
+    const size_t room = *n_io;
+    *n_io = n;
+    for (size_t k = 0; k < n && k < room && hashes_out; ++k) record_hash(s.recs[k], hashes_out + k * HASH_BYTES);
+    set_ok(status);
+    return 0;
+}
+
+// rho_i for i in [first, first + count): four per digest H(seed || u64le(j)), j = i / 4
+void fill_rho(const uint8_t seed[32], uint64_t first, uint64_t count, uint8_t* out) {
+    uint8_t msg[40], d[HASH_BYTES];
+    memcpy(msg, seed, 32);
+    uint64_t have = ~0ull;
+    for (uint64_t i = first; i < first + count; ++i) {
+        const uint64_t j = i / 4;
+        if (j != have) {
+            memcpy(msg + 32, &j, 8);
+            blake2b512(msg, sizeof msg, d);
+            have = j;
+        }
+        memcpy(out + (i - first) * RHO_BYTES, d + RHO_BYTES * (i % 4), RHO_BYTES);
+    }
+}
+
+// d_acc[0] += sum rho_i P_i, d_acc[1] += sum rho_i P'_i over the m points of one piece (device addresses), the per-group sums in
+// d_part (2 blocks_for(m, THREADS) points)
+void enqueue_lincomb(const uint8_t* d_p0, const uint8_t* d_p1, uint32_t lists, uint32_t m, bool canonical, const uint8_t* d_rho, Xyzz<G1>* d_part,
+                     Xyzz<G1>* d_acc, hipStream_t s) {
+    const uint32_t blocks = blocks_for(m, THREADS);
+    hipLaunchKernelGGL(lincomb_kernel, dim3(blocks, lists), dim3(THREADS), 0, s, d_p0, d_p1, m, canonical ? 1u : 0u, (const uint32_t*)d_rho, d_part);
+    hipLaunchKernelGGL(lincomb_sum_kernel, dim3(lists), dim3(THREADS), 0, s, (const Xyzz<G1>*)d_part, blocks, d_acc);
+}
+
+// The four sums of a step check, stored form in out[4][64]: R and R' of section 8, then of section 9.
+bool step_sums(const gwb_zkey& prev, const gwb_zkey& next, const uint8_t seed[32], uint8_t* out, std::string& err) {
+    const uint64_t n_c = prev.c.size() / G1_BYTES, n_h = prev.h.size() / G1_BYTES;
+    const uint64_t chunk = std::max<uint64_t>(1, std::min(chunk_points(), std::max(n_c, n_h)));
+    const uint32_t max_blocks = blocks_for(chunk, THREADS);
+    Stream s;
+    DeviceBuf work;
+    Carve cw;
+    const size_t o_p0 = cw.take(chunk * G1_BYTES), o_p1 = cw.take(chunk * G1_BYTES), o_rho = cw.take(chunk * RHO_BYTES),
+                 o_part = cw.take(2ull * max_blocks * sizeof(Xyzz<G1>)), o_acc = cw.take(4 * sizeof(Xyzz<G1>)), o_out = cw.take(4 * G1_BYTES);
+    hipError_t e = s.create();
+    if (e == hipSuccess) e = work.alloc(cw.o);
+    if (e == hipSuccess) e = hipMemsetAsync(work.as<uint8_t>() + o_acc, 0, 4 * sizeof(Xyzz<G1>), s);
+    if (e != hipSuccess) {
+        err = hip_err("allocating the step check's workspace", e);
+        return false;
+    }
+    uint8_t* W = work.as<uint8_t>();
+    std::vector<uint8_t> rho(chunk * RHO_BYTES);
+    for (int sec = 0; sec < 2; ++sec) {
+        const uint8_t *p0 = sec ? prev.h.data() : prev.c.data(), *p1 = sec ? next.h.data() : next.c.data();
+        const uint64_t n = sec ? n_h : n_c, base = sec ? n_c : 0;
+        for (uint64_t at = 0; at < n; at += chunk) {
+            const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - at);
+            fill_rho(seed, base + at, m, rho.data());
+            e = hipMemcpyAsync(W + o_p0, p0 + at * G1_BYTES, (size_t)m * G1_BYTES, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(W + o_p1, p1 + at * G1_BYTES, (size_t)m * G1_BYTES, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(W + o_rho, rho.data(), (size_t)m * RHO_BYTES, hipMemcpyHostToDevice, s);
+            if (e != hipSuccess) {
+                err = hip_err("uploading the points of a step check", e);
+                return false;
+            }
+            enqueue_lincomb(W + o_p0, W + o_p1, 2, m, false, W + o_rho, (Xyzz<G1>*)(W + o_part), (Xyzz<G1>*)(W + o_acc) + 2 * sec, s);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipStreamSynchronize(s);  // rho is refilled for the next piece
+            if (e != hipSuccess) {
+                err = hip_err("running the linear combinations of a step check", e);
+                return false;
+            }
+        }
+    }
+    enqueue_affine_g1(W + o_acc, 4, W + o_out, false, s);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, W + o_out, 4 * G1_BYTES, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        err = hip_err("reading the linear combinations of a step check", e);
+        return false;
+    }
+    return true;
+}
+
+bool same_record(const Record& a, const Record& b) {
+    return memcmp(a.delta_after, b.delta_after, G1_BYTES) == 0 && memcmp(a.g1_s, b.g1_s, G1_BYTES) == 0 && memcmp(a.g1_sx, b.g1_sx, G1_BYTES) == 0 &&
+           memcmp(a.g2_spx, b.g2_spx, G2_BYTES) == 0 && memcmp(a.transcript, b.transcript, HASH_BYTES) == 0 && a.type == b.type && a.params == b.params;
+}
+
+// what of `next` has to be `prev`'s byte for byte, and the shape of its section 10; "" or what fails
+std::string step_structure(const Key& prev, const Key& next) {
+    const Section10 &a = prev.s10, &b = next.s10;
+    if (b.recs.size() != a.recs.size() + 1)
+        return "zkey step: section 10 of the next key has " + std::to_string(b.recs.size()) + " contributions, the previous key " + std::to_string(a.recs.size()) +
+               ": exactly one more is expected";
+    for (size_t k = 0; k < a.recs.size(); ++k)
+        if (!same_record(a.recs[k], b.recs[k])) return "zkey step: section 10: contribution " + std::to_string(k + 1) + " is not the previous key's";
+    uint8_t want[HASH_BYTES];
+    if (a.blank())
+        sections_hash(prev.secs, want);
+    else
+        memcpy(want, a.cs_hash, HASH_BYTES);
+    if (memcmp(want, b.cs_hash, HASH_BYTES) != 0)
+        return std::string("zkey step: section 10: the csHash is not ") + (a.blank() ? "the hash of the previous key's sections 1 to 9" : "the previous key's");
+    static const char* names[10] = {"", "protocol", "header", "IC", "coefficients", "A", "B1", "B2", "C", "H"};
+    for (uint32_t id : {1u, 3u, 4u, 5u, 6u, 7u})
+        if (prev.secs[id].size != next.secs[id].size || memcmp(prev.secs[id].p, next.secs[id].p, prev.secs[id].size) != 0)
+            return "zkey step: section " + std::to_string(id) + " (" + names[id] + ") differs from the previous key's";
+    if (memcmp(prev.secs[2].p, next.secs[2].p, HDR_DELTA1) != 0)
+        return "zkey step: section 2 (header) differs from the previous key's before delta1 (the sizes, alpha1, beta1, beta2 or gamma2)";
+    return "";
+}
+
+int verify_step(const uint8_t* prev_bytes, size_t prev_len, const uint8_t* next_bytes, size_t next_len, const uint8_t* seed_in, gw_status_t* status) {
+    std::string err;
+    Key prev, next;
+    if (!read_key(prev_bytes, prev_len, prev, err)) return fail2(status, "previous key: " + err);
+    if (!read_key(next_bytes, next_len, next, err)) return fail2(status, "next key: " + err);
+    std::string verdict = step_structure(prev, next);
+    if (!verdict.empty()) return fail(status, verdict);
+    uint8_t seed[32];
+    if (seed_in) {
+        memcpy(seed, seed_in, 32);
+    } else {
+        for (size_t got = 0; got < 32;) {
+            const ssize_t k = getrandom(seed + got, 32 - got, 0);
+            if (k < 0) return fail2(status, "zkey step: getrandom failed");
+            got += (size_t)k;
+        }
+    }
+    const gwb_zkey &zp = *prev.z, &zn = *next.z;
+    const Generators gen;
+    std::vector<PairCheck> checks;
+    uint8_t sp[G2_BYTES];
+    if (is_zero_bytes(zp.delta1, G1_BYTES)) return fail(status, "zkey step: delta1 of the previous key is the point at infinity");
+    const size_t k = next.s10.recs.size() - 1;
+    std::string host_verdict = record_rules(next.s10, k, zp.delta1, sp, checks);
+    if (host_verdict.empty()) host_verdict = delta_rules(zn, next.s10.recs[k].delta_after, gen.g1, gen.g2, checks);
+    uint8_t sums[4 * G1_BYTES];
+    if (host_verdict.empty()) {
+        if (is_zero_bytes(zp.delta2, G2_BYTES) || !g2_stored_in_subgroup(zp.delta2))
+            host_verdict = "zkey step: delta2 of the previous key is not a point of order r";
+    }
+    if (host_verdict.empty()) {
+        if (!step_sums(zp, zn, seed, sums, err)) return fail2(status, err);
+        static const char* what[2] = {"8 (C)", "9 (H)"};
+        for (int sec = 0; sec < 2 && host_verdict.empty(); ++sec) {
+            const uint8_t *r = sums + 2 * sec * G1_BYTES, *r2 = r + G1_BYTES;
+            const std::string msg = std::string("zkey step: section ") + what[sec] + " is not the previous key's section divided by the contribution's secret";
+            const bool inf = is_zero_bytes(r, G1_BYTES), inf2 = is_zero_bytes(r2, G1_BYTES);
+            if (inf != inf2)
+                host_verdict = msg;
+            else if (!inf)
+                checks.push_back({r2, zn.delta2, r, zp.delta2, msg});  // e(R', delta2') = e(R, delta2)
+        }
+    }
+    if (!run_checks(checks, verdict, err)) return fail2(status, err);
+    if (verdict.empty()) verdict = host_verdict;
+    if (!verdict.empty()) return fail(status, verdict);
+    set_ok(status);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gwb_groth16_contribute(const void* zkey, size_t len, const char* name, const uint8_t* delta, void** out, size_t* out_len, void* hash64,
+                           gw_status_t* status) {
+    if (!out || !out_len || !hash64 || (!zkey && len)) return fail(status, "gwb_groth16_contribute: NULL argument");
+    *out = nullptr;
+    *out_len = 0;
+    try {
+        return contribute((const uint8_t*)zkey, len, name, delta, out, out_len, (uint8_t*)hash64, status);
+    } catch (const std::bad_alloc&) {
+        return fail(status, "groth16 contribute: out of host memory");
+    }
+}
+
+int gwb_groth16_contribute_phase_ms(float* ms) { return g_phases.read(ms); }
+
+int gwb_zkey_verify_contributions(const void* zkey, size_t len, void* hashes_out, size_t* n, gw_status_t* status) {
+    if (!n || (!zkey && len) || (*n && !hashes_out)) return fail2(status, "gwb_zkey_verify_contributions: NULL argument");
+    try {
+        return verify_contributions((const uint8_t*)zkey, len, (uint8_t*)hashes_out, n, status);
+    } catch (const std::bad_alloc&) {
+        return fail2(status, "zkey: out of host memory");
+    }
+}
+
+int gwb_zkey_verify_step(const void* prev, size_t prev_len, const void* next, size_t next_len, const uint8_t* seed, gw_status_t* status) {
+    if ((!prev && prev_len) || (!next && next_len)) return fail2(status, "gwb_zkey_verify_step: NULL argument");
+    try {
+        return verify_step((const uint8_t*)prev, prev_len, (const uint8_t*)next, next_len, seed, status);
+    } catch (const std::bad_alloc&) {
+        return fail2(status, "zkey: out of host memory");
+    }
+}
+
+int gwb_bn254_g1_scale_batch_device(const void* d_points, size_t n, const uint8_t* k32, void* d_out, void* hip_stream, gw_status_t* status) {
+    if (!k32 || (n && (!d_points || !d_out))) return fail(status, "gwb_bn254_g1_scale_batch_device: NULL argument");
+    if (n > 0x7fffffffull) return fail(status, "gwb_bn254_g1_scale_batch_device: n above 2^31 - 1");
+    if (n == 0) {
+        set_ok(status);
+        return 0;
+    }
+    Fr k;
+    memcpy(k.v, k32, 32);
+    hipStream_t s = (hipStream_t)hip_stream;
+    Carve cw;
+    const size_t o_x = cw.take(n * sizeof(Xyzz<G1>)), o_k = cw.take(32);
+    void* ws = nullptr;
+    hipError_t e = hipMallocAsync(&ws, cw.o, s);
+    if (e != hipSuccess) return fail(status, hip_err("allocating the scaling workspace", e));
+    uint8_t* W = (uint8_t*)ws;
+    hipLaunchKernelGGL(put_scalar_kernel, dim3(1), dim3(64), 0, s, (Fr*)(W + o_k), k);
+    hipLaunchKernelGGL(scale_points_kernel, dim3(blocks_for(n, THREADS)), dim3(THREADS), 0, s, (const uint8_t*)d_points, (uint32_t)n, 1u, (const Fr*)(W + o_k),
+                       (Xyzz<G1>*)(W + o_x));
+    enqueue_affine_g1(W + o_x, (uint32_t)n, (uint8_t*)d_out, true, s);
+    e = hipGetLastError();
+    const hipError_t ef = hipFreeAsync(ws, s);
+    if (e != hipSuccess) return fail(status, hip_err("launching the scaling", e));
+    if (ef != hipSuccess) return fail(status, hip_err("releasing the scaling workspace", ef));
+    set_ok(status);
+    return 0;
+}
+
+int gwb_bn254_g1_lincomb128_device(const void* d_points, const void* d_rho, size_t n, void* d_out, void* hip_stream, gw_status_t* status) {
+    if (!d_out || (n && (!d_points || !d_rho))) return fail(status, "gwb_bn254_g1_lincomb128_device: NULL argument");
+    if (n > 0x7fffffffull) return fail(status, "gwb_bn254_g1_lincomb128_device: n above 2^31 - 1");
+    hipStream_t s = (hipStream_t)hip_stream;
+    Carve cw;
+    const size_t o_part = cw.take((size_t)blocks_for(n, THREADS) * sizeof(Xyzz<G1>)), o_acc = cw.take(sizeof(Xyzz<G1>));
+    void* ws = nullptr;
+    hipError_t e = hipMallocAsync(&ws, cw.o, s);
+    if (e != hipSuccess) return fail(status, hip_err("allocating the linear combination's workspace", e));
+    uint8_t* W = (uint8_t*)ws;
+    e = hipMemsetAsync(W + o_acc, 0, sizeof(Xyzz<G1>), s);
+    if (e == hipSuccess && n)
+        enqueue_lincomb((const uint8_t*)d_points, (const uint8_t*)d_points, 1, (uint32_t)n, true, (const uint8_t*)d_rho, (Xyzz<G1>*)(W + o_part),
+                        (Xyzz<G1>*)(W + o_acc), s);
+    if (e == hipSuccess) {
+        enqueue_affine_g1(W + o_acc, 1, (uint8_t*)d_out, true, s);
+        e = hipGetLastError();
+    }
+    const hipError_t ef = hipFreeAsync(ws, s);
+    if (e != hipSuccess) return fail(status, hip_err("launching the linear combination", e));
+    if (ef != hipSuccess) return fail(status, hip_err("releasing the linear combination's workspace", ef));
+    set_ok(status);
+    return 0;
+}
+
+}  // extern "C"

@@ -81,6 +81,12 @@ struct PhaseTimes {
         if (ok) memcpy(ms, t, sizeof t);
         valid = ok;
     }
+    // times that the caller added up itself (a call that runs in pieces)
+    void store(const float (&t)[N], bool ok) {
+        std::lock_guard<std::mutex> lock(mutex);
+        if (ok) memcpy(ms, t, sizeof t);
+        valid = ok;
+    }
     int read(float* out) {  // 0, or 1 when there is nothing to report
         if (!out) return 1;
         std::lock_guard<std::mutex> lock(mutex);
