@@ -35,8 +35,6 @@ std::vector<uint8_t> exported_bytes(const Program& p, const std::vector<InputSig
     exported_write(p, inputs, b.data());
     return b;
 }
-void write_file_atomically(const std::string& path, const void* data, size_t n);
-std::vector<uint8_t> cache_wrap(const std::string& path, const void* blob, size_t n);
 
 uint64_t fnv1a(const uint8_t* p, size_t n) {
     uint64_t h = 1469598103934665603ull;
@@ -94,12 +92,8 @@ uint64_t sampled_fingerprint(const uint8_t* p, size_t n) {
     return h;
 }
 
-}  // namespace cwcrt
 
-extern "C" {
-
-int gwb_graph_export(gwb_graph_t* g, uint32_t T, void** blob, size_t* blob_len, gw_status_t* status) {
-    return guarded(status, [&]() -> int {
+int export_graph(gwb_graph* g, const Knobs& k, uint32_t T, void** blob, size_t* blob_len, gw_status_t* status) {
     if (!g || !blob || !blob_len) return fail(status, "null argument");
     std::lock_guard<std::mutex> lk(g->mu);
     Program tmp;
@@ -114,7 +108,7 @@ int gwb_graph_export(gwb_graph_t* g, uint32_t T, void** blob, size_t* blob_len, 
         p = pre->second.get();
     } else {
         if (!g->has_graph) return fail(status, "imported handle has no program for that tile width");
-        if (!compile_program(g->graph, T & ~KEY_MODE_MASK, key_divider_waves(T), tmp, err, key_streams(T))) return fail(status, err);
+        if (!compile_program(g->graph, k, T & ~KEY_MODE_MASK, key_divider_waves(T), tmp, err, key_streams(T))) return fail(status, err);
         p = &tmp;
     }
     const size_t n = exported_size(*p, g->inputs);
@@ -124,11 +118,9 @@ int gwb_graph_export(gwb_graph_t* g, uint32_t T, void** blob, size_t* blob_len, 
     *blob_len = n;
     set_status(status, OK, "");
     return 0;
-    });
 }
 
-int gwb_graph_import(const void* blob, size_t len, gwb_graph_t** out, gw_status_t* status) {
-    return guarded(status, [&]() -> int {
+int import_graph(const void* blob, size_t len, const Knobs& k, gwb_graph** out, gw_status_t* status) {
     if (!blob || !out) return fail(status, "null argument");
     if (len < 24 + 8) return fail(status, "bad blob: too short");
     const uint8_t* b = (const uint8_t*)blob;
@@ -165,14 +157,25 @@ int gwb_graph_import(const void* blob, size_t len, gwb_graph_t** out, gw_status_
     g->n_inputs = dp->host.n_inputs;
     g->n_witness = dp->host.n_witness;
     err = check_device();
-    if (err.empty()) err = upload_program(*dp);
+    if (err.empty()) err = upload_program(*dp, k);
     if (!err.empty()) return fail(status, err);
     const uint32_t T = dp->host.T | key_mode_of_divider(dp->host.divider);
     g->progs[T] = std::move(dp);
     *out = g.release();
     set_status(status, OK, "");
     return 0;
-    });
+}
+
+}  // namespace cwcrt
+
+extern "C" {
+
+int gwb_graph_export(gwb_graph_t* g, uint32_t T, void** blob, size_t* blob_len, gw_status_t* status) {
+    return guarded(status, [&]() -> int { return export_graph(g, read_knobs(), T, blob, blob_len, status); });
+}
+
+int gwb_graph_import(const void* blob, size_t len, gwb_graph_t** out, gw_status_t* status) {
+    return guarded(status, [&]() -> int { return import_graph(blob, len, read_knobs(), out, status); });
 }
 
 // RCCL's entry points are resolved in the running process (the host program has RCCL loaded, e.g. torch's copy; this library
@@ -248,6 +251,7 @@ void gwb_rccl_comm_destroy(void* comm) {
 int gwb_graph_broadcast(gwb_graph_t* g, uint32_t tile_width, size_t batch_per_rank, int root, int rank, void* nccl_comm, void* hip_stream,
                         gwb_graph_t** out, gw_status_t* status) {
     return guarded(status, [&]() -> int {
+    const Knobs k = read_knobs();
     if (!out || !nccl_comm) return fail(status, "null argument");
     typedef int (*bcast_fn)(const void*, void*, size_t, int, int, void*, hipStream_t);
     typedef const char* (*errstr_fn)(int);
@@ -266,11 +270,11 @@ int gwb_graph_broadcast(gwb_graph_t* g, uint32_t tile_width, size_t batch_per_ra
     if (rank == root && g) {
         if (!tile_width) {
             if (!batch_per_rank) root_err = "tile_width = 0 needs the shard size";
-            else if (!(tile_width = gwb_graph_pick_tile_width(g, batch_per_rank))) root_err = "no program for that batch size";
+            else if (!(tile_width = pick_tile_width_searched(g, k, batch_per_rank))) root_err = "no program for that batch size";
         }
         if (root_err.empty()) {
             gw_status_t st2{OK, nullptr};
-            if (gwb_graph_export(g, tile_width, &blob, &blob_len, &st2) != 0) {
+            if (guarded(&st2, [&]() -> int { return export_graph(g, k, tile_width, &blob, &blob_len, &st2); }) != 0) {
                 root_err = st2.error_msg ? st2.error_msg : "export failed";
                 gwb_free_status(&st2);
                 free(blob);
@@ -317,7 +321,7 @@ int gwb_graph_broadcast(gwb_graph_t* g, uint32_t tile_width, size_t batch_per_ra
     bufs.h_blob = malloc((size_t)len64);
     if (!bufs.h_blob) return fail(status, "out of memory");
     if (hipMemcpy(bufs.h_blob, bufs.d_blob, (size_t)len64, hipMemcpyDeviceToHost) != hipSuccess) return fail(status, "hipMemcpy failed");
-    return gwb_graph_import(bufs.h_blob, (size_t)len64, out, status);
+    return import_graph(bufs.h_blob, (size_t)len64, k, out, status);
     });
 }
 

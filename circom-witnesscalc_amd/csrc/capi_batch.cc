@@ -4,13 +4,13 @@
 
 namespace cwcrt {
 
-int load_graph(const void* data, size_t len, gwb_graph** out, std::string& err) {
+int load_graph(const void* data, size_t len, const Knobs& k, gwb_graph** out, std::string& err) {
     std::unique_ptr<gwb_graph> g(new gwb_graph());
     if (!deserialize_witnesscalc_graph((const uint8_t*)data, len, g->graph, err)) return 1;
     g->has_graph = true;
     // validation + statistics (bad indices / Pow / Id are caught here); programs are compiled when a batch size is known
     Program probe;
-    if (!probe_graph(g->graph, probe, err)) return 1;
+    if (!probe_graph(g->graph, k, probe, err)) return 1;
     g->stats = probe.stats;
     g->n_inputs = probe.n_inputs;
     g->n_witness = probe.n_witness;
@@ -18,6 +18,18 @@ int load_graph(const void* data, size_t len, gwb_graph** out, std::string& err) 
     g->input_index = g->graph.input_index;
     *out = g.release();
     return 0;
+}
+
+// the program key the cost model chooses for this graph and batch size (compiles the candidates on the host; no device
+// needed): what rank 0 exports and broadcasts to the other GPUs of a node.  0: no program.
+uint32_t pick_tile_width_searched(gwb_graph* g, const Knobs& k, size_t batch) {
+    if (!g) return 0;
+    try {
+        std::lock_guard<std::mutex> lk(g->mu);
+        return pick_tile_width(g, k, batch, false);  // (what is asked for here is exported / broadcast: the searched program, not the quick first one)
+    } catch (...) {
+        return 0;
+    }
 }
 
 }  // namespace cwcrt
@@ -33,11 +45,12 @@ void gwb_free_status(gw_status_t* status) {
 
 int gwb_graph_load(const void* graph_data, size_t len, gwb_graph_t** out, gw_status_t* status) {
     return guarded(status, [&]() -> int {
+    const Knobs k = read_knobs();
     if (!graph_data) return fail(status, "graph_data is null");
     if (len == 0) return fail(status, "graph_data_len is 0");
     if (!out) return fail(status, "out is null");
     std::string err;
-    if (load_graph(graph_data, len, out, err)) return fail(status, "Failed to load graph: " + err);
+    if (load_graph(graph_data, len, k, out, err)) return fail(status, "Failed to load graph: " + err);
     set_status(status, OK, "");
     return 0;
     });
@@ -95,7 +108,7 @@ int gwb_inputs_from_json(const gwb_graph_t* g, const char* json, void* row, gw_s
     meta.inputs = g->inputs;
     meta.input_index = g->input_index;
     if (!populate_inputs(list, meta, (uint8_t*)row, g->n_inputs, err)) return fail(status, "Failed to calculate witness: " + err);
-    if (quirks())
+    if (read_knobs().quirks)
         for (const auto& kv : list) {  // lib.rs:162
             const InputSignal& s = g->inputs[g->input_index.at(kv.first)];
             printf("input %s, offset %u, len %u\n", kv.first.c_str(), s.offset, s.len);
@@ -108,6 +121,7 @@ int gwb_inputs_from_json(const gwb_graph_t* g, const char* json, void* row, gw_s
 int gwb_inputs_from_json_batch(const gwb_graph_t* g, const char* text, size_t text_len, void* rows, size_t max_rows,
                                size_t* n_rows, gw_status_t* status) {
     return guarded(status, [&]() -> int {
+    const Knobs k = read_knobs();
     if (!g || !text || !n_rows || (!rows && max_rows)) return fail(status, "null argument");
     std::vector<std::pair<size_t, size_t>> spans;
     std::string err;
@@ -119,7 +133,7 @@ int gwb_inputs_from_json_batch(const gwb_graph_t* g, const char* text, size_t te
     meta.input_index = g->input_index;
     // the input sets are independent: parsed on CWC_PARSE_THREADS host threads (default: every core), contiguous
     // ranges each; the error of the lowest failing set is reported, as a sequential loop would
-    unsigned n_threads = env_threads("CWC_PARSE_THREADS", 0);  // (round 2 capped this at 16 threads: 27 k sets/s on a 256-core host)
+    unsigned n_threads = k.parse_threads;
     if (n_threads > spans.size() / 16 + 1) n_threads = (unsigned)(spans.size() / 16 + 1);
     if (spans.size() < 64) n_threads = 1;
     if (n_threads > spans.size()) n_threads = (unsigned)spans.size();
@@ -285,6 +299,7 @@ struct WriterPool {
 extern "C" int gwb_calc_witness_json_to_wtns(gwb_graph_t* g, const char* text, size_t text_len, const char* path_pattern, size_t first_index,
                                              size_t* n_sets, uint32_t* set_status_out, size_t max_sets, gwb_e2e_stats_t* stats, gw_status_t* status) {
     return guarded(status, [&]() -> int {
+    const Knobs knobs = read_knobs();  // (the drain, parse and writer threads below read none of it)
     if (!g || !text || !path_pattern || !n_sets) return fail(status, "null argument");
     const auto t_start = std::chrono::steady_clock::now();
     auto since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
@@ -301,20 +316,12 @@ extern "C" int gwb_calc_witness_json_to_wtns(gwb_graph_t* g, const char* text, s
     err = check_device();
     if (!err.empty()) return fail(status, err);
     const size_t B = spans.size(), NI = g->n_inputs, NW = g->n_witness, row_b = NW * 32;
-    size_t S = 1024;  // (measured on MI355X, authV2-class: 256 -> 10.6 k, 512 -> 14.1 k, 1024 -> 14.3 k witnesses/s; profiles/r03_e2e_ab.txt)
-    if (const char* e = getenv("CWC_E2E_SUBBATCH")) {
-        const long v = atol(e);
-        if (v >= 1) S = (size_t)v;
-    }
+    size_t S = knobs.e2e_subbatch;  // (measured on MI355X, authV2-class: 256 -> 10.6 k, 512 -> 14.1 k, 1024 -> 14.3 k witnesses/s; profiles/r03_e2e_ab.txt)
     if (S > B) S = B;
     const size_t K = (B + S - 1) / S;
     // slices of whole sets, three staging buffers per drain.  CWC_E2E_SLICE_MB (default 96): a device-to-host copy costs
     // ~0.2 ms before it moves anything, so 24 MB slices ran the link at 35 GB/s where one large copy reaches 57
-    size_t slice_mb = 96;
-    if (const char* e = getenv("CWC_E2E_SLICE_MB")) {
-        const long v = atol(e);
-        if (v >= 1 && v <= 1024) slice_mb = (size_t)v;
-    }
+    const size_t slice_mb = knobs.e2e_slice_mb;
     size_t slice_sets = row_b ? std::max<size_t>(1, (slice_mb << 20) / row_b) : 1;
     if (slice_sets > S) slice_sets = S;
     const int kStage = 3;
@@ -357,7 +364,7 @@ extern "C" int gwb_calc_witness_json_to_wtns(gwb_graph_t* g, const char* text, s
     Graph meta;
     meta.inputs = g->inputs;
     meta.input_index = g->input_index;
-    const unsigned n_parse = env_threads("CWC_PARSE_THREADS", 0), n_write = env_threads("CWC_WRITE_THREADS", 16)  /* (more writers fight the copy engine for host memory bandwidth: 64 -> 9.4 k, 32 -> 13.9 k, 16 -> 15.5 k witnesses/s, r03_e2e_ab.txt) */;
+    const unsigned n_parse = knobs.parse_threads, n_write = knobs.write_threads;
     WriterPool pool;
     pool.start(n_write, path_pattern, NW);
     std::atomic<int> pending[2][3];
@@ -492,7 +499,7 @@ extern "C" int gwb_calc_witness_json_to_wtns(gwb_graph_t* g, const char* text, s
             err = "host-to-device copy of the input rows failed";
             break;
         }
-        err = run_device(g, bf.d_in[par], n, bf.d_out[par], (uint32_t*)bf.d_st[par], bf.compute);
+        err = run_device(g, knobs, bf.d_in[par], n, bf.d_out[par], (uint32_t*)bf.d_st[par], bf.compute);
         if (!err.empty()) break;
         if (hipEventRecord(bf.done[par], bf.compute) != hipSuccess) {
             err = "hipEventRecord failed";
@@ -547,12 +554,8 @@ int gwb_set_tile_width(gwb_graph_t* g, uint32_t key) {
 }
 
 uint32_t gwb_graph_pick_tile_width(gwb_graph_t* g, size_t batch) {
-    // the program key the cost model chooses for this graph and batch size (compiles the candidates on the host; no device
-    // needed): what rank 0 exports and broadcasts to the other GPUs of a node
-    if (!g) return 0;
     try {
-        std::lock_guard<std::mutex> lk(g->mu);
-        return pick_tile_width(g, batch, false);  // (what is asked for here is exported / broadcast: the searched program, not the quick first one)
+        return pick_tile_width_searched(g, read_knobs(), batch);
     } catch (...) {
         return 0;
     }
@@ -561,10 +564,11 @@ uint32_t gwb_graph_pick_tile_width(gwb_graph_t* g, size_t batch) {
 int gwb_calc_witness_batch_device(gwb_graph_t* g, const void* d_inputs, size_t batch, void* d_witness,
                                   uint32_t* d_set_status, void* hip_stream, gw_status_t* status) {
     return guarded(status, [&]() -> int {
+    const Knobs k = read_knobs();
     if (!g || (batch && (!d_inputs || !d_witness || !d_set_status))) return fail(status, "null argument");
     std::lock_guard<std::mutex> lk(g->mu);
     std::string err = check_device();
-    if (err.empty()) err = run_device(g, d_inputs, batch, d_witness, d_set_status, (hipStream_t)hip_stream);
+    if (err.empty()) err = run_device(g, k, d_inputs, batch, d_witness, d_set_status, (hipStream_t)hip_stream);
     if (!err.empty()) return fail(status, err);
     set_status(status, OK, "");
     return 0;
@@ -574,12 +578,13 @@ int gwb_calc_witness_batch_device(gwb_graph_t* g, const void* d_inputs, size_t b
 int gwb_calc_witness_batch_handoff(gwb_graph_t* g, const void* d_inputs, size_t batch, void* d_witness, uint32_t* d_set_status,
                                    const gwb_handoff_t* h, gw_status_t* status) {
     return guarded(status, [&]() -> int {
+    const Knobs k = read_knobs();
     if (!g || !h || (batch && (!d_inputs || !d_witness || !d_set_status))) return fail(status, "null argument");
     if (h->struct_size != sizeof(gwb_handoff_t)) return fail(status, "gwb_handoff_t: struct_size does not match this library");
     if (h->form != GWB_FORM_CANONICAL && h->form != GWB_FORM_MONTGOMERY) return fail(status, "gwb_handoff_t: unknown form");
     std::lock_guard<std::mutex> lk(g->mu);
     std::string err = check_device();
-    if (err.empty()) err = run_device(g, d_inputs, batch, d_witness, d_set_status, (hipStream_t)h->hip_stream, h->form == GWB_FORM_MONTGOMERY, (hipEvent_t)h->done_event);
+    if (err.empty()) err = run_device(g, k, d_inputs, batch, d_witness, d_set_status, (hipStream_t)h->hip_stream, h->form == GWB_FORM_MONTGOMERY, (hipEvent_t)h->done_event);
     if (err.empty() && batch == 0 && h->done_event && hipEventRecord((hipEvent_t)h->done_event, (hipStream_t)h->hip_stream) != hipSuccess) err = "hipEventRecord failed";
     if (!err.empty()) return fail(status, err);
     set_status(status, OK, "");
@@ -623,10 +628,11 @@ static double ubench_modmul(uint32_t waves_per_simd, uint32_t iters, bool block_
 int gwb_calc_witness_batch_host(gwb_graph_t* g, const void* inputs, size_t batch, void* witness, uint32_t* set_status_out,
                                 gw_status_t* status) {
     return guarded(status, [&]() -> int {
+    const Knobs k = read_knobs();
     if (!g || (batch && (!inputs || !witness || !set_status_out))) return fail(status, "null argument");
     std::lock_guard<std::mutex> lk(g->mu);
     std::string err = check_device();
-    if (err.empty()) err = run_host(g, inputs, batch, witness, set_status_out);
+    if (err.empty()) err = run_host(g, k, inputs, batch, witness, set_status_out);
     if (!err.empty()) return fail(status, err);
     set_status(status, OK, "");
     return 0;
@@ -728,7 +734,7 @@ int gwb_timing_history(gwb_graph_t* g, size_t max_launches, float* interp_ms, fl
 // One batch through the stamped interpreter instances (diagnostic library): the counters (PROF_WORDS words) and / or the wave
 // census (CENSUS_MAX_WAVES records of CENSUS_WORDS words, program_dev.h) of its last launch.  The device buffer always holds both:
 // the stamped instances write both.
-static int run_stamped(gwb_graph_t* g, const void* d_inputs, size_t batch, void* d_witness, uint32_t* d_set_status, uint64_t* counters,
+static int run_stamped(gwb_graph_t* g, const Knobs& k, const void* d_inputs, size_t batch, void* d_witness, uint32_t* d_set_status, uint64_t* counters,
                        uint64_t* census, gw_status_t* status) {
     if (!gwb_kernels_have_diagnostics())
         return fail(status, "class profiling needs the diagnostic library (make -C circom-witnesscalc_amd/csrc diag; load it with CWC_LIB_PATH=<path of "
@@ -744,7 +750,7 @@ static int run_stamped(gwb_graph_t* g, const void* d_inputs, size_t batch, void*
         return fail(status, "hipMemset failed");
     }
     g->d_prof = d;
-    err = run_device(g, d_inputs, batch, d_witness, d_set_status, nullptr);
+    err = run_device(g, k, d_inputs, batch, d_witness, d_set_status, nullptr);
     g->d_prof = nullptr;
     if (err.empty() && hipDeviceSynchronize() != hipSuccess) err = "hipDeviceSynchronize failed";
     if (err.empty() && counters && hipMemcpy(counters, d, PROF_WORDS * 8, hipMemcpyDeviceToHost) != hipSuccess) err = "hipMemcpy failed";
@@ -760,17 +766,19 @@ int gwb_profile_classes(gwb_graph_t* g, const void* d_inputs, size_t batch, void
     return guarded(status, [&]() -> int {
     // Diagnostic: one batch through the stamped interpreter build; out36[class*4 + {load, compute, store, count}]
     // in shader cycles, summed over the sampled waves (lane 0 of every 64th tile).
+    const Knobs k = read_knobs();
     if (!g || !out36) return fail(status, "null argument");
-    return run_stamped(g, d_inputs, batch, d_witness, d_set_status, out36, nullptr, status);
+    return run_stamped(g, k, d_inputs, batch, d_witness, d_set_status, out36, nullptr, status);
     });
 }
 
 int gwb_wave_census(gwb_graph_t* g, const void* d_inputs, size_t batch, void* d_witness, uint32_t* d_set_status,
                     uint64_t* out, size_t out_words, gw_status_t* status) {
     return guarded(status, [&]() -> int {
+    const Knobs k = read_knobs();
     if (!g || !out) return fail(status, "null argument");
     if (out_words < (size_t)CENSUS_MAX_WAVES * CENSUS_WORDS) return fail(status, "gwb_wave_census: the output buffer is too small");
-    return run_stamped(g, d_inputs, batch, d_witness, d_set_status, nullptr, out, status);
+    return run_stamped(g, k, d_inputs, batch, d_witness, d_set_status, nullptr, out, status);
     });
 }
 

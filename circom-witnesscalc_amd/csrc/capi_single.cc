@@ -58,21 +58,10 @@ std::string sha256_hex(const uint8_t* p, size_t n) {
 // On-disk cache of the single-shot entry point's compiled program: a process that has never seen a graph image finds the
 // program an earlier process compiled for it (the first call otherwise parses, compiles and searches schedules).  One file
 // per (SHA-256 of the image, library build): <dir>/<sha256>-<build>.cwcprog = the blob of gwb_graph_export (checksummed,
-// structurally validated on import: a damaged or stale file is ignored and rewritten).  CWC_PROGRAM_CACHE=<dir> names the
-// directory, CWC_PROGRAM_CACHE=0 turns the cache off; default $XDG_CACHE_HOME or ~/.cache, /circom-witnesscalc-amd.
-std::string program_cache_file(const void* graph_data, size_t len) {
-    std::string dir;
-    if (const char* e = getenv("CWC_PROGRAM_CACHE")) {
-        if (!*e || !strcmp(e, "0") || !strcmp(e, "off")) return "";
-        dir = e;
-    } else if (const char* x = getenv("XDG_CACHE_HOME")) {
-        if (*x) dir = std::string(x) + "/circom-witnesscalc-amd";
-    }
-    if (dir.empty()) {
-        const char* home = getenv("HOME");
-        if (!home || !*home) return "";
-        dir = std::string(home) + "/.cache/circom-witnesscalc-amd";
-    }
+// structurally validated on import: a damaged or stale file is ignored and rewritten).  <dir> is Knobs::cache_dir: CWC_PROGRAM_CACHE=<dir>
+// names it, CWC_PROGRAM_CACHE=0 turns the cache off; default $XDG_CACHE_HOME or ~/.cache, /circom-witnesscalc-amd.
+std::string program_cache_file(const Knobs& k, const void* graph_data, size_t len) {
+    if (k.cache_dir.empty()) return "";
     // (this build -- the content hash of every source under csrc/ as the Makefile stamped it, not a timestamp: the compiler
     // and the kernels that give a program its meaning are compiled separately from this file --, the program format, the
     // cost model's cycle table: a program is chosen under one table)
@@ -80,7 +69,7 @@ std::string program_cache_file(const void* graph_data, size_t len) {
         const std::string id = std::string(CWC_TREE_HASH " format 18 table ") + std::to_string((unsigned long long)model_table_id());
         return sha256_hex((const uint8_t*)id.data(), id.size()).substr(0, 16);
     }();
-    return dir + "/" + sha256_hex((const uint8_t*)graph_data, len) + "-" + build + ".cwcprog";
+    return k.cache_dir + "/" + sha256_hex((const uint8_t*)graph_data, len) + "-" + build + ".cwcprog";
 }
 // A cache file = 96 bytes that name what it is for -- "CWCPROG2", then <sha256 of the graph image>-<build> as in its file name,
 // zero-padded -- followed by the blob of gwb_graph_export: a file that was renamed or copied over another entry, or written
@@ -137,11 +126,6 @@ void write_file_atomically(const std::string& path, const void* data, size_t n) 
     if (fclose(f) != 0 || !ok || rename(tmp.c_str(), path.c_str()) != 0) (void)remove(tmp.c_str());
 }
 
-bool quirks() {
-    const char* e = getenv("GW_REFERENCE_QUIRKS");
-    return e && *e && strcmp(e, "0") != 0;
-}
-
 }  // namespace cwcrt
 
 extern "C" {
@@ -151,6 +135,7 @@ int gw_calc_witness(const char* inputs, const void* graph_data, const size_t gra
                     size_t* wtns_len, const gw_status_t* status_c) {
     return guarded(const_cast<gw_status_t*>(status_c), [&]() -> int {
     gw_status_t* status = const_cast<gw_status_t*>(status_c);  // the reference writes through it too
+    const Knobs k = read_knobs();
     if (!inputs) return fail(status, "inputs is null");                    // lib.rs:51-54
     if (!graph_data) return fail(status, "graph_data is null");            // lib.rs:56-59
     if (graph_data_len == 0) return fail(status, "graph_data_len is 0");   // lib.rs:61-64
@@ -174,10 +159,10 @@ int gw_calc_witness(const char* inputs, const void* graph_data, const size_t gra
     // calc_witness (lib.rs:125-136): inputs first, then the graph
     InputList list;
     std::string err;
-    const bool dbg_single = getenv("CWC_DEBUG_SINGLE") != nullptr;  // diagnostic: where a call's time goes
+    const bool dbg_single = k.debug_single;  // diagnostic: where a call's time goes
     auto now_ms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_in = now_ms();
-    warm_device();
+    warm_device(k);
     if (!deserialize_inputs(inputs, strlen(inputs), list, err)) return fail(status, "Failed to calculate witness: " + err);
     const double t_inputs = now_ms();
 
@@ -191,7 +176,7 @@ int gw_calc_witness(const char* inputs, const void* graph_data, const size_t gra
             if (e.hash == h && e.bytes.size() == graph_data_len && memcmp(e.bytes.data(), graph_data, graph_data_len) == 0) g = e.g;
     }
     if (!g) {
-        const std::string cf = program_cache_file(graph_data, graph_data_len);  // (SHA-256 of the image: once per graph and process)
+        const std::string cf = program_cache_file(k, graph_data, graph_data_len);  // (SHA-256 of the image: once per graph and process)
         std::vector<uint8_t> blob;
         if (!cf.empty() && read_file(cf, blob)) {  // a program an earlier process compiled for this very image (the import checks for a device behind its host work)
             gwb_graph_t* imported = nullptr;
@@ -199,13 +184,13 @@ int gw_calc_witness(const char* inputs, const void* graph_data, const size_t gra
             const uint8_t* body = nullptr;
             size_t body_len = 0;
             if (!cache_unwrap(cf, blob, &body, &body_len)) set_status(&st2, ERROR, "not this graph's / this build's cache entry");
-            else if (gwb_graph_import(body, body_len, &imported, &st2) == 0) g.reset(imported);
-            if (getenv("CWC_DEBUG_CACHE")) fprintf(stderr, "program cache: %s %s%s%s\n", g ? "hit" : "ignored", cf.c_str(), g ? "" : ": ", g ? "" : (st2.error_msg ? st2.error_msg : "?"));
+            else if (guarded(&st2, [&]() -> int { return import_graph(body, body_len, k, &imported, &st2); }) == 0) g.reset(imported);
+            if (k.debug_cache) fprintf(stderr, "program cache: %s %s%s%s\n", g ? "hit" : "ignored", cf.c_str(), g ? "" : ": ", g ? "" : (st2.error_msg ? st2.error_msg : "?"));
             gwb_free_status(&st2);  // (a damaged / stale file: fall through to the compiler, the file is rewritten)
         }
         if (!g) {
             gwb_graph* raw = nullptr;
-            if (load_graph(graph_data, graph_data_len, &raw, err)) return fail(status, "Failed to calculate witness: " + err);
+            if (load_graph(graph_data, graph_data_len, k, &raw, err)) return fail(status, "Failed to calculate witness: " + err);
             g.reset(raw);
             g->cache_path = cf;  // where the refined program goes once the background search has finished
         }
@@ -220,7 +205,7 @@ int gw_calc_witness(const char* inputs, const void* graph_data, const size_t gra
         meta.input_index = g->input_index;
         if (!populate_inputs(list, meta, row.data(), g->n_inputs, err)) return fail(status, "Failed to calculate witness: " + err);
     }
-    if (quirks())
+    if (k.quirks)
         for (const auto& kv : list) {
             const InputSignal& s = g->inputs[g->input_index.at(kv.first)];
             printf("input %s, offset %u, len %u\n", kv.first.c_str(), s.offset, s.len);
@@ -230,10 +215,10 @@ int gw_calc_witness(const char* inputs, const void* graph_data, const size_t gra
     double t_device = t_graph;
     {
         std::lock_guard<std::mutex> lk(g->mu);
-        (void)pick_tile_width(g.get(), 1);  // host work first: a new graph's program is compiled while warm_device's thread brings the device up
+        (void)pick_tile_width(g.get(), k, 1);  // host work first: a new graph's program is compiled while warm_device's thread brings the device up
         err = check_device();
         t_device = now_ms();
-        if (err.empty()) err = run_host(g.get(), row.data(), 1, wit.data(), &st);
+        if (err.empty()) err = run_host(g.get(), k, row.data(), 1, wit.data(), &st);
     }
     if (!err.empty()) return fail(status, "Failed to calculate witness: " + err);
     if (dbg_single) {
@@ -256,10 +241,10 @@ int gw_calc_witness(const char* inputs, const void* graph_data, const size_t gra
             void* blob = nullptr;
             size_t blob_len = 0;
             gw_status_t st2{OK, nullptr};
-            if (gwb_graph_export(g.get(), key, &blob, &blob_len, &st2) == 0) {
+            if (guarded(&st2, [&]() -> int { return export_graph(g.get(), k, key, &blob, &blob_len, &st2); }) == 0) {
                 const std::vector<uint8_t> wrapped = cache_wrap(cf, blob, blob_len);
                 write_file_atomically(cf, wrapped.data(), wrapped.size());
-                if (getenv("CWC_DEBUG_CACHE")) fprintf(stderr, "program cache: wrote %s (program key %#x, %zu bytes)\n", cf.c_str(), key, blob_len);
+                if (k.debug_cache) fprintf(stderr, "program cache: wrote %s (program key %#x, %zu bytes)\n", cf.c_str(), key, blob_len);
             }
             gwb_free_status(&st2);
             free(blob);
@@ -273,7 +258,7 @@ int gw_calc_witness(const char* inputs, const void* graph_data, const size_t gra
     wtns_from_witness(wit.data(), g->n_witness, (uint8_t*)buf);
     *wtns_len = n;
     *wtns_data = buf;
-    if (quirks()) {
+    if (k.quirks) {
         set_status(status, ERROR, "test error");  // lib.rs:106
         printf("OK\n");                            // lib.rs:108
     } else {

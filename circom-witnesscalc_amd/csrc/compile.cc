@@ -33,50 +33,20 @@ SharedRewrites* make_shared_rewrites() {
     return s;
 }
 void free_shared_rewrites(SharedRewrites* s) { delete s; }
-static bool compile_variant(const Graph& g_in, uint32_t T, uint32_t divider, bool bit_fusion, const VariantOptions& opt, const CompileKnobs& k, Program& out,
+static bool compile_variant(const Graph& g_in, uint32_t T, uint32_t divider, bool bit_fusion, const VariantOptions& opt, const Knobs& k, Program& out,
                             std::string& err, RewriteCache* cache = nullptr, bool probe_only = false, uint32_t streams = 1);
 
-CompileKnobs read_compile_knobs() {
-    auto on = [](const char* name) { return getenv(name) != nullptr; };
-    auto u32 = [](const char* name) -> std::optional<uint32_t> {
-        if (const char* e = getenv(name)) return (uint32_t)atol(e);
-        return std::nullopt;
-    };
-    CompileKnobs k = {};
-    k.coop_fill = u32("CWC_COOP_FILL"), k.coop_slack = u32("CWC_COOP_SLACK"), k.no_coop_mul = on("CWC_NO_COOP_MUL");
-    k.no_schedule_variants = on("CWC_NO_SCHEDULE_VARIANTS"), k.no_bit_fusion = on("CWC_NO_BIT_FUSION"), k.no_rep_inference = on("CWC_NO_REP_INFERENCE");
-    k.conv_always = on("CWC_CONV_ALWAYS"), k.no_fuse = on("CWC_NO_FUSE");
-    if (const char* e = getenv("CWC_FUSE")) k.fuse = (uint32_t)atoi(e);
-    if (const char* e = getenv("CWC_WITNESS_SLOTS")) k.witness_slots = atoi(e) != 0;
-    k.debug_compile_times = on("CWC_DEBUG_COMPILE_TIMES"), k.no_load_optimize = on("CWC_NO_LOAD_OPTIMIZE");
-    if (const char* e = getenv("CWC_RANDOM_EVAL")) k.random_eval = atoi(e) != 0;
-    k.no_lin_heavy_weights = on("CWC_NO_LIN_HEAVY_WEIGHTS");
-    if (const char* e = getenv("CWC_SCHED_LIN_COST")) k.sched_lin_cost = (uint32_t)atoi(e);
-    if (const char* e = getenv("CWC_SCHED_MUL_COST")) k.sched_mul_cost = (uint32_t)atoi(e);
-    k.no_tree_reduction = on("CWC_NO_TREE_REDUCTION");
-    if (const char* e = getenv("CWC_TREE_LEAVES")) k.tree_leaves = (size_t)std::max(2, atoi(e));
-    k.no_scan = on("CWC_NO_SCAN"), k.no_bit_graph = on("CWC_NO_BIT_GRAPH"), k.no_mul_cc = on("CWC_NO_MUL_CC"), k.no_conv = on("CWC_NO_CONV");
-    if (const char* e = getenv("CWC_SCHED_DIV_WAIT")) k.sched_div_wait = (uint32_t)atoi(e);
-    k.sched_tie_reverse = on("CWC_SCHED_TIE_REVERSE"), k.no_ride_along = on("CWC_NO_RIDE_ALONG"), k.scan_eager = on("CWC_SCAN_EAGER");
-    if (const char* e = getenv("CWC_STREAM_PROLOGUE")) k.stream_prologue = atof(e);
-    k.debug_critical_path = on("CWC_DEBUG_CRITICAL_PATH"), k.debug_streams = on("CWC_DEBUG_STREAMS"), k.debug_node_mix = on("CWC_DEBUG_NODE_MIX");
-    if (const char* e = getenv("CWC_DEBUG_SCHED")) k.debug_sched = (uint32_t)atoi(e);
-    k.nowhere = !(getenv("CWC_NOWHERE") && atoi(getenv("CWC_NOWHERE")) == 0);
-    return k;
-}
-
 // Validation and statistics of a loaded graph without compiling a program (what gwb_graph_load needs).
-bool probe_graph(const Graph& g, Program& out, std::string& err) {
-    return compile_variant(g, 64, 0, false, VariantOptions{0, 0}, read_compile_knobs(), out, err, nullptr, true);
+bool probe_graph(const Graph& g, const Knobs& k, Program& out, std::string& err) {
+    return compile_variant(g, 64, 0, false, VariantOptions{0, 0}, k, out, err, nullptr, true);
 }
 
 // The list scheduler is a heuristic, and exact rewrites and the narrow-bundle policy shift how the chains of a graph line
 // up in bundles: the program is compiled with and without the bit-extract fusion, then under a few narrow-bundle
 // policies, and the cheapest schedule by the measured cycles per bundle class (program_wave_cycles) is kept -- the
 // policies are not fitted to one graph, the cost model picks per graph and tile width.
-bool compile_program(const Graph& g, uint32_t T, uint32_t divider, Program& out, std::string& err, uint32_t streams, bool quick, SharedRewrites* shared) {
+bool compile_program(const Graph& g, const Knobs& k, uint32_t T, uint32_t divider, Program& out, std::string& err, uint32_t streams, bool quick, SharedRewrites* shared) {
     const uint32_t G = T ? 64 / T : 1;
-    const CompileKnobs k = read_compile_knobs();
     VariantOptions base{k.coop_fill.value_or(G), k.coop_slack.value_or(~0u)};  // narrow whenever everything ready fits
     const bool forced = k.coop_fill || k.coop_slack;
     if (k.no_coop_mul || coop_nodes(T) == 0) base.fill = 0;
@@ -281,7 +251,7 @@ struct PreparedGraph {
 };
 
 // ---- load-time re-optimiser, exact depth-reducing rewrites, scheduling weights ----
-static void rewrite_graph(bool bit_fusion, uint32_t G, const uint32_t* weight_table, const CompileKnobs& k, PhaseTimer& phase, ProgramStats& st, PreparedGraph& pg) {
+static void rewrite_graph(bool bit_fusion, uint32_t G, const uint32_t* weight_table, const Knobs& k, PhaseTimer& phase, ProgramStats& st, PreparedGraph& pg) {
     Graph& g = pg.g;
     // (the statistics above describe the graph as loaded)
     if (!k.no_load_optimize) {
@@ -317,14 +287,14 @@ static void rewrite_graph(bool bit_fusion, uint32_t G, const uint32_t* weight_ta
     if (G > 1 && !k.no_tree_reduction) {
         // whole chains at T = 1 (small batches: depth is everything); at most 8 leaves per tree otherwise, where the
         // extra nodes of wide trees cost lanes and memory traffic (measured on sha256_512: 293 k vs 265 k wit/s at 4096 sets)
-        reduce_tree_height(g, k.tree_leaves.value_or(G >= 64 ? 64 : 8), pg.class_cost);  // (CWC_TREE_LEAVES: A/B knob)
+        reduce_tree_height(g, k.tree_leaves.value_or(G >= 64 ? 64 : 8), pg.class_cost, k);  // (CWC_TREE_LEAVES: A/B knob)
     }
     for (const Node& n : g.nodes) st.n_op_compiled += arity_of(n) ? 1 : 0;
 }
 
 // Validate, levels, rewrites: the working graph (from the rewrite cache when a variant of the same call made it), its
 // statistics and the scheduling weights.  probe_only: the graph as loaded, up to the levels.
-static bool prepare_graph(const Graph& g_in, uint32_t T, uint32_t& divider, bool bit_fusion, const VariantOptions& opt, const CompileKnobs& k, RewriteCache* cache,
+static bool prepare_graph(const Graph& g_in, uint32_t T, uint32_t& divider, bool bit_fusion, const VariantOptions& opt, const Knobs& k, RewriteCache* cache,
                           bool probe_only, PhaseTimer& phase, Program& out, PreparedGraph& pg, std::string& err) {
     const uint32_t* weight_table = opt.fill && T <= 2 ? kClassCostNarrow : kClassCost;
     const RewriteCache::Entry* hit = nullptr;
@@ -389,7 +359,7 @@ static bool prepare_graph(const Graph& g_in, uint32_t T, uint32_t& divider, bool
 
 // ---- one form per value (Montgomery or canonical, inserting the conversions; see infer_representations), scan chains
 // (the steps of serial limb recurrences as pairs of N_SCAN nodes, class C_SCAN), fused narrow chains ----
-static NodeForms choose_forms(Graph& g, uint32_t T, uint32_t divider, const VariantOptions& opt, const CompileKnobs& k, const uint32_t* class_cost, PhaseTimer& phase,
+static NodeForms choose_forms(Graph& g, uint32_t T, uint32_t divider, const VariantOptions& opt, const Knobs& k, const uint32_t* class_cost, PhaseTimer& phase,
                               ProgramStats& st) {
     const uint32_t G = 64 / T;
     NodeForms f;
@@ -400,14 +370,14 @@ static NodeForms choose_forms(Graph& g, uint32_t T, uint32_t divider, const Vari
     const bool limb_graph = mode2_ok && !k.no_scan && st.depth_scan * 10 < st.depth * 8;
     // bit graphs (sha256-like: one operation in thirty-two or more is a bit extract): canonical inputs, every product canonical
     const bool bit_graph = mode2_ok && !k.no_bit_graph && !opt.all_montgomery && st.n_bitx_nodes * 32 >= st.n_op && st.n_op > 0;
-    infer_representations(g, f.rep, f.vflags, st.n_conversions, st.n_canonical, opt.all_montgomery, (limb_graph || bit_graph) && !k.no_mul_cc, f.n_mul_cc, bit_graph);
+    infer_representations(g, f.rep, f.vflags, st.n_conversions, st.n_canonical, opt.all_montgomery, (limb_graph || bit_graph) && !k.no_mul_cc, f.n_mul_cc, bit_graph, k);
     phase("representation inference");
     if (mode2_ok && !k.no_scan && !opt.no_scans) {
-        detect_scans(g, f.rep, f.vflags, f.scan_imm, f.scan_partner, st.n_scan_steps);
+        detect_scans(g, f.rep, f.vflags, f.scan_imm, f.scan_partner, st.n_scan_steps, k);
         // borrow chains / most-significant-difference comparisons of multi-register integers (limb graphs: the step kinds live in the MODE 2 instances)
-        if (limb_graph) detect_bit_scans(g, f.rep, f.vflags, f.scan_imm, f.scan_partner, st.n_scan_steps);
+        if (limb_graph) detect_bit_scans(g, f.rep, f.vflags, f.scan_imm, f.scan_partner, st.n_scan_steps, k);
         // schoolbook limb products: the column sums of a k x k block as one bundle (2k - 1 columns, one node slot each)
-        if (f.n_mul_cc && !opt.no_conv && !k.no_conv) detect_convolutions(g, f.rep, f.vflags, f.scan_imm, f.scan_partner, G, st.n_conv_products);
+        if (f.n_mul_cc && !opt.no_conv && !k.no_conv) detect_convolutions(g, f.rep, f.vflags, f.scan_imm, f.scan_partner, G, st.n_conv_products, k);
         phase("scan chains");
     }
     if (opt.fuse && opt.fill && T <= COOP_FUSE_MAX_T && G > 1 && divider <= 1 && st.n_scan_steps == 0 && f.n_mul_cc == 0) {  // (a program has fused bundles or scan bundles: one interpreter instance each)
@@ -603,7 +573,7 @@ void dump_critical_path(const Graph& g, const Priorities& pr) {
     fprintf(stderr, "\n  start: %s\n", seq.c_str());
 }
 
-void compute_priorities(const Graph& g, const NodeForms& f, const uint32_t* class_cost, const CompileKnobs& k, Priorities& pr) {
+void compute_priorities(const Graph& g, const NodeForms& f, const uint32_t* class_cost, const Knobs& k, Priorities& pr) {
     const size_t N = g.nodes.size();
     pr.height.assign(N, 0);
     pr.users.resize(N);
@@ -704,7 +674,7 @@ struct ListParams {
     // bundle).
     size_t coop_cap, coop_fill;
     uint64_t coop_slack;
-    const CompileKnobs& k;
+    const Knobs& k;
 };
 
 // diagnostic (CWC_DEBUG_SCHED): the first bundles, node by node
@@ -1215,7 +1185,7 @@ void append_stream(const Graph& g, uint32_t divider, uint32_t s, const StreamSch
 
 }  // namespace
 
-bool schedule_program(const Graph& g, const NodeForms& f, const ProgramStats& st, const uint32_t* class_cost, const VariantOptions& opt, const CompileKnobs& k,
+bool schedule_program(const Graph& g, const NodeForms& f, const ProgramStats& st, const uint32_t* class_cost, const VariantOptions& opt, const Knobs& k,
                       uint32_t T, uint32_t divider, uint32_t streams, bool refuse_one_part, Schedule& sc, std::string& err) {
     const size_t N = g.nodes.size();
     const uint32_t G = 64 / T;
@@ -1695,7 +1665,7 @@ void Encoder::finish() {
     }
 }
 
-static bool allocate_and_encode(const Graph& g, const NodeForms& f, const Schedule& sc, const Routing& rt, ConstTable& ct, const uint32_t* class_cost, const CompileKnobs& k,
+static bool allocate_and_encode(const Graph& g, const NodeForms& f, const Schedule& sc, const Routing& rt, ConstTable& ct, const uint32_t* class_cost, const Knobs& k,
                                 uint32_t divider, size_t n_in_buf, Program& out, std::string& err) {
     const uint32_t T = out.T, G = out.G, NB = (uint32_t)sc.bundle_start.size() - 1;
     out.hdr.resize(NB);
@@ -1731,7 +1701,7 @@ static bool allocate_and_encode(const Graph& g, const NodeForms& f, const Schedu
     return true;
 }
 
-static bool compile_variant(const Graph& g_in, uint32_t T, uint32_t divider, bool bit_fusion, const VariantOptions& opt, const CompileKnobs& k, Program& out,
+static bool compile_variant(const Graph& g_in, uint32_t T, uint32_t divider, bool bit_fusion, const VariantOptions& opt, const Knobs& k, Program& out,
                             std::string& err, RewriteCache* cache, bool probe_only, uint32_t streams) {
     if (streams != 1 && streams != 2 && streams != 4) {
         err = "a tile is evaluated by 1, 2 or 4 streams";

@@ -101,15 +101,17 @@ inline bool is_integer_class(int c) { return c == C_BIT || c == C_IDIVMOD || c =
 // ---- the exact rewrites (rewrite.cc), in pipeline order ----
 void rewrite_pow2_divisions(Graph& g);
 void fuse_bit_extract(Graph& g);
-void reduce_tree_height(Graph& g, size_t kMaxLeaves, const uint32_t* class_cost);
+void reduce_tree_height(Graph& g, size_t kMaxLeaves, const uint32_t* class_cost, const Knobs& k);
 void infer_representations(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>& vflags, uint64_t& n_conversions, uint64_t& n_canonical, bool all_montgomery,
-                           bool allow_cc, uint64_t& n_cc, bool canonical_inputs);
-void detect_scans(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>& vflags, std::vector<uint32_t>& scan_imm, std::vector<uint32_t>& scan_partner, uint64_t& n_steps);
+                           bool allow_cc, uint64_t& n_cc, bool canonical_inputs, const Knobs& k);
+void detect_scans(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>& vflags, std::vector<uint32_t>& scan_imm, std::vector<uint32_t>& scan_partner, uint64_t& n_steps,
+                  const Knobs& k);
 // borrow chains of register-wise subtractions and most-significant-difference comparisons (SCAN_OP_BORROW / SCAN_OP_LEX)
-void detect_bit_scans(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>& vflags, std::vector<uint32_t>& scan_imm, std::vector<uint32_t>& scan_partner, uint64_t& n_steps);
+void detect_bit_scans(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>& vflags, std::vector<uint32_t>& scan_imm, std::vector<uint32_t>& scan_partner, uint64_t& n_steps,
+                      const Knobs& k);
 // scan_imm[column node] = column | k << 8, scan_partner[column node] = the node of column 0 (the group's name)
 void detect_convolutions(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>& vflags, std::vector<uint32_t>& scan_imm, std::vector<uint32_t>& scan_partner, uint32_t max_columns,
-                         uint64_t& n_products);
+                         uint64_t& n_products, const Knobs& k);
 void fuse_narrow_chains(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>& vflags, const uint32_t* class_cost, uint32_t slack_permille, bool two_stage_only,
                         uint64_t& n_fused);
 
@@ -135,7 +137,8 @@ static const double kCyclesScanBits = 700;  // a bundle of one-bit recurrences (
 // a fused narrow bundle (C_MULF) is priced with all three stages (product, product, addition); what a bundle without
 // the second product / without additions saves
 static const double kCyclesFusedStageMul = 760, kCyclesFusedStageLin = 300;
-// The table above was measured on one box.  Overrides, read once when the library is loaded: CWC_MODEL_CYCLES=
+// The table above was measured on one box.  Overrides, from the snapshot of the environment taken when the library is loaded
+// (costmodel.cc: the one snapshot that is not an entry point's): CWC_MODEL_CYCLES=
 // "class:cycles,..." (what-if runs of the cost model), else the calibration file tools/gpu_calibrate.py --write leaves
 // behind after measuring the classes on the machine at hand with the stamped interpreter build -- CWC_MODEL_CYCLES_FILE, or
 // model_cycles.txt in the program cache's directory (CWC_PROGRAM_CACHE / XDG_CACHE_HOME / ~/.cache/circom-witnesscalc-amd;
@@ -155,30 +158,14 @@ struct CycleTable {
             if (*end != ',') break;
         }
     }
-    CycleTable() {
+    explicit CycleTable(const Knobs& k) {
         for (int c = 0; c < (int)C_COUNT; ++c) v[c] = kCyclesDefault[c];
-        if (const char* e = getenv("CWC_MODEL_CYCLES")) {
-            parse(e, false);
+        if (k.model_cycles) {
+            parse(k.model_cycles->c_str(), false);
             return;
         }
-        std::string path;
-        if (const char* f = getenv("CWC_MODEL_CYCLES_FILE")) {
-            path = f;
-        } else {
-            std::string dir;
-            if (const char* e = getenv("CWC_PROGRAM_CACHE")) {
-                if (*e && strcmp(e, "0") && strcmp(e, "off")) dir = e;
-                else return;
-            } else if (const char* x = getenv("XDG_CACHE_HOME")) {
-                if (*x) dir = std::string(x) + "/circom-witnesscalc-amd";
-            }
-            if (dir.empty()) {
-                const char* home = getenv("HOME");
-                if (!home || !*home) return;
-                dir = std::string(home) + "/.cache/circom-witnesscalc-amd";
-            }
-            path = dir + "/model_cycles.txt";
-        }
+        if (!k.model_cycles_file && k.cache_dir.empty()) return;
+        const std::string path = k.model_cycles_file ? *k.model_cycles_file : k.cache_dir + "/model_cycles.txt";
         if (FILE* f = fopen(path.c_str(), "rb")) {
             char buf[1024];
             const size_t n = fread(buf, 1, sizeof buf - 1, f);
@@ -193,26 +180,6 @@ struct CycleTable {
 // (round 2, bigint-class graph with every operand and result canonical: BIT 2 650, IDIVMOD 2 880, CMPS 1 900 net of stamps)
 static const double kCyclesBitStraight = 1500;  // what a Shr-only / Band-only bundle saves against the per-lane select over all bit operations
 static const double kCyclesBitx = 1300, kCyclesCoopRiders = 60, kCyclesOperandForm = 1200, kCyclesResultForm = 1450, kCyclesBitxOperandForm = 600;
-// Every CWC_* variable the graph compiler reads (A/B and diagnostic knobs), read once per compile_program / probe_graph
-// call -- tests change them between calls.  An unset optional: the knob is not set.
-struct CompileKnobs {
-    std::optional<uint32_t> coop_fill, coop_slack;  // CWC_COOP_FILL / CWC_COOP_SLACK: force one narrow-bundle policy
-    bool no_coop_mul, no_schedule_variants, no_bit_fusion, no_rep_inference, conv_always, no_fuse;
-    std::optional<uint32_t> fuse;                   // CWC_FUSE: the one fused-chain policy tried, whatever it costs
-    std::optional<bool> witness_slots;              // CWC_WITNESS_SLOTS: force witness-ordered slots on / off
-    bool debug_compile_times, no_load_optimize, random_eval, no_lin_heavy_weights, no_tree_reduction;
-    std::optional<uint32_t> sched_lin_cost, sched_mul_cost;  // overrides of the priority weights
-    std::optional<size_t> tree_leaves;
-    bool no_scan, no_bit_graph, no_mul_cc, no_conv;
-    uint32_t sched_div_wait = 3;  // (measured 3 against 6 and 10: +1.4 % at 1024 sets and +2.6 % at 2048 with divider waves, +1.4 % at 8192 and 16384 sets with inline inversions)
-    bool sched_tie_reverse, no_ride_along, scan_eager;
-    double stream_prologue = 30000;  // (cycles of dependent operations from the inputs that still count as prologue)
-    bool debug_critical_path, debug_streams, debug_node_mix;
-    uint32_t debug_sched = 0;  // CWC_DEBUG_SCHED=n: the first n bundles, node by node
-    bool nowhere = true;       // (CWC_NOWHERE=0: the zero constant's slot and the trash slot as before round 4, for A/B runs)
-};
-CompileKnobs read_compile_knobs();
-
 // The options of one schedule variant (compile_program compiles several and keeps the cheapest).
 // When a multiplication step becomes a narrow (four lanes per product) bundle: `fill` or more ready multiplications make
 // a full-width bundle instead (it costs the same with 10 or 32 nodes); otherwise a narrow one if the multiplications
@@ -261,6 +228,6 @@ struct Schedule {
 };
 // refuse_one_part: a stream program whose graph has one independent part is an error (compile_program's siblings include
 // the one-stream program)
-bool schedule_program(const Graph& g, const NodeForms& f, const ProgramStats& st, const uint32_t* class_cost, const VariantOptions& opt, const CompileKnobs& k,
+bool schedule_program(const Graph& g, const NodeForms& f, const ProgramStats& st, const uint32_t* class_cost, const VariantOptions& opt, const Knobs& k,
                       uint32_t T, uint32_t divider, uint32_t streams, bool refuse_one_part, Schedule& sc, std::string& err);
 }  // namespace cwc

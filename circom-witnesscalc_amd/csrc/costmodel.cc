@@ -4,7 +4,9 @@
 
 namespace cwc {
 
-const CycleTable kCycles;
+// (the one snapshot of the environment that no entry point takes: the table is global and built when the library is loaded --
+// tests that change CWC_MODEL_CYCLES* run the library in a process of their own)
+const CycleTable kCycles(read_knobs());
 double model_class_cycles(int c) { return c >= 0 && c < (int)C_COUNT ? kCycles[c] : 0.0; }
 // a word that changes with the table: programs are chosen (and cached on disk) under one table
 uint64_t model_table_id() {

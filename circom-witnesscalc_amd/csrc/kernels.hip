@@ -1511,19 +1511,17 @@ hipError_t launch_fill_consts(uint32_t T, const ProgramDev& p, const WsTable& ws
     return hipGetLastError();
 }
 
-hipError_t launch_pack(uint32_t T, const ProgramDev& p, const WsTable& wst, void* out, uint32_t batch, hipStream_t stream, bool montgomery, uint32_t first) {
+hipError_t launch_pack(uint32_t T, const ProgramDev& p, const WsTable& wst, void* out, uint32_t batch, hipStream_t stream, bool montgomery, int pack_shape, uint32_t first) {
     if (p.n_witness == 0 || batch == 0 || first >= p.n_witness) return hipSuccess;
     const uint32_t count = p.n_witness - first;  // (first == 0: every witness index, today's grid)
     const uint32_t n_tiles = (batch + T - 1) / T;
-    static const bool v1 = getenv("CWC_PACK_V1") != nullptr;
-    if (v1 || T > 4) {  // (tiles of 8 sets and more: a thread walking all sets of its slot serialises 8..64 conversions -- 22.6 ms
+    if (pack_shape == 1 || T > 4) {  // (tiles of 8 sets and more: a thread walking all sets of its slot serialises 8..64 conversions -- 22.6 ms
                         // against 9.5 ms for the 8192-set pack at T = 8; the sets of a slot stay spread over the waves of a block)
         dim3 grid((count + 63) / 64, n_tiles < 32768u ? n_tiles : 32768u), block(64, T < 4 ? T : 4);
         if (montgomery) pack_kernel_v1<true><<<grid, block, 0, stream>>>(p, wst, (uint4*)out, batch, T, first);
         else pack_kernel_v1<false><<<grid, block, 0, stream>>>(p, wst, (uint4*)out, batch, T, first);
         return hipGetLastError();
     }
-    static const int pack_shape = getenv("CWC_PACK") ? atoi(getenv("CWC_PACK")) : 3;  // (2: one thread per slot, the round-2 shape, for A/B)
     if (pack_shape == 3 && T >= 2) {  // (T = 1: the two shapes are the same kernel)
         dim3 grid3((count + 256 / T - 1) / (256 / T), n_tiles < 32768u ? n_tiles : 32768u), block3(256);
 #define CWC_PACK3(MM, TT) pack_kernel_v3<MM, TT><<<grid3, block3, 0, stream>>>(p, wst, (uint4*)out, batch, first)

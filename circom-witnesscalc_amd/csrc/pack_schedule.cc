@@ -20,7 +20,7 @@ namespace cwcrt {
 // (stamped build, authV2-class graph, profiles/inline_pack_ab.txt).
 static const double kCyclesDividerServe = 52200, kCyclesPackPass = 2300;
 
-std::string make_pack_schedule(const Program& p, PackSchedule& out) {
+std::string make_pack_schedule(const Program& p, const Knobs& knobs, PackSchedule& out) {
     const uint32_t nw = p.n_witness, G = p.G, nreq = p.n_div_requests;
     out.order.resize(nw);
     out.ready.assign((size_t)nreq + 1, 0u);
@@ -63,8 +63,7 @@ std::string make_pack_schedule(const Program& p, PackSchedule& out) {
     for (uint32_t k = 1; k <= nreq; ++k) out.ready[k] += out.ready[k - 1];
     // Replay of a launch: how far the divider wave gets in the gaps between its requests.  In a gap it has seen k posts
     // (k requests served) and packs whole groups of G entries below ready[k]; a new post ends the gap.
-    double pass_cycles = kCyclesPackPass;
-    if (const char* e = getenv("CWC_PACK_PASS_CYCLES")) pass_cycles = std::max(1.0, atof(e));  // (what-if runs, like CWC_MODEL_CYCLES)
+    const double pass_cycles = knobs.pack_pass_cycles.value_or(kCyclesPackPass);  // (CWC_PACK_PASS_CYCLES: what-if runs, like CWC_MODEL_CYCLES)
     double clock = 0, div_free = 0, served = 0;
     uint32_t next = 0, k = 0;
     for (uint32_t b = 0; b < p.n_bundles && k <= nreq; ++b) {
@@ -87,10 +86,10 @@ std::string make_pack_schedule(const Program& p, PackSchedule& out) {
 
 }  // namespace cwcrt
 
-static int schedule_out(const Program& p, uint32_t* pack_order, size_t order_cap, uint32_t* pack_ready, size_t ready_cap, uint32_t* n_witness, uint32_t* n_ready,
+static int schedule_out(const Program& p, const Knobs& k, uint32_t* pack_order, size_t order_cap, uint32_t* pack_ready, size_t ready_cap, uint32_t* n_witness, uint32_t* n_ready,
                         uint32_t* n_inline, gw_status_t* status) {
     PackSchedule s;
-    const std::string err = make_pack_schedule(p, s);
+    const std::string err = make_pack_schedule(p, k, s);
     if (!err.empty()) return fail(status, err);
     if (n_witness) *n_witness = (uint32_t)s.order.size();
     if (n_ready) *n_ready = (uint32_t)s.ready.size();
@@ -104,6 +103,7 @@ static int schedule_out(const Program& p, uint32_t* pack_order, size_t order_cap
 extern "C" int gwb_pack_schedule_of_blob(const void* blob, size_t len, uint32_t* pack_order, size_t order_cap, uint32_t* pack_ready, size_t ready_cap,
                                          uint32_t* n_witness, uint32_t* n_ready, uint32_t* n_inline, gw_status_t* status) {
     return guarded(status, [&]() -> int {
+        const Knobs k = read_knobs();
         if (!blob) return fail(status, "null argument");
         if (len < 24 + 8) return fail(status, "bad blob: too short");
         const uint8_t* b = (const uint8_t*)blob;
@@ -114,13 +114,14 @@ extern "C" int gwb_pack_schedule_of_blob(const void* blob, size_t len, uint32_t*
         Program p;
         std::string err;
         if (!program_from_blob(b, (size_t)tr[0], p, err) || !validate_program(p, err)) return fail(status, "bad program blob: " + err);
-        return schedule_out(p, pack_order, order_cap, pack_ready, ready_cap, n_witness, n_ready, n_inline, status);
+        return schedule_out(p, k, pack_order, order_cap, pack_ready, ready_cap, n_witness, n_ready, n_inline, status);
     });
 }
 
 extern "C" int gwb_pack_schedule(gwb_graph_t* g, uint32_t program_key, uint32_t* pack_order, size_t order_cap, uint32_t* pack_ready, size_t ready_cap,
                                  uint32_t* n_witness, uint32_t* n_ready, uint32_t* n_inline, gw_status_t* status) {
     return guarded(status, [&]() -> int {
+        const Knobs k = read_knobs();
         if (!g) return fail(status, "null argument");
         std::lock_guard<std::mutex> lk(g->mu);
         Program tmp;
@@ -135,9 +136,9 @@ extern "C" int gwb_pack_schedule(gwb_graph_t* g, uint32_t program_key, uint32_t*
             p = pre->second.get();
         } else {
             if (!g->has_graph) return fail(status, "imported handle has no program for that key");
-            if (!compile_program(g->graph, program_key & ~KEY_MODE_MASK, key_divider_waves(program_key), tmp, err, key_streams(program_key))) return fail(status, err);
+            if (!compile_program(g->graph, k, program_key & ~KEY_MODE_MASK, key_divider_waves(program_key), tmp, err, key_streams(program_key))) return fail(status, err);
             p = &tmp;
         }
-        return schedule_out(*p, pack_order, order_cap, pack_ready, ready_cap, n_witness, n_ready, n_inline, status);
+        return schedule_out(*p, k, pack_order, order_cap, pack_ready, ready_cap, n_witness, n_ready, n_inline, status);
     });
 }

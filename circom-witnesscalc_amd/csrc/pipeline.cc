@@ -21,7 +21,7 @@ int fail(gw_status_t* st, const std::string& msg) {
     set_status(st, ERROR, msg);
     return 1;
 }
-std::string upload_program(DeviceProgram& dp) {
+std::string upload_program(DeviceProgram& dp, const Knobs& k) {
     const Program& p = dp.host;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     // (the interpreter reads the header two bundles ahead without a clamp: 16 bytes of zero padding behind the array)
@@ -31,7 +31,7 @@ std::string upload_program(DeviceProgram& dp) {
                  o_entries = o_order + al(p.witness_refs.size() * 4 + 4), o_ready = o_entries + al((p.witness_refs.size() + PACK_ENTRY_PAD) * 8),
                  total = o_ready + al(((size_t)p.n_div_requests + 1) * 4);
     {   // the pack schedule (pack_schedule.cc): derived here so that compiled, imported and cached programs all get one
-        const std::string serr = make_pack_schedule(p, dp.sched);
+        const std::string serr = make_pack_schedule(p, k, dp.sched);
         if (!serr.empty()) return serr;
     }
     HIP_TRY(hipMalloc(&dp.d_blob, total));
@@ -61,7 +61,7 @@ std::string upload_program(DeviceProgram& dp) {
     // their parallel form, 128-bit canonical products) live in interpreter instances of their own (MODE 3): a program with a borrow /
     // comparison bundle, or a carry-chain bundle of another width than 64 bits, runs there; every other limb program in the MODE 2
     // instances, whose code these kinds would only push apart (kernels.hip).
-    if (dp.dev.has_fused == 2u && getenv("CWC_FORCE_MODE3")) dp.dev.has_fused = 3u;  // (layout experiments: any limb program in the MODE 3 instances)
+    if (dp.dev.has_fused == 2u && k.force_mode3) dp.dev.has_fused = 3u;  // (layout experiments: any limb program in the MODE 3 instances)
     if (dp.dev.has_fused == 2u)
         for (uint32_t h : p.hdr)
             if ((h & HDR_CLASS_MASK) == C_SCAN && !(h & HDR_SCAN_CONV) &&
@@ -96,15 +96,15 @@ std::string upload_program(DeviceProgram& dp) {
 }
 
 // two-stream programs with divider waves: are two tiles one workgroup of eight waves? (see waves_per_workgroup)
-static bool stream_pair_workgroups(uint32_t divider, uint64_t tiles, uint32_t streams) {
+static bool stream_pair_workgroups(const Knobs& k, uint32_t divider, uint64_t tiles, uint32_t streams) {
     if (streams != 2 || divider != 1) return false;
-    if (const char* e = getenv("CWC_STREAM_TILES_PER_WORKGROUP")) return atoi(e) == 2;
+    if (k.stream_tiles_per_workgroup) return *k.stream_tiles_per_workgroup == 2;
     return tiles > 256;
 }
 // Interpreter waves per workgroup for programs without a divider wave: workgroups of four deal the waves evenly round
 // the four SIMDs of a CU (kernels.hip); below one wave per SIMD of the chip single-wave workgroups spread further.
 // CWC_WAVES_PER_WORKGROUP (1 or 4) overrides.
-uint32_t waves_per_workgroup(uint32_t divider, uint64_t tiles, uint32_t streams) {
+uint32_t waves_per_workgroup(const Knobs& k, uint32_t divider, uint64_t tiles, uint32_t streams) {
     // Two streams with their divider waves, more tiles than CUs: two tiles are ONE workgroup of eight waves, [A.s0, A.s1, B.s0, B.s1,
     // then the four divider waves in that order].  The waves of a workgroup are dealt round the CU's four SIMDs, so waves w and
     // w + 4 share one: every stream sits with its own divider wave, which mostly sleeps while the stream runs (stream 0 of the
@@ -112,23 +112,21 @@ uint32_t waves_per_workgroup(uint32_t divider, uint64_t tiles, uint32_t streams)
     // four-wave workgroups, two per CU, the second workgroup's waves land on the first one's SIMDs role by role (s0 + s1 on one
     // SIMD, the two dividers on another: tools/gpu_wave_census.py), 12.4 against 9.95 ms of interpreter launch at 1024 sets
     // (profiles/asym_streams_ab.txt).  CWC_STREAM_TILES_PER_WORKGROUP (1 or 2) overrides for measurements.
-    if (stream_pair_workgroups(divider, tiles, streams)) return 4u;
+    if (stream_pair_workgroups(k, divider, tiles, streams)) return 4u;
     // other programs of several streams: the streams of a tile (and their divider waves) are one workgroup
     if (streams > 1) return divider ? streams : 4u;
-    const char* e = getenv("CWC_WAVES_PER_WORKGROUP");
-    if (divider == 1) return e ? (atoi(e) >= 4 ? 2u : 1u) : (tiles > 256 ? 2u : 1u);  // units of (interpreter + divider)
+    const std::optional<int>& e = k.waves_per_workgroup;
+    if (divider == 1) return e ? (*e >= 4 ? 2u : 1u) : (tiles > 256 ? 2u : 1u);  // units of (interpreter + divider)
     if (divider) return 1;
-    if (e) return atoi(e) == 4 ? 4u : 1u;
+    if (e) return *e == 4 ? 4u : 1u;
     return tiles > 512 ? 4u : 1u;
 }
 
-uint64_t workspace_budget() {
-    const char* e = getenv("CWC_WORKSPACE_GB");
-    double gb = e ? atof(e) : 8.0;
+uint64_t workspace_budget(const Knobs& k) {
+    double gb = k.workspace_gb;
     if (gb < 1e-4) gb = 1e-4;  // tiny budgets are allowed (tests use them to force chunking); one tile is the floor
     return (uint64_t)(gb * (double)(1ull << 30));
 }
-}  // namespace cwcrt
 
 // Program choice (measured on MI355X, profiles/r01_sweep_batch_tile.txt).  A wave's time is the sum of its bundles;
 // wider tiles use the lanes better but need more bundles, and the chip holds 2048 of these waves (LDS: 8 per CU).
@@ -137,17 +135,20 @@ uint64_t workspace_budget() {
 // that serves the divisions while the interpreter goes on) pays while the extra waves find free SIMDs: up to 1024 tiles.
 // CWC_TARGET_WAVES (default 2048) and CWC_DIVIDER_TILES (default 1024) move the rules; gwb_set_tile_width /
 // CWC_TILE_WIDTH override them.
-extern "C" uint32_t gwb_pick_tile_width(size_t batch) {
-    size_t target = 2048, divider_tiles = 1024;
-    if (const char* e = getenv("CWC_TARGET_WAVES")) {
-        long v = atol(e);
-        if (v > 0) target = (size_t)v;
-    }
-    if (const char* e = getenv("CWC_DIVIDER_TILES")) divider_tiles = (size_t)atol(e);
+static uint32_t static_tile_rule(const Knobs& k, size_t batch) {
     uint32_t t = batch <= 256 ? 1 : batch <= 1024 ? 2 : 4;
-    while (t < 64 && (batch + t - 1) / t > target) t *= 2;
+    while (t < 64 && (batch + t - 1) / t > k.target_waves) t *= 2;
     const size_t tiles = (batch + t - 1) / t;
-    return t | (tiles <= divider_tiles && t < 64 ? KEY_DIVIDER : 0u);
+    return t | (tiles <= k.divider_tiles && t < 64 ? KEY_DIVIDER : 0u);
+}
+}  // namespace cwcrt
+
+extern "C" uint32_t gwb_pick_tile_width(size_t batch) {
+    try {
+        return static_tile_rule(read_knobs(), batch);
+    } catch (...) {  // (the snapshot allocates: no exception crosses the C boundary)
+        return 0;
+    }
 }
 
 namespace cwcrt {
@@ -182,7 +183,7 @@ std::string check_device() {
 // at 1024 tiles (measured / modelled 1.19-1.26 in rounds 2 and 3 against 1.11-1.25 for the pair programs: at x1.23 the model
 // took T = 2 + group divider for 2048 sets, 6 % behind T = 4 + pairs in both rounds' sweeps), rounds of 1024 tiles beyond.
 // (profiles/r01_sweep_batch_tile.txt, r03_sweep_batch_tile.txt)
-double estimate_cycles(const Program& p, size_t batch) {
+double estimate_cycles(const Knobs& k, const Program& p, size_t batch) {
     // (tiles of 8 sets and more: their bundles measure ~10 % above the per-class table, which was taken at T = 2 --
     // round 2, authV2-class: 8192 sets T = 4 41.2 ms, T = 8 44.2 ms, T = 8 + group divider 45.0 ms; 16384 sets T = 8 69.2 ms)
     const double wide = p.T >= 8 ? 1.10 : 1.0;
@@ -194,7 +195,7 @@ double estimate_cycles(const Program& p, size_t batch) {
         // per CU, 256 tiles at a time), 49 KiB for two; without, four waves of 20 KiB.  More live waves than SIMDs
         // (2 x 512 tiles + dividers measured x1.3) slow each other down.
         const double tiles = (double)((batch + p.T - 1) / p.T);
-        if (stream_pair_workgroups(p.divider, (uint64_t)tiles, p.n_streams)) {
+        if (stream_pair_workgroups(k, p.divider, (uint64_t)tiles, p.n_streams)) {
             // Two tiles per eight-wave workgroup (waves_per_workgroup): every stream shares its SIMD with its own divider wave and
             // with nothing else, 512 tiles at a time.  A stream takes the longer of its lone time and the work of its SIMD --
             // its bundles and its divider's inversions -- at the rate of two waves on one SIMD: kTwoWaves of their sum.
@@ -239,9 +240,7 @@ double estimate_cycles(const Program& p, size_t batch) {
 }
 
 // candidate program keys for a batch (the static rule's tile width and its neighbours, the divider / stream modes that fit)
-std::vector<uint32_t> candidate_keys(const ProgramStats& stats, size_t batch, uint32_t rule, uint32_t min_t) {
-    size_t divider_tiles = 1024;
-    if (const char* e = getenv("CWC_DIVIDER_TILES")) divider_tiles = (size_t)atol(e);
+std::vector<uint32_t> candidate_keys(const Knobs& k, const ProgramStats& stats, size_t batch, uint32_t rule, uint32_t min_t) {
     const bool has_div = stats.class_nodes[C_DIV] > 0;
     const uint32_t t0 = rule & ~KEY_MODE_MASK;
     std::vector<uint32_t> keys;
@@ -251,15 +250,15 @@ std::vector<uint32_t> candidate_keys(const ProgramStats& stats, size_t batch, ui
             if (tiles > 4 * 2048) continue;
             // divider waves: while every pair is resident; one divider per four interpreters: where a five-wave
             // workgroup per CU covers more than half of the batch at once
-            const bool divider_fits = has_div && tiles <= divider_tiles;
+            const bool divider_fits = has_div && tiles <= k.divider_tiles;
             if (mode == 0 && divider_fits) continue;  // (measured: with every pair resident the divider program always wins)
             if (mode == KEY_DIVIDER && !divider_fits) continue;
-            if (mode == KEY_TRIPLE && !(has_div && tiles > 512 && tiles <= 768 && !getenv("CWC_NO_GROUP_DIVIDER"))) continue;
-            if (mode == KEY_GROUP && !(has_div && tiles > 512 && tiles <= 1024 && !getenv("CWC_NO_GROUP_DIVIDER"))) continue;
+            if (mode == KEY_TRIPLE && !(has_div && tiles > 512 && tiles <= 768 && !k.no_group_divider)) continue;
+            if (mode == KEY_GROUP && !(has_div && tiles > 512 && tiles <= 1024 && !k.no_group_divider)) continue;
             keys.push_back(t | mode);
             // the graph's independent parts on wavefronts of their own (streams): while every stream of every tile has
             // a SIMD to itself (small batches, the single-shot entry point)
-            if ((mode == 0 || mode == KEY_DIVIDER) && t < 64 && !getenv("CWC_NO_STREAMS")) {
+            if ((mode == 0 || mode == KEY_DIVIDER) && t < 64 && !k.no_streams) {
                 if (tiles <= 256) keys.push_back(t | mode | KEY_STREAMS4);
                 else if (tiles <= 340) keys.push_back(t | mode | KEY_STREAMS2);
                 // ... and up to two tiles per CU where every stream has a divider wave to share its SIMD with (waves_per_workgroup).
@@ -268,25 +267,25 @@ std::vector<uint32_t> candidate_keys(const ProgramStats& stats, size_t batch, ui
                 // waves' pack through the automatic choice, profiles/inline_pack_ab.txt 2 and 4): the switches act on one-stream
                 // programs only, so under them the choice stays among the candidates it had before this offer existed and both
                 // arms of such an A/B run the program the switch acts on.
-                else if (mode == KEY_DIVIDER && t >= 2 && tiles <= 512 && !getenv("CWC_INLINE_PACK") && !getenv("CWC_INLINE_PACK_ROWS"))
+                else if (mode == KEY_DIVIDER && t >= 2 && tiles <= 512 && !k.inline_pack && !k.inline_pack_rows)
                     keys.push_back(t | mode | KEY_STREAMS2);
             }
         }
     return keys;
 }
 
-// the full choice for a batch size, on a thread of its own (reads the graph only): every candidate compiled with the
+// the full choice for a batch size, on a thread of its own (reads the graph and its copy of the knobs only): every candidate compiled with the
 // search over schedule variants, priced by the cost model
-gwb_graph::Refined refine_choice(const Graph& graph, const ProgramStats& stats, size_t batch, uint32_t rule, uint32_t min_t) {
+gwb_graph::Refined refine_choice(const Knobs& k, const Graph& graph, const ProgramStats& stats, size_t batch, uint32_t rule, uint32_t min_t) {
     gwb_graph::Refined r;
     try {
         double best_cost = -1;
         std::unique_ptr<SharedRewrites, void (*)(SharedRewrites*)> rewrites(make_shared_rewrites(), free_shared_rewrites);  // (one rewritten graph per tile width)
-        for (uint32_t key : candidate_keys(stats, batch, rule, min_t)) {
+        for (uint32_t key : candidate_keys(k, stats, batch, rule, min_t)) {
             std::unique_ptr<Program> p(new Program());
             std::string err;
-            if (!compile_program(graph, key & ~KEY_MODE_MASK, key_divider_waves(key), *p, err, key_streams(key), false, rewrites.get())) continue;
-            const double cost = estimate_cycles(*p, batch);
+            if (!compile_program(graph, k, key & ~KEY_MODE_MASK, key_divider_waves(key), *p, err, key_streams(key), false, rewrites.get())) continue;
+            const double cost = estimate_cycles(k, *p, batch);
             if (best_cost < 0 || cost < best_cost) {
                 best_cost = cost;
                 r.best = key;
@@ -304,34 +303,33 @@ gwb_graph::Refined refine_choice(const Graph& graph, const ProgramStats& stats, 
 // compiled (host only) and priced with the cost model; the choice is remembered per batch size.
 // allow_quick = false: the caller wants the searched program now (the program that is exported / broadcast to other ranks:
 // imported handles are never refined, a provisional single-schedule program would stay with them for good).
-uint32_t pick_tile_width(gwb_graph* g, size_t batch, bool allow_quick) {
+uint32_t pick_tile_width(gwb_graph* g, const Knobs& k, size_t batch, bool allow_quick) {
     if (!g->has_graph && !g->progs.empty()) return g->progs.begin()->first;  // imported: the one program it has
     if (g->forced_T) return g->forced_T;
-    if (const char* e = getenv("CWC_TILE_WIDTH")) {  // width, or width + 256 for the asynchronous divider
-        const uint32_t key = (uint32_t)atoi(e), t = key & ~KEY_MODE_MASK;
+    if (k.tile_width) {  // width, or width + 256 for the asynchronous divider
+        const uint32_t key = *k.tile_width, t = key & ~KEY_MODE_MASK;
         if (t >= 1 && t <= 64 && !(t & (t - 1))) return key;
     }
-    uint32_t rule = gwb_pick_tile_width(batch);
+    uint32_t rule = static_tile_rule(k, batch);
     // Deep graphs: a program is one header word, G records and G third-operand words per bundle, and a bundle per
     // dependency level at least -- 1 KiB per bundle at T = 1 (1.6 GB for the 10.5 M-node bigint-class graph of
     // BASELINE config 5, depth 1.29 M).  Small batches fill the same number of SIMDs whatever the tile width (every tile
     // is one wave), so the width is raised until the program stream fits CWC_PROGRAM_MB (default 960): 0.85 GB at T = 2.
     uint32_t min_t = 1;
     {
-        double budget = 960.0;
-        if (const char* e = getenv("CWC_PROGRAM_MB")) budget = atof(e);
+        const double budget = k.program_mb;
         const double per_bundle_t1 = 4.0 + 64.0 * 16.0;
         // (tile widths with scan bundles: limb recurrences take a tenth of their depth in bundles)
-        auto levels = [&](uint32_t t) { return (double)(t <= SCAN_MAX_T && !getenv("CWC_NO_SCAN") && g->stats.depth_scan ? g->stats.depth_scan : g->stats.depth); };
+        auto levels = [&](uint32_t t) { return (double)(t <= SCAN_MAX_T && !k.no_scan && g->stats.depth_scan ? g->stats.depth_scan : g->stats.depth); };
         while (min_t < 16 && levels(min_t) * 1.25 * (4.0 + (per_bundle_t1 - 4.0) / min_t) > budget * 1048576.0) min_t *= 2;
         if ((rule & ~KEY_MODE_MASK) < min_t) rule = min_t | ((rule & KEY_MODE_MASK) && min_t < 64 ? (rule & KEY_MODE_MASK) : 0u);
     }
-    if (getenv("CWC_STATIC_TILE_RULE") || !g->has_graph) return rule;
+    if (k.static_tile_rule || !g->has_graph) return rule;
     auto hit = g->chosen.find(batch);
     if (hit != g->chosen.end()) return hit->second;
     // ---- small batches: quick program first, the full choice in the background (see gwb_graph::refining) ----
     // (graphs beyond two million nodes have one schedule anyway: nothing for the background to search)
-    if (batch < 64 && g->graph.nodes.size() <= 2000000 && !getenv("CWC_NO_QUICK_FIRST_CALL")) {
+    if (batch < 64 && g->graph.nodes.size() <= 2000000 && !k.no_quick_first_call) {
         auto job = g->refining.find(batch);
         if (job != g->refining.end()) {
             if (!allow_quick) {  // wait for the search that is under way
@@ -360,11 +358,11 @@ uint32_t pick_tile_width(gwb_graph* g, size_t batch, bool allow_quick) {
         }
         const bool has_div0 = g->stats.class_nodes[C_DIV] > 0;
         const uint32_t t1 = std::max(1u, min_t);
-        const uint32_t quick_key = t1 | (has_div0 && t1 < 64 ? KEY_DIVIDER : 0u) | (t1 < 64 && !getenv("CWC_NO_STREAMS") ? KEY_STREAMS4 : 0u);
+        const uint32_t quick_key = t1 | (has_div0 && t1 < 64 ? KEY_DIVIDER : 0u) | (t1 < 64 && !k.no_streams ? KEY_STREAMS4 : 0u);
         if (allow_quick && !g->progs.count(quick_key) && !g->compiled.count(quick_key)) {
             std::unique_ptr<Program> p(new Program());
             std::string err;
-            if (compile_program(g->graph, quick_key & ~KEY_MODE_MASK, key_divider_waves(quick_key), *p, err, key_streams(quick_key), true)) g->compiled[quick_key] = std::move(p);
+            if (compile_program(g->graph, k, quick_key & ~KEY_MODE_MASK, key_divider_waves(quick_key), *p, err, key_streams(quick_key), true)) g->compiled[quick_key] = std::move(p);
         }
         if (allow_quick && (g->progs.count(quick_key) || g->compiled.count(quick_key))) {
             const Graph* graph = &g->graph;
@@ -377,15 +375,16 @@ uint32_t pick_tile_width(gwb_graph* g, size_t batch, bool allow_quick) {
             if (!g->refine_gate) g->refine_gate = std::make_shared<std::atomic<bool>>(false);
             g->refine_gate->store(false);
             std::shared_ptr<std::atomic<bool>> gate = g->refine_gate;
-            g->refining[batch] = std::async(std::launch::async, [graph, stats, batch, rule, min_t, cache_file, inputs, gate]() {
+            // (the task holds its own copy of this call's knobs: it compiles long after the call has returned)
+            g->refining[batch] = std::async(std::launch::async, [k, graph, stats, batch, rule, min_t, cache_file, inputs, gate]() {
                 for (int waited = 0; !gate->load() && waited < 2000; ++waited) std::this_thread::sleep_for(std::chrono::milliseconds(1));
-                gwb_graph::Refined r = refine_choice(*graph, stats, batch, rule, min_t);
+                gwb_graph::Refined r = refine_choice(k, *graph, stats, batch, rule, min_t);
                 auto best = r.programs.find(r.best);
                 if (!cache_file.empty() && r.best && best != r.programs.end()) {
                     try {
                         const std::vector<uint8_t> b0 = exported_bytes(*best->second, inputs), b = cache_wrap(cache_file, b0.data(), b0.size());
                         write_file_atomically(cache_file, b.data(), b.size());
-                        if (getenv("CWC_DEBUG_CACHE")) fprintf(stderr, "program cache: wrote %s (program key %#x, %zu bytes)\n", cache_file.c_str(), r.best, b.size());
+                        if (k.debug_cache) fprintf(stderr, "program cache: wrote %s (program key %#x, %zu bytes)\n", cache_file.c_str(), r.best, b.size());
                     } catch (...) {
                     }
                 }
@@ -394,11 +393,11 @@ uint32_t pick_tile_width(gwb_graph* g, size_t batch, bool allow_quick) {
             return quick_key;
         }
     }
-    const bool debug = getenv("CWC_DEBUG_COST") != nullptr;
+    const bool debug = k.debug_cost;
     uint32_t best = rule;
     double best_cost = -1;
-    const std::vector<uint32_t> keys = candidate_keys(g->stats, batch, rule, min_t);
-    // the candidates that are not compiled yet, each on a thread of its own (the compiler only reads the graph)
+    const std::vector<uint32_t> keys = candidate_keys(k, g->stats, batch, rule, min_t);
+    // the candidates that are not compiled yet, each on a thread of its own (the compiler only reads the graph and the thread's copy of the knobs)
     // (candidates of one tile width share the rewritten graph: the first thread through rewrites, the others copy)
     std::unique_ptr<SharedRewrites, void (*)(SharedRewrites*)> rewrites(make_shared_rewrites(), free_shared_rewrites);
     std::vector<std::pair<uint32_t, std::future<std::unique_ptr<Program>>>> jobs;
@@ -406,10 +405,10 @@ uint32_t pick_tile_width(gwb_graph* g, size_t batch, bool allow_quick) {
         if (!g->progs.count(key) && !g->compiled.count(key)) {
             const Graph* graph = &g->graph;
             SharedRewrites* shared = rewrites.get();
-            jobs.emplace_back(key, std::async(std::launch::async, [graph, key, shared]() {
+            jobs.emplace_back(key, std::async(std::launch::async, [k, graph, key, shared]() {
                                   std::unique_ptr<Program> p(new Program());
                                   std::string err;
-                                  if (!compile_program(*graph, key & ~KEY_MODE_MASK, key_divider_waves(key), *p, err, key_streams(key), false, shared)) p.reset();
+                                  if (!compile_program(*graph, k, key & ~KEY_MODE_MASK, key_divider_waves(key), *p, err, key_streams(key), false, shared)) p.reset();
                                   return p;
                               }));
         }
@@ -424,7 +423,7 @@ uint32_t pick_tile_width(gwb_graph* g, size_t batch, bool allow_quick) {
         if (up != g->progs.end()) p = &up->second->host;
         else if (pre != g->compiled.end()) p = pre->second.get();
         else continue;  // (did not compile: not a candidate)
-        const double cost = estimate_cycles(*p, batch);
+        const double cost = estimate_cycles(k, *p, batch);
         if (debug) fprintf(stderr, "cost model: batch %zu key %#x -> %.1f Mcycles\n", batch, key, cost / 1e6);
         if (best_cost < 0 || cost < best_cost) {
             best_cost = cost;
@@ -435,7 +434,7 @@ uint32_t pick_tile_width(gwb_graph* g, size_t batch, bool allow_quick) {
     return best;
 }
 
-std::string get_program(gwb_graph* g, uint32_t key, DeviceProgram** out) {
+std::string get_program(gwb_graph* g, const Knobs& k, uint32_t key, DeviceProgram** out) {
     const uint32_t T = key & ~KEY_MODE_MASK;
     if (T == 64) key = T;  // no divider programs at T = 64
     auto it = g->progs.find(key);
@@ -450,10 +449,10 @@ std::string get_program(gwb_graph* g, uint32_t key, DeviceProgram** out) {
     if (pre != g->compiled.end()) {  // already compiled for the cost model
         dp->host = std::move(*pre->second);
         g->compiled.erase(pre);
-    } else if (!compile_program(g->graph, T, key_divider_waves(key), dp->host, err, key_streams(key))) {
+    } else if (!compile_program(g->graph, k, T, key_divider_waves(key), dp->host, err, key_streams(key))) {
         return err;
     }
-    err = upload_program(*dp);
+    err = upload_program(*dp, k);
     if (!err.empty()) return err;
     *out = dp.get();
     g->progs[key] = std::move(dp);
@@ -461,14 +460,14 @@ std::string get_program(gwb_graph* g, uint32_t key, DeviceProgram** out) {
 }
 
 static const bool kInlinePackDefault = true;  // (same-box A/B: profiles/inline_pack_ab.txt)
-std::string run_device(gwb_graph* g, const void* d_inputs, size_t batch, void* d_witness, uint32_t* d_status,
+std::string run_device(gwb_graph* g, const Knobs& k, const void* d_inputs, size_t batch, void* d_witness, uint32_t* d_status,
                        hipStream_t stream, bool montgomery, hipEvent_t done_event) {
     if (batch == 0) return "";
     if (batch > 0x7fffffffull) return "batch too large";
-    static const bool dbg_steps = getenv("CWC_DEBUG_SINGLE") != nullptr;  // diagnostic: program choice / upload of a call
+    const bool dbg_steps = k.debug_single;  // diagnostic: program choice / upload of a call
     auto now_ms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_0 = dbg_steps ? now_ms() : 0.0;
-    const uint32_t key = pick_tile_width(g, batch);
+    const uint32_t key = pick_tile_width(g, k, batch);
     struct OpenGate {  // every way out of this call (errors included) lets a waiting background search start
         gwb_graph* g;
         ~OpenGate() {
@@ -477,7 +476,7 @@ std::string run_device(gwb_graph* g, const void* d_inputs, size_t batch, void* d
     } open_gate{g};
     const double t_1 = dbg_steps ? now_ms() : 0.0;
     DeviceProgram* dp = nullptr;
-    std::string err = get_program(g, key, &dp);
+    std::string err = get_program(g, k, key, &dp);
     if (!err.empty()) return err;
     const double t_2 = dbg_steps ? now_ms() : 0.0;
     g->last_key = (key & ~KEY_MODE_MASK) == 64 ? 64u : key;
@@ -504,7 +503,7 @@ std::string run_device(gwb_graph* g, const void* d_inputs, size_t batch, void* d
     // Workspace: tiles of (constants | value slots | trash slot), grouped into separately allocated chunks of at most
     // CWC_WORKSPACE_GB; larger batches than WS_MAX_CHUNKS chunks hold are evaluated in several launches.
     const uint64_t bytes_per_tile = ws_tile_bytes(p.n_const, p.n_slots, T);
-    const uint64_t budget = workspace_budget();
+    const uint64_t budget = workspace_budget(k);
     if (bytes_per_tile > 0xffffffffull) return "graph too large for the 4 GiB tile window";
     uint64_t max_tiles = budget / bytes_per_tile;
     if (max_tiles == 0) max_tiles = 1;
@@ -516,10 +515,7 @@ std::string run_device(gwb_graph* g, const void* d_inputs, size_t batch, void* d
     // chunks per launch: all of them when they fit the table (CWC_STREAMS caps the number); otherwise several
     // launches, one after the other
     size_t per_launch = n_chunks < WS_MAX_CHUNKS ? n_chunks : WS_MAX_CHUNKS;
-    if (const char* e = getenv("CWC_STREAMS")) {
-        const long v = atol(e);
-        if (v >= 1 && (size_t)v < per_launch) per_launch = (size_t)v;
-    }
+    if (k.streams >= 1 && (size_t)k.streams < per_launch) per_launch = (size_t)k.streams;
     bool refill = g->filled_prog != dp || g->filled_tiles_per_chunk != chunk_tiles || g->filled_chunks < per_launch;
     for (size_t l = 0; l < per_launch; ++l) {
         if (need > g->vals_bytes[l]) {
@@ -551,11 +547,12 @@ std::string run_device(gwb_graph* g, const void* d_inputs, size_t batch, void* d
     g->timing.streams = p.n_streams;
     g->timing.n_bundles = p.n_bundles;
     g->timing.n_slots = p.n_slots;
-    // CWC_INLINE_PACK (read per call: one process can run both paths): 0 the pack kernel packs every row, 1 the divider
-    // waves take the schedule's prefix, 2 everything that is ever ready in front of the last request (tests, measurements)
+    // CWC_INLINE_PACK (per call: one process can run both paths; the same snapshot the program choice saw): 0 the pack kernel packs
+    // every row, 1 the divider waves take the schedule's prefix, 2 everything that is ever ready in front of the last request (tests, measurements)
     uint32_t n_inline = kInlinePackDefault ? dp->dev.n_inline : 0u;
-    if (const char* e = getenv("CWC_INLINE_PACK")) n_inline = atoi(e) >= 2 ? dp->dev.n_ready_last : atoi(e) == 1 ? dp->dev.n_inline : 0u;
-    if (const char* e = getenv("CWC_INLINE_PACK_ROWS")) n_inline = std::min<uint32_t>(n_inline, (uint32_t)atol(e));  // (measurements: a cap on the divider waves' share)
+    if (k.inline_pack) n_inline = *k.inline_pack >= 2 ? dp->dev.n_ready_last : *k.inline_pack == 1 ? dp->dev.n_inline : 0u;
+    if (k.inline_pack_rows) n_inline = std::min<uint32_t>(n_inline, *k.inline_pack_rows);  // (measurements: a cap on the divider waves' share)
+    const int pack_shape = k.pack_v1 ? 1 : k.pack == 3 ? 3 : 2;
     const size_t launch_sets = per_launch * chunk_sets;
     for (size_t s0 = 0; s0 < batch; s0 += launch_sets) {
         const uint32_t nb = (uint32_t)((batch - s0) < launch_sets ? (batch - s0) : launch_sets);
@@ -580,10 +577,10 @@ std::string run_device(gwb_graph* g, const void* d_inputs, size_t batch, void* d
         g->pending.push_back(gwb_graph::ChunkEvents{e0, e1, e2});  // (owned by the handle from here on, also on an early return)
         HIP_TRY(hipEventRecord(e0, stream));
         void* const out = (char*)d_witness + s0 * (size_t)p.n_witness * 32;
-        HIP_TRY(launch_interp(T, p.divider, waves_per_workgroup(p.divider, (nb + T - 1) / T, p.n_streams), p.n_div_requests, dp->dev.div_lanes, dp->dev, wst, (const char*)d_inputs + s0 * p.n_inputs * 32, d_status + s0, nb, stream, g->d_prof,
+        HIP_TRY(launch_interp(T, p.divider, waves_per_workgroup(k, p.divider, (nb + T - 1) / T, p.n_streams), p.n_div_requests, dp->dev.div_lanes, dp->dev, wst, (const char*)d_inputs + s0 * p.n_inputs * 32, d_status + s0, nb, stream, g->d_prof,
                               out, n_inline, montgomery));
         HIP_TRY(hipEventRecord(e1, stream));  // (interp_ms includes the rows the divider waves packed, pack_ms is the rest's)
-        HIP_TRY(launch_pack(T, dp->dev, wst, out, nb, stream, montgomery, n_inline));
+        HIP_TRY(launch_pack(T, dp->dev, wst, out, nb, stream, montgomery, pack_shape, n_inline));
         HIP_TRY(hipEventRecord(e2, stream));
         g->last_call_launches++;
         g->timing.n_launches++;
@@ -610,27 +607,7 @@ bool is_pinned_host(const void* p) {
     return a.type == hipMemoryTypeHost;
 }
 
-unsigned env_threads(const char* name, unsigned cap) {
-    long v = 0;
-    if (const char* e = getenv(name)) v = atol(e);
-    if (v <= 0) {
-        v = (long)std::thread::hardware_concurrency();
-        if (cap && v > (long)cap) v = cap;
-    }
-    return v < 1 ? 1u : (unsigned)v;
-}
-
-unsigned copy_threads() {
-    long v = 0;
-    if (const char* e = getenv("CWC_COPY_THREADS")) v = atol(e);
-    if (v <= 0) {
-        v = (long)std::thread::hardware_concurrency();
-        if (v > 16) v = 16;
-    }
-    return v < 1 ? 1u : (unsigned)v;
-}
-
-std::string device_to_host_rows(gwb_graph* g, void* dst, const void* d_src, size_t bytes) {
+std::string device_to_host_rows(gwb_graph* g, const Knobs& k, void* dst, const void* d_src, size_t bytes) {
     if (bytes == 0) return "";
     if (!g->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&g->copy_stream, hipStreamNonBlocking));
     if (is_pinned_host(dst)) {
@@ -638,11 +615,7 @@ std::string device_to_host_rows(gwb_graph* g, void* dst, const void* d_src, size
         HIP_TRY(hipStreamSynchronize(g->copy_stream));
         return "";
     }
-    size_t slice = 32u << 20;
-    if (const char* e = getenv("CWC_COPY_SLICE_MB")) {
-        const long v = atol(e);
-        if (v >= 1 && v <= 1024) slice = (size_t)v << 20;
-    }
+    size_t slice = k.copy_slice_mb << 20;
     // (pinned memory is slow to get -- two 32 MB buffers were 90 ms of the single-shot entry point's first call: a transfer
     // that fits one slice takes one buffer of its own size)
     if (bytes < slice) slice = std::max<size_t>(g->stage_bytes, (bytes + (1u << 20) - 1) & ~(size_t)((1u << 20) - 1));
@@ -660,7 +633,7 @@ std::string device_to_host_rows(gwb_graph* g, void* dst, const void* d_src, size
     for (int i = 0; i < 2; ++i)
         if (!g->stage_done[i]) HIP_TRY(hipEventCreateWithFlags(&g->stage_done[i], hipEventDisableTiming));
     const size_t n_slices = (bytes + slice - 1) / slice;
-    const unsigned n_workers = bytes < (8u << 20) ? 1u : copy_threads();
+    const unsigned n_workers = bytes < (8u << 20) ? 1u : k.copy_threads;
     // workers: slice k is theirs once `ready` > k; each takes one stripe of it and counts itself in consumed[k]
     std::atomic<long> ready{0};
     std::atomic<bool> abort{false};
@@ -714,7 +687,7 @@ std::string device_to_host_rows(gwb_graph* g, void* dst, const void* d_src, size
     return err;
 }
 
-std::string run_host(gwb_graph* g, const void* inputs, size_t batch, void* witness, uint32_t* set_status) {
+std::string run_host(gwb_graph* g, const Knobs& k, const void* inputs, size_t batch, void* witness, uint32_t* set_status) {
     if (batch == 0) return "";
     const size_t in_b = batch * (size_t)g->n_inputs * 32, out_b = batch * (size_t)g->n_witness * 32;
     auto grow = [](void*& p, size_t& have, size_t need) -> std::string {
@@ -726,7 +699,7 @@ std::string run_host(gwb_graph* g, const void* inputs, size_t batch, void* witne
         have = need;
         return "";
     };
-    static const bool dbg_steps = getenv("CWC_DEBUG_SINGLE") != nullptr;  // diagnostic: the steps of a host-rows call
+    const bool dbg_steps = k.debug_single;  // diagnostic: the steps of a host-rows call
     auto now_ms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = dbg_steps ? now_ms() : 0.0;
     std::string err = grow(g->h_in, g->h_in_bytes, in_b ? in_b : 32);
@@ -735,12 +708,12 @@ std::string run_host(gwb_graph* g, const void* inputs, size_t batch, void* witne
     if (!err.empty()) return err;
     HIP_TRY(hipMemcpy(g->h_in, inputs, in_b, hipMemcpyHostToDevice));
     const double t1 = dbg_steps ? now_ms() : 0.0;
-    err = run_device(g, g->h_in, batch, g->h_out, (uint32_t*)g->h_st, nullptr);
+    err = run_device(g, k, g->h_in, batch, g->h_out, (uint32_t*)g->h_st, nullptr);
     if (!err.empty()) return err;
     const double t2 = dbg_steps ? now_ms() : 0.0;
     HIP_TRY(hipDeviceSynchronize());
     const double t3 = dbg_steps ? now_ms() : 0.0;
-    err = device_to_host_rows(g, witness, g->h_out, out_b);
+    err = device_to_host_rows(g, k, witness, g->h_out, out_b);
     if (!err.empty()) return err;
     HIP_TRY(hipMemcpy(set_status, g->h_st, batch * 4, hipMemcpyDeviceToHost));
     if (dbg_steps && now_ms() - t0 > 20.0)
@@ -762,7 +735,7 @@ std::string set_status_text(uint32_t bits) {
 // point, beside the host's parsing and compiling of a new graph (~120 ms for the authV2-class graph) -- the calling thread
 // does its host work first and touches the device last (it then waits on the runtime's own locks for what is left).
 // Errors are left to the calling thread's own checks.
-void warm_device() {
+void warm_device(const Knobs& k) {
     // (joined when the process exits -- an error return may leave the caller free to exit while the runtime is still
     // coming up on this thread; the holder is made on first use, so it is destroyed before the runtime's own statics)
     struct Joined {
@@ -773,8 +746,8 @@ void warm_device() {
     };
     static Joined warm;
     static std::once_flag once;
-    std::call_once(once, []() {
-        if (getenv("CWC_NO_WARM_THREAD")) return;
+    std::call_once(once, [&k]() {  // (the first call's snapshot decides for the process, as the first call's environment did)
+        if (k.no_warm_thread) return;
         warm.t = std::thread([]() {
             int n = 0;
             if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "graph.hpp"
+#include "knobs.hpp"
 #include "program_dev.h"
 
 namespace cwc {
@@ -58,7 +59,8 @@ struct Program {
 };
 
 // Validates the graph (backward references, evaluable ops, index ranges) and compiles it for tile width T
-// (power of two, 1..64); divider = W > 0 compiles divisions for a divider wave shared by W interpreter waves (W = 1 or
+// (power of two, 1..64) under the knobs of `k` (knobs.hpp: the caller's snapshot of the environment, the compiler reads
+// nothing else); divider = W > 0 compiles divisions for a divider wave shared by W interpreter waves (W = 1 or
 // 4, T < 64 only).
 // streams = 2 or 4: the graph's independent parts are spread over that many wavefronts per tile (fewer when it has fewer
 // parts; divider 0 or 1 only).
@@ -70,10 +72,10 @@ struct Program {
 struct SharedRewrites;
 SharedRewrites* make_shared_rewrites();
 void free_shared_rewrites(SharedRewrites*);
-bool compile_program(const Graph& g, uint32_t T, uint32_t divider, Program& out, std::string& err, uint32_t streams = 1, bool quick = false,
+bool compile_program(const Graph& g, const Knobs& k, uint32_t T, uint32_t divider, Program& out, std::string& err, uint32_t streams = 1, bool quick = false,
                      SharedRewrites* shared = nullptr);
 // Validation and statistics of a loaded graph without compiling a program: out.stats, out.n_inputs, out.n_witness.
-bool probe_graph(const Graph& g, Program& out, std::string& err);
+bool probe_graph(const Graph& g, const Knobs& k, Program& out, std::string& err);
 // "program key" used by the runtime and the C-ABI wherever a tile width is passed: T | KEY_DIVIDER | KEY_GROUP
 static const uint32_t KEY_DIVIDER = 0x100u;  // one divider wave per interpreter wave
 static const uint32_t KEY_GROUP = 0x200u;    // one divider wave per four interpreter waves

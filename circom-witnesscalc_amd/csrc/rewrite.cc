@@ -115,7 +115,7 @@ void fuse_bit_extract(Graph& g) {
 // round).  The intermediate nodes of the chain are still computed wherever something else (a witness element, another
 // node) needs them; common subexpressions are shared; nodes that end up unused are dropped.
 // Only Add/Mul nodes are touched, so every operation that can fail (graph.rs:634, :686-716) survives unchanged.
-void reduce_tree_height(Graph& g, size_t kMaxLeaves, const uint32_t* class_cost) {
+void reduce_tree_height(Graph& g, size_t kMaxLeaves, const uint32_t* class_cost, const Knobs& k) {
     // <functional> comparators below
     const size_t N = g.nodes.size();
     Graph h;
@@ -200,8 +200,7 @@ void reduce_tree_height(Graph& g, size_t kMaxLeaves, const uint32_t* class_cost)
         // the limb chains in scan bundles those linear bundles are 34 of 62 bundles per round instead of 19 of 49, 15 % of
         // the run time, and the rest of the compile got cheaper -- 1 M nodes: rewrites 1.17 -> 0.27 s;
         // CWC_TREE_INNER_SKIP=1 / 0 forces either way).
-        const char* force = getenv("CWC_TREE_INNER_SKIP");
-        if (kMaxLeaves >= 64 && (force ? atoi(force) != 0 : N > 16000000)) {
+        if (kMaxLeaves >= 64 && k.tree_inner_skip.value_or(N > 16000000)) {
             for (size_t i = 0; i < N; ++i) inner[i] = n_users[i] == 1 && same_op_users[i] == 1;
             kMaxLeaves = 1u << 16;
         }
@@ -363,9 +362,9 @@ void reduce_tree_height(Graph& g, size_t kMaxLeaves, const uint32_t* class_cost)
 // limb products are far below r, and the kernel multiplies limb-sized integers directly (general operands: two Montgomery
 // products).
 void infer_representations(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>& vflags, uint64_t& n_conversions, uint64_t& n_canonical, bool all_montgomery,
-                                  bool allow_cc, uint64_t& n_cc, bool canonical_inputs) {
+                                  bool allow_cc, uint64_t& n_cc, bool canonical_inputs, const Knobs& k) {
     const size_t N = g.nodes.size();
-    const bool off = all_montgomery || getenv("CWC_NO_REP_INFERENCE") != nullptr;
+    const bool off = all_montgomery || k.no_rep_inference;
     // what the users of a value would rather read: > 0 canonical
     std::vector<float> pref(N, 0.0f);
     for (size_t i = N; !off && i-- > 0;) {
@@ -569,7 +568,7 @@ static void compact_dead(Graph& g, const std::vector<uint8_t>& dead, std::vector
 // index of the constant 2^k (its Montgomery form is what the general path multiplies with).
 // scan_partner[node]: the other node of the step.
 void detect_scans(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>& vflags, std::vector<uint32_t>& scan_imm, std::vector<uint32_t>& scan_partner,
-                         uint64_t& n_steps) {
+                         uint64_t& n_steps, const Knobs& k) {
     const size_t N = g.nodes.size();
     static const uint32_t NONE = 0xffffffffu;
     std::vector<uint32_t> uses(N, 0);
@@ -683,7 +682,7 @@ void detect_scans(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>& vfl
             reg_of_operand[steps[k].x] = reg_of_operand[steps[k].acc_in] = (uint32_t)k;
         }
         const size_t n_regular = steps.size();
-        if (getenv("CWC_DEBUG_SCAN")) {
+        if (k.debug_scan) {
             size_t pairs = 0, not_t = 0, can = 0, linked = 0;
             for (size_t x = 0; x < N; ++x) {
                 if (end_out[x] >= NONE - 1 || end_acc[x] >= NONE - 1) continue;
@@ -695,8 +694,7 @@ void detect_scans(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>& vfl
             }
             fprintf(stderr, "chain ends: %zu values with an OUT / ACC pair, %zu besides the regular steps, %zu canonical, %zu linked to a regular step\n", pairs, not_t, can, linked);
         }
-        const bool no_ends = getenv("CWC_NO_SCAN_ENDS") != nullptr;
-        for (size_t x = 0; x < N && !no_ends; ++x) {
+        for (size_t x = 0; x < N && !k.no_scan_ends; ++x) {
             const uint32_t o = end_out[x], a = end_acc[x];
             if (o >= NONE - 1 || a >= NONE - 1 || is_t[x] || !canon((uint32_t)x)) continue;
             const Node &O = g.nodes[o], &A = g.nodes[a];
@@ -719,7 +717,7 @@ void detect_scans(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>& vfl
     // optimiser's sweep -- only limb = (x + carry) & (2^n - 1) is there (the top register of a long_scalar_mult whose carry is dropped).
     // The sum, read by nothing else, becomes the step's ACC node (its value, the carry, is read by nothing): the step joins its chain's
     // bundle instead of costing an Add bundle and a Band bundle on the chain's critical path.
-    if (!getenv("CWC_NO_SCAN_ENDS")) {
+    if (!k.no_scan_ends) {
         std::vector<uint32_t> acc_of_regular(N, NONE);
         for (size_t k = 0; k < steps.size(); ++k)
             if (!steps[k].div) acc_of_regular[steps[k].acc] = (uint32_t)k;
@@ -737,7 +735,7 @@ void detect_scans(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>& vfl
             steps.push_back(Step{NONE, o, (uint32_t)t, b_is ? T_.a : T_.b, b_is ? T_.b : T_.a, 0, (uint32_t)n, false});
         }
     }
-    if (getenv("CWC_DEBUG_SCAN")) {
+    if (k.debug_scan) {
         size_t n_band = 0, n_shr = 0, pairs = 0, uses_ok = 0, rep_ok = 0, canon_ok = 0;
         for (size_t t = 0; t < N; ++t) {
             n_band += user_out[t] < NONE - 1;
@@ -821,10 +819,11 @@ struct LinForm {  // sum of coeff * node + k (field constant), at most 6 terms
 };
 }  // namespace
 
-void detect_bit_scans(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>& vflags, std::vector<uint32_t>& scan_imm, std::vector<uint32_t>& scan_partner, uint64_t& n_steps) {
+void detect_bit_scans(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>& vflags, std::vector<uint32_t>& scan_imm, std::vector<uint32_t>& scan_partner, uint64_t& n_steps,
+                      const Knobs& k) {
     const size_t N = g.nodes.size();
     static const uint32_t NONE = 0xffffffffu;
-    if (getenv("CWC_NO_BIT_SCANS")) return;
+    if (k.no_bit_scans) return;
     if (scan_imm.size() != N) scan_imm.assign(N, 0);
     if (scan_partner.size() != N) scan_partner.assign(N, NONE);
     // users of every comparison node (CSR over the nodes that are candidates for a condition)
@@ -1048,21 +1047,18 @@ void detect_bit_scans(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>&
     // Exact: the same comparison (graph.rs:130-133, 723-769) and the same selection (:221-225) on the same values.
     struct Sel { uint32_t out, acc, a, b, p, q, imm; bool nez; };
     std::vector<Sel> sels;
-    static const bool sel_always = getenv("CWC_SEL_ALWAYS") && atoi(getenv("CWC_SEL_ALWAYS")) != 0;
-    // (knobs read once, not per TernCond node: 1.6 M of them in the ten-million-node RSA graph, each getenv a scan of the environment)
-    const bool no_sel_cmp = getenv("CWC_NO_SEL_CMP") != nullptr, no_sel_nez = getenv("CWC_NO_SEL_NEZ") != nullptr;
-    if ((!steps.empty() || sel_always) && !getenv("CWC_NO_SEL_SCANS")) {
+    if ((!steps.empty() || k.sel_always) && !k.no_sel_scans) {
         for (size_t j = 0; j < N; ++j) {
             const Node& n = g.nodes[j];
             if (n.kind != N_TRES || taken[j]) continue;
             const Node& C = g.nodes[n.a];
             const bool ordered = C.kind == N_DUO && (C.op == OP_LT || C.op == OP_GT || C.op == OP_LEQ || C.op == OP_GEQ);
             const uint8_t want = VF_A_CANON | VF_B_CANON;
-            if (ordered && !no_sel_cmp && uses[n.a] == 1 && !wit_uses[n.a] && !taken[n.a] && (vflags[n.a] & want) == want && canon(C.a) && canon(C.b)) {
+            if (ordered && !k.no_sel_cmp && uses[n.a] == 1 && !wit_uses[n.a] && !taken[n.a] && (vflags[n.a] & want) == want && canon(C.a) && canon(C.b)) {
                 const uint32_t code = C.op == OP_LT ? SEL_LT : C.op == OP_GT ? SEL_GT : C.op == OP_LEQ ? SEL_LEQ : SEL_GEQ;
                 sels.push_back(Sel{n.a, (uint32_t)j, C.a, C.b, n.b, n.c, code, false});
                 taken[n.a] = taken[j] = 1;
-            } else if (!no_sel_nez) {
+            } else if (!k.no_sel_nez) {
                 // (the scheduler's priorities must know that the step's ACC value waits for the OUT node's operands -- compile.cc, the heights
                 // of a selection pair -- or whatever computes the condition is scheduled as if nothing waited for it: 562 bundles per
                 // multiplication of the RSA-class graph instead of 495)
@@ -1072,7 +1068,7 @@ void detect_bit_scans(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>&
             }
         }
     }
-    if (getenv("CWC_DEBUG_SCAN")) {
+    if (k.debug_scan) {
         size_t nb = 0;
         for (const Step& st : steps) nb += (st.op & SCAN_OP_BORROW) != 0;
         fprintf(stderr, "selections with their comparison: %zu\n", sels.size());
@@ -1144,7 +1140,7 @@ void detect_bit_scans(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>&
 // anti-diagonals: with x_0 y_0 the lone product of a one-leaf tree, j(y) = leaves(tree of x_0 y) - 1 and i(x) likewise, every
 // leaf x y of a tree then has the same i(x) + j(y), and the 2k - 1 trees have distinct columns.
 void detect_convolutions(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_t>& vflags, std::vector<uint32_t>& scan_imm, std::vector<uint32_t>& scan_partner,
-                         uint32_t max_columns, uint64_t& n_products) {
+                         uint32_t max_columns, uint64_t& n_products, const Knobs& k) {
     const size_t N = g.nodes.size();
     static const uint32_t NONE = 0xffffffffu;
     if (scan_imm.size() != N) scan_imm.assign(N, 0);
@@ -1205,7 +1201,7 @@ void detect_convolutions(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_
     // any factor (field products) cost more than the unfused block's bundles (k x two Montgomery products against k^2 / 64
     // bundles of them).  Known: a Band with a constant, the limb a carry chain's step leaves (t mod 2^n), a constant.
     // CWC_CONV_ANY_WIDTH=1 (tests of the field-arithmetic rounds) lifts the rule.
-    const bool any_width = getenv("CWC_CONV_ANY_WIDTH") != nullptr;
+    const bool any_width = k.conv_any_width;
     auto const_bits = [&](uint32_t i) -> uint32_t {
         const Fr& v = g.const_values[g.nodes[i].a];
         for (int w = 7; w >= 0; --w)
@@ -1222,8 +1218,8 @@ void detect_convolutions(Graph& g, std::vector<uint8_t>& rep, std::vector<uint8_
     };
     std::vector<uint8_t> dead(N, 0), taken(N, 0);
     bool any = false;
-    const bool debug = getenv("CWC_DEBUG_CONV") != nullptr;
-    const bool skip_dependency_check = getenv("CWC_CONV_SKIP_DEPENDENCY_CHECK") != nullptr;  // (the knob: tests of compile_program's fallback)
+    const bool debug = k.debug_conv;
+    const bool skip_dependency_check = k.conv_skip_dependency_check;  // (the knob: tests of compile_program's fallback)
     std::vector<uint32_t> walk_epoch;  // the dependency walk's "seen in this block" marks
     uint32_t walk_now = 0;
     size_t n_dependent_blocks = 0;     // complete blocks left unfused because a factor depends on the block (CWC_DEBUG_CONV prints it)

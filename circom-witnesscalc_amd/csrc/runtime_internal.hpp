@@ -39,8 +39,9 @@ namespace cwc {
 hipError_t launch_interp(uint32_t T, uint32_t W, uint32_t pack, uint32_t n_div_requests, const uint32_t* div_lanes, const ProgramDev& p,
                          const WsTable& wst, const void* inputs, uint32_t* status, uint32_t batch, hipStream_t stream, unsigned long long* prof,
                          void* out = nullptr, uint32_t n_inline = 0, bool montgomery = false);
+// pack_shape: 3 a block per 256 / T slots (tile widths 2 and 4), 2 one thread per slot, 1 the first pack kernel (what tile widths beyond 4 always run)
 // first > 0: entries [first, n_witness) of the program's pack order; 0: every witness index in its own order (no indirection)
-hipError_t launch_pack(uint32_t T, const ProgramDev& p, const WsTable& wst, void* out, uint32_t batch, hipStream_t stream, bool montgomery, uint32_t first = 0);
+hipError_t launch_pack(uint32_t T, const ProgramDev& p, const WsTable& wst, void* out, uint32_t batch, hipStream_t stream, bool montgomery, int pack_shape, uint32_t first = 0);
 hipError_t launch_modmul_ubench(uint32_t n_cus, uint32_t waves_per_simd, uint32_t iters, uint32_t* sink, hipStream_t stream, bool block_multiplier);
 hipError_t launch_fill_consts(uint32_t T, const ProgramDev& p, const WsTable& wst, uint32_t n_tiles, hipStream_t stream);
 hipError_t launch_warm(hipStream_t stream);
@@ -78,7 +79,7 @@ struct PackSchedule {
     std::vector<uint32_t> ready;  // [n_div_requests + 1] ready[k]: entries of `order` that may be packed once k posts have been seen
     uint32_t n_inline = 0;        // the prefix of `order` the divider wave takes (0: the program is out of scope)
 };
-std::string make_pack_schedule(const Program& p, PackSchedule& out);
+std::string make_pack_schedule(const Program& p, const Knobs& k, PackSchedule& out);
 
 struct DeviceProgram {
     Program host;
@@ -212,20 +213,20 @@ struct gwb_graph {
 };
 
 namespace cwcrt {
+// `k` everywhere below: the snapshot of the environment the extern "C" entry point took on its caller's thread (knobs.hpp).
 // ---- pipeline.cc: device check, program choice (cost model), upload, the launches of a batch ----
-std::string upload_program(DeviceProgram& dp);
-uint32_t waves_per_workgroup(uint32_t divider, uint64_t tiles, uint32_t streams = 1);
-uint64_t workspace_budget();
+std::string upload_program(DeviceProgram& dp, const Knobs& k);
+uint32_t waves_per_workgroup(const Knobs& k, uint32_t divider, uint64_t tiles, uint32_t streams = 1);
+uint64_t workspace_budget(const Knobs& k);
 std::string check_device();
-double estimate_cycles(const Program& p, size_t batch);
-uint32_t pick_tile_width(gwb_graph* g, size_t batch, bool allow_quick = true);
-std::string get_program(gwb_graph* g, uint32_t key, DeviceProgram** out);
-std::string run_device(gwb_graph* g, const void* d_inputs, size_t batch, void* d_witness, uint32_t* d_status, hipStream_t stream, bool montgomery = false,
-                       hipEvent_t done_event = nullptr);
-std::string run_host(gwb_graph* g, const void* inputs, size_t batch, void* witness, uint32_t* set_status);
-unsigned env_threads(const char* name, unsigned cap);
+double estimate_cycles(const Knobs& k, const Program& p, size_t batch);
+uint32_t pick_tile_width(gwb_graph* g, const Knobs& k, size_t batch, bool allow_quick = true);
+std::string get_program(gwb_graph* g, const Knobs& k, uint32_t key, DeviceProgram** out);
+std::string run_device(gwb_graph* g, const Knobs& k, const void* d_inputs, size_t batch, void* d_witness, uint32_t* d_status, hipStream_t stream,
+                       bool montgomery = false, hipEvent_t done_event = nullptr);
+std::string run_host(gwb_graph* g, const Knobs& k, const void* inputs, size_t batch, void* witness, uint32_t* set_status);
 std::string set_status_text(uint32_t bits);
-void warm_device();
+void warm_device(const Knobs& k);
 // ---- bcast.cc: program images (export / import / broadcast) ----
 uint64_t fnv1a(const uint8_t* p, size_t n);
 uint64_t blob_checksum(const uint8_t* p, size_t n);
@@ -233,11 +234,13 @@ uint64_t sampled_fingerprint(const uint8_t* p, size_t n);
 size_t exported_size(const Program& p, const std::vector<InputSignal>& inputs);
 void exported_write(const Program& p, const std::vector<InputSignal>& inputs, uint8_t* dst);
 std::vector<uint8_t> exported_bytes(const Program& p, const std::vector<InputSignal>& inputs);
+int export_graph(gwb_graph* g, const Knobs& k, uint32_t key, void** blob, size_t* blob_len, gw_status_t* status);  // gwb_graph_export
+int import_graph(const void* blob, size_t len, const Knobs& k, gwb_graph** out, gw_status_t* status);               // gwb_graph_import
 // ---- capi_single.cc: the on-disk program cache of the single-shot entry point ----
 void write_file_atomically(const std::string& path, const void* data, size_t n);
 std::vector<uint8_t> cache_wrap(const std::string& path, const void* blob, size_t n);
-bool quirks();  // GW_REFERENCE_QUIRKS: the reference's prints and its status quirk (lib.rs:106-108)
 // ---- capi_batch.cc ----
-int load_graph(const void* data, size_t len, gwb_graph** out, std::string& err);
+int load_graph(const void* data, size_t len, const Knobs& k, gwb_graph** out, std::string& err);
+uint32_t pick_tile_width_searched(gwb_graph* g, const Knobs& k, size_t batch);  // gwb_graph_pick_tile_width
 }  // namespace cwcrt
 extern "C" int gwb_kernels_have_diagnostics();  // kernels.hip

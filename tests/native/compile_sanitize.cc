@@ -15,6 +15,7 @@ using namespace cwc;
 
 int main(int argc, char** argv) {
     int rc = 0;
+    const Knobs k = read_knobs();
     for (int a = 1; a < argc; ++a) {
         std::ifstream f(argv[a], std::ios::binary);
         std::vector<uint8_t> data((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
@@ -32,7 +33,7 @@ int main(int argc, char** argv) {
         for (uint32_t T : widths)
             for (uint32_t W : dividers) {
                 Program p, q;
-                if (!compile_program(g, T, W, p, err)) {
+                if (!compile_program(g, k, T, W, p, err)) {
                     printf("%s: T=%u W=%u: %s\n", argv[a], T, W, err.c_str());
                     continue;
                 }

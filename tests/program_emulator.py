@@ -39,6 +39,14 @@ SCAN_MAX_T, HDR_SCAN_DIV, HDR_SCAN_CONV, HDR_SCAN_SHIFT_SHIFT, HDR_SCAN_ITER_SHI
 HDR_SCAN_BORROW, HDR_SCAN_LEX, HDR_SCAN_KG, HDR_SCAN_KL = 1 << 13, 1 << 14, 1 << 15, 1 << 16
 
 
+def scan_kinds(blob):
+    """Scan bundles of a program by kind: (borrow chains, comparisons, plain carry chains).  A selection bundle carries both the
+    borrow and the comparison bit, so it counts in the first two: a program without one-bit recurrences has (0, 0, n)."""
+    scan = [h for h in blob.hdr if (h & 0xF) == CLASS_NAMES.index("SCAN")]
+    return (sum(1 for h in scan if h & HDR_SCAN_BORROW), sum(1 for h in scan if h & HDR_SCAN_LEX),
+            sum(1 for h in scan if not h & (HDR_SCAN_BORROW | HDR_SCAN_LEX | HDR_SCAN_DIV | HDR_SCAN_CONV)))
+
+
 def blob_checksum(body):
     """The trailer checksum of an exported image (bcast.cc blob_checksum): position-dependent sum over 64-bit words."""
     import numpy as np

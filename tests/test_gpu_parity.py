@@ -829,6 +829,37 @@ def test_bit_recurrence_variants_on_the_gpu(pkg, monkeypatch):
     assert n_scan > 300
 
 
+def test_background_refinement_compiles_under_its_calls_knobs(pkg, monkeypatch):
+    """A call's snapshot of the environment (csrc/knobs.hpp) holds for everything the call starts.  The first small batch on a
+    handle runs a quick program and leaves the search over all candidates to a background task that starts compiling after the call
+    has returned; the call was made with CWC_NO_BIT_SCANS set and the variable is removed as soon as it returns.  The program the
+    task settles on must still hold no borrow / comparison / selection bundles (the graph has 31 and 30 of them at this key
+    otherwise), and both programs must compute the Python model's rows."""
+    import program_emulator as pe
+    b = C.build_bit_recurrence_variants(0)  # (four independent parts: key 1 with four streams is a four-stream program)
+    nodes, wit, _ = b.finalize()
+    data = b.to_bin()
+    rnd = random.Random(5)
+    rows = [[1] + [rnd.choice([0, 1, rnd.getrandbits(rnd.choice([8, 64, 121, 128, 200])), rnd.randrange(M), M - 1 - rnd.getrandbits(20)]) for _ in range(b.n_inputs - 1)]
+            for _s in range(3)]
+    want = [model.evaluate(nodes, row, wit) for row in rows]
+    inp = cbind.ints_to_array(rows)
+    nb, nl, _ = pe.scan_kinds(pe.Blob(pkg.Graph(data).export_blob(1 | STREAMS4)))
+    assert nb > 0 and nl > 0  # (without the knob the program has them)
+    monkeypatch.setenv("CWC_NO_BIT_SCANS", "1")
+    g = pkg.Graph(data)
+    got, st = g.calc_witness_batch(inp)  # the quick program; launches the background task
+    monkeypatch.delenv("CWC_NO_BIT_SCANS")
+    assert g.last_timing()["streams"] == 4
+    assert not st.any() and [cbind.array_to_ints(r) for r in got] == want
+    key = g.pick_tile_width(3)  # waits for the task and adopts its programs
+    nb, nl, _ = pe.scan_kinds(pe.Blob(g.export_blob(key)))
+    assert nb == 0 and nl == 0, (hex(key), nb, nl)
+    got, st = g.calc_witness_batch(inp)
+    assert g.program_stats(0)["tile_width"] == key & 0xff
+    assert not st.any() and [cbind.array_to_ints(r) for r in got] == want
+
+
 # BabyJubjub in twisted Edwards form a x^2 + y^2 = 1 + d x^2 y^2 (a = 168700, d = 168696), independent of the generator's
 # Montgomery-form gadgets: the unified addition law and double-and-add on Python integers.
 _BJ_A, _BJ_D = 168700, 168696

@@ -731,10 +731,7 @@ def test_bit_recurrence_scans_are_exact(pkg, monkeypatch):
     the recognition off; the RSA program must hold all three kinds of wide-register chains."""
     rnd = random.Random(41)
 
-    def kinds(blob):
-        scan = [h for h in blob.hdr if (h & 0xF) == pe.CLASS_NAMES.index("SCAN")]
-        return (sum(1 for h in scan if h & pe.HDR_SCAN_BORROW), sum(1 for h in scan if h & pe.HDR_SCAN_LEX),
-                sum(1 for h in scan if not h & (pe.HDR_SCAN_BORROW | pe.HDR_SCAN_LEX | pe.HDR_SCAN_DIV | pe.HDR_SCAN_CONV)))
+    kinds = pe.scan_kinds
 
     for n, k, muls in [(121, 17, 1), (64, 4, 2), (33, 6, 1), (121, 3, 2), (100, 6, 2)]:
         b = C.build_rsa_long_div_class(n=n, k=k, muls=muls, range_checks=(k < 17))
@@ -1112,7 +1109,7 @@ def test_compiler_rewrites_are_exact_on_chain_heavy_graphs(pkg, key):
 
 
 def test_loader_and_compiler_under_sanitizers(tmp_path):
-    """graph.cc + compile.cc + rewrite.cc + costmodel.cc + program_blob.cc + optimize.cc (loader, load-time optimiser, exact rewrites, scheduler, encoder, blob) under ASan + UBSan on generated graphs,
+    """graph.cc + knobs.cc + compile.cc + rewrite.cc + costmodel.cc + program_blob.cc + optimize.cc (loader, load-time optimiser, exact rewrites, scheduler, encoder, blob) under ASan + UBSan on generated graphs,
     a fuzzed DAG, the chain-heavy graphs and a few corrupted files (no GPU involved)."""
     import subprocess
     src = os.path.join(ROOT, "circom-witnesscalc_amd", "csrc")
@@ -1120,7 +1117,7 @@ def test_loader_and_compiler_under_sanitizers(tmp_path):
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                            "-Wno-unknown-pragmas", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-o", exe,
                            os.path.join(ROOT, "tests", "native", "compile_sanitize.cc"),
-                           os.path.join(src, "graph.cc"), os.path.join(src, "compile.cc"), os.path.join(src, "rewrite.cc"), os.path.join(src, "costmodel.cc"),
+                           os.path.join(src, "graph.cc"), os.path.join(src, "knobs.cc"), os.path.join(src, "compile.cc"), os.path.join(src, "rewrite.cc"), os.path.join(src, "costmodel.cc"),
                            os.path.join(src, "program_blob.cc"), os.path.join(src, "optimize.cc")])
     files = []
     cases = {"gadgets": C.build_gadgets(), "poseidon3": C.build_poseidon(3), "dag": C.build_random_dag(5, n_ops=300),
