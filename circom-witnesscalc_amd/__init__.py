@@ -631,6 +631,10 @@ def r1cs_lib():
         L.gwb_zkey_contribution_challenge.argtypes = [vp, vp]
         L.gwb_bn254_g1_scale_batch_device.argtypes = [vp, sz, vp, vp, vp, stp]
         L.gwb_bn254_g1_lincomb128_device.argtypes = [vp, vp, sz, vp, vp, stp]
+        L.gwb_bn254_g2_lincomb128_device.argtypes = [vp, vp, sz, vp, vp, stp]
+        L.gwb_ptau_check_powers.argtypes = [vp, sz, u32, vp, stp]
+        L.gwb_zkey_verify_key.argtypes = [vp, sz, vp, vp, sz, u32, u32, vp, vp, ctypes.POINTER(sz), stp]
+        L.gwb_zkey_verify_key_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_float)]
         _r1cs_lib = L
     return _r1cs_lib
 
@@ -1246,7 +1250,7 @@ def groth16_verify_contributions(zkey):
     """Checks every contribution record of a key on the GPU and returns their hashes, oldest first ([] for a key without
     records, whose delta must then be the generator).  Raises WitnessCalcError naming the first failing record and rule, for
     example "zkey: contribution 2: deltaAfter is not deltaPrev times the proven secret".  This checks the chain of deltas; it does not compare the key with its circuit or
-    its powers-of-tau file."""
+    its powers-of-tau file: groth16_verify_key does."""
     data = bytes(zkey)
     room = len(zkey_contributions(data)["contributions"])
     hashes = ctypes.create_string_buffer(max(1, room * CONTRIBUTION_HASH_BYTES))
@@ -1290,24 +1294,101 @@ def bn254_g1_scale_batch_device(d_points, k, stream=None):
     return out
 
 
-def bn254_g1_lincomb128_device(d_points, d_rho, stream=None):
-    """Measurement and test aid of the step check's kernels: device G1 points (uint8 cuda [n, 64], canonical affine) and
-    128-bit little-endian scalars (uint8 cuda [n, 16]) -> sum_i rho_i P_i as uint8 cuda [64].  Asynchronous on `stream` or the
-    current stream."""
+def _lincomb128_device(group, d_points, d_rho, stream):
     import torch
-    n = d_points.shape[0]
-    assert tuple(d_points.shape) == (n, 64) and d_points.is_cuda and d_points.is_contiguous() and d_points.dtype == torch.uint8
+    n, width = d_points.shape[0], 64 * group
+    assert tuple(d_points.shape) == (n, width) and d_points.is_cuda and d_points.is_contiguous() and d_points.dtype == torch.uint8
     assert tuple(d_rho.shape) == (n, 16) and d_rho.is_cuda and d_rho.is_contiguous() and d_rho.dtype == torch.uint8
     s = stream if stream is not None else torch.cuda.current_stream(d_points.device)
-    out = torch.empty((64,), dtype=torch.uint8, device=d_points.device)
+    out = torch.empty((width,), dtype=torch.uint8, device=d_points.device)
     st = GwStatus()
+    call = r1cs_lib().gwb_bn254_g1_lincomb128_device if group == 1 else r1cs_lib().gwb_bn254_g2_lincomb128_device
     with torch.cuda.device(d_points.device):
-        rc = r1cs_lib().gwb_bn254_g1_lincomb128_device(d_points.data_ptr(), d_rho.data_ptr(), n, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
+        rc = call(d_points.data_ptr(), d_rho.data_ptr(), n, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
     _r1cs_check(rc, st)
     d_points.record_stream(s)
     d_rho.record_stream(s)
     out.record_stream(s)
     return out
+
+
+def bn254_g1_lincomb128_device(d_points, d_rho, stream=None):
+    """Measurement and test aid of the step check's kernels: device G1 points (uint8 cuda [n, 64], canonical affine) and
+    128-bit little-endian scalars (uint8 cuda [n, 16]) -> sum_i rho_i P_i as uint8 cuda [64].  Asynchronous on `stream` or the
+    current stream."""
+    return _lincomb128_device(1, d_points, d_rho, stream)
+
+
+def bn254_g2_lincomb128_device(d_points, d_rho, stream=None):
+    """The same in G2, the aid of the powers check's kernels: device G2 points (uint8 cuda [n, 128], canonical affine x.c0,
+    x.c1, y.c0, y.c1, zero bytes for infinity) and 128-bit scalars (uint8 cuda [n, 16]) -> sum_i rho_i P_i as uint8 cuda [128]."""
+    return _lincomb128_device(2, d_points, d_rho, stream)
+
+
+def _seed32(seed):
+    if seed is None:
+        return None
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise WitnessCalcError("seed: 32 bytes expected")
+    return seed
+
+
+def ptau_check_powers(ptau, domain_power, seed=None):
+    """Raises WitnessCalcError unless the monomial points that groth16_setup_ptau reads from this file for a circuit of domain
+    n = 2^domain_power under lagrange="compute" are what their sections say: tauG1[0 .. 2n) and tauG2[0 .. n) consecutive powers
+    of one tau, alphaTauG1[0 .. n) and betaTauG1[0 .. n) those powers times their first point, betaG2 with the same beta.  First
+    ptau_check's refusals and ptau_check_g2's subgroup rule, with their messages; then random linear combinations of the points
+    on the current GPU and five pairing equations (synchronous; a wrong point passes with probability about 2^-128 over the
+    seed).  seed: 32 bytes for a reproducible check, or None to draw them.  The message names the section: "ptau: section 2
+    (tauG1): the first 2n points are not consecutive powers of the tau of section 3".  Not checked: points beyond the
+    prefixes, the prepared sections 12 to 15, the ceremony's own contribution records."""
+    seed = _seed32(seed)
+    keep, addr, n = _ptau_buffer(ptau)
+    st = GwStatus()
+    rc = r1cs_lib().gwb_ptau_check_powers(addr, n, int(domain_power), seed, ctypes.byref(st))
+    _r1cs_check(rc, st)
+    del keep
+
+
+GROTH16_VERIFY_KEY_PHASES = ("remake", "lincomb", "pairings")
+VERIFY_KEY_SKIP_RECORDS, VERIFY_KEY_CHECK_PTAU = 1, 2
+
+
+def groth16_verify_key(zkey, r1cs, ptau, lagrange="compute", records=True, check_ptau=False, seed=None):
+    """Checks on the GPU that `zkey` is the honest key of the R1cs and the powers-of-tau file (bytes or any buffer, an mmap
+    included), with a delta that only its recorded contributions touched (what `snarkjs zkey verify` answers; synchronous),
+    and returns the contribution hashes, oldest first.  The key is remade from circuit and file with delta = 1; section 4 is
+    compared with the circuit, sections 1, 3, 5, 6, 7 and the header's alpha1, beta1, beta2, gamma2 with the remade key byte
+    for byte, the records by groth16_verify_contributions's rules with the csHash of the remade key, and sections 8 (C) and 9
+    (H) against the remade key's and delta2 through random linear combinations (a wrong point passes with probability about
+    2^-128 over the seed).  Raises WitnessCalcError with the first rule that fails, for example "zkey verify: section 8 (C) is
+    not the remade key's section divided by delta".  lagrange: "compute" (default) keeps the verdict off the file's prepared
+    sections 12 to 15, which nothing verifies; "auto" and "file" read them.  records=False passes over section 10 (for keys
+    that carry snarkjs's records, which this library cannot verify): the points are still checked against circuit, file and
+    the key's own delta.  check_ptau=True first runs ptau_check_powers for the circuit's domain.  Not verified: the
+    ceremony's own records in the file, and its points beyond the prefixes a setup reads."""
+    mode = _lagrange_mode(lagrange)
+    seed = _seed32(seed)
+    data = bytes(zkey)
+    room = len(zkey_contributions(data)["contributions"])
+    hashes = ctypes.create_string_buffer(max(1, room * CONTRIBUTION_HASH_BYTES))
+    n = ctypes.c_size_t(room)
+    flags = (0 if records else VERIFY_KEY_SKIP_RECORDS) | (VERIFY_KEY_CHECK_PTAU if check_ptau else 0)
+    keep, addr, n_in = _ptau_buffer(ptau)
+    st = GwStatus()
+    rc = r1cs_lib().gwb_zkey_verify_key(data, len(data), r1cs._h, addr, n_in, mode, flags, seed, hashes, ctypes.byref(n), ctypes.byref(st))
+    del keep
+    _r1cs_check(rc, st)
+    return [hashes.raw[64 * k:64 * k + 64] for k in range(n.value)]
+
+
+def groth16_verify_key_phase_ms():
+    """{remake, lincomb, pairings} in ms of the process's last accepted groth16_verify_key call (host clock)."""
+    ms = (ctypes.c_float * 3)()
+    if r1cs_lib().gwb_zkey_verify_key_phase_ms(ms) != 0:
+        raise WitnessCalcError("no key check phase times (no accepted groth16_verify_key call yet)")
+    return dict(zip(GROTH16_VERIFY_KEY_PHASES, (float(x) for x in ms)))
 
 
 # -- Groth16 verifier (include/graph_witness_groth16_verify.h, libcwc_r1cs.so) ------------------------------------------------

@@ -1,7 +1,8 @@
 // Groth16 phase-2 contributions on gfx950 (include/graph_witness_groth16_contribute.h has the definitions): the contribution
-// itself, the check of a key's records and the check of one step between two keys.  Section 10, BLAKE2b, the transcript and
-// the challenge point are contributions.cc's (contribute_internal.hpp); the pairing is verify.hip's and the conversion to
-// affine bytes setup.hip's, both through their enqueue functions.
+// itself, the check of a key's records, the check of one step between two keys, the check of a key against its circuit and its
+// powers-of-tau file, and the powers check of such a file (include/graph_witness_groth16_ptau.h).  Section 10, BLAKE2b, the
+// transcript and the challenge point are contributions.cc's (contribute_internal.hpp); the pairing is verify.hip's and the
+// conversion to affine bytes setup.hip's, both through their enqueue functions.
 //
 // Contribute.  The few single points (g1_s, g1_sx, g2_spx, delta1, delta2) are multiplied on the host.  Sections 8 and 9 are one
 // list of stored G1 points that goes through the device in pieces of CWC_CONTRIBUTE_CHUNK points: scale_points_kernel decodes
@@ -11,31 +12,47 @@
 //
 // Step check.  R = sum rho_i P_i over a section of the previous key and R' over the same section of the next key, rho_i of 128
 // bits, the same for both: lincomb_kernel takes one point per thread (blockIdx.y picks the list), multiplies it by its rho
-// (four words of double-and-add) and the workgroup adds its 256 products through LDS, halving the active threads each round;
+// (four words of double-and-add) and the workgroup adds its products through LDS, halving the active threads each round;
 // lincomb_sum_kernel, one workgroup per list, adds the per-group sums to the running sum of the list.  The bucket method of
 // msm.hip was not reused: it is built around the prover's resident bases and 254-bit scalars, and this sum is a small part
 // of a step check next to its pairings.
 //
-// Registers (hipcc -Rpass-analysis=kernel-resource-usage for gfx950; every kernel: 0 bytes of scratch, no AGPRs; VGPRs, waves / SIMD):
-//   scale_points_kernel 156, 3      lincomb_kernel 164, 3 (32 KB LDS)      lincomb_sum_kernel 119, 4 (32 KB LDS)      put_scalar_kernel 10, 8
+// Key check.  The key of the circuit and the file with delta = 1 is remade (gwb_groth16_setup_ptau) and takes the place of the
+// previous key of a step whose secret is the whole delta: the same functions compare the sections, check the records and the
+// delta points and form R and R', and one run_checks carries all pairings.
+//
+// Powers check.  Sums over the file's own lists with one rho: tauG1 against itself one point on (U, V, and V_n as V's state
+// after the first n points), alphaTauG1 and betaTauG1 as the two lists of one launch, and tauG2 through the G2 instance of the
+// two kernels.  Both kernels are templates over the group.  A G1 workgroup has 256 threads.  A G2 workgroup is one wave of
+// 64: an Xyzz<G2> is 256 bytes (256 of them would be 64 KB of LDS), and the G2 double-and-add keeps the multiplicand, the
+// accumulator and an addition's temporaries, which needs the unified register file of a wave that has its SIMD to itself.
+//
+// Registers (hipcc -Rpass-analysis=kernel-resource-usage for gfx950; every kernel: 0 bytes of scratch; VGPRs + AGPRs, waves / SIMD):
+//   scale_points_kernel 156, 3      lincomb_kernel<G1> 164, 3 (32 KB LDS)      lincomb_sum_kernel<G1> 119, 4 (32 KB LDS)      put_scalar_kernel 10, 8
+//   lincomb_kernel<G2> 256 + 79, 1 (16 KB LDS)      lincomb_sum_kernel<G2> 256 + 12, 1 (16 KB LDS)
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
 #include <sys/random.h>
 
 #include <algorithm>
+#include <chrono>
+#include <initializer_list>
 #include <memory>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/graph_witness_groth16_contribute.h"
+#include "../../include/graph_witness_groth16_ptau.h"
 #include "../../include/graph_witness_groth16_setup.h"
 #include "../../include/graph_witness_groth16_verify.h"
 #include "binfile.hpp"
 #include "bn254_points_gfx950.hpp"
 #include "contribute_internal.hpp"
 #include "groth16_internal.hpp"
+#include "ptau_internal.hpp"
 #include "setup_internal.hpp"
 
 using namespace cwc_r1cs;
@@ -65,40 +82,53 @@ __global__ __launch_bounds__(64) void put_scalar_kernel(Fr* __restrict__ out, Fr
     if (threadIdx.x == 0) *out = v;
 }
 
-// the sum of sh[0 .. THREADS) into sh[0]
-__device__ __forceinline__ void block_sum(Xyzz<G1>* sh) {
+// threads of a workgroup of the linear-combination kernels, and the stored bytes of a point, per group (the header has the why)
+template <class T>
+constexpr uint32_t LC_THREADS = THREADS;
+template <>
+constexpr uint32_t LC_THREADS<G2> = 64;
+template <class T>
+constexpr size_t POINT_BYTES = G1_BYTES;
+template <>
+constexpr size_t POINT_BYTES<G2> = G2_BYTES;
+
+// the sum of sh[0 .. LC_THREADS<T>) into sh[0]
+template <class T>
+__device__ __forceinline__ void block_sum(Xyzz<T>* sh) {
     __syncthreads();
-    for (uint32_t stride = THREADS / 2; stride > 0; stride >>= 1) {
+    for (uint32_t stride = LC_THREADS<T> / 2; stride > 0; stride >>= 1) {
         if (threadIdx.x < stride) sh[threadIdx.x] = xyzz_add(sh[threadIdx.x], sh[threadIdx.x + stride]);
         __syncthreads();
     }
 }
 
 // part[blockIdx.y gridDim.x + blockIdx.x] = sum over the workgroup's i of rho[i] P_i, P = in0 or (blockIdx.y = 1) in1
-__global__ __launch_bounds__(THREADS) void lincomb_kernel(const uint8_t* __restrict__ in0, const uint8_t* __restrict__ in1, uint32_t n, uint32_t canonical,
-                                                          const uint32_t* __restrict__ rho, Xyzz<G1>* __restrict__ part) {
-    __shared__ Xyzz<G1> sh[THREADS];
+template <class T>
+__global__ __launch_bounds__(LC_THREADS<T>) void lincomb_kernel(const uint8_t* __restrict__ in0, const uint8_t* __restrict__ in1, uint32_t n,
+                                                                uint32_t canonical, const uint32_t* __restrict__ rho, Xyzz<T>* __restrict__ part) {
+    __shared__ Xyzz<T> sh[LC_THREADS<T>];
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    Xyzz<G1> acc = xyzz_inf<G1>();
+    Xyzz<T> acc = xyzz_inf<T>();
     if (i < n) {
         const uint8_t* in = blockIdx.y ? in1 : in0;
-        A1 a;
-        get_coords<G1>(in + (size_t)i * G1_BYTES, canonical != 0, a.x, a.y);
+        Affine<T> a;
+        get_coords<T>(in + (size_t)i * POINT_BYTES<T>, canonical != 0, a.x, a.y);
         const uint32_t* r = rho + 4 * (size_t)i;
         acc = xyzz_mul_short(from_affine(a), Fr{{r[0], r[1], r[2], r[3], 0, 0, 0, 0}});
     }
     sh[threadIdx.x] = acc;
-    block_sum(sh);
+    block_sum<T>(sh);
     if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = sh[0];
 }
 
 // acc[blockIdx.x] += sum of part[blockIdx.x n_part .. + n_part)
-__global__ __launch_bounds__(THREADS) void lincomb_sum_kernel(const Xyzz<G1>* __restrict__ part, uint32_t n_part, Xyzz<G1>* __restrict__ acc) {
-    __shared__ Xyzz<G1> sh[THREADS];
-    Xyzz<G1> s = xyzz_inf<G1>();
-    for (uint32_t j = threadIdx.x; j < n_part; j += THREADS) s = xyzz_add(s, part[(size_t)blockIdx.x * n_part + j]);
+template <class T>
+__global__ __launch_bounds__(LC_THREADS<T>) void lincomb_sum_kernel(const Xyzz<T>* __restrict__ part, uint32_t n_part, Xyzz<T>* __restrict__ acc) {
+    __shared__ Xyzz<T> sh[LC_THREADS<T>];
+    Xyzz<T> s = xyzz_inf<T>();
+    for (uint32_t j = threadIdx.x; j < n_part; j += LC_THREADS<T>) s = xyzz_add(s, part[(size_t)blockIdx.x * n_part + j]);
     sh[threadIdx.x] = s;
-    block_sum(sh);
+    block_sum<T>(sh);
     if (threadIdx.x == 0) acc[blockIdx.x] = xyzz_add(acc[blockIdx.x], sh[0]);
 }
 
@@ -339,13 +369,30 @@ std::string record_rules(const Section10& s, size_t k, const uint8_t* delta_prev
     return "";
 }
 
-// The rules about the header's delta points after the last record (`last`: its deltaAfter, or nullptr without records).
-std::string delta_rules(const gwb_zkey& z, const uint8_t* last, const uint8_t* gen1, const uint8_t* gen2, std::vector<PairCheck>& checks) {
+// The rules about the header's delta points after the last record (`last`: its deltaAfter, or nullptr without records): delta1
+// continues the chain, then delta2 belongs to delta1.  The key check asks the second alone when it passes over the records.
+std::string delta1_rule(const gwb_zkey& z, const uint8_t* last, const uint8_t* gen1) {
     if (!last && memcmp(z.delta1, gen1, G1_BYTES) != 0) return "zkey: delta is not the generator and no contribution accounts for it";
     if (last && memcmp(z.delta1, last, G1_BYTES) != 0) return "zkey: delta1 is not the deltaAfter of the last contribution";
+    return "";
+}
+std::string delta2_rules(const gwb_zkey& z, const uint8_t* gen1, const uint8_t* gen2, std::vector<PairCheck>& checks) {
     if (is_zero_bytes(z.delta2, G2_BYTES)) return "zkey: delta2 is the point at infinity";
     if (!g2_stored_in_subgroup(z.delta2)) return "zkey: delta2 is not in the order-r subgroup of G2";
     checks.push_back({z.delta1, gen2, gen1, z.delta2, "zkey: delta2 is not the G2 generator times delta1's scalar"});
+    return "";
+}
+std::string delta_rules(const gwb_zkey& z, const uint8_t* last, const uint8_t* gen1, const uint8_t* gen2, std::vector<PairCheck>& checks) {
+    const std::string v = delta1_rule(z, last, gen1);
+    return v.empty() ? delta2_rules(z, gen1, gen2, checks) : v;
+}
+
+// e(a1, a2) = e(b1, b2) where a side with a point at infinity is 1: one such side alone is the failure `msg`, two pass without
+// a pairing, none goes to `checks`.
+std::string pair_rule(const uint8_t* a1, const uint8_t* a2, const uint8_t* b1, const uint8_t* b2, const std::string& msg, std::vector<PairCheck>& checks) {
+    const bool inf_a = is_zero_bytes(a1, G1_BYTES) || is_zero_bytes(a2, G2_BYTES), inf_b = is_zero_bytes(b1, G1_BYTES) || is_zero_bytes(b2, G2_BYTES);
+    if (inf_a != inf_b) return msg;
+    if (!inf_a) checks.push_back({a1, a2, b1, b2, msg});
     return "";
 }
 
@@ -430,12 +477,22 @@ void fill_rho(const uint8_t seed[32], uint64_t first, uint64_t count, uint8_t* o
 }
 
 // d_acc[0] += sum rho_i P_i, d_acc[1] += sum rho_i P'_i over the m points of one piece (device addresses), the per-group sums in
-// d_part (2 blocks_for(m, THREADS) points)
-void enqueue_lincomb(const uint8_t* d_p0, const uint8_t* d_p1, uint32_t lists, uint32_t m, bool canonical, const uint8_t* d_rho, Xyzz<G1>* d_part,
-                     Xyzz<G1>* d_acc, hipStream_t s) {
-    const uint32_t blocks = blocks_for(m, THREADS);
-    hipLaunchKernelGGL(lincomb_kernel, dim3(blocks, lists), dim3(THREADS), 0, s, d_p0, d_p1, m, canonical ? 1u : 0u, (const uint32_t*)d_rho, d_part);
-    hipLaunchKernelGGL(lincomb_sum_kernel, dim3(lists), dim3(THREADS), 0, s, (const Xyzz<G1>*)d_part, blocks, d_acc);
+// d_part (lists blocks_for(m, LC_THREADS<T>) points)
+template <class T>
+void enqueue_lincomb(const uint8_t* d_p0, const uint8_t* d_p1, uint32_t lists, uint32_t m, bool canonical, const uint8_t* d_rho, Xyzz<T>* d_part,
+                     Xyzz<T>* d_acc, hipStream_t s) {
+    const uint32_t blocks = blocks_for(m, LC_THREADS<T>);
+    hipLaunchKernelGGL(lincomb_kernel<T>, dim3(blocks, lists), dim3(LC_THREADS<T>), 0, s, d_p0, d_p1, m, canonical ? 1u : 0u, (const uint32_t*)d_rho, d_part);
+    hipLaunchKernelGGL(lincomb_sum_kernel<T>, dim3(lists), dim3(LC_THREADS<T>), 0, s, (const Xyzz<T>*)d_part, blocks, d_acc);
+}
+
+// XYZZ points of either group -> affine bytes (setup.hip's shared inversions)
+template <class T>
+void enqueue_affine(const void* d_xyzz, uint32_t n, uint8_t* d_out, bool canonical, hipStream_t s) {
+    if constexpr (std::is_same<T, G1>::value)
+        enqueue_affine_g1(d_xyzz, n, d_out, canonical, s);
+    else
+        cwc_setup::enqueue_affine_g2(d_xyzz, n, d_out, canonical, s);
 }
 
 // The four sums of a step check, stored form in out[4][64]: R and R' of section 8, then of section 9.
@@ -495,6 +552,17 @@ bool same_record(const Record& a, const Record& b) {
            memcmp(a.g2_spx, b.g2_spx, G2_BYTES) == 0 && memcmp(a.transcript, b.transcript, HASH_BYTES) == 0 && a.type == b.type && a.params == b.params;
 }
 
+// sections `ids` of b are a's byte for byte, and so is the header before delta1; "" or `who` + which section differs from `whose`
+std::string same_sections(const Key& a, const Key& b, std::initializer_list<uint32_t> ids, const std::string& who, const std::string& whose) {
+    static const char* names[10] = {"", "protocol", "header", "IC", "coefficients", "A", "B1", "B2", "C", "H"};
+    for (uint32_t id : ids)
+        if (a.secs[id].size != b.secs[id].size || memcmp(a.secs[id].p, b.secs[id].p, a.secs[id].size) != 0)
+            return who + "section " + std::to_string(id) + " (" + names[id] + ") differs from " + whose;
+    if (memcmp(a.secs[2].p, b.secs[2].p, HDR_DELTA1) != 0)
+        return who + "section 2 (header) differs from " + whose + " before delta1 (the sizes, alpha1, beta1, beta2 or gamma2)";
+    return "";
+}
+
 // what of `next` has to be `prev`'s byte for byte, and the shape of its section 10; "" or what fails
 std::string step_structure(const Key& prev, const Key& next) {
     const Section10 &a = prev.s10, &b = next.s10;
@@ -510,12 +578,34 @@ std::string step_structure(const Key& prev, const Key& next) {
         memcpy(want, a.cs_hash, HASH_BYTES);
     if (memcmp(want, b.cs_hash, HASH_BYTES) != 0)
         return std::string("zkey step: section 10: the csHash is not ") + (a.blank() ? "the hash of the previous key's sections 1 to 9" : "the previous key's");
-    static const char* names[10] = {"", "protocol", "header", "IC", "coefficients", "A", "B1", "B2", "C", "H"};
-    for (uint32_t id : {1u, 3u, 4u, 5u, 6u, 7u})
-        if (prev.secs[id].size != next.secs[id].size || memcmp(prev.secs[id].p, next.secs[id].p, prev.secs[id].size) != 0)
-            return "zkey step: section " + std::to_string(id) + " (" + names[id] + ") differs from the previous key's";
-    if (memcmp(prev.secs[2].p, next.secs[2].p, HDR_DELTA1) != 0)
-        return "zkey step: section 2 (header) differs from the previous key's before delta1 (the sizes, alpha1, beta1, beta2 or gamma2)";
+    return same_sections(prev, next, {1u, 3u, 4u, 5u, 6u, 7u}, "zkey step: ", "the previous key's");
+}
+
+// the caller's 32 bytes, or without them 32 from getrandom()
+bool take_seed(const uint8_t* in, uint8_t seed[32]) {
+    if (in) {
+        memcpy(seed, in, 32);
+        return true;
+    }
+    for (size_t got = 0; got < 32;) {
+        const ssize_t k = getrandom(seed + got, 32 - got, 0);
+        if (k < 0) return false;
+        got += (size_t)k;
+    }
+    return true;
+}
+
+// e(R', delta2') = e(R, delta2) for the sums of step_sums, section 8 before 9; "" or the failure `head` + "8 (C)" + `tail`
+std::string sums_rules(const uint8_t* sums, const uint8_t* delta2_prev, const uint8_t* delta2_next, const std::string& head, const std::string& tail,
+                       std::vector<PairCheck>& checks) {
+    static const char* what[2] = {"8 (C)", "9 (H)"};
+    for (int sec = 0; sec < 2; ++sec) {
+        const uint8_t *r = sums + 2 * sec * G1_BYTES, *r2 = r + G1_BYTES;
+        const std::string msg = head + what[sec] + tail;
+        const bool inf = is_zero_bytes(r, G1_BYTES), inf2 = is_zero_bytes(r2, G1_BYTES);
+        if (inf != inf2) return msg;
+        if (!inf) checks.push_back({r2, delta2_next, r, delta2_prev, msg});  // e(R', delta2') = e(R, delta2)
+    }
     return "";
 }
 
@@ -527,15 +617,7 @@ int verify_step(const uint8_t* prev_bytes, size_t prev_len, const uint8_t* next_
     std::string verdict = step_structure(prev, next);
     if (!verdict.empty()) return fail(status, verdict);
     uint8_t seed[32];
-    if (seed_in) {
-        memcpy(seed, seed_in, 32);
-    } else {
-        for (size_t got = 0; got < 32;) {
-            const ssize_t k = getrandom(seed + got, 32 - got, 0);
-            if (k < 0) return fail2(status, "zkey step: getrandom failed");
-            got += (size_t)k;
-        }
-    }
+    if (!take_seed(seed_in, seed)) return fail2(status, "zkey step: getrandom failed");
     const gwb_zkey &zp = *prev.z, &zn = *next.z;
     const Generators gen;
     std::vector<PairCheck> checks;
@@ -551,20 +633,261 @@ int verify_step(const uint8_t* prev_bytes, size_t prev_len, const uint8_t* next_
     }
     if (host_verdict.empty()) {
         if (!step_sums(zp, zn, seed, sums, err)) return fail2(status, err);
-        static const char* what[2] = {"8 (C)", "9 (H)"};
-        for (int sec = 0; sec < 2 && host_verdict.empty(); ++sec) {
-            const uint8_t *r = sums + 2 * sec * G1_BYTES, *r2 = r + G1_BYTES;
-            const std::string msg = std::string("zkey step: section ") + what[sec] + " is not the previous key's section divided by the contribution's secret";
-            const bool inf = is_zero_bytes(r, G1_BYTES), inf2 = is_zero_bytes(r2, G1_BYTES);
-            if (inf != inf2)
-                host_verdict = msg;
-            else if (!inf)
-                checks.push_back({r2, zn.delta2, r, zp.delta2, msg});  // e(R', delta2') = e(R, delta2)
-        }
+        host_verdict = sums_rules(sums, zp.delta2, zn.delta2, "zkey step: section ", " is not the previous key's section divided by the contribution's secret", checks);
     }
     if (!run_checks(checks, verdict, err)) return fail2(status, err);
     if (verdict.empty()) verdict = host_verdict;
     if (!verdict.empty()) return fail(status, verdict);
+    set_ok(status);
+    return 0;
+}
+
+// ---- the powers check of a `.ptau` and the key check -------------------------------------------------------------------------
+
+// rc and message of a C ABI call, for the callers below
+struct Outcome {
+    int rc = 0;
+    std::string msg;
+};
+Outcome outcome_of(int rc, gw_status_t& st) {
+    Outcome o{rc, st.error_msg ? st.error_msg : ""};
+    free(st.error_msg);
+    st.error_msg = nullptr;
+    return o;
+}
+
+// The six sums of the powers check for the domain n = 2^p, stored form: g1[5][64] = V, U, V_n, S_A, S_B and g2[128] = S_2.  T1 goes
+// through the device in two ranges, [0, n) and [n, 2n - 1), so that V_n is V's state between them; a piece of m points of a
+// range is uploaded with the point after it, and U's list is the same buffer one point on.
+bool powers_sums(const cwc_ptau::Plan& pl, const uint8_t seed[32], uint8_t* g1, uint8_t* g2, std::string& err) {
+    const uint64_t n = 1ull << pl.p;
+    const uint64_t chunk = std::max<uint64_t>(1, std::min(chunk_points(), n));
+    const uint32_t blocks1 = blocks_for(chunk, LC_THREADS<G1>), blocks2 = blocks_for(chunk, LC_THREADS<G2>);
+    Stream s;
+    DeviceBuf work;
+    Carve cw;
+    const size_t o_p0 = cw.take((chunk + 1) * G1_BYTES), o_p1 = cw.take(chunk * G1_BYTES), o_q = cw.take(chunk * G2_BYTES), o_rho = cw.take(chunk * RHO_BYTES),
+                 o_part1 = cw.take(2ull * blocks1 * sizeof(Xyzz<G1>)), o_part2 = cw.take((size_t)blocks2 * sizeof(Xyzz<G2>)),
+                 o_acc1 = cw.take(5 * sizeof(Xyzz<G1>)), o_acc2 = cw.take(sizeof(Xyzz<G2>)), o_out1 = cw.take(5 * G1_BYTES), o_out2 = cw.take(G2_BYTES);
+    hipError_t e = s.create();
+    if (e == hipSuccess) e = work.alloc(cw.o);
+    if (e == hipSuccess) e = hipMemsetAsync(work.as<uint8_t>() + o_acc1, 0, o_out1 - o_acc1, s);  // the accumulators of both groups
+    if (e != hipSuccess) {
+        err = hip_err("allocating the powers check's workspace", e);
+        return false;
+    }
+    uint8_t* W = work.as<uint8_t>();
+    Xyzz<G1>* acc1 = (Xyzz<G1>*)(W + o_acc1);
+    std::vector<uint8_t> rho(chunk * RHO_BYTES);
+    // one piece: rho[first .. first + m) on the lists a (m + extra points uploaded) and b (nullptr: a one point on) into acc[0], acc[1]
+    auto piece1 = [&](const uint8_t* a, const uint8_t* b, uint64_t first, uint32_t m, Xyzz<G1>* acc) {
+        fill_rho(seed, first, m, rho.data());
+        e = hipMemcpyAsync(W + o_p0, a + first * G1_BYTES, (size_t)(m + (b ? 0 : 1)) * G1_BYTES, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && b) e = hipMemcpyAsync(W + o_p1, b + first * G1_BYTES, (size_t)m * G1_BYTES, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(W + o_rho, rho.data(), (size_t)m * RHO_BYTES, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) return;
+        enqueue_lincomb<G1>(W + o_p0, b ? W + o_p1 : W + o_p0 + G1_BYTES, 2, m, false, W + o_rho, (Xyzz<G1>*)(W + o_part1), acc, s);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);  // rho is refilled for the next piece
+    };
+    const uint64_t ends[2] = {n, 2 * n - 1};  // T1: V and U over [0, n), V_n = V there, then [n, 2n - 1)
+    for (int range = 0; range < 2 && e == hipSuccess; ++range) {
+        for (uint64_t at = range ? n : 0; at < ends[range] && e == hipSuccess; at += chunk)
+            piece1(pl.t1, nullptr, at, (uint32_t)std::min<uint64_t>(chunk, ends[range] - at), acc1);
+        if (range == 0 && e == hipSuccess) e = hipMemcpyAsync(acc1 + 2, acc1, sizeof(Xyzz<G1>), hipMemcpyDeviceToDevice, s);
+    }
+    for (uint64_t at = 0; at < n && e == hipSuccess; at += chunk) piece1(pl.at, pl.bt, at, (uint32_t)std::min<uint64_t>(chunk, n - at), acc1 + 3);
+    for (uint64_t at = 0; at < n && e == hipSuccess; at += chunk) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - at);
+        fill_rho(seed, at, m, rho.data());
+        e = hipMemcpyAsync(W + o_q, pl.t2 + at * G2_BYTES, (size_t)m * G2_BYTES, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(W + o_rho, rho.data(), (size_t)m * RHO_BYTES, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) break;
+        enqueue_lincomb<G2>(W + o_q, W + o_q, 1, m, false, W + o_rho, (Xyzz<G2>*)(W + o_part2), (Xyzz<G2>*)(W + o_acc2), s);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (e == hipSuccess) {
+        enqueue_affine<G1>(W + o_acc1, 5, W + o_out1, false, s);
+        enqueue_affine<G2>(W + o_acc2, 1, W + o_out2, false, s);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(g1, W + o_out1, 5 * G1_BYTES, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(g2, W + o_out2, G2_BYTES, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        err = hip_err("running the linear combinations of the powers check", e);
+        return false;
+    }
+    return true;
+}
+
+// gwb_ptau_check_powers: rc 0, 1 (msg: the verdict) or 2
+Outcome check_powers(const uint8_t* data, size_t len, uint32_t domain_power, const uint8_t* seed_in) {
+    std::string err;
+    cwc_ptau::View view;
+    cwc_ptau::Plan pl;
+    if (!cwc_ptau::parse(data, len, view, err) || !cwc_ptau::plan(view, domain_power, GWB_PTAU_LAGRANGE_COMPUTE, pl, err) ||
+        !cwc_ptau::check_header_points(pl, err) || !cwc_ptau::check_bulk_points(pl, err))
+        return {2, err};
+    gw_status_t st{};
+    Outcome sub = outcome_of(gwb_ptau_check_g2(data, len, domain_power, GWB_PTAU_LAGRANGE_COMPUTE, &st), st);
+    if (sub.rc != 0) return {sub.msg.find("order-r subgroup") != std::string::npos ? 1 : 2, sub.msg};  // its other refusals were made above
+    uint8_t seed[32];
+    if (!take_seed(seed_in, seed)) return {2, "ptau: getrandom failed"};
+    uint8_t g1[5 * G1_BYTES], s2[G2_BYTES];
+    if (!powers_sums(pl, seed, g1, s2, err)) return {2, err};
+    const uint8_t *V = g1, *U = g1 + G1_BYTES, *Vn = g1 + 2 * G1_BYTES, *SA = g1 + 3 * G1_BYTES, *SB = g1 + 4 * G1_BYTES;
+    const Generators gen;
+    const uint8_t* t2_1 = pl.t2 + G2_BYTES;
+    const struct {
+        const uint8_t *a1, *a2, *b1, *b2;
+        const char* msg;
+    } eqs[5] = {{U, gen.g2, V, t2_1, "ptau: section 2 (tauG1): the first 2n points are not consecutive powers of the tau of section 3"},
+                {gen.g1, s2, Vn, gen.g2, "ptau: section 3 (tauG2): the first n points are not the powers of the tau of section 2"},
+                {SA, gen.g2, pl.at, s2, "ptau: section 4 (alphaTauG1): the first n points are not alphaTauG1[0] times the powers of tau"},
+                {SB, gen.g2, pl.bt, s2, "ptau: section 5 (betaTauG1): the first n points are not betaTauG1[0] times the powers of tau"},
+                {pl.bt, gen.g2, gen.g1, pl.beta2, "ptau: section 6 (betaG2): the point is not the G2 generator times the beta of betaTauG1[0]"}};
+    std::vector<PairCheck> checks;
+    std::string host_verdict, verdict;
+    for (int i = 0; i < 5 && host_verdict.empty(); ++i) host_verdict = pair_rule(eqs[i].a1, eqs[i].a2, eqs[i].b1, eqs[i].b2, eqs[i].msg, checks);
+    if (!run_checks(checks, verdict, err)) return {2, err};
+    if (verdict.empty()) verdict = host_verdict;
+    return {verdict.empty() ? 0 : 1, verdict};
+}
+
+// a verdict of the functions that the contribution check shares with the key check, under the key check's name
+std::string as_key_verdict(const std::string& msg) { return msg.compare(0, 6, "zkey: ") == 0 ? "zkey verify: " + msg.substr(6) : msg; }
+
+PhaseTimes<3> g_key_phases;  // remake, linear combinations, pairings: host clock around the three synchronous parts
+
+float ms_since(const std::chrono::steady_clock::time_point& t0) {
+    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+Outcome verify_key(const uint8_t* zkey, size_t len, gwb_r1cs* r, const uint8_t* ptau, size_t ptau_len, uint32_t mode, uint32_t flags, const uint8_t* seed_in,
+                   uint8_t* hashes_out, size_t* n_io) {
+    std::string err;
+    // 1. parse
+    Key key;
+    if (!read_key(zkey, len, key, err)) return {2, err};
+    gw_status_t st{};
+    gwb_r1cs_qap_info_t qi;
+    if (gwb_r1cs_qap_info(r, &qi, &st) != 0) return {2, outcome_of(1, st).msg};
+    {
+        cwc_ptau::View view;
+        cwc_ptau::Plan pl;
+        if (!cwc_ptau::parse(ptau, ptau_len, view, err) || !cwc_ptau::plan(view, qi.domain_power, mode, pl, err) || !cwc_ptau::check_header_points(pl, err))
+            return {2, err};
+    }
+    // 2. sizes
+    const gwb_zkey& z = *key.z;
+    const uint64_t want[3] = {r->info.n_wires, (uint64_t)r->info.n_pub_out + r->info.n_pub_in, qi.domain_size};
+    const uint64_t have[3] = {z.info.n_vars, z.info.n_public, z.info.domain_size};
+    static const char* size_names[3] = {"nVars", "nPublic", "domainSize"};
+    for (int i = 0; i < 3; ++i)
+        if (have[i] != want[i])
+            return {1, std::string("zkey verify: ") + size_names[i] + " of the key is " + std::to_string(have[i]) + ", the circuit's is " + std::to_string(want[i])};
+    uint8_t seed[32];
+    if (!take_seed(seed_in, seed)) return {2, "zkey verify: getrandom failed"};
+    // 3. the powers check
+    if (flags & GWB_VERIFY_KEY_CHECK_PTAU) {
+        const Outcome o = check_powers(ptau, ptau_len, qi.domain_power, seed);
+        if (o.rc != 0) return o;
+    }
+    // 4. the key of the circuit and the file with delta = 1
+    auto t0 = std::chrono::steady_clock::now();
+    float ms[3] = {0, 0, 0};
+    const uint8_t one[32] = {1};
+    void* remade = nullptr;
+    size_t remade_len = 0;
+    if (gwb_groth16_setup_ptau(r, ptau, ptau_len, one, mode, &remade, &remade_len, &st) != 0) return {2, outcome_of(2, st).msg};
+    free(st.error_msg);
+    st.error_msg = nullptr;
+    struct Release {
+        void* p;
+        ~Release() { gwb_groth16_setup_free(p); }
+    } release{remade};
+    Key key0;
+    if (!read_key(remade, remade_len, key0, err)) return {2, "zkey verify: the remade key: " + err};
+    ms[0] = ms_since(t0);
+    // 5. structure
+    if (gwb_zkey_check_r1cs(key.z.get(), r, &st) != 0) return {1, as_key_verdict(outcome_of(1, st).msg)};
+    free(st.error_msg);
+    st.error_msg = nullptr;
+    std::string verdict = same_sections(key0, key, {1u, 3u, 5u, 6u, 7u}, "zkey verify: ", "the key remade from the circuit and the powers-of-tau file");
+    if (!verdict.empty()) return {1, verdict};
+    // 6 to 8: host rules in order, their pairings in one launch
+    const Section10& s = key.s10;
+    const size_t n = s.recs.size();
+    const Generators gen;
+    std::vector<PairCheck> checks;
+    std::vector<uint8_t> sp(std::max<size_t>(n, 1) * G2_BYTES);
+    std::string host_verdict;
+    if (!(flags & GWB_VERIFY_KEY_SKIP_RECORDS)) {
+        if (!s.blank()) {
+            uint8_t want_hash[HASH_BYTES];
+            sections_hash(key0.secs, want_hash);
+            if (memcmp(want_hash, s.cs_hash, HASH_BYTES) != 0)
+                host_verdict = "zkey verify: section 10: the csHash is not the hash of sections 1 to 9 of the remade key";
+        }
+        for (size_t k = 0; k < n && host_verdict.empty(); ++k)
+            host_verdict = record_rules(s, k, k ? s.recs[k - 1].delta_after : gen.g1, sp.data() + k * G2_BYTES, checks);
+        if (host_verdict.empty()) host_verdict = delta1_rule(z, n ? s.recs[n - 1].delta_after : nullptr, gen.g1);
+    }
+    if (host_verdict.empty() && is_zero_bytes(z.delta1, G1_BYTES)) host_verdict = "zkey verify: delta1 is the point at infinity";
+    if (host_verdict.empty()) host_verdict = delta2_rules(z, gen.g1, gen.g2, checks);
+    uint8_t sums[4 * G1_BYTES];
+    if (host_verdict.empty()) {
+        t0 = std::chrono::steady_clock::now();
+        if (!step_sums(*key0.z, z, seed, sums, err)) return {2, err};
+        ms[1] = ms_since(t0);
+        host_verdict = sums_rules(sums, key0.z->delta2, z.delta2, "zkey verify: section ", " is not the remade key's section divided by delta", checks);
+    }
+    t0 = std::chrono::steady_clock::now();
+    if (!run_checks(checks, verdict, err)) return {2, err};
+    ms[2] = ms_since(t0);
+    if (verdict.empty()) verdict = host_verdict;
+    if (!verdict.empty()) return {1, as_key_verdict(verdict)};
+    g_key_phases.store(ms, true);
+    const size_t room = *n_io;
+    *n_io = n;
+    for (size_t k = 0; k < n && k < room && hashes_out; ++k) record_hash(s.recs[k], hashes_out + k * HASH_BYTES);
+    return {0, ""};
+}
+
+int finish(const Outcome& o, gw_status_t* status) {
+    if (o.rc == 0) {
+        set_ok(status);
+        return 0;
+    }
+    set_status(status, o.msg);
+    return o.rc;
+}
+
+// the aid of the linear-combination kernels for one group (the extern functions below)
+template <class T>
+int lincomb_aid(const char* fn, const void* d_points, const void* d_rho, size_t n, void* d_out, void* hip_stream, gw_status_t* status) {
+    if (!d_out || (n && (!d_points || !d_rho))) return fail(status, std::string(fn) + ": NULL argument");
+    if (n > 0x7fffffffull) return fail(status, std::string(fn) + ": n above 2^31 - 1");
+    hipStream_t s = (hipStream_t)hip_stream;
+    Carve cw;
+    const size_t o_part = cw.take((size_t)blocks_for(n, LC_THREADS<T>) * sizeof(Xyzz<T>)), o_acc = cw.take(sizeof(Xyzz<T>));
+    void* ws = nullptr;
+    hipError_t e = hipMallocAsync(&ws, cw.o, s);
+    if (e != hipSuccess) return fail(status, hip_err("allocating the linear combination's workspace", e));
+    uint8_t* W = (uint8_t*)ws;
+    e = hipMemsetAsync(W + o_acc, 0, sizeof(Xyzz<T>), s);
+    if (e == hipSuccess && n)
+        enqueue_lincomb<T>((const uint8_t*)d_points, (const uint8_t*)d_points, 1, (uint32_t)n, true, (const uint8_t*)d_rho, (Xyzz<T>*)(W + o_part),
+                           (Xyzz<T>*)(W + o_acc), s);
+    if (e == hipSuccess) {
+        enqueue_affine<T>(W + o_acc, 1, (uint8_t*)d_out, true, s);
+        e = hipGetLastError();
+    }
+    const hipError_t ef = hipFreeAsync(ws, s);
+    if (e != hipSuccess) return fail(status, hip_err("launching the linear combination", e));
+    if (ef != hipSuccess) return fail(status, hip_err("releasing the linear combination's workspace", ef));
     set_ok(status);
     return 0;
 }
@@ -605,6 +928,28 @@ int gwb_zkey_verify_step(const void* prev, size_t prev_len, const void* next, si
     }
 }
 
+int gwb_ptau_check_powers(const void* data, size_t len, uint32_t domain_power, const uint8_t* seed, gw_status_t* status) {
+    if (!data && len) return fail2(status, "gwb_ptau_check_powers: NULL argument");
+    try {
+        return finish(check_powers((const uint8_t*)data, len, domain_power, seed), status);
+    } catch (const std::bad_alloc&) {
+        return fail2(status, "ptau: out of host memory");
+    }
+}
+
+int gwb_zkey_verify_key(const void* zkey, size_t len, gwb_r1cs_t* r, const void* ptau, size_t ptau_len, uint32_t lagrange_mode, uint32_t flags,
+                        const uint8_t* seed, void* hashes_out, size_t* n, gw_status_t* status) {
+    if (!n || !r || (!zkey && len) || (!ptau && ptau_len) || (*n && !hashes_out)) return fail2(status, "gwb_zkey_verify_key: NULL argument");
+    if (flags & ~(uint32_t)(GWB_VERIFY_KEY_SKIP_RECORDS | GWB_VERIFY_KEY_CHECK_PTAU)) return fail2(status, "gwb_zkey_verify_key: unknown flags " + std::to_string(flags));
+    try {
+        return finish(verify_key((const uint8_t*)zkey, len, r, (const uint8_t*)ptau, ptau_len, lagrange_mode, flags, seed, (uint8_t*)hashes_out, n), status);
+    } catch (const std::bad_alloc&) {
+        return fail2(status, "zkey: out of host memory");
+    }
+}
+
+int gwb_zkey_verify_key_phase_ms(float* ms) { return g_key_phases.read(ms); }
+
 int gwb_bn254_g1_scale_batch_device(const void* d_points, size_t n, const uint8_t* k32, void* d_out, void* hip_stream, gw_status_t* status) {
     if (!k32 || (n && (!d_points || !d_out))) return fail(status, "gwb_bn254_g1_scale_batch_device: NULL argument");
     if (n > 0x7fffffffull) return fail(status, "gwb_bn254_g1_scale_batch_device: n above 2^31 - 1");
@@ -634,28 +979,11 @@ int gwb_bn254_g1_scale_batch_device(const void* d_points, size_t n, const uint8_
 }
 
 int gwb_bn254_g1_lincomb128_device(const void* d_points, const void* d_rho, size_t n, void* d_out, void* hip_stream, gw_status_t* status) {
-    if (!d_out || (n && (!d_points || !d_rho))) return fail(status, "gwb_bn254_g1_lincomb128_device: NULL argument");
-    if (n > 0x7fffffffull) return fail(status, "gwb_bn254_g1_lincomb128_device: n above 2^31 - 1");
-    hipStream_t s = (hipStream_t)hip_stream;
-    Carve cw;
-    const size_t o_part = cw.take((size_t)blocks_for(n, THREADS) * sizeof(Xyzz<G1>)), o_acc = cw.take(sizeof(Xyzz<G1>));
-    void* ws = nullptr;
-    hipError_t e = hipMallocAsync(&ws, cw.o, s);
-    if (e != hipSuccess) return fail(status, hip_err("allocating the linear combination's workspace", e));
-    uint8_t* W = (uint8_t*)ws;
-    e = hipMemsetAsync(W + o_acc, 0, sizeof(Xyzz<G1>), s);
-    if (e == hipSuccess && n)
-        enqueue_lincomb((const uint8_t*)d_points, (const uint8_t*)d_points, 1, (uint32_t)n, true, (const uint8_t*)d_rho, (Xyzz<G1>*)(W + o_part),
-                        (Xyzz<G1>*)(W + o_acc), s);
-    if (e == hipSuccess) {
-        enqueue_affine_g1(W + o_acc, 1, (uint8_t*)d_out, true, s);
-        e = hipGetLastError();
-    }
-    const hipError_t ef = hipFreeAsync(ws, s);
-    if (e != hipSuccess) return fail(status, hip_err("launching the linear combination", e));
-    if (ef != hipSuccess) return fail(status, hip_err("releasing the linear combination's workspace", ef));
-    set_ok(status);
-    return 0;
+    return lincomb_aid<G1>("gwb_bn254_g1_lincomb128_device", d_points, d_rho, n, d_out, hip_stream, status);
+}
+
+int gwb_bn254_g2_lincomb128_device(const void* d_points, const void* d_rho, size_t n, void* d_out, void* hip_stream, gw_status_t* status) {
+    return lincomb_aid<G2>("gwb_bn254_g2_lincomb128_device", d_points, d_rho, n, d_out, hip_stream, status);
 }
 
 }  // extern "C"

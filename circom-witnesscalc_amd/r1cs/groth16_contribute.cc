@@ -3,12 +3,21 @@
 // in [1, r), for reproducible keys).  Prints the contribution hash in hex.
 // groth16-contribute --verify <key.zkey>: checks the key's contribution records and prints their hashes.
 // groth16-contribute --verify-step <prev.zkey> <next.zkey>: checks that next is prev after exactly one contribution.
+// groth16-contribute --verify-key [--lagrange auto|file|compute] [--skip-records] [--check-ptau] <circuit.r1cs> <pot.ptau> <key.zkey>:
+// checks the key against its circuit and its powers-of-tau file (snarkjs `zkey verify`, with its argument order) and prints the
+// hashes of its records.  The file is mapped into memory, not read; --lagrange defaults to compute, which keeps the verdict
+// off the file's prepared sections; --skip-records passes over section 10 (a key with snarkjs's records); --check-ptau first
+// checks that the points read from the file are powers of one tau.
 // The records are this library's own: they are not interchangeable with snarkjs's (see the header).  Exit status 0 on success;
 // 1 for a failed verification, with its message; 2 on a usage, file or format error.  Every input is parsed before the device
 // is touched.
+#include <fcntl.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <fstream>
@@ -17,6 +26,7 @@
 #include <vector>
 
 #include "../../include/graph_witness_groth16_contribute.h"
+#include "../../include/graph_witness_groth16_ptau.h"
 #include "../../include/graph_witness_groth16_setup.h"
 
 static bool read_file(const char* path, std::vector<char>& out) {
@@ -25,6 +35,31 @@ static bool read_file(const char* path, std::vector<char>& out) {
     out.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
     return !f.bad();
 }
+
+// a file mapped read-only; size 0 maps nothing
+struct Mapped {
+    void* data = NULL;
+    size_t len = 0;
+    bool open(const char* path) {
+        const int fd = ::open(path, O_RDONLY);
+        if (fd < 0) return false;
+        struct stat st;
+        bool ok = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
+        if (ok && st.st_size > 0) {
+            void* p = mmap(NULL, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+            ok = p != MAP_FAILED;
+            if (ok) {
+                data = p;
+                len = (size_t)st.st_size;
+            }
+        }
+        close(fd);
+        return ok;
+    }
+    ~Mapped() {
+        if (data) munmap(data, len);
+    }
+};
 
 static bool write_file(const char* path, const void* data, size_t n) {
     FILE* f = fopen(path, "wb");
@@ -81,8 +116,21 @@ static int usage() {
     fprintf(stderr,
             "usage: groth16-contribute [--name NAME] [--delta FILE] <in.zkey> <out.zkey>\n"
             "       groth16-contribute --verify <key.zkey>\n"
-            "       groth16-contribute --verify-step <prev.zkey> <next.zkey>\n");
+            "       groth16-contribute --verify-step <prev.zkey> <next.zkey>\n"
+            "       groth16-contribute --verify-key [--lagrange auto|file|compute] [--skip-records] [--check-ptau] <circuit.r1cs> <pot.ptau> <key.zkey>\n");
     return 2;
+}
+
+// the number of records of a key, from the host-only reader; false with st set
+static bool record_count(const std::vector<char>& key, size_t& n, gw_status_t& st) {
+    void* image = NULL;
+    size_t image_len = 0;
+    if (gwb_zkey_contributions(key.data(), key.size(), &image, &image_len, &st) != 0) return false;
+    uint32_t count;
+    memcpy(&count, (const uint8_t*)image + GWB_CONTRIBUTION_HASH_BYTES, 4);
+    gwb_groth16_setup_free(image);
+    n = count;
+    return true;
 }
 
 static int report(int rc, gw_status_t& st) {
@@ -91,9 +139,48 @@ static int report(int rc, gw_status_t& st) {
     return rc == 1 ? 1 : 2;
 }
 
+static int run_verify_key(const char* r1cs_path, const char* ptau_path, const char* key_path, const char* lagrange, bool skip_records, bool check_ptau) {
+    uint32_t mode = GWB_PTAU_LAGRANGE_COMPUTE;
+    if (lagrange) {
+        if (strcmp(lagrange, "auto") == 0)
+            mode = GWB_PTAU_LAGRANGE_AUTO;
+        else if (strcmp(lagrange, "file") == 0)
+            mode = GWB_PTAU_LAGRANGE_FILE;
+        else if (strcmp(lagrange, "compute") != 0)
+            return usage();
+    }
+    std::vector<char> circuit, key;
+    Mapped ptau;
+    const char* unread = !read_file(r1cs_path, circuit) ? r1cs_path : !ptau.open(ptau_path) ? ptau_path : !read_file(key_path, key) ? key_path : NULL;
+    if (unread) {
+        fprintf(stderr, "error: cannot read %s\n", unread);
+        return 2;
+    }
+    gw_status_t st{};
+    gwb_r1cs_t* r = NULL;
+    if (gwb_r1cs_load(circuit.data(), circuit.size(), &r, &st) != 0) {
+        fprintf(stderr, "error: %s: %s\n", r1cs_path, st.error_msg ? st.error_msg : "load failed");
+        free(st.error_msg);
+        return 2;
+    }
+    size_t n = 0;
+    if (!record_count(key, n, st)) {
+        gwb_r1cs_free(r);
+        return report(2, st);
+    }
+    std::vector<uint8_t> hashes(n * GWB_CONTRIBUTION_HASH_BYTES + 1);
+    const uint32_t flags = (skip_records ? GWB_VERIFY_KEY_SKIP_RECORDS : 0u) | (check_ptau ? GWB_VERIFY_KEY_CHECK_PTAU : 0u);
+    const int rc = gwb_zkey_verify_key(key.data(), key.size(), r, ptau.data, ptau.len, mode, flags, NULL, hashes.data(), &n, &st);
+    gwb_r1cs_free(r);
+    if (rc != 0) return report(rc, st);
+    printf("OK! %s is the key of %s and %s, %zu contributions%s\n", key_path, r1cs_path, ptau_path, n, skip_records ? " (not verified)" : "");
+    for (size_t k = 0; k < n; ++k) print_hex(hashes.data() + k * GWB_CONTRIBUTION_HASH_BYTES, GWB_CONTRIBUTION_HASH_BYTES);
+    return 0;
+}
+
 int main(int argc, char** argv) {
-    const char *name = "", *delta_path = NULL;
-    bool verify = false, step = false;
+    const char *name = "", *delta_path = NULL, *lagrange = NULL;
+    bool verify = false, step = false, verify_key = false, skip_records = false, check_ptau = false;
     std::vector<const char*> paths;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -105,13 +192,23 @@ int main(int argc, char** argv) {
             verify = true;
         else if (a == "--verify-step")
             step = true;
+        else if (a == "--verify-key")
+            verify_key = true;
+        else if (a == "--skip-records")
+            skip_records = true;
+        else if (a == "--check-ptau")
+            check_ptau = true;
+        else if (a == "--lagrange" && i + 1 < argc)
+            lagrange = argv[++i];
         else if (a.size() > 1 && a[0] == '-')
             return usage();
         else
             paths.push_back(argv[i]);
     }
-    if ((verify && step) || ((verify || step) && (delta_path || *name))) return usage();
-    if (paths.size() != (verify ? 1u : 2u)) return usage();
+    if (verify + step + verify_key > 1 || ((verify || step || verify_key) && (delta_path || *name))) return usage();
+    if (!verify_key && (lagrange || skip_records || check_ptau)) return usage();
+    if (paths.size() != (verify ? 1u : verify_key ? 3u : 2u)) return usage();
+    if (verify_key) return run_verify_key(paths[0], paths[1], paths[2], lagrange, skip_records, check_ptau);
     std::vector<char> first, second;
     if (!read_file(paths[0], first)) {
         fprintf(stderr, "error: cannot read %s\n", paths[0]);
@@ -123,13 +220,8 @@ int main(int argc, char** argv) {
     }
     gw_status_t st{};
     if (verify) {
-        void* image = NULL;  // the record count, from the host-only reader
-        size_t image_len = 0;
-        if (gwb_zkey_contributions(first.data(), first.size(), &image, &image_len, &st) != 0) return report(2, st);
-        uint32_t count;
-        memcpy(&count, (const uint8_t*)image + GWB_CONTRIBUTION_HASH_BYTES, 4);
-        gwb_groth16_setup_free(image);
-        size_t n = count;
+        size_t n = 0;
+        if (!record_count(first, n, st)) return report(2, st);
         std::vector<uint8_t> hashes(n * GWB_CONTRIBUTION_HASH_BYTES + 1);
         const int rc = gwb_zkey_verify_contributions(first.data(), first.size(), hashes.data(), &n, &st);
         if (rc != 0) return report(rc, st);

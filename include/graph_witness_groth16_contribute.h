@@ -51,7 +51,7 @@
  *
  * Return and status conventions are those of graph_witness_r1cs.h, with one addition: the two verification functions return
  * 1 when the key was read and a rule failed (status names the first failing record and rule), and 2 for every other failure
- * (bytes that are no key, a device error). */
+ * (bytes that are no key, a device error).  gwb_zkey_verify_key follows them too. */
 #ifndef CWC_AMD_GRAPH_WITNESS_GROTH16_CONTRIBUTE_H
 #define CWC_AMD_GRAPH_WITNESS_GROTH16_CONTRIBUTE_H
 
@@ -93,6 +93,42 @@ int gwb_zkey_verify_contributions(const void *zkey, size_t len, void *hashes_out
  * point is accepted with probability about 2^-128 over the seed, so a verifier draws the seed after it has seen the key. */
 int gwb_zkey_verify_step(const void *prev, size_t prev_len, const void *next, size_t next_len, const uint8_t *seed, gw_status_t *status);
 
+/* Checks that `zkey` is the honest key of the circuit `r` and the powers-of-tau file `ptau`, with a delta that only the recorded
+ * contributions touched: what `snarkjs zkey verify circuit.r1cs pot.ptau key.zkey` answers.  The rules, in this order; the first
+ * failure is the message:
+ *   1. Parse.  The key parses as for the functions above; the file passes the loader's checks of graph_witness_groth16_ptau.h
+ *      for the circuit's domain under lagrange_mode (returns 2 with their messages).
+ *   2. Sizes.  nVars, nPublic and domainSize of the key are the circuit's ("zkey verify: nVars of the key is 7, the circuit's
+ *      is 9").  Everything up to here runs before the device is touched.
+ *   3. With GWB_VERIFY_KEY_CHECK_PTAU: gwb_ptau_check_powers for the circuit's domain power, with its messages ("ptau: ...").
+ *   4. Remake.  key0 = gwb_groth16_setup_ptau(r, ptau, delta = 1, lagrange_mode) (a failure returns 2 with its message).
+ *      GWB_PTAU_LAGRANGE_COMPUTE keeps the verdict off the file's sections 12 to 15, which nothing verifies.
+ *   5. Structure.  Section 4 agrees with the circuit by gwb_zkey_check_r1cs's rule (not by bytes); sections 1, 3, 5, 6, 7 and
+ *      the header before delta1 (the sizes, alpha1, beta1, beta2, gamma2) are key0's byte for byte ("zkey verify: section 5 (A)
+ *      differs from the key remade from the circuit and the powers-of-tau file").
+ *   6. Records, unless GWB_VERIFY_KEY_SKIP_RECORDS: the csHash is blank (only without records) or H(sections 1 to 9 of key0);
+ *      then every rule of gwb_zkey_verify_contributions, so without records delta1 and delta2 are the generators.
+ *   7. delta, always: neither delta point at infinity, delta2 in the order-r subgroup, e(delta1, G2) = e(G1, delta2).
+ *   8. C and H: with the 128-bit rho of gwb_zkey_verify_step over key0's and the key's C || H, per section
+ *      e(R', delta2) = e(R, G2); a sum at infinity on one side only is a failure ("zkey verify: section 8 (C) is not the remade
+ *      key's section divided by delta").
+ * All pairings of rules 6 to 8 run in one batched launch.  A verdict of a rule shared with gwb_zkey_verify_contributions reads
+ * "zkey verify: ..." where that function says "zkey: ...".  GWB_VERIFY_KEY_SKIP_RECORDS is for keys that carry snarkjs's
+ * records, which this library cannot verify by design: their points are still checked against circuit, file and their own
+ * delta, but then nothing shows who made that delta.
+ * NOT verified: the ceremony's own contribution records in the `.ptau`; the file's points beyond the prefixes a setup reads;
+ * sections 12 to 15 of the file, on which the verdict rests unless lagrange_mode is GWB_PTAU_LAGRANGE_COMPUTE; records made by
+ * snarkjs.  seed: 32 bytes for rho (here and in rule 3), or NULL to draw them.  hashes_out and *n as for
+ * gwb_zkey_verify_contributions, filled on success.  Returns 0; 1 when a rule failed, with a message that starts
+ * "zkey verify:" or "ptau:"; 2 otherwise.  Synchronous, on the current device. */
+#define GWB_VERIFY_KEY_SKIP_RECORDS 1u
+#define GWB_VERIFY_KEY_CHECK_PTAU 2u
+int gwb_zkey_verify_key(const void *zkey, size_t len, gwb_r1cs_t *r, const void *ptau, size_t ptau_len, uint32_t lagrange_mode,
+                        uint32_t flags, const uint8_t *seed, void *hashes_out, size_t *n, gw_status_t *status);
+/* {remake, linear combinations, pairings} in ms of the process's last accepted gwb_zkey_verify_key call (host clock around the
+ * three synchronous parts; the powers check of rule 3 is in none of them); 1 when there is none. */
+int gwb_zkey_verify_key_phase_ms(float *ms);
+
 /* Host-only aids.  The records of a key's section 10 as a flat image (freed with gwb_groth16_setup_free): 64 B csHash, u32 n,
  * then per record deltaAfter, g1_s, g1_sx (64 B each), g2_spx (128 B), canonical little-endian as the C ABI's points,
  * transcript (64 B), hash (64 B), u32 type, u32 nameLen, name. */
@@ -107,6 +143,8 @@ void gwb_zkey_contribution_challenge(const void *t64, void *out128);
 int gwb_bn254_g1_scale_batch_device(const void *d_points, size_t n, const uint8_t *k32, void *d_out, void *hip_stream, gw_status_t *status);
 /* *d_out (one point) = sum_i rho_i d_points[i], d_rho device [n][16] little-endian */
 int gwb_bn254_g1_lincomb128_device(const void *d_points, const void *d_rho, size_t n, void *d_out, void *hip_stream, gw_status_t *status);
+/* the same in G2: points of 128 B (x.c0, x.c1, y.c0, y.c1), one point of 128 B out */
+int gwb_bn254_g2_lincomb128_device(const void *d_points, const void *d_rho, size_t n, void *d_out, void *hip_stream, gw_status_t *status);
 
 #ifdef __cplusplus
 }

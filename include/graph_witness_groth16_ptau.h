@@ -3,7 +3,8 @@
  * from the caller (graph_witness_groth16_setup.h is the setup from a known trapdoor).
  *
  * TRUST.  tau, alpha and beta are those of the ceremony behind the file: nobody knows them if one participant of that
- * ceremony was honest, and this library does not verify the ceremony (no `powersoftau verify`, no contribution records).
+ * ceremony was honest, and this library does not verify the ceremony's contribution records (no `powersoftau verify`);
+ * gwb_ptau_check_powers checks, when asked, that the points a setup reads are powers of one tau at all.
  * gamma is 1, as in snarkjs.  delta is the caller's:
  *   delta = 1 gives the state of snarkjs `zkey new`: a key that is to be handed to a phase-2 ceremony, NOT to be used, since
  *   everybody knows its delta and knowing delta alone is enough to forge proofs;
@@ -79,6 +80,26 @@ int gwb_ptau_check(const void *data, size_t len, uint32_t domain_power, uint32_t
  * 13: "ptau: section 3 (tauG2) point 5 is not in the order-r subgroup of G2" (a coordinate >= q or a point off the curve among
  * them is named as gwb_ptau_check names it). */
 int gwb_ptau_check_g2(const void *data, size_t len, uint32_t domain_power, uint32_t lagrange_mode, gw_status_t *status);
+
+/* Checks that the monomial prefixes a setup for the domain n = 2^domain_power reads under GWB_PTAU_LAGRANGE_COMPUTE are what their
+ * sections' names say: T1 = tauG1[0 .. 2n), T2 = tauG2[0 .. n), AT = alphaTauG1[0 .. n), BT = betaTauG1[0 .. n) and beta2.  First
+ * everything gwb_ptau_check refuses, with its messages (returns 2); then the subgroup rule of gwb_ptau_check_g2 (the pairing is
+ * bilinear on the order-r subgroup only; returns 1 with its message); then, with 128-bit rho_0 .. rho_{2n-2} cut from `seed` as
+ * gwb_zkey_verify_step cuts them (32 bytes, or NULL to draw them), six sums computed on the device from points that go there in
+ * pieces of CWC_CONTRIBUTE_CHUNK:
+ *   U = sum_{i<2n-1} rho_i T1_{i+1}   V = sum_{i<2n-1} rho_i T1_i   V_n = sum_{i<n} rho_i T1_i
+ *   S_A = sum_{i<n} rho_i AT_i        S_B = sum_{i<n} rho_i BT_i    S_2 = sum_{i<n} rho_i T2_i (in G2)
+ * and five equations in one batched pairing launch; the first that fails is the verdict (returns 1):
+ *   e(U, G2) = e(V, T2_1)        "ptau: section 2 (tauG1): the first 2n points are not consecutive powers of the tau of section 3"
+ *   e(G1, S_2) = e(V_n, G2)      "ptau: section 3 (tauG2): ..."
+ *   e(S_A, G2) = e(AT_0, S_2)    "ptau: section 4 (alphaTauG1): ..."
+ *   e(S_B, G2) = e(BT_0, S_2)    "ptau: section 5 (betaTauG1): ..."
+ *   e(BT_0, G2) = e(G1, beta2)   "ptau: section 6 (betaG2): ..."
+ * A side with a point at infinity is 1: one such side alone fails its equation, two pass.  A file with a wrong point among the
+ * prefixes passes with probability about 2^-128 over the seed.  NOT checked: the points beyond the prefixes (tauG1[2n] may be
+ * anything); the Lagrange sections 12 to 15; the ceremony's own contribution records in section 7, whose challenge derivation
+ * (snarkjs's) cannot be restated here.  Returns 2 for anything that is not a verdict.  Synchronous, on the current device. */
+int gwb_ptau_check_powers(const void *data, size_t len, uint32_t domain_power, const uint8_t *seed, gw_status_t *status);
 
 /* delta: 32 bytes canonical little-endian in [1, r), or NULL to draw it (the prover's rejection sampler over getrandom()).
  * *zkey is released with gwb_groth16_setup_free. */
