@@ -635,6 +635,11 @@ def r1cs_lib():
         L.gwb_ptau_check_powers.argtypes = [vp, sz, u32, vp, stp]
         L.gwb_zkey_verify_key.argtypes = [vp, sz, vp, vp, sz, u32, u32, vp, vp, ctypes.POINTER(sz), stp]
         L.gwb_zkey_verify_key_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_float)]
+        L.gwb_ptau_prepare_phase2.argtypes = [vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
+        L.gwb_ptau_prepare_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_float)]
+        L.gwb_ptau_check_lagrange.argtypes = [vp, sz, u32, vp, stp]
+        L.gwb_bn254_g1_lincomb_device.argtypes = [vp, vp, sz, u32, vp, vp, stp]
+        L.gwb_bn254_g2_lincomb_device.argtypes = [vp, vp, sz, u32, vp, vp, stp]
         _r1cs_lib = L
     return _r1cs_lib
 
@@ -1351,11 +1356,95 @@ def ptau_check_powers(ptau, domain_power, seed=None):
     del keep
 
 
+# -- the prepared sections 12 to 15 of a `.ptau` (include/graph_witness_groth16_ptau.h) ------------------------------------------
+PTAU_PREPARE_PHASES = ("load", "idft_g1", "idft_g2", "affine")
+PTAU_ALL_LEVELS = 0xffffffff
+
+
+def ptau_prepare_phase2(ptau):
+    """What snarkjs `powersoftau prepare phase2` does, on the GPU (synchronous): a `.ptau` image (bytes or any buffer, an mmap
+    included) -> the image with its Lagrange sections 12 to 15 made from the monomial sections 2 to 5, as bytes.  Every other
+    section is carried byte for byte in the input's order; sections 12 to 15 follow, replacing any the input had.  Level m of
+    a Lagrange section is Lag_m of the first 2^m monomial points at point offset 2^m - 1; section 12's extra level power + 1
+    takes the point at infinity for the input that section 2 lacks.  groth16_setup_ptau and groth16_verify_key read the
+    result under lagrange="file" and skip their own transforms.  The file is parsed and sized before the GPU is touched; all
+    levels of one section must fit CWC_GROTH16_WORKSPACE_MB on the device.  No snarkjs-prepared file was compared."""
+    keep, addr, n_in = _ptau_buffer(ptau)
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    st = GwStatus()
+    rc = r1cs_lib().gwb_ptau_prepare_phase2(addr, n_in, ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
+    del keep
+    _r1cs_check(rc, st)
+    try:
+        return ctypes.string_at(out, n.value)
+    finally:
+        r1cs_lib().gwb_groth16_setup_free(out)
+
+
+def ptau_prepare_phase_ms():
+    """{load, idft_g1, idft_g2, affine} in ms of the process's last ptau_prepare_phase2 call, summed over the four sections."""
+    ms = (ctypes.c_float * 4)()
+    if r1cs_lib().gwb_ptau_prepare_phase_ms(ms) != 0:
+        raise WitnessCalcError("no prepare phase times (no ptau_prepare_phase2 call yet)")
+    return dict(zip(PTAU_PREPARE_PHASES, (float(x) for x in ms)))
+
+
+def ptau_check_lagrange(ptau, domain_power=None, seed=None):
+    """Raises WitnessCalcError unless the Lagrange sections 12 to 15 of a prepared `.ptau` are the Lagrange forms of its
+    monomial sections 2 to 5.  domain_power=p: the levels groth16_setup_ptau reads for a circuit of domain 2^p under
+    lagrange="file" (level p of the four sections, level p + 1 of section 12); None: every level of every section.  First
+    ptau_check's refusals, point faults among the points read and the refusal of a file without prepared sections, with
+    their messages; for section 13 the subgroup rule of ptau_check_g2; then per section one random linear combination of
+    the Lagrange points against one of the monomial points on the current GPU, compared as points (synchronous; a wrong point
+    passes with probability about 2^-128 over the seed).  seed: 32 bytes for a reproducible check, or None to draw them.  The
+    message names the section and the level: "ptau: section 14 (lagrange alphaTauG1) level 3 does not hold the Lagrange
+    forms of section 4".  Not checked: that sections 2 to 5 are powers of one tau (ptau_check_powers)."""
+    seed = _seed32(seed)
+    keep, addr, n = _ptau_buffer(ptau)
+    st = GwStatus()
+    rc = r1cs_lib().gwb_ptau_check_lagrange(addr, n, PTAU_ALL_LEVELS if domain_power is None else int(domain_power), seed, ctypes.byref(st))
+    _r1cs_check(rc, st)
+    del keep
+
+
+def _lincomb_device(group, d_points, d_scalars, form, stream):
+    import torch
+    if form not in ("canonical", "montgomery"):
+        raise WitnessCalcError("form must be canonical or montgomery")
+    n, width = d_points.shape[0], 64 * group
+    assert tuple(d_points.shape) == (n, width) and d_points.is_cuda and d_points.is_contiguous() and d_points.dtype == torch.uint8
+    assert tuple(d_scalars.shape) == (n, 32) and d_scalars.is_cuda and d_scalars.is_contiguous() and d_scalars.dtype == torch.uint8
+    s = stream if stream is not None else torch.cuda.current_stream(d_points.device)
+    out = torch.empty((width,), dtype=torch.uint8, device=d_points.device)
+    st = GwStatus()
+    call = r1cs_lib().gwb_bn254_g1_lincomb_device if group == 1 else r1cs_lib().gwb_bn254_g2_lincomb_device
+    with torch.cuda.device(d_points.device):
+        rc = call(d_points.data_ptr(), d_scalars.data_ptr(), n, 0 if form == "canonical" else 1, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
+    _r1cs_check(rc, st)
+    d_points.record_stream(s)
+    d_scalars.record_stream(s)
+    out.record_stream(s)
+    return out
+
+
+def bn254_g1_lincomb_device(d_points, d_scalars, form="canonical", stream=None):
+    """Measurement and test aid of the Lagrange check's right-hand side, beside bn254_g1_lincomb128_device: device G1 points
+    (uint8 cuda [n, 64], affine in `form`, "canonical" or "montgomery"; zero bytes for infinity) and canonical little-endian
+    scalars below r (uint8 cuda [n, 32]) -> sum_i scalar_i P_i as uint8 cuda [64] in the same form.  Asynchronous on `stream`
+    or the current stream."""
+    return _lincomb_device(1, d_points, d_scalars, form, stream)
+
+
+def bn254_g2_lincomb_device(d_points, d_scalars, form="canonical", stream=None):
+    """The same in G2: uint8 cuda [n, 128] points (x.c0, x.c1, y.c0, y.c1) and [n, 32] scalars -> uint8 cuda [128]."""
+    return _lincomb_device(2, d_points, d_scalars, form, stream)
+
+
 GROTH16_VERIFY_KEY_PHASES = ("remake", "lincomb", "pairings")
 VERIFY_KEY_SKIP_RECORDS, VERIFY_KEY_CHECK_PTAU = 1, 2
 
 
-def groth16_verify_key(zkey, r1cs, ptau, lagrange="compute", records=True, check_ptau=False, seed=None):
+def groth16_verify_key(zkey, r1cs, ptau, lagrange="compute", records=True, check_ptau=False, seed=None, check_lagrange=False):
     """Checks on the GPU that `zkey` is the honest key of the R1cs and the powers-of-tau file (bytes or any buffer, an mmap
     included), with a delta that only its recorded contributions touched (what `snarkjs zkey verify` answers; synchronous),
     and returns the contribution hashes, oldest first.  The key is remade from circuit and file with delta = 1; section 4 is
@@ -1364,14 +1453,19 @@ def groth16_verify_key(zkey, r1cs, ptau, lagrange="compute", records=True, check
     (H) against the remade key's and delta2 through random linear combinations (a wrong point passes with probability about
     2^-128 over the seed).  Raises WitnessCalcError with the first rule that fails, for example "zkey verify: section 8 (C) is
     not the remade key's section divided by delta".  lagrange: "compute" (default) keeps the verdict off the file's prepared
-    sections 12 to 15, which nothing verifies; "auto" and "file" read them.  records=False passes over section 10 (for keys
-    that carry snarkjs's records, which this library cannot verify): the points are still checked against circuit, file and
-    the key's own delta.  check_ptau=True first runs ptau_check_powers for the circuit's domain.  Not verified: the
-    ceremony's own records in the file, and its points beyond the prefixes a setup reads."""
+    sections 12 to 15; "auto" and "file" read them, verified only under check_lagrange.  records=False passes over section 10
+    (for keys that carry snarkjs's records, which this library cannot verify): the points are still checked against circuit,
+    file and the key's own delta.  check_ptau=True first runs ptau_check_powers for the circuit's domain.  check_lagrange=True, with
+    lagrange "auto" or "file", first runs ptau_check_lagrange for the circuit's domain (under "auto" only when the file has
+    prepared sections), and its failure is the verdict: the prepared sections that the remake reads are then verified against
+    the monomial ones, for much less than "compute" spends on making them again; with "compute" the flag has nothing to
+    check.  Not verified: the ceremony's own records in the file, and its points beyond the prefixes a setup reads."""
     mode = _lagrange_mode(lagrange)
     seed = _seed32(seed)
     data = bytes(zkey)
     room = len(zkey_contributions(data)["contributions"])
+    if check_lagrange and lagrange != "compute" and (lagrange == "file" or ptau_info(ptau)["prepared"]):
+        ptau_check_lagrange(ptau, r1cs.qap_info()["domain_power"], seed)
     hashes = ctypes.create_string_buffer(max(1, room * CONTRIBUTION_HASH_BYTES))
     n = ctypes.c_size_t(room)
     flags = (0 if records else VERIFY_KEY_SKIP_RECORDS) | (VERIFY_KEY_CHECK_PTAU if check_ptau else 0)

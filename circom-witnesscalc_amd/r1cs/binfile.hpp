@@ -6,12 +6,19 @@
 #include <string.h>
 
 #include <string>
+#include <vector>
 
 namespace cwc_r1cs {
 
 struct BinSection {
     const uint8_t* p = nullptr;  // into the caller's bytes; nullptr: the file has no such section
     uint64_t size = 0;
+};
+
+struct BinEntry {  // one section as the file has it, known id or not
+    uint32_t id;
+    const uint8_t* p;
+    uint64_t size;
 };
 
 inline uint32_t rd32(const uint8_t* p) {
@@ -22,8 +29,10 @@ inline uint32_t rd32(const uint8_t* p) {
 
 // Walks the table of the file d[0 .. len) whose magic is `kind` ("zkey"), which also starts every message ("zkey: ...").  The
 // sections whose id has its bit set in `accepted` (ids below 32) go to out[id], and none of them may occur twice; the others
-// are passed over.  Every section must lie inside the file and the last one must end it.
-inline bool binfile_sections(const uint8_t* d, size_t len, const char* kind, uint32_t accepted, BinSection* out, std::string& err) {
+// are passed over.  Every section must lie inside the file and the last one must end it.  order != nullptr gets every section
+// in file order, the ones passed over included.
+inline bool binfile_sections(const uint8_t* d, size_t len, const char* kind, uint32_t accepted, BinSection* out, std::string& err,
+                             std::vector<BinEntry>* order = nullptr) {
     const std::string pre = std::string(kind) + ": ";
     if (len < 12 || memcmp(d, kind, 4) != 0) {
         err = pre + "bad magic (not a ." + kind + " file)";
@@ -56,6 +65,7 @@ inline bool binfile_sections(const uint8_t* d, size_t len, const char* kind, uin
             }
             out[id] = BinSection{d + off, size};
         }
+        if (order) order->push_back(BinEntry{id, d + off, size});
         off += size;
     }
     if (off != len) {

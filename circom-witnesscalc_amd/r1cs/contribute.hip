@@ -1,6 +1,6 @@
 // Groth16 phase-2 contributions on gfx950 (include/graph_witness_groth16_contribute.h has the definitions): the contribution
 // itself, the check of a key's records, the check of one step between two keys, the check of a key against its circuit and its
-// powers-of-tau file, and the powers check of such a file (include/graph_witness_groth16_ptau.h).  Section 10, BLAKE2b, the
+// powers-of-tau file, and the powers check and the Lagrange check of such a file (include/graph_witness_groth16_ptau.h).  Section 10, BLAKE2b, the
 // transcript and the challenge point are contributions.cc's (contribute_internal.hpp); the pairing is verify.hip's and the
 // conversion to affine bytes setup.hip's, both through their enqueue functions.
 //
@@ -27,9 +27,22 @@
 // 64: an Xyzz<G2> is 256 bytes (256 of them would be 64 KB of LDS), and the G2 double-and-add keeps the multiplicand, the
 // accumulator and an addition's temporaries, which needs the unified register file of a wave that has its SIMD to itself.
 //
+// Lagrange check (gwb_ptau_check_lagrange; the header has the equation).  Per section and set of levels, the left side is
+// lincomb_kernel over the Lagrange points with the 128-bit rho of their slots, as above.  The right side multiplies the
+// monomial points by c, the same transform applied to rho, which has the full width of r: lincomb_kernel takes the scalar's
+// words as a template parameter, 4 or 8 (xyzz_mul_short starts from the top nonzero word either way; the four-word
+// instantiations are the kernels of the checks above, unchanged).  c is made on the device in the section's all-level layout:
+// rho_levels_kernel (widened to eight words, bit-reversed per level; the values stay canonical and only the twiddles and
+// 1 / 2^m are in Montgomery form, so nothing is converted), fr_levels_stage_kernel once per stage for all levels (the thread
+// layout of setup_ptau.hip's idft_levels_stage_kernel), fold_levels_kernel (the factor 1 / 2^m and the sum over the
+// levels, canonical).  qap.hip's passes were not used: they transform rows of one length on a handle's tables.  The two sums
+// are converted to affine bytes and compared on the host.  rho is uploaded once per call and neither it nor c comes back.
+//
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage for gfx950; every kernel: 0 bytes of scratch; VGPRs + AGPRs, waves / SIMD):
-//   scale_points_kernel 156, 3      lincomb_kernel<G1> 164, 3 (32 KB LDS)      lincomb_sum_kernel<G1> 119, 4 (32 KB LDS)      put_scalar_kernel 10, 8
-//   lincomb_kernel<G2> 256 + 79, 1 (16 KB LDS)      lincomb_sum_kernel<G2> 256 + 12, 1 (16 KB LDS)
+//   scale_points_kernel 156, 3      lincomb_kernel<G1, 4> 164, 3 (32 KB LDS)      lincomb_sum_kernel<G1> 119, 4 (32 KB LDS)      put_scalar_kernel 10, 8
+//   lincomb_kernel<G2, 4> 256 + 79, 1 (16 KB LDS)      lincomb_sum_kernel<G2> 256 + 12, 1 (16 KB LDS)
+//   lincomb_kernel<G1, 8> 166, 3 (32 KB LDS)           lincomb_kernel<G2, 8> 256 + 80, 1 (16 KB LDS)
+//   rho_levels_kernel 11, 8      fr_powers_kernel 35, 8      fr_levels_stage_kernel 42, 8      fold_levels_kernel 57, 8
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -64,7 +77,6 @@ using cwc_setup::enqueue_affine_g1;
 namespace {
 
 constexpr uint32_t THREADS = 256;
-constexpr uint64_t DEFAULT_CHUNK = 1ull << 18;
 constexpr size_t RHO_BYTES = 16;
 
 // out[i] = k in[i] for the stored points in[0 .. n) (Montgomery, or canonical), XYZZ
@@ -102,10 +114,12 @@ __device__ __forceinline__ void block_sum(Xyzz<T>* sh) {
     }
 }
 
-// part[blockIdx.y gridDim.x + blockIdx.x] = sum over the workgroup's i of rho[i] P_i, P = in0 or (blockIdx.y = 1) in1
-template <class T>
+// part[blockIdx.y gridDim.x + blockIdx.x] = sum over the workgroup's i of rho[i] P_i, P = in0 or (blockIdx.y = 1) in1; rho[i] has
+// WORDS words: 4 (the 128-bit rho of the step, key and powers checks) or 8 (canonical scalars below r: the Lagrange check's c)
+template <class T, uint32_t WORDS>
 __global__ __launch_bounds__(LC_THREADS<T>) void lincomb_kernel(const uint8_t* __restrict__ in0, const uint8_t* __restrict__ in1, uint32_t n,
                                                                 uint32_t canonical, const uint32_t* __restrict__ rho, Xyzz<T>* __restrict__ part) {
+    static_assert(WORDS == 4 || WORDS == 8, "a scalar of 4 or 8 words");
     __shared__ Xyzz<T> sh[LC_THREADS<T>];
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     Xyzz<T> acc = xyzz_inf<T>();
@@ -113,8 +127,11 @@ __global__ __launch_bounds__(LC_THREADS<T>) void lincomb_kernel(const uint8_t* _
         const uint8_t* in = blockIdx.y ? in1 : in0;
         Affine<T> a;
         get_coords<T>(in + (size_t)i * POINT_BYTES<T>, canonical != 0, a.x, a.y);
-        const uint32_t* r = rho + 4 * (size_t)i;
-        acc = xyzz_mul_short(from_affine(a), Fr{{r[0], r[1], r[2], r[3], 0, 0, 0, 0}});
+        const uint32_t* r = rho + WORDS * (size_t)i;
+        if constexpr (WORDS == 4)
+            acc = xyzz_mul_short(from_affine(a), Fr{{r[0], r[1], r[2], r[3], 0, 0, 0, 0}});
+        else
+            acc = xyzz_mul_short(from_affine(a), Fr{{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]}});
     }
     sh[threadIdx.x] = acc;
     block_sum<T>(sh);
@@ -132,6 +149,56 @@ __global__ __launch_bounds__(LC_THREADS<T>) void lincomb_sum_kernel(const Xyzz<T
     if (threadIdx.x == 0) acc[blockIdx.x] = xyzz_add(acc[blockIdx.x], sh[0]);
 }
 
+// The Lagrange check's scalars (the header's "Lagrange check"): the transform of setup_ptau.hip's idft_levels_stage_kernel on
+// field elements in the same all-level layout, level m in the slots [2^m - 1, 2^(m+1) - 1).  N log N field products next to
+// the N point multiplications they feed: plain radix 2 in global memory.
+
+// x[slot of level m, position bitrev_m(k)] = rho_i, for the slots i = 2^m - 1 + k in [lo, hi).  The values stay canonical through
+// the transform: the product of a canonical value with a twiddle in Montgomery form is their canonical product.
+__global__ __launch_bounds__(THREADS) void rho_levels_kernel(const uint32_t* __restrict__ rho, uint32_t lo, uint32_t hi, Fr* __restrict__ x) {
+    const uint32_t i = lo + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= hi) return;
+    const uint32_t m = 31u - (uint32_t)__builtin_clz(i + 1u), first = (1u << m) - 1u, k = i - first;
+    const uint32_t* r = rho + 4 * (size_t)i;
+    x[first + (m ? __brev(k) >> (32 - m) : 0u)] = Fr{{r[0], r[1], r[2], r[3], 0, 0, 0, 0}};
+}
+
+// out[k] = base^k in Montgomery form for k < count (bp.v[b] = base^(2^b))
+__global__ __launch_bounds__(THREADS) void fr_powers_kernel(Fr* __restrict__ out, uint32_t count, Pows bp) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    Fr x = cwc::fr_one();
+    for (uint32_t b = 0; b <= MAX_DOMAIN_POWER; ++b)
+        if ((k >> b) & 1u) x = cwc::fr_mul(x, bp.v[b]);
+    out[k] = x;
+}
+
+// stage s of the levels m in [max(m_lo, s + 1), top]; tw[k << tw_shift] = w_(2^(s+1))^(-k), Montgomery form; 2^top threads
+__global__ __launch_bounds__(THREADS) void fr_levels_stage_kernel(Fr* __restrict__ x, uint32_t top, uint32_t s, uint32_t m_lo, uint32_t tw_shift,
+                                                                  const Fr* __restrict__ tw) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    cwc_ptau::LevelButterfly b;
+    if ((v >> top) != 0 || !cwc_ptau::level_butterfly(v, top, s, b) || b.m < m_lo) return;
+    Fr* lo = x + (((size_t)1 << b.m) - 1) + ((size_t)b.grp << (s + 1)) + b.k;
+    const Fr a = lo[0], c = cwc::fr_mul(lo[(size_t)1 << s], tw[(size_t)b.k << tw_shift]);
+    lo[0] = cwc::fr_add(a, c);
+    lo[(size_t)1 << s] = cwc::fr_sub(a, c);
+}
+
+struct InvPowersOfTwo {
+    Fr v[cwc_ptau::MAX_POWER + 2];  // 1 / 2^m, Montgomery form
+};
+
+// c[i] = sum over the levels m in [m_lo, m_hi] with 2^m > i of x[2^m - 1 + i] / 2^m, canonical, for i < 2^m_hi
+__global__ __launch_bounds__(THREADS) void fold_levels_kernel(const Fr* __restrict__ x, uint32_t m_lo, uint32_t m_hi, InvPowersOfTwo inv, Fr* __restrict__ c) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if ((i >> m_hi) != 0) return;
+    Fr acc = cwc::fr_zero();
+    for (uint32_t m = m_lo; m <= m_hi; ++m)
+        if ((i >> m) == 0) acc = cwc::fr_add(acc, cwc::fr_mul(x[(((size_t)1 << m) - 1) + i], inv.v[m]));
+    c[i] = acc;
+}
+
 // ---- host -----------------------------------------------------------------------------------------------------------------
 
 int fail2(gw_status_t* status, const std::string& msg) {  // a failure that is not a verdict about the key
@@ -139,12 +206,7 @@ int fail2(gw_status_t* status, const std::string& msg) {  // a failure that is n
     return 2;
 }
 
-uint64_t chunk_points() {
-    const char* v = getenv("CWC_CONTRIBUTE_CHUNK");
-    if (!v || !*v) return DEFAULT_CHUNK;
-    const unsigned long long c = strtoull(v, nullptr, 10);
-    return c >= 1 && c <= (1ull << 24) ? c : DEFAULT_CHUNK;
-}
+uint64_t chunk_points() { return piece_points("CWC_CONTRIBUTE_CHUNK"); }
 
 struct ZkeyFree {
     void operator()(gwb_zkey_t* z) const { gwb_zkey_free(z); }
@@ -477,12 +539,12 @@ void fill_rho(const uint8_t seed[32], uint64_t first, uint64_t count, uint8_t* o
 }
 
 // d_acc[0] += sum rho_i P_i, d_acc[1] += sum rho_i P'_i over the m points of one piece (device addresses), the per-group sums in
-// d_part (lists blocks_for(m, LC_THREADS<T>) points)
-template <class T>
+// d_part (lists blocks_for(m, LC_THREADS<T>) points); rho_i of WORDS words
+template <class T, uint32_t WORDS = 4>
 void enqueue_lincomb(const uint8_t* d_p0, const uint8_t* d_p1, uint32_t lists, uint32_t m, bool canonical, const uint8_t* d_rho, Xyzz<T>* d_part,
                      Xyzz<T>* d_acc, hipStream_t s) {
     const uint32_t blocks = blocks_for(m, LC_THREADS<T>);
-    hipLaunchKernelGGL(lincomb_kernel<T>, dim3(blocks, lists), dim3(LC_THREADS<T>), 0, s, d_p0, d_p1, m, canonical ? 1u : 0u, (const uint32_t*)d_rho, d_part);
+    hipLaunchKernelGGL((lincomb_kernel<T, WORDS>), dim3(blocks, lists), dim3(LC_THREADS<T>), 0, s, d_p0, d_p1, m, canonical ? 1u : 0u, (const uint32_t*)d_rho, d_part);
     hipLaunchKernelGGL(lincomb_sum_kernel<T>, dim3(lists), dim3(LC_THREADS<T>), 0, s, (const Xyzz<T>*)d_part, blocks, d_acc);
 }
 
@@ -756,6 +818,161 @@ Outcome check_powers(const uint8_t* data, size_t len, uint32_t domain_power, con
     return {verdict.empty() ? 0 : 1, verdict};
 }
 
+// ---- the Lagrange check of a prepared `.ptau` ------------------------------------------------------------------------------------
+
+// The device side of one Lagrange check: a stream and one workspace sized for the largest level asked for.  rho_i belongs to
+// the slot i of a section's all-level layout and is the same in the four sections (every section has an equation of its own).
+struct LagrangeDevice {
+    Stream s;
+    DeviceBuf work;
+    uint64_t chunk = 0;
+    uint32_t top = 0;
+    InvPowersOfTwo inv;
+    size_t o_rho = 0, o_x = 0, o_c = 0, o_tw = 0, o_pts = 0, o_part = 0, o_acc = 0, o_out = 0;
+
+    bool open(uint32_t top_level, const uint8_t seed[32], std::string& err) {
+        top = top_level;
+        const uint64_t slots = (2ull << top) - 1;
+        chunk = std::min(chunk_points(), slots);
+        Carve cw;
+        o_rho = cw.take(slots * RHO_BYTES);
+        o_x = cw.take(slots * 32);
+        o_c = cw.take((1ull << top) * 32);
+        o_tw = cw.take((1ull << (top - 1)) * 32);
+        o_pts = cw.take(chunk * G2_BYTES);
+        o_part = cw.take((size_t)blocks_for(chunk, LC_THREADS<G2>) * sizeof(Xyzz<G2>));  // more than G1's blocks of 256 need
+        o_acc = cw.take(2 * sizeof(Xyzz<G2>));
+        o_out = cw.take(2 * G2_BYTES);
+        hipError_t e = s.create();
+        if (e == hipSuccess) e = work.alloc(cw.o);
+        if (e != hipSuccess) {
+            err = hip_err("allocating the Lagrange check's workspace", e);
+            return false;
+        }
+        uint8_t* W = work.as<uint8_t>();
+        std::vector<uint8_t> rho(slots * RHO_BYTES);
+        fill_rho(seed, 0, slots, rho.data());
+        Fr wn, g, rm1 = cwc::fr_p();
+        qap_roots(top - 1, wn, g);  // g = w_(2^top)
+        rm1.v[0] -= 1;
+        for (uint32_t m = 0; m <= cwc_ptau::MAX_POWER + 1; ++m) {
+            Fr k{{1, 0, 0, 0, 0, 0, 0, 0}};
+            if (m >= 1 && m <= 28) cwc::u256_sub(k, cwc::fr_p(), cwc::u256_shr(rm1, m));  // 1 / 2^m = r - (r - 1) / 2^m
+            inv.v[m] = cwc::fr_to_mont(k);
+        }
+        e = hipMemcpyAsync(W + o_rho, rho.data(), rho.size(), hipMemcpyHostToDevice, s);
+        hipLaunchKernelGGL(fr_powers_kernel, dim3(blocks_for(1ull << (top - 1), THREADS)), dim3(THREADS), 0, s, (Fr*)(W + o_tw), 1u << (top - 1),
+                           powers_of(cwc::fr_inv_fermat(g)));
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);  // the copy has left the host array
+        if (e != hipSuccess) err = hip_err("uploading the Lagrange check's scalars", e);
+        return e == hipSuccess;
+    }
+
+    // acc += sum scalar_i P_i over the n stored points at host address p, in pieces; the scalars are on the device
+    template <class T, uint32_t WORDS>
+    hipError_t sum(const uint8_t* p, uint64_t n, const uint8_t* d_scalars, Xyzz<T>* acc) {
+        uint8_t* W = work.as<uint8_t>();
+        hipError_t e = hipSuccess;
+        for (uint64_t at = 0; at < n && e == hipSuccess; at += chunk) {
+            const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - at);
+            e = hipMemcpyAsync(W + o_pts, p + at * POINT_BYTES<T>, (size_t)m * POINT_BYTES<T>, hipMemcpyHostToDevice, s);
+            if (e != hipSuccess) break;
+            enqueue_lincomb<T, WORDS>(W + o_pts, W + o_pts, 1, m, false, d_scalars + at * (4 * WORDS), (Xyzz<T>*)(W + o_part), acc, s);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipStreamSynchronize(s);  // the piece's buffer is written again by the next upload
+        }
+        return e;
+    }
+
+    // sum_{m in [m_lo, m_hi]} sum_k rho_{m,k} Lag_m[k] over section id against sum_i c_i T_i over section id - 10; `equal`: the verdict
+    template <class T>
+    bool levels(const cwc_ptau::View& v, uint32_t id, uint32_t m_lo, uint32_t m_hi, bool& equal, std::string& err) {
+        uint8_t* W = work.as<uint8_t>();
+        const uint32_t lo = (1u << m_lo) - 1u, hi = (2u << m_hi) - 1u;
+        const uint64_t n_right = (1ull << m_hi) - (id == 12 && m_hi == v.power + 1 ? 1 : 0);  // c_{2n-1} multiplies O: dropped
+        Xyzz<T>* acc = (Xyzz<T>*)(W + o_acc);
+        Fr *x = (Fr*)(W + o_x), *c = (Fr*)(W + o_c);
+        hipError_t e = hipMemsetAsync(acc, 0, 2 * sizeof(Xyzz<T>), s);
+        if (e == hipSuccess) e = sum<T, 4>(v.sec[id].p + (size_t)lo * POINT_BYTES<T>, hi - lo, W + o_rho + (size_t)lo * RHO_BYTES, acc);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(rho_levels_kernel, dim3(blocks_for(hi - lo, THREADS)), dim3(THREADS), 0, s, (const uint32_t*)(W + o_rho), lo, hi, x);
+            for (uint32_t st = 0; st < m_hi; ++st)
+                hipLaunchKernelGGL(fr_levels_stage_kernel, dim3(blocks_for(1ull << m_hi, THREADS)), dim3(THREADS), 0, s, x, m_hi, st, m_lo, top - 1 - st,
+                                   (const Fr*)(W + o_tw));
+            hipLaunchKernelGGL(fold_levels_kernel, dim3(blocks_for(1ull << m_hi, THREADS)), dim3(THREADS), 0, s, (const Fr*)x, m_lo, m_hi, inv, c);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = sum<T, 8>(v.sec[id - 10].p, n_right, (const uint8_t*)c, acc + 1);
+        uint8_t out[2 * G2_BYTES];
+        if (e == hipSuccess) {
+            enqueue_affine<T>(acc, 2, W + o_out, false, s);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(out, W + o_out, 2 * POINT_BYTES<T>, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            err = hip_err("running the linear combinations of the Lagrange check", e);
+            return false;
+        }
+        equal = memcmp(out, out + POINT_BYTES<T>, POINT_BYTES<T>) == 0;
+        return true;
+    }
+    bool levels(const cwc_ptau::View& v, uint32_t id, uint32_t m_lo, uint32_t m_hi, bool& equal, std::string& err) {
+        return id == 13 ? levels<G2>(v, id, m_lo, m_hi, equal, err) : levels<G1>(v, id, m_lo, m_hi, equal, err);
+    }
+};
+
+// gwb_ptau_check_lagrange: rc 0, 1 (msg: the verdict) or 2
+Outcome check_lagrange(const uint8_t* data, size_t len, uint32_t domain_power, const uint8_t* seed_in) {
+    std::string err;
+    cwc_ptau::View view;
+    if (!cwc_ptau::parse(data, len, view, err)) return {2, err};
+    const bool all = domain_power == GWB_PTAU_ALL_LEVELS;
+    struct Job {
+        uint32_t id, m_lo, m_hi;
+    };
+    std::vector<Job> jobs;
+    if (all) {
+        if (!cwc_ptau::need_prepared(view, err)) return {2, err};
+        for (uint32_t id = 12; id <= 15; ++id) jobs.push_back({id, 0, cwc_ptau::top_level(view, id)});
+    } else {
+        cwc_ptau::Plan pl;
+        if (!cwc_ptau::plan(view, domain_power, GWB_PTAU_LAGRANGE_FILE, pl, err) || !cwc_ptau::check_header_points(pl, err)) return {2, err};
+        const uint32_t p = domain_power;
+        jobs = {{12, p, p}, {12, p + 1, p + 1}, {13, p, p}, {14, p, p}, {15, p, p}};
+    }
+    const uint32_t top = all ? view.power + 1 : domain_power + 1;
+    if (top > MAX_DOMAIN_POWER + 1)
+        return {2, "ptau: the Lagrange check of level " + std::to_string(top) + " needs a root of unity of order 2^" + std::to_string(top) + ", which r does not have"};
+    for (const Job& j : jobs)
+        if (!cwc_ptau::check_lagrange_points(view, j.id, j.m_lo, j.m_hi, err)) return {2, err};
+    for (const Job& j : jobs) {  // the equality below sees a small-order component with probability 1 / order only
+        if (j.id != 13) continue;
+        const uint64_t lo = (1ull << j.m_lo) - 1, hi = (2ull << j.m_hi) - 1;
+        const int rc = cwc_ptau::check_g2_points(13, lo, view.sec[13].p + lo * G2_BYTES, hi - lo, err);
+        if (rc != 0) return {rc, err};
+    }
+    uint8_t seed[32];
+    if (!take_seed(seed_in, seed)) return {2, "ptau: getrandom failed"};  // drawn after the file is seen
+    LagrangeDevice D;
+    if (!D.open(top, seed, err)) return {2, err};
+    for (const Job& j : jobs) {
+        bool equal = false;
+        if (!D.levels(view, j.id, j.m_lo, j.m_hi, equal, err)) return {2, err};
+        if (equal) continue;
+        const std::string who = "ptau: section " + std::to_string(j.id) + " (" + cwc_ptau::section_name(j.id) + ")";
+        const std::string what = " not hold the Lagrange forms of section " + std::to_string(j.id - 10);
+        if (j.m_lo == j.m_hi) return {1, who + " level " + std::to_string(j.m_lo) + " does" + what};
+        for (uint32_t m = j.m_lo; m <= j.m_hi; ++m) {  // which level: one by one, after the verdict is known
+            if (!D.levels(view, j.id, m, m, equal, err)) return {2, err};
+            if (!equal) return {1, who + " does" + what + ": level " + std::to_string(m) + " is the first that does not"};
+        }
+        return {1, who + " does" + what};
+    }
+    return {0, ""};
+}
+
 // a verdict of the functions that the contribution check shares with the key check, under the key check's name
 std::string as_key_verdict(const std::string& msg) { return msg.compare(0, 6, "zkey: ") == 0 ? "zkey verify: " + msg.substr(6) : msg; }
 
@@ -866,8 +1083,10 @@ int finish(const Outcome& o, gw_status_t* status) {
 }
 
 // the aid of the linear-combination kernels for one group (the extern functions below)
-template <class T>
-int lincomb_aid(const char* fn, const void* d_points, const void* d_rho, size_t n, void* d_out, void* hip_stream, gw_status_t* status) {
+template <class T, uint32_t WORDS>
+int lincomb_aid(const char* fn, const void* d_points, const void* d_rho, size_t n, uint32_t form, void* d_out, void* hip_stream, gw_status_t* status) {
+    if (form != GWB_FORM_CANONICAL && form != GWB_FORM_MONTGOMERY) return fail(status, std::string(fn) + ": unknown form " + std::to_string(form));
+    const bool canonical = form == GWB_FORM_CANONICAL;
     if (!d_out || (n && (!d_points || !d_rho))) return fail(status, std::string(fn) + ": NULL argument");
     if (n > 0x7fffffffull) return fail(status, std::string(fn) + ": n above 2^31 - 1");
     hipStream_t s = (hipStream_t)hip_stream;
@@ -879,10 +1098,10 @@ int lincomb_aid(const char* fn, const void* d_points, const void* d_rho, size_t 
     uint8_t* W = (uint8_t*)ws;
     e = hipMemsetAsync(W + o_acc, 0, sizeof(Xyzz<T>), s);
     if (e == hipSuccess && n)
-        enqueue_lincomb<T>((const uint8_t*)d_points, (const uint8_t*)d_points, 1, (uint32_t)n, true, (const uint8_t*)d_rho, (Xyzz<T>*)(W + o_part),
+        enqueue_lincomb<T, WORDS>((const uint8_t*)d_points, (const uint8_t*)d_points, 1, (uint32_t)n, canonical, (const uint8_t*)d_rho, (Xyzz<T>*)(W + o_part),
                            (Xyzz<T>*)(W + o_acc), s);
     if (e == hipSuccess) {
-        enqueue_affine<T>(W + o_acc, 1, (uint8_t*)d_out, true, s);
+        enqueue_affine<T>(W + o_acc, 1, (uint8_t*)d_out, canonical, s);
         e = hipGetLastError();
     }
     const hipError_t ef = hipFreeAsync(ws, s);
@@ -979,11 +1198,28 @@ int gwb_bn254_g1_scale_batch_device(const void* d_points, size_t n, const uint8_
 }
 
 int gwb_bn254_g1_lincomb128_device(const void* d_points, const void* d_rho, size_t n, void* d_out, void* hip_stream, gw_status_t* status) {
-    return lincomb_aid<G1>("gwb_bn254_g1_lincomb128_device", d_points, d_rho, n, d_out, hip_stream, status);
+    return lincomb_aid<G1, 4>("gwb_bn254_g1_lincomb128_device", d_points, d_rho, n, GWB_FORM_CANONICAL, d_out, hip_stream, status);
 }
 
 int gwb_bn254_g2_lincomb128_device(const void* d_points, const void* d_rho, size_t n, void* d_out, void* hip_stream, gw_status_t* status) {
-    return lincomb_aid<G2>("gwb_bn254_g2_lincomb128_device", d_points, d_rho, n, d_out, hip_stream, status);
+    return lincomb_aid<G2, 4>("gwb_bn254_g2_lincomb128_device", d_points, d_rho, n, GWB_FORM_CANONICAL, d_out, hip_stream, status);
+}
+
+int gwb_bn254_g1_lincomb_device(const void* d_points, const void* d_scalars, size_t n, uint32_t form, void* d_out, void* hip_stream, gw_status_t* status) {
+    return lincomb_aid<G1, 8>("gwb_bn254_g1_lincomb_device", d_points, d_scalars, n, form, d_out, hip_stream, status);
+}
+
+int gwb_bn254_g2_lincomb_device(const void* d_points, const void* d_scalars, size_t n, uint32_t form, void* d_out, void* hip_stream, gw_status_t* status) {
+    return lincomb_aid<G2, 8>("gwb_bn254_g2_lincomb_device", d_points, d_scalars, n, form, d_out, hip_stream, status);
+}
+
+int gwb_ptau_check_lagrange(const void* data, size_t len, uint32_t domain_power, const uint8_t* seed, gw_status_t* status) {
+    if (!data && len) return fail2(status, "gwb_ptau_check_lagrange: NULL argument");
+    try {
+        return finish(check_lagrange((const uint8_t*)data, len, domain_power, seed), status);
+    } catch (const std::bad_alloc&) {
+        return fail2(status, "ptau: out of host memory");
+    }
 }
 
 }  // extern "C"

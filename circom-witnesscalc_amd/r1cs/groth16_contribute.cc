@@ -3,11 +3,12 @@
 // in [1, r), for reproducible keys).  Prints the contribution hash in hex.
 // groth16-contribute --verify <key.zkey>: checks the key's contribution records and prints their hashes.
 // groth16-contribute --verify-step <prev.zkey> <next.zkey>: checks that next is prev after exactly one contribution.
-// groth16-contribute --verify-key [--lagrange auto|file|compute] [--skip-records] [--check-ptau] <circuit.r1cs> <pot.ptau> <key.zkey>:
+// groth16-contribute --verify-key [--lagrange auto|file|compute] [--skip-records] [--check-ptau] [--check-lagrange] <circuit.r1cs> <pot.ptau> <key.zkey>:
 // checks the key against its circuit and its powers-of-tau file (snarkjs `zkey verify`, with its argument order) and prints the
 // hashes of its records.  The file is mapped into memory, not read; --lagrange defaults to compute, which keeps the verdict
 // off the file's prepared sections; --skip-records passes over section 10 (a key with snarkjs's records); --check-ptau first
-// checks that the points read from the file are powers of one tau.
+// checks that the points read from the file are powers of one tau; --check-lagrange (with --lagrange auto or file) first checks
+// the prepared sections that the remake reads against the monomial ones (gwb_ptau_check_lagrange), and its failure is the verdict.
 // The records are this library's own: they are not interchangeable with snarkjs's (see the header).  Exit status 0 on success;
 // 1 for a failed verification, with its message; 2 on a usage, file or format error.  Every input is parsed before the device
 // is touched.
@@ -117,7 +118,7 @@ static int usage() {
             "usage: groth16-contribute [--name NAME] [--delta FILE] <in.zkey> <out.zkey>\n"
             "       groth16-contribute --verify <key.zkey>\n"
             "       groth16-contribute --verify-step <prev.zkey> <next.zkey>\n"
-            "       groth16-contribute --verify-key [--lagrange auto|file|compute] [--skip-records] [--check-ptau] <circuit.r1cs> <pot.ptau> <key.zkey>\n");
+            "       groth16-contribute --verify-key [--lagrange auto|file|compute] [--skip-records] [--check-ptau] [--check-lagrange] <circuit.r1cs> <pot.ptau> <key.zkey>\n");
     return 2;
 }
 
@@ -139,7 +140,8 @@ static int report(int rc, gw_status_t& st) {
     return rc == 1 ? 1 : 2;
 }
 
-static int run_verify_key(const char* r1cs_path, const char* ptau_path, const char* key_path, const char* lagrange, bool skip_records, bool check_ptau) {
+static int run_verify_key(const char* r1cs_path, const char* ptau_path, const char* key_path, const char* lagrange, bool skip_records, bool check_ptau,
+                          bool check_lagrange) {
     uint32_t mode = GWB_PTAU_LAGRANGE_COMPUTE;
     if (lagrange) {
         if (strcmp(lagrange, "auto") == 0)
@@ -168,6 +170,16 @@ static int run_verify_key(const char* r1cs_path, const char* ptau_path, const ch
         gwb_r1cs_free(r);
         return report(2, st);
     }
+    if (check_lagrange && mode != GWB_PTAU_LAGRANGE_COMPUTE) {  // under auto, only a file that has the sections
+        gwb_ptau_info_t pi;
+        gwb_r1cs_qap_info_t qi;
+        int rc = gwb_ptau_info(ptau.data, ptau.len, &pi, &st) != 0 || gwb_r1cs_qap_info(r, &qi, &st) != 0 ? 2 : 0;
+        if (rc == 0 && (mode == GWB_PTAU_LAGRANGE_FILE || pi.prepared)) rc = gwb_ptau_check_lagrange(ptau.data, ptau.len, qi.domain_power, NULL, &st);
+        if (rc != 0) {
+            gwb_r1cs_free(r);
+            return report(rc, st);
+        }
+    }
     std::vector<uint8_t> hashes(n * GWB_CONTRIBUTION_HASH_BYTES + 1);
     const uint32_t flags = (skip_records ? GWB_VERIFY_KEY_SKIP_RECORDS : 0u) | (check_ptau ? GWB_VERIFY_KEY_CHECK_PTAU : 0u);
     const int rc = gwb_zkey_verify_key(key.data(), key.size(), r, ptau.data, ptau.len, mode, flags, NULL, hashes.data(), &n, &st);
@@ -180,7 +192,7 @@ static int run_verify_key(const char* r1cs_path, const char* ptau_path, const ch
 
 int main(int argc, char** argv) {
     const char *name = "", *delta_path = NULL, *lagrange = NULL;
-    bool verify = false, step = false, verify_key = false, skip_records = false, check_ptau = false;
+    bool verify = false, step = false, verify_key = false, skip_records = false, check_ptau = false, check_lagrange = false;
     std::vector<const char*> paths;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -198,6 +210,8 @@ int main(int argc, char** argv) {
             skip_records = true;
         else if (a == "--check-ptau")
             check_ptau = true;
+        else if (a == "--check-lagrange")
+            check_lagrange = true;
         else if (a == "--lagrange" && i + 1 < argc)
             lagrange = argv[++i];
         else if (a.size() > 1 && a[0] == '-')
@@ -206,9 +220,9 @@ int main(int argc, char** argv) {
             paths.push_back(argv[i]);
     }
     if (verify + step + verify_key > 1 || ((verify || step || verify_key) && (delta_path || *name))) return usage();
-    if (!verify_key && (lagrange || skip_records || check_ptau)) return usage();
+    if (!verify_key && (lagrange || skip_records || check_ptau || check_lagrange)) return usage();
     if (paths.size() != (verify ? 1u : verify_key ? 3u : 2u)) return usage();
-    if (verify_key) return run_verify_key(paths[0], paths[1], paths[2], lagrange, skip_records, check_ptau);
+    if (verify_key) return run_verify_key(paths[0], paths[1], paths[2], lagrange, skip_records, check_ptau, check_lagrange);
     std::vector<char> first, second;
     if (!read_file(paths[0], first)) {
         fprintf(stderr, "error: cannot read %s\n", paths[0]);

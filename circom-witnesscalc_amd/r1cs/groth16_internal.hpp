@@ -45,6 +45,9 @@ bool qap_enqueue(gwb_zkey* z, const void* d_witness, size_t batch, uint32_t form
                  std::string& err);
 // qap.hip: the roots of the domain of 2^p points, Montgomery form: w_n of order n, g of order 2n with g^2 = w_n
 void qap_roots(uint32_t p, cwc::Fr& wn, cwc::Fr& g);
+// msm.hip: CWC_GROTH16_WORKSPACE_MB in bytes (4096 MB without it), read once per process: the prover's cap on a sub-batch's
+// workspace, and the cap on the workspace of gwb_ptau_prepare_phase2 (setup_ptau.hip)
+uint64_t groth16_workspace_cap();
 // msm.hip: a uniform draw from [0, r), by rejection sampling from getrandom()
 bool draw_fr(cwc::Fr& x, std::string& err);
 }  // namespace cwc_r1cs

@@ -7,6 +7,11 @@
 // and beta are the ceremony's, gamma is 1, and delta is drawn and discarded or read from FILE (one decimal integer in [1, r);
 // 1 gives the state of snarkjs `zkey new`).  --check-g2 (with --ptau only) first checks the G2 points the setup reads from
 // the file for membership in the order-r subgroup, on the GPU, and refuses the file before a key is made if one is outside it.
+// groth16-setup --prepare-ptau <in.ptau> <out.ptau>: what snarkjs `powersoftau prepare phase2` does (gwb_ptau_prepare_phase2): the
+// input is mapped, the output is the input with its Lagrange sections 12 to 15 made on the GPU; nothing is printed on success.
+// groth16-setup --check-lagrange [--domain-power P] <file.ptau>: checks sections 12 to 15 against 2 to 5 on the GPU
+// (gwb_ptau_check_lagrange), the levels a setup for the domain 2^P reads or, without P, all of them; prints OK!, or exits with
+// status 1 and the verdict.
 // --ptau and --trapdoor exclude each other.  With a third path the verifying key is written too, in snarkjs's
 // verification_key.json shape with vk_alphabeta_12.  Exit status 0 on success; 2 on a usage, file or format error.  Every
 // input is parsed before the device is touched.
@@ -212,7 +217,69 @@ static bool vk_json(const void* zkey, size_t len, std::string& out, std::string&
     return true;
 }
 
+static int usage_error(const char* argv0) {
+    fprintf(stderr,
+            "usage: %s [--trapdoor FILE] <circuit.r1cs> <circuit.zkey> [verification_key.json]\n"
+            "       %s --ptau FILE [--delta FILE] [--lagrange auto|file|compute] [--check-g2] <circuit.r1cs> <circuit.zkey> [verification_key.json]\n"
+            "       %s --prepare-ptau <in.ptau> <out.ptau>\n"
+            "       %s --check-lagrange [--domain-power P] <file.ptau>\n"
+            "  --check-g2  refuse a file whose G2 points, as far as this setup reads them, are not all in the order-r subgroup\n"
+            "  --prepare-ptau  write the file with its Lagrange sections 12 to 15 (snarkjs powersoftau prepare phase2)\n"
+            "  --check-lagrange  check sections 12 to 15 against 2 to 5: the levels a setup for 2^P reads, or all of them\n",
+            argv0, argv0, argv0, argv0);
+    return 2;
+}
+
+// --prepare-ptau and --check-lagrange: the file is mapped and parsed before the device is touched
+static int ptau_tool(int argc, char** argv) {
+    const bool prepare = strcmp(argv[1], "--prepare-ptau") == 0;
+    uint32_t domain_power = GWB_PTAU_ALL_LEVELS;
+    int at = 2;
+    if (!prepare && argc > at + 1 && strcmp(argv[at], "--domain-power") == 0) {
+        char* end = NULL;
+        const unsigned long v = strtoul(argv[at + 1], &end, 10);
+        if (!*argv[at + 1] || *end || v > 28) return usage_error(argv[0]);
+        domain_power = (uint32_t)v;
+        at += 2;
+    }
+    if (argc - at != (prepare ? 2 : 1)) return usage_error(argv[0]);
+    for (int i = at; i < argc; ++i)
+        if (strncmp(argv[i], "--", 2) == 0) return usage_error(argv[0]);
+    const char* path = argv[at];
+    Mapped in;
+    if (!in.open(path)) {
+        fprintf(stderr, "error: cannot read %s\n", path);
+        return 2;
+    }
+    gw_status_t st = {OK, NULL};  // both calls parse the file before they touch the device
+    if (!prepare) {
+        const int rc = gwb_ptau_check_lagrange(in.data, in.len, domain_power, NULL, &st);
+        if (rc != 0) {
+            fprintf(stderr, "error: %s: %s\n", path, st.error_msg ? st.error_msg : "check failed");
+            gw_free_status(&st);
+            return rc == 1 ? 1 : 2;
+        }
+        printf("OK!\n");
+        return 0;
+    }
+    void* out = NULL;
+    size_t len = 0;
+    if (gwb_ptau_prepare_phase2(in.data, in.len, &out, &len, &st) != 0) {
+        fprintf(stderr, "error: %s: %s\n", path, st.error_msg ? st.error_msg : "prepare failed");
+        gw_free_status(&st);
+        return 2;
+    }
+    int code = 0;
+    if (!write_file(argv[at + 1], out, len)) {
+        fprintf(stderr, "error: cannot write %s\n", argv[at + 1]);
+        code = 2;
+    }
+    gwb_groth16_setup_free(out);
+    return code;
+}
+
 int main(int argc, char** argv) {
+    if (argc > 1 && (strcmp(argv[1], "--prepare-ptau") == 0 || strcmp(argv[1], "--check-lagrange") == 0)) return ptau_tool(argc, argv);
     const char *trapdoor_path = NULL, *ptau_path = NULL, *delta_path = NULL, *lagrange = NULL;
     std::vector<const char*> pos;
     bool usage = false, check_g2 = false;
@@ -245,14 +312,7 @@ int main(int argc, char** argv) {
     }
     // --ptau and --trapdoor exclude each other; --delta, --lagrange and --check-g2 belong to --ptau
     if ((ptau_path && trapdoor_path) || (!ptau_path && (delta_path || lagrange || check_g2))) usage = true;
-    if (usage || (pos.size() != 2 && pos.size() != 3)) {
-        fprintf(stderr,
-                "usage: %s [--trapdoor FILE] <circuit.r1cs> <circuit.zkey> [verification_key.json]\n"
-                "       %s --ptau FILE [--delta FILE] [--lagrange auto|file|compute] [--check-g2] <circuit.r1cs> <circuit.zkey> [verification_key.json]\n"
-                "  --check-g2  refuse a file whose G2 points, as far as this setup reads them, are not all in the order-r subgroup\n",
-                argv[0], argv[0]);
-        return 2;
-    }
+    if (usage || (pos.size() != 2 && pos.size() != 3)) return usage_error(argv[0]);
     std::vector<char> file;
     if (!read_file(pos[0], file)) {
         fprintf(stderr, "error: cannot read %s\n", pos[0]);

@@ -3,6 +3,7 @@
 // the device side of a key setup with its phase timer.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -26,6 +27,15 @@ struct Carve {
         return at;
     }
 };
+
+// points per piece of a call that sends a long list through the device in pieces: the knob's value when it lies in
+// [1, 2^24], else 2^18; read at each call
+inline uint64_t piece_points(const char* knob) {
+    const char* v = getenv(knob);
+    if (!v || !*v) return 1ull << 18;
+    const unsigned long long c = strtoull(v, nullptr, 10);
+    return c >= 1 && c <= (1ull << 24) ? c : 1ull << 18;
+}
 
 constexpr uint32_t MAX_DOMAIN_POWER = 27;  // 2-adicity of r is 28; the coset needs a 2n-th root
 

@@ -276,14 +276,7 @@ __global__ __launch_bounds__(THREADS) void finish_kernel(const P1* __restrict__ 
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
 
-uint64_t ws_cap() {  // CWC_GROTH16_WORKSPACE_MB, read once per process
-    static const uint64_t cap = [] {
-        const char* s = getenv("CWC_GROTH16_WORKSPACE_MB");
-        const unsigned long long mb = s && *s ? strtoull(s, nullptr, 10) : 0ull;
-        return (mb ? (uint64_t)mb : 4096ull) << 20;
-    }();
-    return cap;
-}
+uint64_t ws_cap() { return groth16_workspace_cap(); }
 
 uint32_t bits_for(uint64_t x) {  // smallest b with 2^b > x
     uint32_t b = 0;
@@ -508,6 +501,15 @@ bool enqueue_sub(gwb_zkey* z, gwb_r1cs* r, const Layout& L, const uint8_t* d_w, 
 }  // namespace
 
 namespace cwc_r1cs {
+uint64_t groth16_workspace_cap() {  // CWC_GROTH16_WORKSPACE_MB, read once per process
+    static const uint64_t cap = [] {
+        const char* s = getenv("CWC_GROTH16_WORKSPACE_MB");
+        const unsigned long long mb = s && *s ? strtoull(s, nullptr, 10) : 0ull;
+        return (mb ? (uint64_t)mb : 4096ull) << 20;
+    }();
+    return cap;
+}
+
 bool draw_fr(Fr& x, std::string& err) {
     do {
         uint8_t* p = (uint8_t*)x.v;

@@ -26,13 +26,13 @@ using cwc_r1cs::rd32;
 
 namespace cwc_ptau {
 
-namespace {
-
 const char* section_name(uint32_t id) {
     static const char* names[MAX_SECTION + 1] = {"", "header", "tauG1", "tauG2", "alphaTauG1", "betaTauG1", "betaG2", "contributions",
                                                  "", "", "", "", "lagrange tauG1", "lagrange tauG2", "lagrange alphaTauG1", "lagrange betaTauG1"};
     return id <= MAX_SECTION ? names[id] : "";
 }
+
+namespace {
 
 // n points at p, every `stride`-th from `first`: coordinates below q, on the curve unless all zero
 bool check_points(uint32_t section, const uint8_t* p, uint64_t base_index, uint64_t n, uint64_t first, uint64_t stride, bool g2, std::string& err) {
@@ -59,7 +59,7 @@ std::string point_message(uint32_t section, uint64_t index, PointFault fault, bo
 }
 
 bool parse(const uint8_t* d, size_t len, View& v, std::string& err) {
-    if (!cwc_r1cs::binfile_sections(d, len, "ptau", 0xf0feu, v.sec, err)) return false;  // sections 1 to 7 and 12 to 15
+    if (!cwc_r1cs::binfile_sections(d, len, "ptau", 0xf0feu, v.sec, err, &v.order)) return false;  // sections 1 to 7 and 12 to 15
     for (uint32_t id = 1; id <= 6; ++id)
         if (!v.sec[id].p) {
             err = "ptau: missing section " + std::to_string(id) + " (" + section_name(id) + ")";
@@ -109,6 +109,19 @@ bool parse(const uint8_t* d, size_t len, View& v, std::string& err) {
     return true;
 }
 
+bool need_prepared(const View& v, std::string& err) {
+    if (v.prepared) return true;
+    err = "ptau: lagrange = file, but the file has no prepared sections 12 to 15 (run `powersoftau prepare phase2`, or use auto or compute)";
+    return false;
+}
+
+bool check_lagrange_points(const View& v, uint32_t id, uint32_t m_lo, uint32_t m_hi, std::string& err) {
+    const bool g2 = id == 13;
+    const uint64_t lo = (1ull << m_lo) - 1, hi = (2ull << m_hi) - 1, bytes = g2 ? G2_BYTES : G1_BYTES;
+    const uint64_t prefix = (1ull << m_hi) - (id == 12 && m_hi == v.power + 1 ? 1 : 0);
+    return check_points(id, v.sec[id].p + lo * bytes, lo, hi - lo, 0, 1, g2, err) && check_points(id - 10, v.sec[id - 10].p, 0, prefix, 0, 1, g2, err);
+}
+
 bool plan(const View& v, uint32_t p, uint32_t mode, Plan& pl, std::string& err) {
     if (mode > GWB_PTAU_LAGRANGE_COMPUTE) {
         err = "ptau: lagrange mode " + std::to_string(mode) + " (0 = auto, 1 = file, 2 = compute expected)";
@@ -119,10 +132,7 @@ bool plan(const View& v, uint32_t p, uint32_t mode, Plan& pl, std::string& err) 
               std::to_string(v.power) + " (the truncated top level that snarkjs accepts for 2^power is not supported)";
         return false;
     }
-    if (mode == GWB_PTAU_LAGRANGE_FILE && !v.prepared) {
-        err = "ptau: lagrange = file, but the file has no prepared sections 12 to 15 (run `powersoftau prepare phase2`, or use auto or compute)";
-        return false;
-    }
+    if (mode == GWB_PTAU_LAGRANGE_FILE && !need_prepared(v, err)) return false;
     pl.p = p;
     pl.from_file = mode == GWB_PTAU_LAGRANGE_FILE || (mode == GWB_PTAU_LAGRANGE_AUTO && v.prepared);
     pl.t1 = v.sec[2].p;

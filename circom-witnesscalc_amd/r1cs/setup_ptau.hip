@@ -32,9 +32,29 @@
 // skips; delta1 and delta2 are the generators times delta.  delta and 1 / delta reach the kernels through a device buffer
 // that is zeroed before it is released.
 //
+// Prepare (gwb_ptau_prepare_phase2: sections 12 to 15 from 2 to 5).  A Lagrange section holds every level m = 0 .. top, level m
+// being Lag_m of the monomial section's first 2^m points.  The workspace of a section is the section's own layout in XYZZ:
+// level m in the slots [2^m - 1, 2^(m+1) - 1).  The monomial prefix is uploaded once and load_kernel reads it once per level,
+// bit-reversed for that level (the top level's launch reads every point and checks it).  idft_levels_stage_kernel then runs
+// stage s of every level m > s in one launch, top launches for a section where level by level they would be top (top + 1) / 2.
+// The twiddle of a butterfly, w_(2^(s+1))^(-k), depends on (s, k) and not on the level, so one table of 2^power values
+// (w_(2^(power+1))^(-j), indexed k << (power - s)) serves every level of every section, and butterflies of different levels
+// with one k can share a wave: with v = k 2^(top-s) + w they do while top - s >= 6, that is in every stage but the last five
+// of the launch.  Level by level (idft_stage_kernel) only the levels m >= s + 7 have 64 groups to give a wave, so at stage s the
+// levels s + 1 .. s + 6 run divergent there; here they fill the wave together (ptau_internal.hpp's level_butterfly has the
+// decode, a count of leading zeros).  In the last five stages fewer than 63 butterflies have one k, and the lanes take
+// consecutive k as before.  k = 0 has no multiplication.  scale_levels_kernel applies 1 / 2^m to the whole array in one
+// launch, the level from the slot index and the power + 2 scalars from a small device table; a wave is inside one level from
+// level 6 on, so its scalar is uniform.  The four sections run as four passes through one workspace, section 12 with its extra
+// level (the missing last input is O) and no batching of the three G1 sections: the passes differ in length by one level, and
+// one pass already fills the device from power 10 on.  Results leave through the shared-inversion kernel and come back in
+// pieces of CWC_CONTRIBUTE_CHUNK points.
+//
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage for gfx950; every kernel: 0 bytes of scratch; VGPRs + AGPRs, waves / SIMD):
 //   load_kernel<G1> 53, 8           load_kernel<G2> 110, 4            twiddle_kernel 36, 8        put_fr_kernel 10, 8
 //   idft_stage_kernel<G1> 188, 2    idft_stage_kernel<G2> 256 + 170, 1     odd_half_kernel<G1> 152, 3
+//   idft_levels_stage_kernel<G1> 188, 2    idft_levels_stage_kernel<G2> 256 + 170, 1
+//   scale_levels_kernel<G1> 124, 4         scale_levels_kernel<G2> 256 + 14, 1
 //   scale_kernel<G1> 114, 4         scale_kernel<G2> 256 + 1, 1
 //   segments_kernel<G1> 186, 2      segments_kernel<G2> 256 + 151, 1
 //   wires_g1_kernel 232, 2          wires_one_kernel<G2> 246, 2
@@ -45,6 +65,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -144,6 +165,34 @@ __global__ __launch_bounds__(THREADS) void scale_kernel(Xyzz<T>* __restrict__ x,
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     x[i] = xyzz_mul_short(x[i], *k);
+}
+
+// Stage s of the transforms of every level m in (s, top] of one section (the header's "Prepare"; ptau_internal.hpp's
+// level_butterfly has the thread layout): x holds level m in the slots [2^m - 1, 2^(m+1) - 1), inputs bit-reversed per level;
+// tw[j] = w_N^(-j) for one N >= 2^top, and tw_shift = log2(N) - 1 - s, so that tw[k << tw_shift] = w_(2 half)^(-k) whatever
+// the level.  2^top threads.
+template <class T>
+__global__ __launch_bounds__(THREADS) void idft_levels_stage_kernel(Xyzz<T>* __restrict__ x, uint32_t top, uint32_t s, uint32_t tw_shift,
+                                                                    const Fr* __restrict__ tw) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    cwc_ptau::LevelButterfly b;
+    if ((v >> top) != 0 || !cwc_ptau::level_butterfly(v, top, s, b)) return;
+    const uint32_t half = 1u << s;
+    Xyzz<T>* lo = x + (((size_t)1 << b.m) - 1) + ((size_t)b.grp << (s + 1)) + b.k;
+    const Xyzz<T> a = lo[0];
+    Xyzz<T> c = lo[half];
+    if (b.k) c = xyzz_mul_short(c, tw[(size_t)b.k << tw_shift]);
+    lo[0] = xyzz_add(a, c);
+    lo[half] = xyzz_add(a, xyzz_neg(c));
+}
+
+// x[i] = inv[m] x[i] for the slots i < count of the levels m = floor(log2(i + 1)) >= 1: the factor 1 / 2^m of every level, canonical
+template <class T>
+__global__ __launch_bounds__(THREADS) void scale_levels_kernel(Xyzz<T>* __restrict__ x, uint32_t count, const Fr* __restrict__ inv) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t m = 31u - (uint32_t)__builtin_clz(i + 1u);
+    if (m) x[i] = xyzz_mul_short(x[i], inv[m]);
 }
 
 // part[s] = sum of coefficient x pts[constraint] over the terms ent[seg_off[s] .. seg_off[s + 1]) of one (wire, matrix)
@@ -475,9 +524,185 @@ int idft_aid(const void* d_points, uint32_t log_n, void* d_out, hipStream_t s, g
     return 0;
 }
 
+// ---- prepare phase 2: sections 12 to 15 from sections 2 to 5 -------------------------------------------------------------------
+
+PhaseTimes<4> g_prepare_phases;  // load, idft_g1, idft_g2, affine: summed over the four section passes
+
+struct PrepareDevice {
+    Stream s;
+    PhaseEvents<4> ev;
+    DeviceBuf work;
+    size_t raw = 0, x = 0, tw = 0, inv = 0, out = 0, flag = 0;  // offsets into work
+};
+
+// One section pass: the first 2^top points of section id - 10 -> the 2^(top+1) - 1 points of section id at `body`, through the
+// device in pieces of `chunk` points; ms gets the pass's times.  err: a point fault in point_message's words, or the runtime's.
+template <class T>
+bool lagrange_section(const cwc_ptau::View& view, uint32_t id, PrepareDevice& D, uint64_t chunk, uint8_t* body, float (&ms)[4], bool& timed,
+                      std::string& err) {
+    constexpr bool g2 = sizeof(typename T::E) != 32;
+    constexpr size_t PB = g2 ? G2_BYTES : G1_BYTES;
+    const uint32_t src = id - 10, top = cwc_ptau::top_level(view, id);
+    const uint64_t n_in = view.sec[src].size / PB, slots = (2ull << top) - 1;  // n_in = 2^top, or one fewer in section 2
+    uint8_t* W = D.work.as<uint8_t>();
+    Xyzz<T>* x = (Xyzz<T>*)(W + D.x);
+    unsigned long long* flag = (unsigned long long*)(W + D.flag);
+    D.ev.record(0, D.s);
+    hipError_t e = hipMemcpyAsync(W + D.raw, view.sec[src].p, n_in * PB, hipMemcpyHostToDevice, D.s);
+    if (e == hipSuccess && n_in < (1ull << top)) e = hipMemsetAsync(W + D.raw + n_in * PB, 0, PB, D.s);  // the missing last input: O
+    if (e == hipSuccess) e = hipMemsetAsync(flag, 0xff, sizeof *flag, D.s);
+    if (e != hipSuccess) {
+        err = hip_err("uploading a section of ceremony points", e);
+        return false;
+    }
+    for (uint32_t m = 0; m <= top; ++m)  // the top level reads every point: it checks them
+        enqueue_load<T>(W + D.raw, 1u << m, 0, 1, false, m, x + (((size_t)1 << m) - 1), m == top ? flag : nullptr, D.s);
+    D.ev.record(1, D.s);
+    for (uint32_t st = 0; st < top; ++st)
+        hipLaunchKernelGGL(idft_levels_stage_kernel<T>, dim3(blocks_for(1ull << top, THREADS)), dim3(THREADS), 0, D.s, x, top, st, view.power - st,
+                           (const Fr*)(W + D.tw));
+    hipLaunchKernelGGL(scale_levels_kernel<T>, dim3(blocks_for(slots, THREADS)), dim3(THREADS), 0, D.s, x, (uint32_t)slots, (const Fr*)(W + D.inv));
+    D.ev.record(2, D.s);
+    unsigned long long fault = NO_FAULT;
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&fault, flag, sizeof fault, hipMemcpyDeviceToHost, D.s);
+    for (uint64_t at = 0; at < slots && e == hipSuccess; at += chunk) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, slots - at);
+        if (g2)
+            enqueue_affine_g2(x + at, m, W + D.out, false, D.s);
+        else
+            enqueue_affine_g1(x + at, m, W + D.out, false, D.s);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(body + at * PB, W + D.out, (size_t)m * PB, hipMemcpyDeviceToHost, D.s);
+        if (e == hipSuccess) e = hipStreamSynchronize(D.s);  // the piece's buffer is written again by the next piece
+        if (e == hipSuccess && fault != NO_FAULT) {
+            err = cwc_ptau::point_message(src, fault >> 1, (PointFault)(fault & 1), g2);
+            return false;
+        }
+    }
+    D.ev.record(3, D.s);
+    if (e != hipSuccess) {
+        err = hip_err("transforming a section of ceremony points", e);
+        return false;
+    }
+    float t[3];
+    if (D.ev.elapsed(t) == hipSuccess) {
+        ms[0] += t[0];
+        ms[g2 ? 2 : 1] += t[1];
+        ms[3] += t[2];
+    } else {
+        timed = false;
+    }
+    return true;
+}
+
+void put_u32(uint8_t* at, uint32_t v) { memcpy(at, &v, 4); }
+void put_u64(uint8_t* at, uint64_t v) { memcpy(at, &v, 8); }
+
+int prepare(const uint8_t* ptau, size_t len, void** out, size_t* out_len, gw_status_t* status) {
+    std::string err;
+    cwc_ptau::View view;
+    if (!cwc_ptau::parse(ptau, len, view, err)) return fail(status, err);
+    const uint32_t power = view.power;
+    if (power > MAX_LOG_N)
+        return fail(status, "ptau prepare: power " + std::to_string(power) + " is above " + std::to_string(MAX_LOG_N) + ", the largest whose top level has a root of unity here");
+    const uint64_t np = 1ull << power;
+    // the workspace: the largest all-level array (section 12's 4 np - 1 G1 points against section 13's 2 np - 1 G2 points), the
+    // uploaded prefix, the twiddles and one piece of output
+    const uint64_t x_bytes = std::max((4 * np - 1) * sizeof(Xyzz<G1>), (2 * np - 1) * sizeof(Xyzz<G2>)), cap = groth16_workspace_cap();
+    const uint64_t chunk = std::min(piece_points("CWC_CONTRIBUTE_CHUNK"), 4 * np - 1);
+    PrepareDevice D;
+    Carve cw;
+    D.raw = cw.take(2 * np * G1_BYTES);  // = np G2 points
+    D.x = cw.take(x_bytes);
+    D.tw = cw.take(np * 32);
+    D.inv = cw.take((power + 2) * 32);
+    D.out = cw.take(chunk * G2_BYTES);
+    D.flag = cw.take(sizeof(unsigned long long));
+    if (cw.o > cap)
+        return fail(status, "ptau prepare: power " + std::to_string(power) + " needs " + std::to_string(cw.o) + " bytes of device workspace (" +
+                                std::to_string(x_bytes) + " of them for all levels of one section), above the " + std::to_string(cap) +
+                                " of CWC_GROTH16_WORKSPACE_MB (an out-of-core transform is not supported)");
+    // the image: the input's sections other than 12 to 15 in its order, then 12 to 15
+    const uint64_t lag_points[4] = {4 * np - 1, 2 * np - 1, 2 * np - 1, 2 * np - 1};
+    uint64_t total = 12;
+    uint32_t n_out = 4;
+    for (const BinEntry& sct : view.order)
+        if (sct.id < 12 || sct.id > 15) {
+            total += 12 + sct.size;
+            ++n_out;
+        }
+    uint64_t lag_off[4];
+    for (int k = 0; k < 4; ++k) {
+        lag_off[k] = total + 12;
+        total += 12 + lag_points[k] * (k == 1 ? G2_BYTES : G1_BYTES);
+    }
+    struct Free {
+        void operator()(void* p) const { free(p); }
+    };
+    std::unique_ptr<uint8_t, Free> img((uint8_t*)malloc(total));
+    if (!img) return fail(status, "ptau prepare: out of host memory");
+    uint8_t* o = img.get();
+    memcpy(o, ptau, 8);
+    put_u32(o + 8, n_out);
+    uint64_t w = 12;
+    for (const BinEntry& sct : view.order)
+        if (sct.id < 12 || sct.id > 15) {
+            put_u32(o + w, sct.id);
+            put_u64(o + w + 4, sct.size);
+            memcpy(o + w + 12, sct.p, sct.size);
+            w += 12 + sct.size;
+        }
+    for (int k = 0; k < 4; ++k) {
+        put_u32(o + lag_off[k] - 12, 12 + k);
+        put_u64(o + lag_off[k] - 8, lag_points[k] * (k == 1 ? G2_BYTES : G1_BYTES));
+    }
+
+    hipError_t e = D.s.create();
+    if (e == hipSuccess) e = D.ev.on();
+    if (e == hipSuccess) e = D.work.alloc(cw.o);
+    if (e != hipSuccess) return fail(status, hip_err("allocating the workspace of the Lagrange sections", e));
+    uint8_t* W = D.work.as<uint8_t>();
+    // tw[j] = w_(2 np)^(-j) for j < np: every level of every section takes its twiddles from it; inv[m] = 1 / 2^m = r - (r - 1) / 2^m
+    Fr wn, g, rm1 = cwc::fr_p();
+    qap_roots(power, wn, g);
+    rm1.v[0] -= 1;
+    std::vector<Fr> inv(power + 2, Fr{{1, 0, 0, 0, 0, 0, 0, 0}});
+    for (uint32_t m = 1; m < power + 2; ++m) cwc::u256_sub(inv[m], cwc::fr_p(), cwc::u256_shr(rm1, m));
+    hipLaunchKernelGGL(twiddle_kernel, dim3(blocks_for(np, THREADS)), dim3(THREADS), 0, D.s, (Fr*)(W + D.tw), (uint32_t)np, powers_of(cwc::fr_inv_fermat(g)));
+    e = hipMemcpyAsync(W + D.inv, inv.data(), inv.size() * 32, hipMemcpyHostToDevice, D.s);
+    if (e == hipSuccess) e = hipStreamSynchronize(D.s);  // the copy has left the host array
+    if (e != hipSuccess) return fail(status, hip_err("making the twiddles of the Lagrange sections", e));
+    float ms[4] = {0, 0, 0, 0};
+    bool timed = true;
+    for (int k = 0; k < 4; ++k) {
+        const bool ok = k == 1 ? lagrange_section<G2>(view, 12 + k, D, chunk, o + lag_off[k], ms, timed, err)
+                               : lagrange_section<G1>(view, 12 + k, D, chunk, o + lag_off[k], ms, timed, err);
+        if (!ok) return fail(status, err);
+    }
+    g_prepare_phases.store(ms, timed);
+    *out = img.release();
+    *out_len = total;
+    set_ok(status);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gwb_ptau_prepare_phase2(const void* ptau, size_t ptau_len, void** out, size_t* out_len, gw_status_t* status) {
+    if (!out || !out_len || (!ptau && ptau_len)) return fail(status, "gwb_ptau_prepare_phase2: NULL argument");
+    *out = nullptr;
+    *out_len = 0;
+    try {
+        return prepare((const uint8_t*)ptau, ptau_len, out, out_len, status);
+    } catch (const std::bad_alloc&) {
+        return fail(status, "ptau prepare: out of host memory");
+    }
+}
+
+int gwb_ptau_prepare_phase_ms(float* ms) { return g_prepare_phases.read(ms); }
 
 int gwb_groth16_setup_ptau(gwb_r1cs_t* r, const void* ptau, size_t ptau_len, const uint8_t* delta, uint32_t lagrange_mode, void** zkey,
                            size_t* zkey_len, gw_status_t* status) {

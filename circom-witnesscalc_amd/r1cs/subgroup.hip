@@ -207,6 +207,17 @@ int check_ptau(const uint8_t* data, size_t len, uint32_t domain_power, uint32_t 
 
 }  // namespace
 
+int cwc_ptau::check_g2_points(uint32_t section, uint64_t base, const uint8_t* p, uint64_t n, std::string& msg) {
+    Checker c;
+    uint64_t first, count;
+    uint32_t st;
+    if (!c.open(std::max<uint64_t>(1, n), msg) || !c.run(p, n, first, st, count, nullptr, msg)) return 2;
+    if (first == NONE_BAD) return 0;
+    const PointFault fault = st == GWB_G16V_SUBGROUP ? PointFault::SUBGROUP : point_fault<G2>(p + first * G2_BYTES, false);
+    msg = point_message(section, base + first, fault, true);
+    return 1;
+}
+
 extern "C" {
 
 int gwb_bn254_g2_check_batch_device(const void* d_points, size_t n, uint32_t form, uint32_t method, void* d_status, void* hip_stream,

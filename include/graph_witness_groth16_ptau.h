@@ -39,7 +39,8 @@
  *
  * Lagrange source.  A file that went through `powersoftau prepare phase2` carries L1, L2, LA, LB and M already (sections 12
  * to 15).  GWB_PTAU_LAGRANGE_AUTO reads them when they are present and computes them otherwise, _FILE fails with a message
- * when they are absent, _COMPUTE ignores them.  What the prepared sections hold is not compared with the monomial ones.
+ * when they are absent, _COMPUTE ignores them.  gwb_ptau_prepare_phase2 writes them; a setup does not compare what they hold
+ * with the monomial sections, gwb_ptau_check_lagrange does.
  *
  * Return and status conventions are those of graph_witness_r1cs.h.  gwb_groth16_setup_ptau is synchronous and runs on the
  * current device. */
@@ -100,6 +101,63 @@ int gwb_ptau_check_g2(const void *data, size_t len, uint32_t domain_power, uint3
  * anything); the Lagrange sections 12 to 15; the ceremony's own contribution records in section 7, whose challenge derivation
  * (snarkjs's) cannot be restated here.  Returns 2 for anything that is not a verdict.  Synchronous, on the current device. */
 int gwb_ptau_check_powers(const void *data, size_t len, uint32_t domain_power, const uint8_t *seed, gw_status_t *status);
+
+/* What `powersoftau prepare phase2` does: the file with its Lagrange sections 12 to 15 made on the current device from its
+ * monomial sections 2 to 5.  Section 12 + j (j = 0 .. 3) holds the levels m = 0 .. power of section 2 + j one after the other,
+ * level m being the 2^m points Lag_m(P_0 .. P_{2^m - 1}) of the section's first 2^m points P, at point offset 2^m - 1.  Section 12
+ * has one level more, m = power + 1: section 2 holds only 2^(power+1) - 1 points, the missing last input is the point at
+ * infinity, and the level is Lag_(power+1)(T1_0, .., T1_{2n-2}, O) for n = 2^power, as in snarkjs (a setup never reads it: it
+ * needs p + 1 <= power).  So the sections hold 4n - 1 G1, 2n - 1 G2, 2n - 1 G1 and 2n - 1 G1 points.
+ * *out is a complete `.ptau` image, released with gwb_groth16_setup_free: every section of the input other than 12 to 15 byte
+ * for byte and in the input's order, ids this library does not know included, then sections 12, 13, 14 and 15; an input that
+ * already has them gets them replaced.  The file is parsed as gwb_ptau_info parses it, and the size rules below are applied,
+ * before the device is touched; every monomial point is then checked on the device as the setup checks the ones it reads
+ * (coordinates, curve; the same messages).  One section at a time has all its levels on the device in extended coordinates
+ * ((4n - 1) 128 bytes for section 12, (2n - 1) 256 for section 13): a file for which that, with the uploaded prefix, the twiddles
+ * and one piece of output, is more than CWC_GROTH16_WORKSPACE_MB (the prover's knob, read once per process; 4096 without it) is
+ * refused with a message naming the power and the bytes, and so is a power above 27.  The results come
+ * back in pieces of CWC_CONTRIBUTE_CHUNK points.  No snarkjs-prepared file was available to compare the container or the
+ * points with.  Returns 0 or 1.  Synchronous. */
+int gwb_ptau_prepare_phase2(const void *ptau, size_t ptau_len, void **out, size_t *out_len, gw_status_t *status);
+
+/* ms[4] of the last gwb_ptau_prepare_phase2 call of the process (HIP events, summed over the four sections): load (upload,
+ * point checks and the per-level bit reversal), idft_g1, idft_g2 (the stages and the factors 1 / 2^m), affine (conversion and
+ * the copies back).  1 when no call has completed yet. */
+int gwb_ptau_prepare_phase_ms(float *ms);
+
+#define GWB_PTAU_ALL_LEVELS 0xffffffffu
+
+/* Checks the Lagrange sections 12 to 15 of a prepared file against its monomial sections 2 to 5 on the current device.  With
+ * domain_power = p the levels a setup for the domain 2^p reads under GWB_PTAU_LAGRANGE_FILE: level p of sections 12 to 15 and
+ * level p + 1 of section 12; with GWB_PTAU_ALL_LEVELS every level of every section (section 12's last level as
+ * gwb_ptau_prepare_phase2 defines it).  First, returning 2 with their own messages: everything gwb_ptau_check refuses about the
+ * header, the section table and the plan (a file without sections 12 to 15 gets GWB_PTAU_LAGRANGE_FILE's refusal), then a
+ * coordinate >= q or a point off its curve among the points read, Lagrange and monomial.  Then, for section 13, the subgroup
+ * rule of gwb_ptau_check_g2 over the Lagrange points read (returns 1): the equation below sees a component of small order
+ * with probability 1 / order only.  Then per section, with 128-bit rho_{m,k} cut from `seed` (32 bytes, or NULL to draw them
+ * after the file is seen) as gwb_zkey_verify_step cuts them, rho_{m,k} = rho of index 2^m - 1 + k:
+ *   sum_m sum_k rho_{m,k} Lag_m[k]  =  sum_i c_i P_i,   c_i = sum_{m: i < 2^m} (1 / 2^m) sum_k w_(2^m)^(-k i) rho_{m,k}
+ * over the checked levels m; the transform's matrix is symmetric, so c is the sum of Lag_m of the rho of level m, and it is
+ * computed on the device.  Both sides are sums the device forms (the left with the 128-bit rho, the right with the full-width
+ * c) and they are compared as points: no pairing.  For the last level of section 12, c_{2n-1} multiplies O and is dropped.  In
+ * domain mode every level has an equation of its own and the verdict names it: "ptau: section 14 (lagrange alphaTauG1) level 3
+ * does not hold the Lagrange forms of section 4"; for all levels a section has one equation and one full-width combination
+ * of its monomial points, and after a failure the levels are tried one by one to name the first: "ptau: section 12 (lagrange
+ * tauG1) does not hold the Lagrange forms of section 2: level 4 is the first that does not".  Sections are checked in the order
+ * 12 to 15.  A file with a wrong point among the checked levels passes with probability about 2^-128 over the seed.  NOT
+ * checked: that sections 2 to 5 are powers of one tau (gwb_ptau_check_powers).  Returns 2 for anything that is not a verdict.
+ * Synchronous. */
+int gwb_ptau_check_lagrange(const void *data, size_t len, uint32_t domain_power, const uint8_t *seed, gw_status_t *status);
+
+/* Measurement and test aids of the Lagrange check's right-hand side: d_points [n][64 B] (g1) or [128 B] (g2) affine in `form`
+ * (GWB_FORM_CANONICAL or GWB_FORM_MONTGOMERY of graph_witness_batch.h; zero bytes = infinity, not checked) and d_scalars [n][32 B]
+ * canonical little-endian values below r -> d_out, one point in the same form: sum_i scalar_i P_i.  Beside
+ * gwb_bn254_g1_lincomb128_device and its G2 twin (graph_witness_groth16_contribute.h), whose kernels these instantiate with
+ * eight scalar words.  Asynchronous on hip_stream. */
+int gwb_bn254_g1_lincomb_device(const void *d_points, const void *d_scalars, size_t n, uint32_t form, void *d_out, void *hip_stream,
+                                gw_status_t *status);
+int gwb_bn254_g2_lincomb_device(const void *d_points, const void *d_scalars, size_t n, uint32_t form, void *d_out, void *hip_stream,
+                                gw_status_t *status);
 
 /* delta: 32 bytes canonical little-endian in [1, r), or NULL to draw it (the prover's rejection sampler over getrandom()).
  * *zkey is released with gwb_groth16_setup_free. */
