@@ -640,6 +640,14 @@ def r1cs_lib():
         L.gwb_ptau_check_lagrange.argtypes = [vp, sz, u32, vp, stp]
         L.gwb_bn254_g1_lincomb_device.argtypes = [vp, vp, sz, u32, vp, vp, stp]
         L.gwb_bn254_g2_lincomb_device.argtypes = [vp, vp, sz, u32, vp, vp, stp]
+        L.gwb_ptau_new.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
+        L.gwb_ptau_contribute.argtypes = [vp, sz, ctypes.c_char_p, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), vp, stp]
+        L.gwb_ptau_contribute_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_float)]
+        L.gwb_ptau_contributions.argtypes = [vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
+        L.gwb_ptau_verify.argtypes = [vp, sz, u32, vp, vp, ctypes.POINTER(sz), stp]
+        L.gwb_ptau_verify_step.argtypes = [vp, sz, vp, sz, vp, stp]
+        L.gwb_bn254_g1_mul_batch_device.argtypes = [vp, vp, sz, u32, u32, vp, vp, stp]
+        L.gwb_bn254_g2_mul_batch_device.argtypes = [vp, vp, sz, u32, u32, vp, vp, stp]
         _r1cs_lib = L
     return _r1cs_lib
 
@@ -1347,7 +1355,7 @@ def ptau_check_powers(ptau, domain_power, seed=None):
     on the current GPU and five pairing equations (synchronous; a wrong point passes with probability about 2^-128 over the
     seed).  seed: 32 bytes for a reproducible check, or None to draw them.  The message names the section: "ptau: section 2
     (tauG1): the first 2n points are not consecutive powers of the tau of section 3".  Not checked: points beyond the
-    prefixes, the prepared sections 12 to 15, the ceremony's own contribution records."""
+    prefixes (ptau_verify checks the whole file), the prepared sections 12 to 15, records made by snarkjs."""
     seed = _seed32(seed)
     keep, addr, n = _ptau_buffer(ptau)
     st = GwStatus()
@@ -1440,6 +1448,175 @@ def bn254_g2_lincomb_device(d_points, d_scalars, form="canonical", stream=None):
     return _lincomb_device(2, d_points, d_scalars, form, stream)
 
 
+# -- the powers-of-tau ceremony itself (include/graph_witness_groth16_ceremony.h) ---------------------------------------------------
+PTAU_CONTRIBUTE_PHASES = ("load", "scalars", "mul_g1", "mul_g2", "affine")
+PTAU_VERIFY_SKIP_RECORDS = 1
+MUL_METHODS = {"window": 0, "plain": 1}
+
+
+def _take_image(out, n):
+    try:
+        return ctypes.string_at(out, n.value)
+    finally:
+        r1cs_lib().gwb_groth16_setup_free(out)
+
+
+def ptau_new(power):
+    """What snarkjs `powersoftau new` does (host only): the `.ptau` bytes of a new ceremony of the given power, 1 to 28, with
+    tau = alpha = beta = 1: every point is its group's generator and section 7 holds no record.  Such a file is the start of a
+    ceremony, nothing more: keys made from it before anyone contributed can be forged against by everybody."""
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    st = GwStatus()
+    rc = r1cs_lib().gwb_ptau_new(int(power), ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
+    _r1cs_check(rc, st)
+    return _take_image(out, n)
+
+
+def ptau_contribute(ptau, name="", secrets=None):
+    """One contribution to a powers-of-tau ceremony on the GPU (synchronous): a `.ptau` image (bytes or any buffer, an mmap
+    included) -> (new `.ptau` bytes, the 64-byte hash to publish: the new record's nextChallenge).  Every point of sections 2
+    to 5 is multiplied by its own scalar (tau'^i, alpha' tau'^i, beta' tau'^i), betaG2 by beta', and a record with three proofs
+    of knowledge is appended to section 7; section 1 and unknown sections stay byte for byte; the prepared sections 12 to 15 are
+    dropped (ptau_prepare_phase2 makes them again).  secrets: (tau', alpha', beta') as ints in [1, r) for reproducible files, or
+    None: drawn, applied and discarded.  name: at most 255 bytes of UTF-8.  The records are this library's own: `snarkjs
+    powersoftau verify` does not accept them, while sections 1 to 6 are ordinary."""
+    nm = name.encode("utf-8") if isinstance(name, str) else bytes(name)
+    if b"\0" in nm:
+        raise WitnessCalcError("the name holds a zero byte")
+    buf = None
+    if secrets is not None:
+        xs = [int(x) for x in secrets]
+        if len(xs) != 3 or not all(0 <= x < (1 << 256) for x in xs):
+            raise WitnessCalcError("secrets: three integers in [0, 2^256) expected (tau, alpha, beta)")
+        buf = ctypes.create_string_buffer(b"".join(x.to_bytes(32, "little") for x in xs), 96)
+    keep, addr, n_in = _ptau_buffer(ptau)
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    digest = ctypes.create_string_buffer(CONTRIBUTION_HASH_BYTES)
+    st = GwStatus()
+    try:
+        rc = r1cs_lib().gwb_ptau_contribute(addr, n_in, nm, buf, ctypes.byref(out), ctypes.byref(n), digest, ctypes.byref(st))
+    finally:
+        if buf is not None:
+            ctypes.memset(buf, 0, 96)
+    del keep
+    _r1cs_check(rc, st)
+    return _take_image(out, n), digest.raw
+
+
+def ptau_contribute_phase_ms():
+    """{load, scalars, mul_g1, mul_g2, affine} in ms of the process's last ptau_contribute call, summed over its pieces."""
+    ms = (ctypes.c_float * 5)()
+    if r1cs_lib().gwb_ptau_contribute_phase_ms(ms) != 0:
+        raise WitnessCalcError("no contribution phase times (no ptau_contribute call yet)")
+    return dict(zip(PTAU_CONTRIBUTE_PHASES, (float(x) for x in ms)))
+
+
+PTAU_RECORD_POINTS = (("tau_g1", 64), ("tau_g2", 128), ("alpha_g1", 64), ("beta_g1", 64), ("beta_g2", 128), ("tau_g1_s", 64), ("tau_g1_sx", 64),
+                      ("alpha_g1_s", 64), ("alpha_g1_sx", 64), ("beta_g1_s", 64), ("beta_g1_sx", 64), ("tau_g2_spx", 128), ("alpha_g2_spx", 128),
+                      ("beta_g2_spx", 128))
+
+
+def ptau_contributions(ptau):
+    """Section 7 of a `.ptau` (host only): [{"name", "type", the five after-values "tau_g1", "tau_g2", "alpha_g1", "beta_g1",
+    "beta_g2", the nine key points "tau_g1_s", "tau_g1_sx", ..., "beta_g2_spx", "next_challenge"}], oldest first.  Points are
+    canonical little-endian bytes (64 for G1, 128 for G2: x.c0, x.c1, y.c0, y.c1), type is 0 (contribution) or 1 (beacon),
+    next_challenge is the hash the participant published.  Nothing is verified beyond the section's form; a malformed section
+    raises with a message starting "ptau: section 7"."""
+    keep, addr, n_in = _ptau_buffer(ptau)
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    st = GwStatus()
+    rc = r1cs_lib().gwb_ptau_contributions(addr, n_in, ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
+    del keep
+    _r1cs_check(rc, st)
+    img = _take_image(out, n)
+    count = int.from_bytes(img[:4], "little")
+    off, recs = 4, []
+    for _ in range(count):
+        rec = {}
+        for key, size in PTAU_RECORD_POINTS:
+            rec[key] = img[off:off + size]
+            off += size
+        rec["next_challenge"] = img[off:off + 64]
+        rec["type"], name_len = (int.from_bytes(img[off + 64 + 4 * i:off + 68 + 4 * i], "little") for i in range(2))
+        off += 72
+        rec["name"] = img[off:off + name_len].decode("utf-8", "replace")
+        off += name_len
+        recs.append(rec)
+    return recs
+
+
+def ptau_verify(ptau, records=True, seed=None):
+    """Verifies a ceremony file on the GPU (synchronous) and returns the hashes of its records, oldest first.  Every record is
+    checked against the one before it (its challenge, its three proofs of knowledge, its after-values; the first against the
+    generators), the last record's after-values against the file's points, and then the whole file: every tauG2 in the order-r
+    subgroup, every section consecutive powers of one tau through random linear combinations of ALL its points and five
+    pairing equations (a wrong point passes with probability about 2^-128 over the seed).  records=False passes over section 7:
+    for files that carry snarkjs's records, which this library cannot verify.  seed: 32 bytes for a reproducible check, or None
+    to draw them.  Raises WitnessCalcError naming the first failing record and rule, or the section, for example "ptau:
+    contribution 2: alphaG1 is not the previous alphaG1 times the proven secret"."""
+    seed = _seed32(seed)
+    keep, addr, n_in = _ptau_buffer(ptau)
+    room = ptau_info(ptau)["n_contributions"]
+    hashes = ctypes.create_string_buffer(max(1, room * CONTRIBUTION_HASH_BYTES))
+    n = ctypes.c_size_t(room)
+    st = GwStatus()
+    rc = r1cs_lib().gwb_ptau_verify(addr, n_in, 0 if records else PTAU_VERIFY_SKIP_RECORDS, seed, hashes, ctypes.byref(n), ctypes.byref(st))
+    del keep
+    _r1cs_check(rc, st)
+    return [hashes.raw[64 * k:64 * k + 64] for k in range(min(room, n.value))]
+
+
+def ptau_verify_step(prev, next, seed=None):
+    """Checks on the GPU that the file `next` is the file `prev` after exactly one contribution: section 1 identical, one record
+    more with the earlier ones byte for byte, the new record's proofs against the five anchor points of `prev` (tauG1[1],
+    tauG2[1], alphaTauG1[0], betaTauG1[0], betaG2), its after-values in `next`, and the whole-file check of ptau_verify on
+    `next`.  Works on top of records this library cannot verify.  Raises WitnessCalcError naming what fails."""
+    seed = _seed32(seed)
+    ka, aa, na = _ptau_buffer(prev)
+    kb, ab, nb = _ptau_buffer(next)
+    st = GwStatus()
+    rc = r1cs_lib().gwb_ptau_verify_step(aa, na, ab, nb, seed, ctypes.byref(st))
+    del ka, kb
+    _r1cs_check(rc, st)
+
+
+def _mul_batch_device(group, d_points, d_scalars, form, method, stream):
+    import torch
+    if form not in ("canonical", "montgomery"):
+        raise WitnessCalcError("form must be canonical or montgomery")
+    if method not in MUL_METHODS:
+        raise WitnessCalcError("method must be one of %s" % ", ".join(MUL_METHODS))
+    n, width = d_points.shape[0], 64 * group
+    assert tuple(d_points.shape) == (n, width) and d_points.is_cuda and d_points.is_contiguous() and d_points.dtype == torch.uint8
+    assert tuple(d_scalars.shape) == (n, 32) and d_scalars.is_cuda and d_scalars.is_contiguous() and d_scalars.dtype == torch.uint8
+    s = stream if stream is not None else torch.cuda.current_stream(d_points.device)
+    out = torch.empty_like(d_points)
+    st = GwStatus()
+    call = r1cs_lib().gwb_bn254_g1_mul_batch_device if group == 1 else r1cs_lib().gwb_bn254_g2_mul_batch_device
+    with torch.cuda.device(d_points.device):
+        rc = call(d_points.data_ptr(), d_scalars.data_ptr(), n, 0 if form == "canonical" else 1, MUL_METHODS[method], out.data_ptr(), s.cuda_stream,
+                  ctypes.byref(st))
+    _r1cs_check(rc, st)
+    if n:
+        d_points.record_stream(s)
+        d_scalars.record_stream(s)
+        out.record_stream(s)
+    return out
+
+
+def bn254_g1_mul_batch_device(d_points, d_scalars, form="canonical", method="window", stream=None):
+    """Measurement and test aid of the ceremony's multiplication kernel: device G1 points (uint8 cuda [n, 64], affine in `form`,
+    "canonical" or "montgomery"; zero bytes for infinity, not validated) and canonical little-endian scalars below r (uint8 cuda
+    [n, 32]) -> scalar_i P_i for every i, uint8 cuda [n, 64] in the same form.  method: "window" (signed digits, the table of
+    multiples in LDS) or "plain" (double-and-add per thread).  Asynchronous on `stream` or the current stream."""
+    return _mul_batch_device(1, d_points, d_scalars, form, method, stream)
+
+
+def bn254_g2_mul_batch_device(d_points, d_scalars, form="canonical", method="window", stream=None):
+    """The same in G2: uint8 cuda [n, 128] points (x.c0, x.c1, y.c0, y.c1) and [n, 32] scalars -> uint8 cuda [n, 128]."""
+    return _mul_batch_device(2, d_points, d_scalars, form, method, stream)
+
+
 GROTH16_VERIFY_KEY_PHASES = ("remake", "lincomb", "pairings")
 VERIFY_KEY_SKIP_RECORDS, VERIFY_KEY_CHECK_PTAU = 1, 2
 
@@ -1459,7 +1636,8 @@ def groth16_verify_key(zkey, r1cs, ptau, lagrange="compute", records=True, check
     lagrange "auto" or "file", first runs ptau_check_lagrange for the circuit's domain (under "auto" only when the file has
     prepared sections), and its failure is the verdict: the prepared sections that the remake reads are then verified against
     the monomial ones, for much less than "compute" spends on making them again; with "compute" the flag has nothing to
-    check.  Not verified: the ceremony's own records in the file, and its points beyond the prefixes a setup reads."""
+    check.  Not verified: records made by snarkjs in the file, and its points beyond the prefixes a setup reads (ptau_verify
+    checks this library's records and the whole file)."""
     mode = _lagrange_mode(lagrange)
     seed = _seed32(seed)
     data = bytes(zkey)

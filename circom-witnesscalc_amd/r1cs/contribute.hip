@@ -26,6 +26,9 @@
 // two kernels.  Both kernels are templates over the group.  A G1 workgroup has 256 threads.  A G2 workgroup is one wave of
 // 64: an Xyzz<G2> is 256 bytes (256 of them would be 64 KB of LDS), and the G2 double-and-add keeps the multiplicand, the
 // accumulator and an addition's temporaries, which needs the unified register file of a wave that has its SIMD to itself.
+// The lengths of the sums are arguments (powers_rules): the prefixes of one setup here, every point of the file for the
+// ceremony's verification (ceremony.hip, gwb_ptau_verify), which shares the sums, the equations and the batched pairings
+// through contribute_internal.hpp.
 //
 // Lagrange check (gwb_ptau_check_lagrange; the header has the equation).  Per section and set of levels, the left side is
 // lincomb_kernel over the Lagrange points with the 128-bit rho of their slots, as above.  The right side multiplies the
@@ -403,12 +406,6 @@ int contribute(const uint8_t* zkey, size_t len, const char* name, const uint8_t*
 
 // ---- verification -----------------------------------------------------------------------------------------------------------
 
-// e(a1, a2) = e(b1, b2)?  Stored points; `msg` is what the failure says.
-struct PairCheck {
-    const uint8_t *a1, *a2, *b1, *b2;
-    std::string msg;
-};
-
 // The host rules of record k of s (its transcript, no infinity, g2_spx in the subgroup); "" or what fails.  The record's two
 // pairing rules go to `checks`; g2_sp (stored) gets the record's challenge point and has to outlive the checks.
 std::string record_rules(const Section10& s, size_t k, const uint8_t* delta_prev, uint8_t* g2_sp, std::vector<PairCheck>& checks) {
@@ -718,11 +715,12 @@ Outcome outcome_of(int rc, gw_status_t& st) {
     return o;
 }
 
-// The six sums of the powers check for the domain n = 2^p, stored form: g1[5][64] = V, U, V_n, S_A, S_B and g2[128] = S_2.  T1 goes
-// through the device in two ranges, [0, n) and [n, 2n - 1), so that V_n is V's state between them; a piece of m points of a
-// range is uploaded with the point after it, and U's list is the same buffer one point on.
-bool powers_sums(const cwc_ptau::Plan& pl, const uint8_t seed[32], uint8_t* g1, uint8_t* g2, std::string& err) {
-    const uint64_t n = 1ull << pl.p;
+// The six sums of the powers check, stored form: g1[5][64] = V, U, V_n, S_A, S_B and g2[128] = S_2, over the first n points of
+// sections 3 to 5 and the first `pairs` points of section 2 with the point after each (2n - 1 for a setup's prefixes of the
+// domain n, 2n - 2 for a whole file of 2n - 1 points).  T1 goes through the device in two ranges, [0, n) and [n, pairs), so that
+// V_n is V's state between them; a piece of m points of a range is uploaded with the point after it, and U's list is the same
+// buffer one point on.
+bool powers_sums(const cwc_ptau::Plan& pl, uint64_t n, uint64_t pairs, const uint8_t seed[32], uint8_t* g1, uint8_t* g2, std::string& err) {
     const uint64_t chunk = std::max<uint64_t>(1, std::min(chunk_points(), n));
     const uint32_t blocks1 = blocks_for(chunk, LC_THREADS<G1>), blocks2 = blocks_for(chunk, LC_THREADS<G2>);
     Stream s;
@@ -752,7 +750,7 @@ bool powers_sums(const cwc_ptau::Plan& pl, const uint8_t seed[32], uint8_t* g1, 
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(s);  // rho is refilled for the next piece
     };
-    const uint64_t ends[2] = {n, 2 * n - 1};  // T1: V and U over [0, n), V_n = V there, then [n, 2n - 1)
+    const uint64_t ends[2] = {n, pairs};  // T1: V and U over [0, n), V_n = V there, then [n, pairs)
     for (int range = 0; range < 2 && e == hipSuccess; ++range) {
         for (uint64_t at = range ? n : 0; at < ends[range] && e == hipSuccess; at += chunk)
             piece1(pl.t1, nullptr, at, (uint32_t)std::min<uint64_t>(chunk, ends[range] - at), acc1);
@@ -784,6 +782,36 @@ bool powers_sums(const cwc_ptau::Plan& pl, const uint8_t seed[32], uint8_t* g1, 
     return true;
 }
 
+}  // namespace
+
+// The six sums (kept in `keep`, which has to outlive the checks) and the five equations of the powers check over the lengths of
+// powers_sums; whole: the lengths are a whole file's, and the messages say so.  The equations go to `checks`; host_verdict: the
+// first of them that fails without a pairing.
+bool cwc_contrib::powers_rules(const cwc_ptau::Plan& pl, uint64_t n, uint64_t pairs, bool whole, const uint8_t seed[32], PowersSums& keep,
+                               std::vector<PairCheck>& checks, std::string& host_verdict, std::string& err) {
+    if (!powers_sums(pl, n, pairs, seed, keep.g1, keep.s2, err)) return false;
+    const Generators gen;
+    memcpy(keep.gen1, gen.g1, G1_BYTES);
+    memcpy(keep.gen2, gen.g2, G2_BYTES);
+    const uint8_t *V = keep.g1, *U = V + G1_BYTES, *Vn = V + 2 * G1_BYTES, *SA = V + 3 * G1_BYTES, *SB = V + 4 * G1_BYTES;
+    const uint8_t* t2_1 = pl.t2 + G2_BYTES;
+    const std::string first2n = whole ? "the points" : "the first 2n points", firstn = whole ? "the points" : "the first n points";
+    const struct {
+        const uint8_t *a1, *a2, *b1, *b2;
+        std::string msg;
+    } eqs[5] = {{U, keep.gen2, V, t2_1, "ptau: section 2 (tauG1): " + first2n + " are not consecutive powers of the tau of section 3"},
+                {keep.gen1, keep.s2, Vn, keep.gen2, "ptau: section 3 (tauG2): " + firstn + " are not the powers of the tau of section 2"},
+                {SA, keep.gen2, pl.at, keep.s2, "ptau: section 4 (alphaTauG1): " + firstn + " are not alphaTauG1[0] times the powers of tau"},
+                {SB, keep.gen2, pl.bt, keep.s2, "ptau: section 5 (betaTauG1): " + firstn + " are not betaTauG1[0] times the powers of tau"},
+                {pl.bt, keep.gen2, keep.gen1, pl.beta2, "ptau: section 6 (betaG2): the point is not the G2 generator times the beta of betaTauG1[0]"}};
+    for (int i = 0; i < 5 && host_verdict.empty(); ++i) host_verdict = pair_rule(eqs[i].a1, eqs[i].a2, eqs[i].b1, eqs[i].b2, eqs[i].msg, checks);
+    return true;
+}
+bool cwc_contrib::run_pair_checks(const std::vector<PairCheck>& checks, std::string& verdict, std::string& err) { return run_checks(checks, verdict, err); }
+bool cwc_contrib::seed_or_draw(const uint8_t* in, uint8_t seed[32]) { return take_seed(in, seed); }
+
+namespace {
+
 // gwb_ptau_check_powers: rc 0, 1 (msg: the verdict) or 2
 Outcome check_powers(const uint8_t* data, size_t len, uint32_t domain_power, const uint8_t* seed_in) {
     std::string err;
@@ -797,22 +825,10 @@ Outcome check_powers(const uint8_t* data, size_t len, uint32_t domain_power, con
     if (sub.rc != 0) return {sub.msg.find("order-r subgroup") != std::string::npos ? 1 : 2, sub.msg};  // its other refusals were made above
     uint8_t seed[32];
     if (!take_seed(seed_in, seed)) return {2, "ptau: getrandom failed"};
-    uint8_t g1[5 * G1_BYTES], s2[G2_BYTES];
-    if (!powers_sums(pl, seed, g1, s2, err)) return {2, err};
-    const uint8_t *V = g1, *U = g1 + G1_BYTES, *Vn = g1 + 2 * G1_BYTES, *SA = g1 + 3 * G1_BYTES, *SB = g1 + 4 * G1_BYTES;
-    const Generators gen;
-    const uint8_t* t2_1 = pl.t2 + G2_BYTES;
-    const struct {
-        const uint8_t *a1, *a2, *b1, *b2;
-        const char* msg;
-    } eqs[5] = {{U, gen.g2, V, t2_1, "ptau: section 2 (tauG1): the first 2n points are not consecutive powers of the tau of section 3"},
-                {gen.g1, s2, Vn, gen.g2, "ptau: section 3 (tauG2): the first n points are not the powers of the tau of section 2"},
-                {SA, gen.g2, pl.at, s2, "ptau: section 4 (alphaTauG1): the first n points are not alphaTauG1[0] times the powers of tau"},
-                {SB, gen.g2, pl.bt, s2, "ptau: section 5 (betaTauG1): the first n points are not betaTauG1[0] times the powers of tau"},
-                {pl.bt, gen.g2, gen.g1, pl.beta2, "ptau: section 6 (betaG2): the point is not the G2 generator times the beta of betaTauG1[0]"}};
+    PowersSums sums;
     std::vector<PairCheck> checks;
     std::string host_verdict, verdict;
-    for (int i = 0; i < 5 && host_verdict.empty(); ++i) host_verdict = pair_rule(eqs[i].a1, eqs[i].a2, eqs[i].b1, eqs[i].b2, eqs[i].msg, checks);
+    if (!powers_rules(pl, 1ull << pl.p, (2ull << pl.p) - 1, false, seed, sums, checks, host_verdict, err)) return {2, err};
     if (!run_checks(checks, verdict, err)) return {2, err};
     if (verdict.empty()) verdict = host_verdict;
     return {verdict.empty() ? 0 : 1, verdict};

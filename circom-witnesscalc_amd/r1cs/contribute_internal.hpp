@@ -9,6 +9,7 @@
 
 #include "bn254_points_gfx950.hpp"
 #include "groth16_internal.hpp"
+#include "ptau_internal.hpp"
 
 namespace cwc_contrib {
 
@@ -67,5 +68,27 @@ bool g2_stored_in_subgroup(const uint8_t* in);  // on the twist already; the cri
 // canonical little-endian bytes of a stored point, the C ABI's form (for the pairing and for the record dump)
 void canonical_g1(const uint8_t* stored, uint8_t* out);
 void canonical_g2(const uint8_t* stored, uint8_t* out);
+
+// ---- contribute.hip's checks, shared with the ceremony's verification (ceremony.hip) ---------------------------------------------
+
+// e(a1, a2) = e(b1, b2)?  Stored points; `msg` is what the failure says.
+struct PairCheck {
+    const uint8_t *a1, *a2, *b1, *b2;
+    std::string msg;
+};
+// Runs the pairings of `checks` in one batched launch; verdict = the message of the first check that fails, "" if none does.
+bool run_pair_checks(const std::vector<PairCheck>& checks, std::string& verdict, std::string& err);
+// the caller's 32 bytes, or without them 32 from getrandom()
+bool seed_or_draw(const uint8_t* in, uint8_t seed[32]);
+// The six sums of the powers check and the generators, stored form: what its five equations point into.
+struct PowersSums {
+    uint8_t g1[5 * G1_BYTES], s2[G2_BYTES], gen1[G1_BYTES], gen2[G2_BYTES];
+};
+
+// The six sums over the first n points of sections 3 to 5 and the first `pairs` points of section 2 with the point after each, and
+// the five equations of the powers check (graph_witness_groth16_ptau.h) into `checks`; `keep` has to outlive them.  whole: the
+// lengths are a whole file's and the messages say "the points".  host_verdict: the first equation that fails without a pairing.
+bool powers_rules(const cwc_ptau::Plan& pl, uint64_t n, uint64_t pairs, bool whole, const uint8_t seed[32], PowersSums& keep, std::vector<PairCheck>& checks,
+                  std::string& host_verdict, std::string& err);
 
 }  // namespace cwc_contrib

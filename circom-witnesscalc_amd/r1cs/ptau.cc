@@ -156,6 +156,13 @@ bool check_header_points(const Plan& pl, std::string& err) {
            check_points(6, pl.beta2, 0, 1, 0, 1, true, err);
 }
 
+bool check_all_points(const View& v, std::string& err) {
+    const uint64_t n = 1ull << v.power;
+    return check_points(2, v.sec[2].p, 0, 2 * n - 1, 0, 1, false, err) && check_points(3, v.sec[3].p, 0, n, 0, 1, true, err) &&
+           check_points(4, v.sec[4].p, 0, n, 0, 1, false, err) && check_points(5, v.sec[5].p, 0, n, 0, 1, false, err) &&
+           check_points(6, v.sec[6].p, 0, 1, 0, 1, true, err);
+}
+
 bool check_bulk_points(const Plan& pl, std::string& err) {
     const uint64_t n = 1ull << pl.p;
     if (pl.from_file)

@@ -42,6 +42,8 @@ bool plan(const View& v, uint32_t p, uint32_t mode, Plan& pl, std::string& err);
 bool check_header_points(const Plan& pl, std::string& err);
 // the bulk arrays, on the host (gwb_ptau_check; the setup checks them on the device)
 bool check_bulk_points(const Plan& pl, std::string& err);
+// every point of the monomial sections 2 to 6, on the host (the whole-file check of gwb_ptau_verify)
+bool check_all_points(const View& v, std::string& err);
 // "ptau: section 2 (tauG1) point 5 is not on the G1 curve"; SUBGROUP (subgroup.hip, G2 only): "... is not in the order-r subgroup
 // of G2"; NONE, which no caller should reach, says that host and device disagree
 std::string point_message(uint32_t section, uint64_t index, cwc_g16::PointFault fault, bool g2);

@@ -116,7 +116,8 @@ int gwb_zkey_verify_step(const void *prev, size_t prev_len, const void *next, si
  * "zkey verify: ..." where that function says "zkey: ...".  GWB_VERIFY_KEY_SKIP_RECORDS is for keys that carry snarkjs's
  * records, which this library cannot verify by design: their points are still checked against circuit, file and their own
  * delta, but then nothing shows who made that delta.
- * NOT verified: the ceremony's own contribution records in the `.ptau`; the file's points beyond the prefixes a setup reads;
+ * NOT verified: records made by snarkjs in the `.ptau` (gwb_ptau_verify of graph_witness_groth16_ceremony.h checks this
+ * library's); the file's points beyond the prefixes a setup reads (the same function checks the whole file);
  * sections 12 to 15 of the file, on which the verdict rests unless lagrange_mode is GWB_PTAU_LAGRANGE_COMPUTE; records made by
  * snarkjs.  seed: 32 bytes for rho (here and in rule 3), or NULL to draw them.  hashes_out and *n as for
  * gwb_zkey_verify_contributions, filled on success.  Returns 0; 1 when a rule failed, with a message that starts

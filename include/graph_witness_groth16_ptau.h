@@ -3,7 +3,8 @@
  * from the caller (graph_witness_groth16_setup.h is the setup from a known trapdoor).
  *
  * TRUST.  tau, alpha and beta are those of the ceremony behind the file: nobody knows them if one participant of that
- * ceremony was honest, and this library does not verify the ceremony's contribution records (no `powersoftau verify`);
+ * ceremony was honest, and this library does not verify records made by snarkjs (gwb_ptau_verify of
+ * graph_witness_groth16_ceremony.h checks its own, and the whole file);
  * gwb_ptau_check_powers checks, when asked, that the points a setup reads are powers of one tau at all.
  * gamma is 1, as in snarkjs.  delta is the caller's:
  *   delta = 1 gives the state of snarkjs `zkey new`: a key that is to be handed to a phase-2 ceremony, NOT to be used, since
@@ -98,8 +99,8 @@ int gwb_ptau_check_g2(const void *data, size_t len, uint32_t domain_power, uint3
  *   e(BT_0, G2) = e(G1, beta2)   "ptau: section 6 (betaG2): ..."
  * A side with a point at infinity is 1: one such side alone fails its equation, two pass.  A file with a wrong point among the
  * prefixes passes with probability about 2^-128 over the seed.  NOT checked: the points beyond the prefixes (tauG1[2n] may be
- * anything); the Lagrange sections 12 to 15; the ceremony's own contribution records in section 7, whose challenge derivation
- * (snarkjs's) cannot be restated here.  Returns 2 for anything that is not a verdict.  Synchronous, on the current device. */
+ * anything; gwb_ptau_verify of graph_witness_groth16_ceremony.h checks the whole file); the Lagrange sections 12 to 15; records
+ * made by snarkjs in section 7, whose challenge derivation cannot be restated here.  Returns 2 for anything that is not a verdict.  Synchronous, on the current device. */
 int gwb_ptau_check_powers(const void *data, size_t len, uint32_t domain_power, const uint8_t *seed, gw_status_t *status);
 
 /* What `powersoftau prepare phase2` does: the file with its Lagrange sections 12 to 15 made on the current device from its
