@@ -648,6 +648,13 @@ def r1cs_lib():
         L.gwb_ptau_verify_step.argtypes = [vp, sz, vp, sz, vp, stp]
         L.gwb_bn254_g1_mul_batch_device.argtypes = [vp, vp, sz, u32, u32, vp, vp, stp]
         L.gwb_bn254_g2_mul_batch_device.argtypes = [vp, vp, sz, u32, u32, vp, vp, stp]
+        L.gwb_ptau_beacon.argtypes = [vp, sz, ctypes.c_char_p, vp, sz, u32, ctypes.POINTER(vp), ctypes.POINTER(sz), vp, stp]
+        L.gwb_groth16_beacon.argtypes = [vp, sz, ctypes.c_char_p, vp, sz, u32, ctypes.POINTER(vp), ctypes.POINTER(sz), vp, stp]
+        L.gwb_beacon_scalars.argtypes = [u32, vp, sz, u32, vp]
+        L.gwb_ptau_contribution_params.argtypes = [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
+        L.gwb_zkey_contribution_params.argtypes = [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
+        L.gwb_sha256.restype = None
+        L.gwb_sha256.argtypes = [vp, sz, vp]
         _r1cs_lib = L
     return _r1cs_lib
 
@@ -1233,11 +1240,100 @@ def groth16_contribute_phase_ms():
     return dict(zip(GROTH16_CONTRIBUTE_PHASES, (float(x) for x in ms)))
 
 
+# -- the random beacon of both phases (include/graph_witness_groth16_beacon.h) ---------------------------------------------------
+def _beacon_call(call, addr, n_in, beacon_hash, iterations_exp, name):
+    nm = name.encode("utf-8") if isinstance(name, str) else bytes(name)
+    if b"\0" in nm:
+        raise WitnessCalcError("the name holds a zero byte")
+    digest_in = bytes(beacon_hash)
+    e = int(iterations_exp)
+    if not 0 <= e < (1 << 32):
+        raise WitnessCalcError("beacon: numIterationsExp %d is not in [10, 63]" % e)
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    digest = ctypes.create_string_buffer(CONTRIBUTION_HASH_BYTES)
+    st = GwStatus()
+    rc = call(addr, n_in, nm, digest_in, len(digest_in), e, ctypes.byref(out), ctypes.byref(n), digest, ctypes.byref(st))
+    _r1cs_check(rc, st)
+    return _take_image(out, n), digest.raw
+
+
+def groth16_beacon(zkey, beacon_hash, iterations_exp, name=""):
+    """The random beacon that closes phase 2 (snarkjs `zkey beacon`; synchronous, on the GPU): `.zkey` bytes -> (new `.zkey`
+    bytes, the 64-byte hash of the new record).  It is the contribution of groth16_contribute whose secret and nonce nobody
+    chooses: both are derived from beacon_hash (bytes, 1 to 255 of them: a value that did not exist when the last participant
+    contributed) by 2^iterations_exp chained SHA-256 on the host, 10 <= iterations_exp <= min(63, CWC_BEACON_MAX_EXP, default
+    28).  The record has type 1 and carries both parameters, so anybody can recompute it, and the verifications do; two runs
+    give identical bytes.  The derivation is this library's own: snarkjs does not accept the record."""
+    data = bytes(zkey)
+    return _beacon_call(r1cs_lib().gwb_groth16_beacon, data, len(data), beacon_hash, iterations_exp, name)
+
+
+def ptau_beacon(ptau, beacon_hash, iterations_exp, name=""):
+    """The random beacon that closes phase 1 (snarkjs `powersoftau beacon`; synchronous, on the GPU): a `.ptau` image -> (new
+    `.ptau` bytes, the new record's nextChallenge).  The contribution of ptau_contribute with tau', alpha', beta' and the three
+    nonces derived from beacon_hash and iterations_exp as for groth16_beacon; prepared sections are dropped as there."""
+    keep, addr, n_in = _ptau_buffer(ptau)
+    try:
+        return _beacon_call(r1cs_lib().gwb_ptau_beacon, addr, n_in, beacon_hash, iterations_exp, name)
+    finally:
+        del keep
+
+
+def beacon_scalars(phase, beacon_hash, iterations_exp):
+    """Host only, for audit: the scalars a beacon derives, as ints in [1, r): phase 1 -> [tau', alpha', beta', s_0, s_1, s_2],
+    phase 2 -> [delta', s].  They are public."""
+    digest_in = bytes(beacon_hash)
+    count = {1: 6, 2: 2}.get(phase)
+    e = int(iterations_exp)
+    out = ctypes.create_string_buffer(32 * 6)
+    if count is None or not 0 <= e < (1 << 32) or r1cs_lib().gwb_beacon_scalars(phase, digest_in, len(digest_in), e, out) != 0:
+        raise WitnessCalcError("beacon: phase 1 or 2, a beaconHash of 1 to 255 bytes and numIterationsExp in [10, 63] and at most "
+                               "CWC_BEACON_MAX_EXP expected")
+    return [int.from_bytes(out.raw[32 * j:32 * j + 32], "little") for j in range(count)]
+
+
+def sha256(data):
+    """SHA-256 by the library's host code, the link of the beacon's hash chain (an aid beside gwb_blake2b512)."""
+    data = bytes(data)
+    out = ctypes.create_string_buffer(32)
+    r1cs_lib().gwb_sha256(data, len(data), out)
+    return out.raw
+
+
+def _beacon_items(call, addr, n_in, k, typ):
+    """(iterations_exp, beacon_hash) of record k from its raw parameters (items 02 and 03; the last of each), each None when
+    the record has no such item; (None, None) for a record of type 0."""
+    if typ != 1:
+        return None, None
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    st = GwStatus()
+    rc = call(addr, n_in, k, ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
+    _r1cs_check(rc, st)
+    par = _take_image(out, n)
+    exp, digest, i = None, None, 0
+    while i < len(par):  # the section's reader has checked the items' lengths
+        tag = par[i]
+        if tag == 2:
+            exp = par[i + 1]
+            i += 2
+        else:
+            if tag == 3:
+                digest = par[i + 2:i + 2 + par[i + 1]]
+            i += 2 + par[i + 1]
+    return exp, digest
+
+
+def _require_beacon(records, what):
+    if not records or records[-1]["type"] != 1:
+        raise WitnessCalcError("%s: the last contribution is not a beacon" % what)
+
+
 def zkey_contributions(zkey):
     """Section 10 of a `.zkey` (host only): {"cs_hash", "contributions": [{"name", "type", "delta_after", "g1_s", "g1_sx",
-    "g2_spx", "transcript", "hash"}]}.  Points are canonical little-endian bytes (64 for G1, 128 for G2: x.c0, x.c1, y.c0,
-    y.c1), type is 0 (contribution) or 1 (beacon), hash is what the participant published.  Nothing is verified beyond the
-    section's form; a malformed section raises with a message starting "zkey: section 10"."""
+    "g2_spx", "transcript", "hash", "iterations_exp", "beacon_hash"}]}.  Points are canonical little-endian bytes (64 for G1,
+    128 for G2: x.c0, x.c1, y.c0, y.c1), type is 0 (contribution) or 1 (beacon), hash is what the participant published,
+    iterations_exp and beacon_hash are a beacon's parameters (None for type 0).  Nothing is verified beyond the section's
+    form; a malformed section raises with a message starting "zkey: section 10"."""
     data = bytes(zkey)
     out, n = ctypes.c_void_p(), ctypes.c_size_t()
     st = GwStatus()
@@ -1249,28 +1345,34 @@ def zkey_contributions(zkey):
         r1cs_lib().gwb_groth16_setup_free(out)
     count = int.from_bytes(img[64:68], "little")
     off, recs = 68, []
-    for _ in range(count):
+    for k in range(count):
         fixed = img[off:off + 448]
         typ, name_len = (int.from_bytes(img[off + 448 + 4 * i:off + 452 + 4 * i], "little") for i in range(2))
         off += 456
         recs.append({"name": img[off:off + name_len].decode("utf-8", "replace"), "type": typ, "delta_after": fixed[:64], "g1_s": fixed[64:128],
                      "g1_sx": fixed[128:192], "g2_spx": fixed[192:320], "transcript": fixed[320:384], "hash": fixed[384:448]})
+        recs[-1]["iterations_exp"], recs[-1]["beacon_hash"] = _beacon_items(r1cs_lib().gwb_zkey_contribution_params, data, len(data), k, typ)
         off += name_len
     return {"cs_hash": img[:64], "contributions": recs}
 
 
-def groth16_verify_contributions(zkey):
+def groth16_verify_contributions(zkey, require_beacon=False):
     """Checks every contribution record of a key on the GPU and returns their hashes, oldest first ([] for a key without
     records, whose delta must then be the generator).  Raises WitnessCalcError naming the first failing record and rule, for
     example "zkey: contribution 2: deltaAfter is not deltaPrev times the proven secret".  This checks the chain of deltas; it does not compare the key with its circuit or
-    its powers-of-tau file: groth16_verify_key does."""
+    its powers-of-tau file: groth16_verify_key does.  A beacon record's key must be the one its parameters derive.
+    require_beacon=True additionally raises "zkey: the last contribution is not a beacon" for an accepted key that does not
+    end on one."""
     data = bytes(zkey)
-    room = len(zkey_contributions(data)["contributions"])
+    records = zkey_contributions(data)["contributions"]
+    room = len(records)
     hashes = ctypes.create_string_buffer(max(1, room * CONTRIBUTION_HASH_BYTES))
     n = ctypes.c_size_t(room)
     st = GwStatus()
     rc = r1cs_lib().gwb_zkey_verify_contributions(data, len(data), hashes, ctypes.byref(n), ctypes.byref(st))
     _r1cs_check(rc, st)
+    if require_beacon:
+        _require_beacon(records, "zkey")
     return [hashes.raw[64 * k:64 * k + 64] for k in range(n.value)]
 
 
@@ -1520,18 +1622,18 @@ def ptau_contributions(ptau):
     """Section 7 of a `.ptau` (host only): [{"name", "type", the five after-values "tau_g1", "tau_g2", "alpha_g1", "beta_g1",
     "beta_g2", the nine key points "tau_g1_s", "tau_g1_sx", ..., "beta_g2_spx", "next_challenge"}], oldest first.  Points are
     canonical little-endian bytes (64 for G1, 128 for G2: x.c0, x.c1, y.c0, y.c1), type is 0 (contribution) or 1 (beacon),
-    next_challenge is the hash the participant published.  Nothing is verified beyond the section's form; a malformed section
-    raises with a message starting "ptau: section 7"."""
+    next_challenge is the hash the participant published; "iterations_exp" and "beacon_hash" are a beacon's parameters (None
+    for type 0).  Nothing is verified beyond the section's form; a malformed section raises with a message starting "ptau:
+    section 7"."""
     keep, addr, n_in = _ptau_buffer(ptau)
     out, n = ctypes.c_void_p(), ctypes.c_size_t()
     st = GwStatus()
     rc = r1cs_lib().gwb_ptau_contributions(addr, n_in, ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
-    del keep
     _r1cs_check(rc, st)
     img = _take_image(out, n)
     count = int.from_bytes(img[:4], "little")
     off, recs = 4, []
-    for _ in range(count):
+    for k in range(count):
         rec = {}
         for key, size in PTAU_RECORD_POINTS:
             rec[key] = img[off:off + size]
@@ -1541,11 +1643,13 @@ def ptau_contributions(ptau):
         off += 72
         rec["name"] = img[off:off + name_len].decode("utf-8", "replace")
         off += name_len
+        rec["iterations_exp"], rec["beacon_hash"] = _beacon_items(r1cs_lib().gwb_ptau_contribution_params, addr, n_in, k, rec["type"])
         recs.append(rec)
+    del keep
     return recs
 
 
-def ptau_verify(ptau, records=True, seed=None):
+def ptau_verify(ptau, records=True, seed=None, require_beacon=False):
     """Verifies a ceremony file on the GPU (synchronous) and returns the hashes of its records, oldest first.  Every record is
     checked against the one before it (its challenge, its three proofs of knowledge, its after-values; the first against the
     generators), the last record's after-values against the file's points, and then the whole file: every tauG2 in the order-r
@@ -1553,7 +1657,9 @@ def ptau_verify(ptau, records=True, seed=None):
     pairing equations (a wrong point passes with probability about 2^-128 over the seed).  records=False passes over section 7:
     for files that carry snarkjs's records, which this library cannot verify.  seed: 32 bytes for a reproducible check, or None
     to draw them.  Raises WitnessCalcError naming the first failing record and rule, or the section, for example "ptau:
-    contribution 2: alphaG1 is not the previous alphaG1 times the proven secret"."""
+    contribution 2: alphaG1 is not the previous alphaG1 times the proven secret".  A beacon record's keys must be the ones
+    its parameters derive.  require_beacon=True additionally raises "ptau: the last contribution is not a beacon" for an accepted
+    file that does not end on one."""
     seed = _seed32(seed)
     keep, addr, n_in = _ptau_buffer(ptau)
     room = ptau_info(ptau)["n_contributions"]
@@ -1563,6 +1669,8 @@ def ptau_verify(ptau, records=True, seed=None):
     rc = r1cs_lib().gwb_ptau_verify(addr, n_in, 0 if records else PTAU_VERIFY_SKIP_RECORDS, seed, hashes, ctypes.byref(n), ctypes.byref(st))
     del keep
     _r1cs_check(rc, st)
+    if require_beacon:
+        _require_beacon(ptau_contributions(ptau), "ptau")
     return [hashes.raw[64 * k:64 * k + 64] for k in range(min(room, n.value))]
 
 
@@ -1621,7 +1729,7 @@ GROTH16_VERIFY_KEY_PHASES = ("remake", "lincomb", "pairings")
 VERIFY_KEY_SKIP_RECORDS, VERIFY_KEY_CHECK_PTAU = 1, 2
 
 
-def groth16_verify_key(zkey, r1cs, ptau, lagrange="compute", records=True, check_ptau=False, seed=None, check_lagrange=False):
+def groth16_verify_key(zkey, r1cs, ptau, lagrange="compute", records=True, check_ptau=False, seed=None, check_lagrange=False, require_beacon=False):
     """Checks on the GPU that `zkey` is the honest key of the R1cs and the powers-of-tau file (bytes or any buffer, an mmap
     included), with a delta that only its recorded contributions touched (what `snarkjs zkey verify` answers; synchronous),
     and returns the contribution hashes, oldest first.  The key is remade from circuit and file with delta = 1; section 4 is
@@ -1637,11 +1745,13 @@ def groth16_verify_key(zkey, r1cs, ptau, lagrange="compute", records=True, check
     prepared sections), and its failure is the verdict: the prepared sections that the remake reads are then verified against
     the monomial ones, for much less than "compute" spends on making them again; with "compute" the flag has nothing to
     check.  Not verified: records made by snarkjs in the file, and its points beyond the prefixes a setup reads (ptau_verify
-    checks this library's records and the whole file)."""
+    checks this library's records and the whole file).  require_beacon=True additionally raises "zkey: the last contribution is
+    not a beacon" for an accepted key that does not end on one."""
     mode = _lagrange_mode(lagrange)
     seed = _seed32(seed)
     data = bytes(zkey)
-    room = len(zkey_contributions(data)["contributions"])
+    key_records = zkey_contributions(data)["contributions"]
+    room = len(key_records)
     if check_lagrange and lagrange != "compute" and (lagrange == "file" or ptau_info(ptau)["prepared"]):
         ptau_check_lagrange(ptau, r1cs.qap_info()["domain_power"], seed)
     hashes = ctypes.create_string_buffer(max(1, room * CONTRIBUTION_HASH_BYTES))
@@ -1652,6 +1762,8 @@ def groth16_verify_key(zkey, r1cs, ptau, lagrange="compute", records=True, check
     rc = r1cs_lib().gwb_zkey_verify_key(data, len(data), r1cs._h, addr, n_in, mode, flags, seed, hashes, ctypes.byref(n), ctypes.byref(st))
     del keep
     _r1cs_check(rc, st)
+    if require_beacon:
+        _require_beacon(key_records, "zkey")
     return [hashes.raw[64 * k:64 * k + 64] for k in range(n.value)]
 
 

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/graph_witness_groth16_beacon.h"
 #include "../../include/graph_witness_groth16_ceremony.h"
 #include "binfile.hpp"
 #include "bn254_points_gfx950.hpp"
@@ -352,6 +353,32 @@ int gwb_ptau_contributions(const void* ptau, size_t len, void** out, size_t* out
     } catch (const std::bad_alloc&) {
         return cwc_ceremony::fail2(status, "ptau: out of host memory");
     }
+}
+
+int gwb_ptau_contribution_params(const void* ptau, size_t len, size_t k, void** out, size_t* out_len, gw_status_t* status) {
+    using cwc_ceremony::fail2;
+    if (!out || !out_len || (!ptau && len)) return fail2(status, "gwb_ptau_contribution_params: NULL argument");
+    *out = nullptr;
+    *out_len = 0;
+    try {
+        std::string err;
+        cwc_ptau::View view;
+        cwc_ceremony::Section7 s;
+        if (!cwc_ptau::parse((const uint8_t*)ptau, len, view, err) || !cwc_ceremony::parse_section7(view.sec[7].p, view.sec[7].size, s, err))
+            return fail2(status, err);
+        if (k >= s.recs.size())
+            return fail2(status, "ptau: there is no contribution " + std::to_string(k + 1) + " (the file has " + std::to_string(s.recs.size()) + ")");
+        const std::vector<uint8_t>& par = s.recs[k].params;
+        void* buf = malloc(par.size() ? par.size() : 1);
+        if (!buf) return fail2(status, "ptau: out of host memory");
+        if (!par.empty()) memcpy(buf, par.data(), par.size());
+        *out = buf;
+        *out_len = par.size();
+    } catch (const std::bad_alloc&) {
+        return fail2(status, "ptau: out of host memory");
+    }
+    cwc_r1cs::set_ok(status);
+    return 0;
 }
 
 }  // extern "C"

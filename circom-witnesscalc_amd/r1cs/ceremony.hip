@@ -1,6 +1,6 @@
 // A powers-of-tau ceremony on gfx950 (include/graph_witness_groth16_ceremony.h has the definitions): the batched point
 // multiplication out[i] = s_i P_i with a scalar of its own per point, its scalars c tau'^(first + i), and the contribution to a
-// `.ptau` that is built from the two.  Section 7, the transcript and the new file are ceremony.cc's (ceremony_internal.hpp);
+// `.ptau` that is built from the two, and the beacon, which is that contribution at the scalars of beacon.hpp.  Section 7, the transcript and the new file are ceremony.cc's (ceremony_internal.hpp);
 // the conversion to affine bytes is setup.hip's, through its enqueue functions.
 //
 // mul_points_kernel<T, METHOD>, one point per thread.  METHOD 1 (plain) is fq_gfx950.hpp's xyzz_mul_short: with a scalar of its
@@ -50,7 +50,9 @@
 #include <type_traits>
 #include <vector>
 
+#include "../../include/graph_witness_groth16_beacon.h"
 #include "../../include/graph_witness_groth16_ceremony.h"
+#include "beacon.hpp"
 #include "bn254_points_gfx950.hpp"
 #include "ceremony_internal.hpp"
 #include "contribute_internal.hpp"
@@ -410,27 +412,20 @@ bool draw_nonzero(Fr& x, std::string& err) {
     return true;
 }
 
-int contribute(const uint8_t* ptau, size_t len, const char* name, const uint8_t* secrets96, void** out, size_t* out_len, uint8_t* hash64, gw_status_t* status) {
+// The file and its section 7 as a contribution or a beacon reads them, before the device is touched; 0, or 2 with the message.
+int read_input(const uint8_t* ptau, size_t len, cwc_ptau::View& view, Section7& s7, gw_status_t* status) {
     std::string err;
-    cwc_ptau::View view;
-    Section7 s7;
     if (!cwc_ptau::parse(ptau, len, view, err) || !parse_section7(view.sec[7].p, view.sec[7].size, s7, err)) return fail2(status, err);
     if (point_fault<G2>(view.sec[6].p, false) != PointFault::NONE)
         return fail2(status, cwc_ptau::point_message(6, 0, point_fault<G2>(view.sec[6].p, false), true));
-    const std::string nm = name ? name : "";
-    if (nm.size() > GWB_CONTRIBUTION_NAME_MAX) return fail2(status, "ptau contribute: the name has " + std::to_string(nm.size()) + " bytes, 255 at the most");
-    Secrets sec;
-    static const char* which[3] = {"tau", "alpha", "beta"};
-    for (int j = 0; j < 3; ++j) {
-        if (secrets96) {
-            memcpy(sec.x[j].v, secrets96 + 32 * j, 32);
-            if (cwc::u256_is_zero(sec.x[j]) || !cwc::u256_lt(sec.x[j], cwc::fr_p()))
-                return fail2(status, std::string("ptau contribute: the secret ") + which[j] + " is not in [1, r)");
-        } else if (!draw_nonzero(sec.x[j], err)) {
-            return fail2(status, err);
-        }
-        if (!draw_nonzero(sec.nonce[j], err)) return fail2(status, err);
-    }
+    return 0;
+}
+
+// The one path of a contribution and of a beacon: the secrets sec.x and the nonces sec.nonce, both in [1, r), are applied to the
+// parsed file, and the record of the given type with the given parameters is appended.
+int apply(const cwc_ptau::View& view, Section7& s7, Secrets& sec, uint32_t type, const std::vector<uint8_t>& params, const std::string& nm, void** out,
+          size_t* out_len, uint8_t* hash64, gw_status_t* status) {
+    std::string err;
     for (int j = 0; j < 3; ++j) {
         sec.tab[j][0] = cwc::fr_to_mont(sec.x[0]);
         for (uint32_t b = 1; b < POW_BITS; ++b) sec.tab[j][b] = cwc::fr_mul(sec.tab[j][b - 1], sec.tab[j][b - 1]);
@@ -487,8 +482,8 @@ int contribute(const uint8_t* ptau, size_t len, const char* name, const uint8_t*
         put_stored(sp, key_challenge_point(challenge, j, rec.g1_s[j], rec.g1_sx[j]));
         g2_mul_stored(sp, sec.x[j], rec.g2_spx[j]);
     }
-    rec.type = 0;
-    rec.params = name_params(nm);
+    rec.type = type;
+    rec.params = params;
     rec.name = nm;
     next_challenge(challenge, rec, rec.next_challenge);
     memcpy(hash64, rec.next_challenge, HASH_BYTES);
@@ -496,6 +491,48 @@ int contribute(const uint8_t* ptau, size_t len, const char* name, const uint8_t*
 
     const uint8_t* bodies[5] = {t1.data(), t2.data(), at.data(), bt.data(), beta2};
     return write_contributed(view, bodies, s7, out, out_len, status);
+}
+
+int contribute(const uint8_t* ptau, size_t len, const char* name, const uint8_t* secrets96, void** out, size_t* out_len, uint8_t* hash64, gw_status_t* status) {
+    std::string err;
+    cwc_ptau::View view;
+    Section7 s7;
+    if (read_input(ptau, len, view, s7, status) != 0) return 2;
+    const std::string nm = name ? name : "";
+    if (nm.size() > GWB_CONTRIBUTION_NAME_MAX) return fail2(status, "ptau contribute: the name has " + std::to_string(nm.size()) + " bytes, 255 at the most");
+    Secrets sec;
+    static const char* which[3] = {"tau", "alpha", "beta"};
+    for (int j = 0; j < 3; ++j) {
+        if (secrets96) {
+            memcpy(sec.x[j].v, secrets96 + 32 * j, 32);
+            if (cwc::u256_is_zero(sec.x[j]) || !cwc::u256_lt(sec.x[j], cwc::fr_p()))
+                return fail2(status, std::string("ptau contribute: the secret ") + which[j] + " is not in [1, r)");
+        } else if (!draw_nonzero(sec.x[j], err)) {
+            return fail2(status, err);
+        }
+        if (!draw_nonzero(sec.nonce[j], err)) return fail2(status, err);
+    }
+    return apply(view, s7, sec, 0, name_params(nm), nm, out, out_len, hash64, status);
+}
+
+// A beacon is the contribution whose secrets and nonces its parameters give (beacon.hpp); they are public, so that the zeroing
+// of `Secrets` protects nothing here.
+int beacon(const uint8_t* ptau, size_t len, const char* name, const uint8_t* hash, size_t hash_len, uint32_t exp, void** out, size_t* out_len, uint8_t* hash64,
+           gw_status_t* status) {
+    const std::string nm = name ? name : "";
+    const std::string fault = cwc_beacon::argument_fault(nm.size(), hash_len, exp, cwc_beacon::limit());
+    if (!fault.empty()) return fail2(status, fault);
+    cwc_ptau::View view;
+    Section7 s7;
+    if (read_input(ptau, len, view, s7, status) != 0) return 2;
+    Fr derived[cwc_beacon::PHASE1_SCALARS];
+    cwc_beacon::scalars(1, hash, hash_len, exp, derived);
+    Secrets sec;
+    for (int j = 0; j < 3; ++j) {
+        sec.x[j] = derived[j];
+        sec.nonce[j] = derived[3 + j];
+    }
+    return apply(view, s7, sec, 1, cwc_beacon::write_params(nm, exp, hash, hash_len), nm, out, out_len, hash64, status);
 }
 
 // ---- verification -------------------------------------------------------------------------------------------------------------
@@ -561,6 +598,19 @@ std::string record_rules(const Section7& s, size_t k, const uint8_t challenge[HA
                           who + secret[j] + "G1 is not the previous " + secret[j] + "G1 times the proven secret"});
     checks.push_back({r.tau_g1, gen.g2, gen.g1, r.tau_g2, who + "tauG2 is not the G2 generator times tauG1's scalar"});
     checks.push_back({r.beta_g1, gen.g2, gen.g1, r.beta_g2, who + "betaG2 is not the G2 generator times betaG1's scalar"});
+    if (r.type == 1) {  // the beacon rule: the keys' G1 points are those of the derived secrets and nonces; the pairings above fix the rest
+        const cwc_beacon::Form f = cwc_beacon::form_of(r.params, cwc_beacon::MAX_EXP);  // form and limit were checked before the device
+        if (f.rc != 0) return who + f.msg;
+        Fr derived[cwc_beacon::PHASE1_SCALARS];
+        cwc_beacon::scalars(1, f.items.hash, f.items.hash_len, f.items.exp, derived);
+        for (uint32_t j = 0; j < 3; ++j) {
+            uint8_t g1_s[G1_BYTES], g1_sx[G1_BYTES];
+            g1_mul_stored(gen.g1, derived[3 + j], g1_s);
+            g1_mul_stored(g1_s, derived[j], g1_sx);
+            if (memcmp(g1_s, r.g1_s[j], G1_BYTES) != 0 || memcmp(g1_sx, r.g1_sx[j], G1_BYTES) != 0)
+                return who + "the key of secret " + secret[j] + " is not the one its beaconHash and numIterationsExp give";
+        }
+    }
     return "";
 }
 
@@ -621,6 +671,10 @@ Outcome verify(const uint8_t* ptau, size_t len, uint32_t flags, const uint8_t* s
     Section7 s7;
     if (!cwc_ptau::parse(ptau, len, view, err) || !parse_section7(view.sec[7].p, view.sec[7].size, s7, err) || !cwc_ptau::check_all_points(view, err))
         return {2, err};
+    if (!(flags & GWB_PTAU_VERIFY_SKIP_RECORDS)) {
+        const int rc = cwc_beacon::forms_of(s7.recs, 0, "ptau", err);
+        if (rc != 0) return {rc, err};
+    }
     const size_t n = s7.recs.size();
     const Generators gen;
     std::vector<PairCheck> checks;
@@ -671,6 +725,7 @@ Outcome verify_step(const uint8_t* prev_bytes, size_t prev_len, const uint8_t* n
             return {1, "ptau step: section 7: contribution " + std::to_string(k + 1) + " is not the previous file's"};
         }
     }
+    if (const int rc = cwc_beacon::forms_of(sb.recs, sb.recs.size() - 1, "ptau", err)) return {rc, err};  // the new record, if it is a beacon
     const Anchors before = anchors_of(prev);
     const struct {
         const char* name;
@@ -744,6 +799,18 @@ int gwb_ptau_contribute(const void* ptau, size_t len, const char* name, const ui
         return contribute((const uint8_t*)ptau, len, name, secrets, out, out_len, (uint8_t*)hash64, status);
     } catch (const std::bad_alloc&) {
         return fail2(status, "ptau contribute: out of host memory");
+    }
+}
+
+int gwb_ptau_beacon(const void* ptau, size_t len, const char* name, const void* beacon_hash, size_t hash_len, uint32_t iterations_exp, void** out,
+                    size_t* out_len, void* hash64, gw_status_t* status) {
+    if (!out || !out_len || !hash64 || (!ptau && len) || (!beacon_hash && hash_len)) return fail2(status, "gwb_ptau_beacon: NULL argument");
+    *out = nullptr;
+    *out_len = 0;
+    try {
+        return beacon((const uint8_t*)ptau, len, name, (const uint8_t*)beacon_hash, hash_len, iterations_exp, out, out_len, (uint8_t*)hash64, status);
+    } catch (const std::bad_alloc&) {
+        return fail2(status, "beacon: out of host memory");
     }
 }
 

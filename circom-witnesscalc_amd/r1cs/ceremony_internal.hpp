@@ -30,7 +30,7 @@ struct PtauRecord {
     uint8_t g1_s[3][G1_BYTES], g1_sx[3][G1_BYTES], g2_spx[3][G2_BYTES];
     uint8_t partial_hash[PARTIAL_HASH_BYTES] = {};  // snarkjs's saved hash state: zeros here, kept byte for byte in foreign records
     uint8_t next_challenge[HASH_BYTES];
-    uint32_t type = 0;            // 0 = contribution, 1 = beacon (kept, never made here)
+    uint32_t type = 0;            // 0 = contribution, 1 = beacon (beacon.hpp)
     std::vector<uint8_t> params;  // the tagged items, byte for byte
     std::string name;             // item 01 of params, if there is one
 };

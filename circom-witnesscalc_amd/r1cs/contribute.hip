@@ -60,10 +60,12 @@
 #include <type_traits>
 #include <vector>
 
+#include "../../include/graph_witness_groth16_beacon.h"
 #include "../../include/graph_witness_groth16_contribute.h"
 #include "../../include/graph_witness_groth16_ptau.h"
 #include "../../include/graph_witness_groth16_setup.h"
 #include "../../include/graph_witness_groth16_verify.h"
+#include "beacon.hpp"
 #include "binfile.hpp"
 #include "bn254_points_gfx950.hpp"
 #include "contribute_internal.hpp"
@@ -314,24 +316,12 @@ void put_section(std::vector<uint8_t>& v, uint32_t id, const uint8_t* p, size_t 
 
 constexpr size_t HDR_DELTA1 = 84 + 2 * G1_BYTES + 2 * G2_BYTES, HDR_DELTA2 = HDR_DELTA1 + G1_BYTES;  // in section 2
 
-int contribute(const uint8_t* zkey, size_t len, const char* name, const uint8_t* delta, void** out, size_t* out_len, uint8_t* hash64,
-               gw_status_t* status) {
+// The one path of a contribution and of a beacon: the secret sec.delta and the nonce sec.s, both in [1, r), are applied to the
+// parsed key, and the record of the given type with the given parameters is appended.
+int apply(const Key& key, size_t len, Secrets& sec, uint32_t type, const std::vector<uint8_t>& params, const std::string& nm, void** out, size_t* out_len,
+          uint8_t* hash64, gw_status_t* status) {
     std::string err;
-    Key key;
-    if (!read_key(zkey, len, key, err)) return fail(status, err);
-    const std::string nm = name ? name : "";
-    if (nm.size() > GWB_CONTRIBUTION_NAME_MAX)
-        return fail(status, "groth16 contribute: the name has " + std::to_string(nm.size()) + " bytes, 255 at the most");
-    Secrets sec;
-    if (delta) {
-        memcpy(sec.delta.v, delta, 32);
-        if (cwc::u256_is_zero(sec.delta) || !cwc::u256_lt(sec.delta, cwc::fr_p())) return fail(status, "groth16 contribute: delta is not in [1, r)");
-    } else if (!draw_nonzero(sec.delta, err)) {
-        return fail(status, err);
-    }
     sec.delta_inv = cwc::fr_from_mont(cwc::fr_inv_fermat(cwc::fr_to_mont(sec.delta)));
-    if (!draw_nonzero(sec.s, err)) return fail(status, err);
-
     const gwb_zkey& z = *key.z;
     Section10 s10 = key.s10;
     if (s10.blank()) sections_hash(key.secs, s10.cs_hash);
@@ -346,8 +336,8 @@ int contribute(const uint8_t* zkey, size_t len, const char* name, const uint8_t*
     uint8_t delta2[G2_BYTES];
     g1_mul_stored(z.delta1, sec.delta, rec.delta_after);
     g2_mul_stored(z.delta2, sec.delta, delta2);
-    rec.type = 0;
-    rec.params = name_params(nm);
+    rec.type = type;
+    rec.params = params;
     rec.name = nm;
     record_hash(rec, hash64);
     s10.recs.push_back(rec);
@@ -404,6 +394,43 @@ int contribute(const uint8_t* zkey, size_t len, const char* name, const uint8_t*
     return 0;
 }
 
+int contribute(const uint8_t* zkey, size_t len, const char* name, const uint8_t* delta, void** out, size_t* out_len, uint8_t* hash64,
+               gw_status_t* status) {
+    std::string err;
+    Key key;
+    if (!read_key(zkey, len, key, err)) return fail(status, err);
+    const std::string nm = name ? name : "";
+    if (nm.size() > GWB_CONTRIBUTION_NAME_MAX)
+        return fail(status, "groth16 contribute: the name has " + std::to_string(nm.size()) + " bytes, 255 at the most");
+    Secrets sec;
+    if (delta) {
+        memcpy(sec.delta.v, delta, 32);
+        if (cwc::u256_is_zero(sec.delta) || !cwc::u256_lt(sec.delta, cwc::fr_p())) return fail(status, "groth16 contribute: delta is not in [1, r)");
+    } else if (!draw_nonzero(sec.delta, err)) {
+        return fail(status, err);
+    }
+    if (!draw_nonzero(sec.s, err)) return fail(status, err);
+    return apply(key, len, sec, 0, name_params(nm), nm, out, out_len, hash64, status);
+}
+
+// A beacon is the contribution whose secret and nonce its parameters give (beacon.hpp); they are public, so that the zeroing of
+// `Secrets` protects nothing here.  Every failure returns 2: none is a verdict.
+int beacon(const uint8_t* zkey, size_t len, const char* name, const uint8_t* hash, size_t hash_len, uint32_t exp, void** out, size_t* out_len,
+           uint8_t* hash64, gw_status_t* status) {
+    const std::string nm = name ? name : "";
+    const std::string fault = cwc_beacon::argument_fault(nm.size(), hash_len, exp, cwc_beacon::limit());
+    if (!fault.empty()) return fail2(status, fault);
+    std::string err;
+    Key key;
+    if (!read_key(zkey, len, key, err)) return fail2(status, err);
+    Fr derived[cwc_beacon::PHASE2_SCALARS];
+    cwc_beacon::scalars(2, hash, hash_len, exp, derived);
+    Secrets sec;
+    sec.delta = derived[0];
+    sec.s = derived[1];
+    return apply(key, len, sec, 1, cwc_beacon::write_params(nm, exp, hash, hash_len), nm, out, out_len, hash64, status) == 0 ? 0 : 2;
+}
+
 // ---- verification -----------------------------------------------------------------------------------------------------------
 
 // The host rules of record k of s (its transcript, no infinity, g2_spx in the subgroup); "" or what fails.  The record's two
@@ -425,6 +452,18 @@ std::string record_rules(const Section10& s, size_t k, const uint8_t* delta_prev
     put_stored(g2_sp, hash_to_g2(t));
     checks.push_back({r.g1_s, r.g2_spx, r.g1_sx, g2_sp, who + "g1_sx is not g1_s times the secret that g2_spx proves"});
     checks.push_back({delta_prev, r.g2_spx, r.delta_after, g2_sp, who + "deltaAfter is not deltaPrev times the proven secret"});
+    if (r.type == 1) {  // the beacon rule: g1_s and g1_sx are those of the derived secret and nonce; the pairings above fix the rest
+        const cwc_beacon::Form f = cwc_beacon::form_of(r.params, cwc_beacon::MAX_EXP);  // form and limit were checked before the device
+        if (f.rc != 0) return who + f.msg;
+        Fr derived[cwc_beacon::PHASE2_SCALARS];
+        cwc_beacon::scalars(2, f.items.hash, f.items.hash_len, f.items.exp, derived);
+        uint8_t gen1[G1_BYTES], g1_s[G1_BYTES], g1_sx[G1_BYTES];
+        put_stored(gen1, g1_generator());
+        g1_mul_stored(gen1, derived[1], g1_s);
+        g1_mul_stored(g1_s, derived[0], g1_sx);
+        if (memcmp(g1_s, r.g1_s, G1_BYTES) != 0 || memcmp(g1_sx, r.g1_sx, G1_BYTES) != 0)
+            return who + "the key is not the one its beaconHash and numIterationsExp give";
+    }
     return "";
 }
 
@@ -500,6 +539,7 @@ int verify_contributions(const uint8_t* zkey, size_t len, uint8_t* hashes_out, s
     Key key;
     if (!read_key(zkey, len, key, err)) return fail2(status, err);
     const Section10& s = key.s10;
+    if (const int rc = cwc_beacon::forms_of(s.recs, 0, "zkey", err)) return rc == 1 ? fail(status, err) : fail2(status, err);
     const size_t n = s.recs.size();
     const Generators gen;
     std::vector<PairCheck> checks;
@@ -675,6 +715,8 @@ int verify_step(const uint8_t* prev_bytes, size_t prev_len, const uint8_t* next_
     if (!read_key(next_bytes, next_len, next, err)) return fail2(status, "next key: " + err);
     std::string verdict = step_structure(prev, next);
     if (!verdict.empty()) return fail(status, verdict);
+    if (const int rc = cwc_beacon::forms_of(next.s10.recs, next.s10.recs.size() - 1, "zkey", err))  // the new record, if it is a beacon
+        return rc == 1 ? fail(status, err) : fail2(status, err);
     uint8_t seed[32];
     if (!take_seed(seed_in, seed)) return fail2(status, "zkey step: getrandom failed");
     const gwb_zkey &zp = *prev.z, &zn = *next.z;
@@ -1004,6 +1046,10 @@ Outcome verify_key(const uint8_t* zkey, size_t len, gwb_r1cs* r, const uint8_t* 
     // 1. parse
     Key key;
     if (!read_key(zkey, len, key, err)) return {2, err};
+    if (!(flags & GWB_VERIFY_KEY_SKIP_RECORDS)) {
+        const int rc = cwc_beacon::forms_of(key.s10.recs, 0, "zkey", err);
+        if (rc != 0) return {rc, rc == 1 ? as_key_verdict(err) : err};
+    }
     gw_status_t st{};
     gwb_r1cs_qap_info_t qi;
     if (gwb_r1cs_qap_info(r, &qi, &st) != 0) return {2, outcome_of(1, st).msg};
@@ -1140,6 +1186,18 @@ int gwb_groth16_contribute(const void* zkey, size_t len, const char* name, const
         return contribute((const uint8_t*)zkey, len, name, delta, out, out_len, (uint8_t*)hash64, status);
     } catch (const std::bad_alloc&) {
         return fail(status, "groth16 contribute: out of host memory");
+    }
+}
+
+int gwb_groth16_beacon(const void* zkey, size_t len, const char* name, const void* beacon_hash, size_t hash_len, uint32_t iterations_exp, void** out,
+                       size_t* out_len, void* hash64, gw_status_t* status) {
+    if (!out || !out_len || !hash64 || (!zkey && len) || (!beacon_hash && hash_len)) return fail2(status, "gwb_groth16_beacon: NULL argument");
+    *out = nullptr;
+    *out_len = 0;
+    try {
+        return beacon((const uint8_t*)zkey, len, name, (const uint8_t*)beacon_hash, hash_len, iterations_exp, out, out_len, (uint8_t*)hash64, status);
+    } catch (const std::bad_alloc&) {
+        return fail2(status, "beacon: out of host memory");
     }
 }
 

@@ -34,7 +34,7 @@ void blake2b512(const void* data, size_t len, uint8_t out[HASH_BYTES]);
 // One record; the points as the file stores them (affine, Montgomery, little-endian).
 struct Record {
     uint8_t delta_after[G1_BYTES], g1_s[G1_BYTES], g1_sx[G1_BYTES], g2_spx[G2_BYTES], transcript[HASH_BYTES];
-    uint32_t type = 0;            // 0 = contribution, 1 = beacon (kept, never made here)
+    uint32_t type = 0;            // 0 = contribution, 1 = beacon (beacon.hpp)
     std::vector<uint8_t> params;  // the tagged items, byte for byte
     std::string name;             // item 01 of params, if there is one
 };

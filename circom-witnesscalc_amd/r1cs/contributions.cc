@@ -8,9 +8,13 @@
 //   params: tagged items  01 len name[len]  |  02 numIterationsExp  |  03 len beaconHash[len]
 #include <string.h>
 
+#include <stdlib.h>
+
+#include "beacon.hpp"
 #include "binfile.hpp"
 #include "contribute_internal.hpp"
 #include "g2_subgroup_gfx950.hpp"
+#include "../../include/graph_witness_groth16_beacon.h"
 #include "../../include/graph_witness_groth16_contribute.h"
 
 using namespace cwc_g16;
@@ -388,6 +392,46 @@ using namespace cwc_contrib;
 extern "C" {
 
 void gwb_blake2b512(const void* data, size_t len, void* out64) { blake2b512(data, len, (uint8_t*)out64); }
+
+void gwb_sha256(const void* data, size_t len, void* out32) { cwc_beacon::sha256(data, len, (uint8_t*)out32); }
+
+int gwb_beacon_scalars(uint32_t phase, const void* beacon_hash, size_t hash_len, uint32_t iterations_exp, void* out) {
+    if (!out || !beacon_hash || (phase != 1 && phase != 2)) return 2;
+    if (!cwc_beacon::argument_fault(0, hash_len, iterations_exp, cwc_beacon::limit()).empty()) return 2;
+    Fr x[cwc_beacon::PHASE1_SCALARS];
+    cwc_beacon::scalars(phase, (const uint8_t*)beacon_hash, hash_len, iterations_exp, x);
+    for (uint32_t j = 0; j < cwc_beacon::scalar_count(phase); ++j) memcpy((uint8_t*)out + 32 * j, x[j].v, 32);
+    return 0;
+}
+
+int gwb_zkey_contribution_params(const void* zkey, size_t len, size_t k, void** out, size_t* out_len, gw_status_t* status) {
+    auto fail2 = [&](const std::string& msg) {
+        cwc_r1cs::set_status(status, msg);
+        return 2;
+    };
+    if (!out || !out_len || (!zkey && len)) return fail2("gwb_zkey_contribution_params: NULL argument");
+    *out = nullptr;
+    *out_len = 0;
+    try {
+        cwc_r1cs::BinSection secs[11];
+        std::string err;
+        if (!cwc_r1cs::binfile_sections((const uint8_t*)zkey, len, "zkey", 0x7feu, secs, err)) return fail2(err);
+        if (!secs[10].p) return fail2("zkey: section 10 is missing");
+        Section10 s;
+        if (!parse_section10(secs[10].p, secs[10].size, s, err)) return fail2(err);
+        if (k >= s.recs.size()) return fail2("zkey: there is no contribution " + std::to_string(k + 1) + " (the key has " + std::to_string(s.recs.size()) + ")");
+        const std::vector<uint8_t>& par = s.recs[k].params;
+        void* buf = malloc(par.size() ? par.size() : 1);
+        if (!buf) return fail2("zkey: out of host memory");
+        if (!par.empty()) memcpy(buf, par.data(), par.size());
+        *out = buf;
+        *out_len = par.size();
+    } catch (const std::bad_alloc&) {
+        return fail2("zkey: out of host memory");
+    }
+    cwc_r1cs::set_ok(status);
+    return 0;
+}
 
 void gwb_zkey_contribution_challenge(const void* t64, void* out128) {
     uint8_t stored[G2_BYTES];

@@ -1,7 +1,11 @@
 // groth16-contribute [--name NAME] [--delta FILE] <in.zkey> <out.zkey>: one phase-2 contribution to a Groth16 key, made on the
 // GPU (include/graph_witness_groth16_contribute.h).  The secret is drawn and discarded, or read from FILE (one decimal integer
 // in [1, r), for reproducible keys).  Prints the contribution hash in hex.
-// groth16-contribute --verify <key.zkey>: checks the key's contribution records and prints their hashes.
+// groth16-contribute --beacon [--name NAME] <in.zkey> <out.zkey> <beaconHash(hex)> <numIterationsExp>: the last contribution of phase 2,
+// whose secret nobody chooses: it is derived from the public beaconHash by 2^numIterationsExp chained SHA-256 on the host
+// (include/graph_witness_groth16_beacon.h; snarkjs `zkey beacon`, with its argument order).  Prints the record's hash in hex.
+// groth16-contribute --verify [--require-beacon] <key.zkey>: checks the key's contribution records and prints their hashes;
+// --require-beacon, here and with --verify-key, additionally refuses a key whose last record is not a beacon.
 // groth16-contribute --verify-step <prev.zkey> <next.zkey>: checks that next is prev after exactly one contribution.
 // groth16-contribute --verify-key [--lagrange auto|file|compute] [--skip-records] [--check-ptau] [--check-lagrange] <circuit.r1cs> <pot.ptau> <key.zkey>:
 // checks the key against its circuit and its powers-of-tau file (snarkjs `zkey verify`, with its argument order) and prints the
@@ -26,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/graph_witness_groth16_beacon.h"
 #include "../../include/graph_witness_groth16_contribute.h"
 #include "../../include/graph_witness_groth16_ptau.h"
 #include "../../include/graph_witness_groth16_setup.h"
@@ -116,21 +121,54 @@ static void print_hex(const uint8_t* p, size_t n) {
 static int usage() {
     fprintf(stderr,
             "usage: groth16-contribute [--name NAME] [--delta FILE] <in.zkey> <out.zkey>\n"
+            "       groth16-contribute --beacon [--name NAME] <in.zkey> <out.zkey> <beaconHash(hex)> <numIterationsExp>\n"
             "       groth16-contribute --verify <key.zkey>\n"
+            "       groth16-contribute --verify --require-beacon <key.zkey>\n"
             "       groth16-contribute --verify-step <prev.zkey> <next.zkey>\n"
-            "       groth16-contribute --verify-key [--lagrange auto|file|compute] [--skip-records] [--check-ptau] [--check-lagrange] <circuit.r1cs> <pot.ptau> <key.zkey>\n");
+            "       groth16-contribute --verify-key [--lagrange auto|file|compute] [--skip-records] [--check-ptau] [--check-lagrange] <circuit.r1cs> <pot.ptau> <key.zkey>\n"
+            "       groth16-contribute --verify-key --require-beacon [the options above] <circuit.r1cs> <pot.ptau> <key.zkey>\n");
     return 2;
 }
 
-// the number of records of a key, from the host-only reader; false with st set
-static bool record_count(const std::vector<char>& key, size_t& n, gw_status_t& st) {
+// the number of records of a key and the type of the last one (-1 without records), from the host-only reader; false with st set
+static bool record_count(const std::vector<char>& key, size_t& n, gw_status_t& st, int* last_type = NULL) {
     void* image = NULL;
     size_t image_len = 0;
     if (gwb_zkey_contributions(key.data(), key.size(), &image, &image_len, &st) != 0) return false;
     uint32_t count;
     memcpy(&count, (const uint8_t*)image + GWB_CONTRIBUTION_HASH_BYTES, 4);
+    if (last_type) {
+        *last_type = -1;
+        const uint8_t* p = (const uint8_t*)image + GWB_CONTRIBUTION_HASH_BYTES + 4;  // per record: 448 B, u32 type, u32 nameLen, name
+        for (uint32_t k = 0; k < count; ++k) {
+            uint32_t type, name_len;
+            memcpy(&type, p + 448, 4);
+            memcpy(&name_len, p + 452, 4);
+            *last_type = (int)type;
+            p += 456 + name_len;
+        }
+    }
     gwb_groth16_setup_free(image);
     n = count;
+    return true;
+}
+
+static int not_a_beacon() {
+    fprintf(stderr, "INVALID: zkey: the last contribution is not a beacon\n");
+    return 1;
+}
+
+// an even number of hex digits, either case, no prefix, 1 to 255 bytes
+static bool parse_hex(const char* text, std::vector<uint8_t>& out) {
+    const size_t n = strlen(text);
+    if (n == 0 || n % 2 != 0 || n / 2 > GWB_BEACON_HASH_MAX) return false;
+    out.assign(n / 2, 0);
+    for (size_t i = 0; i < n; ++i) {
+        const char c = text[i];
+        const int v = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
+        if (v < 0) return false;
+        out[i / 2] = (uint8_t)(out[i / 2] << 4 | v);
+    }
     return true;
 }
 
@@ -141,7 +179,7 @@ static int report(int rc, gw_status_t& st) {
 }
 
 static int run_verify_key(const char* r1cs_path, const char* ptau_path, const char* key_path, const char* lagrange, bool skip_records, bool check_ptau,
-                          bool check_lagrange) {
+                          bool check_lagrange, bool require_beacon) {
     uint32_t mode = GWB_PTAU_LAGRANGE_COMPUTE;
     if (lagrange) {
         if (strcmp(lagrange, "auto") == 0)
@@ -166,7 +204,8 @@ static int run_verify_key(const char* r1cs_path, const char* ptau_path, const ch
         return 2;
     }
     size_t n = 0;
-    if (!record_count(key, n, st)) {
+    int last_type = -1;
+    if (!record_count(key, n, st, &last_type)) {
         gwb_r1cs_free(r);
         return report(2, st);
     }
@@ -185,6 +224,7 @@ static int run_verify_key(const char* r1cs_path, const char* ptau_path, const ch
     const int rc = gwb_zkey_verify_key(key.data(), key.size(), r, ptau.data, ptau.len, mode, flags, NULL, hashes.data(), &n, &st);
     gwb_r1cs_free(r);
     if (rc != 0) return report(rc, st);
+    if (require_beacon && last_type != 1) return not_a_beacon();
     printf("OK! %s is the key of %s and %s, %zu contributions%s\n", key_path, r1cs_path, ptau_path, n, skip_records ? " (not verified)" : "");
     for (size_t k = 0; k < n; ++k) print_hex(hashes.data() + k * GWB_CONTRIBUTION_HASH_BYTES, GWB_CONTRIBUTION_HASH_BYTES);
     return 0;
@@ -192,7 +232,8 @@ static int run_verify_key(const char* r1cs_path, const char* ptau_path, const ch
 
 int main(int argc, char** argv) {
     const char *name = "", *delta_path = NULL, *lagrange = NULL;
-    bool verify = false, step = false, verify_key = false, skip_records = false, check_ptau = false, check_lagrange = false;
+    bool verify = false, step = false, verify_key = false, skip_records = false, check_ptau = false, check_lagrange = false, beacon = false,
+         require_beacon = false;
     std::vector<const char*> paths;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -206,6 +247,10 @@ int main(int argc, char** argv) {
             step = true;
         else if (a == "--verify-key")
             verify_key = true;
+        else if (a == "--beacon")
+            beacon = true;
+        else if (a == "--require-beacon")
+            require_beacon = true;
         else if (a == "--skip-records")
             skip_records = true;
         else if (a == "--check-ptau")
@@ -219,10 +264,25 @@ int main(int argc, char** argv) {
         else
             paths.push_back(argv[i]);
     }
-    if (verify + step + verify_key > 1 || ((verify || step || verify_key) && (delta_path || *name))) return usage();
+    if (verify + step + verify_key + beacon > 1 || ((verify || step || verify_key) && (delta_path || *name)) || (beacon && delta_path)) return usage();
+    if (require_beacon && !verify && !verify_key) return usage();
     if (!verify_key && (lagrange || skip_records || check_ptau || check_lagrange)) return usage();
-    if (paths.size() != (verify ? 1u : verify_key ? 3u : 2u)) return usage();
-    if (verify_key) return run_verify_key(paths[0], paths[1], paths[2], lagrange, skip_records, check_ptau, check_lagrange);
+    if (paths.size() != (verify ? 1u : verify_key ? 3u : beacon ? 4u : 2u)) return usage();
+    if (verify_key) return run_verify_key(paths[0], paths[1], paths[2], lagrange, skip_records, check_ptau, check_lagrange, require_beacon);
+    std::vector<uint8_t> beacon_hash;
+    unsigned long beacon_exp = 0;
+    if (beacon) {  // the arguments before the key is read
+        if (!parse_hex(paths[2], beacon_hash)) {
+            fprintf(stderr, "error: beaconHash: an even number of hex digits for 1 to 255 bytes expected, without a prefix\n");
+            return 2;
+        }
+        char* end = NULL;
+        beacon_exp = strtoul(paths[3], &end, 10);
+        if (!*paths[3] || *end || beacon_exp > 0xfffffffful) {
+            fprintf(stderr, "error: numIterationsExp: a decimal number expected\n");
+            return 2;
+        }
+    }
     std::vector<char> first, second;
     if (!read_file(paths[0], first)) {
         fprintf(stderr, "error: cannot read %s\n", paths[0]);
@@ -235,10 +295,12 @@ int main(int argc, char** argv) {
     gw_status_t st{};
     if (verify) {
         size_t n = 0;
-        if (!record_count(first, n, st)) return report(2, st);
+        int last_type = -1;
+        if (!record_count(first, n, st, &last_type)) return report(2, st);
         std::vector<uint8_t> hashes(n * GWB_CONTRIBUTION_HASH_BYTES + 1);
         const int rc = gwb_zkey_verify_contributions(first.data(), first.size(), hashes.data(), &n, &st);
         if (rc != 0) return report(rc, st);
+        if (require_beacon && last_type != 1) return not_a_beacon();
         printf("OK! %zu contributions\n", n);
         for (size_t k = 0; k < n; ++k) print_hex(hashes.data() + k * GWB_CONTRIBUTION_HASH_BYTES, GWB_CONTRIBUTION_HASH_BYTES);
         return 0;
@@ -258,7 +320,8 @@ int main(int argc, char** argv) {
     void* out = NULL;
     size_t out_len = 0;
     uint8_t hash[GWB_CONTRIBUTION_HASH_BYTES];
-    const int rc = gwb_groth16_contribute(first.data(), first.size(), name, delta_path ? delta : NULL, &out, &out_len, hash, &st);
+    const int rc = beacon ? gwb_groth16_beacon(first.data(), first.size(), name, beacon_hash.data(), beacon_hash.size(), (uint32_t)beacon_exp, &out, &out_len, hash, &st)
+                          : gwb_groth16_contribute(first.data(), first.size(), name, delta_path ? delta : NULL, &out, &out_len, hash, &st);
     memset(delta, 0, sizeof delta);
     if (rc != 0) return report(2, st);
     const bool ok = write_file(paths[1], out, out_len);

@@ -12,6 +12,8 @@
 // groth16-setup --check-lagrange [--domain-power P] <file.ptau>: checks sections 12 to 15 against 2 to 5 on the GPU
 // (gwb_ptau_check_lagrange), the levels a setup for the domain 2^P reads or, without P, all of them; prints OK!, or exits with
 // status 1 and the verdict.
+// groth16-setup --export-vk <key.zkey> <verification_key.json>: the verifying key of any zkey in the same JSON shape (snarkjs `zkey
+// export verificationkey`): after a contribution the key's delta has changed, and this writes the key that proofs are verified with.
 // --ptau and --trapdoor exclude each other.  With a third path the verifying key is written too, in snarkjs's
 // verification_key.json shape with vk_alphabeta_12.  Exit status 0 on success; 2 on a usage, file or format error.  Every
 // input is parsed before the device is touched.
@@ -223,10 +225,12 @@ static int usage_error(const char* argv0) {
             "       %s --ptau FILE [--delta FILE] [--lagrange auto|file|compute] [--check-g2] <circuit.r1cs> <circuit.zkey> [verification_key.json]\n"
             "       %s --prepare-ptau <in.ptau> <out.ptau>\n"
             "       %s --check-lagrange [--domain-power P] <file.ptau>\n"
+            "       %s --export-vk <key.zkey> <verification_key.json>\n"
             "  --check-g2  refuse a file whose G2 points, as far as this setup reads them, are not all in the order-r subgroup\n"
             "  --prepare-ptau  write the file with its Lagrange sections 12 to 15 (snarkjs powersoftau prepare phase2)\n"
-            "  --check-lagrange  check sections 12 to 15 against 2 to 5: the levels a setup for 2^P reads, or all of them\n",
-            argv0, argv0, argv0, argv0);
+            "  --check-lagrange  check sections 12 to 15 against 2 to 5: the levels a setup for 2^P reads, or all of them\n"
+            "  --export-vk  write the verifying key of any zkey, a finished ceremony's among them (snarkjs zkey export verificationkey)\n",
+            argv0, argv0, argv0, argv0, argv0);
     return 2;
 }
 
@@ -278,8 +282,29 @@ static int ptau_tool(int argc, char** argv) {
     return code;
 }
 
+// --export-vk: the verifying key of any zkey, a finished ceremony's among them, as verification_key.json
+static int export_vk(int argc, char** argv) {
+    if (argc != 4 || strncmp(argv[2], "--", 2) == 0 || strncmp(argv[3], "--", 2) == 0) return usage_error(argv[0]);
+    std::vector<char> key;
+    if (!read_file(argv[2], key)) {
+        fprintf(stderr, "error: cannot read %s\n", argv[2]);
+        return 2;
+    }
+    std::string json, err;
+    if (!vk_json(key.data(), key.size(), json, err)) {
+        fprintf(stderr, "error: %s: %s\n", argv[2], err.c_str());
+        return 2;
+    }
+    if (!write_file(argv[3], json.data(), json.size())) {
+        fprintf(stderr, "error: cannot write %s\n", argv[3]);
+        return 2;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc > 1 && (strcmp(argv[1], "--prepare-ptau") == 0 || strcmp(argv[1], "--check-lagrange") == 0)) return ptau_tool(argc, argv);
+    if (argc > 1 && strcmp(argv[1], "--export-vk") == 0) return export_vk(argc, argv);
     const char *trapdoor_path = NULL, *ptau_path = NULL, *delta_path = NULL, *lagrange = NULL;
     std::vector<const char*> pos;
     bool usage = false, check_g2 = false;

@@ -2,8 +2,12 @@
 // powersoftau contribute [--name NAME] [--secrets FILE] <in.ptau> <out.ptau>: one contribution, made on the GPU.  The secrets
 // are drawn and discarded, or read from FILE (three decimal integers in [1, r): tau', alpha', beta', for reproducible files).
 // Prints the contribution's hash (the record's nextChallenge) in hex.
-// powersoftau verify [--skip-records] <file.ptau>: checks the file's records and that the whole file holds powers of one tau, and
-// prints the hashes; --skip-records passes over section 7 (a file with snarkjs's records).
+// powersoftau beacon [--name NAME] <in.ptau> <out.ptau> <beaconHash(hex)> <numIterationsExp>: the ceremony's last contribution, whose
+// secrets nobody chooses: they are derived from the public beaconHash by 2^numIterationsExp chained SHA-256 on the host
+// (include/graph_witness_groth16_beacon.h; snarkjs's argument order).  Prints the record's hash in hex.
+// powersoftau verify [--skip-records] [--require-beacon] <file.ptau>: checks the file's records and that the whole file holds powers
+// of one tau, and prints the hashes; --skip-records passes over section 7 (a file with snarkjs's records); --require-beacon
+// additionally refuses a file whose last record is not a beacon.
 // powersoftau verify-step <prev.ptau> <next.ptau>: checks that next is prev after exactly one contribution.
 // The records are this library's own: they are not interchangeable with snarkjs's (see the header).  Inputs are mapped into
 // memory and parsed before the device is touched.  Exit status 0 on success; 1 for a failed verification, with its message; 2 on
@@ -22,6 +26,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/graph_witness_groth16_beacon.h"
 #include "../../include/graph_witness_groth16_ceremony.h"
 #include "../../include/graph_witness_groth16_setup.h"
 
@@ -106,11 +111,45 @@ static void print_hex(const uint8_t* p, size_t n) {
     printf("\n");
 }
 
+// an even number of hex digits, either case, no prefix, 1 to 255 bytes
+static bool parse_hex(const char* text, std::vector<uint8_t>& out) {
+    const size_t n = strlen(text);
+    if (n == 0 || n % 2 != 0 || n / 2 > GWB_BEACON_HASH_MAX) return false;
+    out.assign(n / 2, 0);
+    for (size_t i = 0; i < n; ++i) {
+        const char c = text[i];
+        const int v = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
+        if (v < 0) return false;
+        out[i / 2] = (uint8_t)(out[i / 2] << 4 | v);
+    }
+    return true;
+}
+
+// the type of the file's last record, or -1 without records; false with st set
+static bool last_record_type(const void* data, size_t len, uint32_t n_records, int& type, gw_status_t& st) {
+    void* image = NULL;
+    size_t image_len = 0;
+    if (gwb_ptau_contributions(data, len, &image, &image_len, &st) != 0) return false;
+    const uint8_t* p = (const uint8_t*)image + 4;  // per record: 1216 B of points, 64 B nextChallenge, u32 type, u32 nameLen, name
+    type = -1;
+    for (uint32_t k = 0; k < n_records; ++k) {
+        uint32_t t, name_len;
+        memcpy(&t, p + 1216 + 64, 4);
+        memcpy(&name_len, p + 1216 + 64 + 4, 4);
+        type = (int)t;
+        p += 1216 + 64 + 8 + name_len;
+    }
+    gwb_groth16_setup_free(image);
+    return true;
+}
+
 static int usage() {
     fprintf(stderr,
             "usage: powersoftau new POWER <out.ptau>\n"
             "       powersoftau contribute [--name NAME] [--secrets FILE] <in.ptau> <out.ptau>\n"
+            "       powersoftau beacon [--name NAME] <in.ptau> <out.ptau> <beaconHash(hex)> <numIterationsExp>\n"
             "       powersoftau verify [--skip-records] <file.ptau>\n"
+            "       powersoftau verify [--skip-records] --require-beacon <file.ptau>\n"
             "       powersoftau verify-step <prev.ptau> <next.ptau>\n");
     return 2;
 }
@@ -137,16 +176,18 @@ int main(int argc, char** argv) {
     if (argc < 2) return usage();
     const std::string cmd = argv[1];
     const char *name = "", *secrets_path = NULL;
-    bool skip_records = false;
+    bool skip_records = false, require_beacon = false;
     std::vector<const char*> paths;
     for (int i = 2; i < argc; ++i) {
         const std::string a = argv[i];
-        if (a == "--name" && i + 1 < argc && cmd == "contribute")
+        if (a == "--name" && i + 1 < argc && (cmd == "contribute" || cmd == "beacon"))
             name = argv[++i];
         else if (a == "--secrets" && i + 1 < argc && cmd == "contribute")
             secrets_path = argv[++i];
         else if (a == "--skip-records" && cmd == "verify")
             skip_records = true;
+        else if (a == "--require-beacon" && cmd == "verify")
+            require_beacon = true;
         else if (a.size() > 1 && a[0] == '-')
             return usage();
         else
@@ -181,6 +222,31 @@ int main(int argc, char** argv) {
         print_hex(hash, sizeof hash);
         return 0;
     }
+    if (cmd == "beacon") {
+        if (paths.size() != 4) return usage();
+        std::vector<uint8_t> beacon_hash;
+        if (!parse_hex(paths[2], beacon_hash)) {
+            fprintf(stderr, "error: beaconHash: an even number of hex digits for 1 to 255 bytes expected, without a prefix\n");
+            return 2;
+        }
+        char* end = NULL;
+        const unsigned long exp = strtoul(paths[3], &end, 10);
+        if (!*paths[3] || *end || paths[3][0] == '-' || exp > 0xfffffffful) {
+            fprintf(stderr, "error: numIterationsExp: a decimal number expected\n");
+            return 2;
+        }
+        if (strlen(name) > GWB_CONTRIBUTION_NAME_MAX) {
+            fprintf(stderr, "error: the name has more than 255 bytes\n");
+            return 2;
+        }
+        Mapped in;
+        if (!in.open(paths[0])) return cannot_read(paths[0]);
+        uint8_t hash[GWB_CONTRIBUTION_HASH_BYTES];
+        if (gwb_ptau_beacon(in.data, in.len, name, beacon_hash.data(), beacon_hash.size(), (uint32_t)exp, &out, &out_len, hash, &st) != 0) return report(2, st);
+        if (write_out(paths[1], out, out_len) != 0) return 2;
+        print_hex(hash, sizeof hash);
+        return 0;
+    }
     if (cmd == "verify") {
         if (paths.size() != 1) return usage();
         Mapped in;
@@ -191,6 +257,14 @@ int main(int argc, char** argv) {
         std::vector<uint8_t> hashes(n * GWB_CONTRIBUTION_HASH_BYTES + 1);
         const int rc = gwb_ptau_verify(in.data, in.len, skip_records ? GWB_PTAU_VERIFY_SKIP_RECORDS : 0u, NULL, hashes.data(), &n, &st);
         if (rc != 0) return report(rc, st);
+        if (require_beacon) {
+            int type = -1;
+            if (!last_record_type(in.data, in.len, info.n_contributions, type, st)) return report(2, st);
+            if (type != 1) {
+                fprintf(stderr, "INVALID: ptau: the last contribution is not a beacon\n");
+                return 1;
+            }
+        }
         printf("OK! power %u, %zu contributions%s\n", info.power, n, skip_records ? " (not verified)" : "");
         for (size_t k = 0; k < n && k < info.n_contributions; ++k) print_hex(hashes.data() + k * GWB_CONTRIBUTION_HASH_BYTES, GWB_CONTRIBUTION_HASH_BYTES);
         return 0;

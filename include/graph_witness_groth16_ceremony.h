@@ -28,7 +28,8 @@
  *     64 B nextChallenge
  *     u32 type (0 = contribution, 1 = beacon) | u32 paramsLen | params
  *   params: the tagged items of the zkey's section 10:  01 len name[len]  |  02 numIterationsExp  |  03 len beaconHash[len]
- * Records of type 1 are read and kept byte for byte; none is made here.  The reader refuses, with a message that starts
+ * Records of type 1 are made by gwb_ptau_beacon and checked against their parameters by the verifications below
+ * (graph_witness_groth16_beacon.h); a contribution carries them byte for byte.  The reader refuses, with a message that starts
  * "ptau: section 7": a truncated section, a record count the section cannot hold, a paramsLen or an item length that runs past
  * its end, an unknown tag or type, a coordinate >= q, a point off its curve, trailing bytes.  A file without section 7 has no
  * records.

@@ -15,7 +15,8 @@
  *     deltaAfter G1 64 B | g1_s G1 64 B | g1_sx G1 64 B | g2_spx G2 128 B | transcript 64 B
  *     u32 type (0 = contribution, 1 = beacon) | u32 paramsLen | params
  *   params: tagged items  01 len name[len]  |  02 numIterationsExp  |  03 len beaconHash[len]
- * Records of type 1 are read and kept byte for byte; none is made here.  The reader refuses, with a message that starts
+ * Records of type 1 are made by gwb_groth16_beacon and checked against their parameters by the verifications below
+ * (graph_witness_groth16_beacon.h); a contribution carries them byte for byte.  The reader refuses, with a message that starts
  * "zkey: section 10": a truncated section, a record count the section cannot hold, a paramsLen or an item length that runs
  * past its end, an unknown tag or type, a coordinate >= q, a point off its curve, trailing bytes.
  *

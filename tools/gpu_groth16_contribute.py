@@ -95,6 +95,21 @@ def main():
     same = key1[:len(trap) - 80] == trap[:len(trap) - 80]  # up to the header of section 10
     lines.append("sections 1 to 9 of the contributed key are %s those of the trapdoor setup at delta" % ("byte for byte" if same else "NOT"))
 
+    # the beacon: the contribution's path at a derived secret (include/graph_witness_groth16_beacon.h)
+    phases.clear()
+
+    def beacon():
+        out = pkg.groth16_beacon(key1, bytes(range(32)), 10, name="beacon")
+        phases.append(pkg.groth16_contribute_phase_ms())
+        return out
+
+    (key_b, _), walls_b = walls_of(beacon)
+    pb = {k: float(np.median([x[k] for x in phases])) for k in phases[0]}
+    assert len(pkg.groth16_verify_contributions(key_b, require_beacon=True)) == 2
+    lines.append("beacon on top of it, numIterationsExp 10, warm (%d calls): %.0f ms median, %.0f ms min on the host clock; device phases: %s; sum "
+                 "%.2f ms (the contribution's kernels at a derived secret)" %
+                 (REPS, np.median(walls_b), min(walls_b), ", ".join("%s %.2f" % kv for kv in pb.items()), sum(pb.values())))
+
     pkg.groth16_verify_contribution_step(key0, key1)
     _, walls = walls_of(lambda: pkg.groth16_verify_contribution_step(key0, key1))
     lines.append("step check key0 -> key1, warm (%d calls): %.0f ms median, %.0f ms min on the host clock (both keys parsed and checked on "

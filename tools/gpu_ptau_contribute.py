@@ -3,6 +3,7 @@
   rounds of one process (HIP events around each call; the call holds the multiplication kernel and the conversion to affine,
   the same for both methods);
   ptau_contribute on a power-18 file with its five phases (HIP events, summed over the pieces) and the host clock around the call;
+  ptau_beacon on that file with its phases (the contribution's path at derived scalars) and the host's hash-chain rate;
   ptau_verify on that file with one and with two records, with the records and without them (the whole-file check alone), host
   clock;
   beside them in the same run groth16_setup_ptau's delta_scale phase on the authV2-class R1CS, the one-scalar reference point
@@ -31,6 +32,7 @@ POWER = 18
 N_PUB = 3
 R = F.R
 TAU, ALPHA, BETA, DELTA = 0x1234567 << 200 | 5, 7 << 180 | 11, 13 << 190 | 17, 29 << 210 | 31
+BEACON_HASH, BEACON_EXP = bytes(range(32)), 10
 
 
 def scalars_device(n, seed):
@@ -124,6 +126,28 @@ def main():
                  (REPS, np.median(walls), min(walls), (5 << POWER) - 1, 1 << POWER))
     lines.append("  its phases (HIP events, median ms, summed over the pieces): %s; sum %.1f ms" % (", ".join("%s %.1f" % kv for kv in ph.items()), sum(ph.values())))
     lines.append("  the rest of the call is host work: the file's sections, the record's nine single-point multiplications and three hash_to_g2, the new image")
+
+    # -- the beacon: the contribution's path at derived scalars; the host's hash chain is timed apart at a larger exponent
+    phases.clear()
+
+    def beacon(image):
+        out = pkg.ptau_beacon(image, BEACON_HASH, BEACON_EXP)
+        phases.append(pkg.ptau_contribute_phase_ms())
+        return out
+
+    (fb, _), walls_b = walls_of(lambda: beacon(f1))
+    pb = {k: float(np.median([x[k] for x in phases])) for k in phases[0]}
+    lines.append("ptau_beacon on the file with two records, numIterationsExp %d, warm (%d calls): %.0f ms median, %.0f ms min on the host clock; its "
+                 "phases: %s; sum %.1f ms (the contribution's kernels at derived scalars)" %
+                 (BEACON_EXP, REPS, np.median(walls_b), min(walls_b), ", ".join("%s %.1f" % kv for kv in pb.items()), sum(pb.values())))
+    t0 = time.perf_counter()
+    pkg.beacon_scalars(1, BEACON_HASH, 22)
+    dt = time.perf_counter() - t0
+    lines.append("  the hash chain on this host's CPU: 2^22 links in %.2f s = %.2f million links per second; 2^28 links take %.0f s at that rate" %
+                 (dt, (1 << 22) / dt / 1e6, dt * 64))
+    assert len(pkg.ptau_verify(fb, require_beacon=True)) == 3
+    _, walls_v = walls_of(lambda: pkg.ptau_verify(fb))
+    lines.append("ptau_verify of that file (two records and the beacon), warm (%d calls, host clock): %.0f ms median" % (REPS, np.median(walls_v)))
 
     # -- the verification
     for image, n_rec in ((base, 1), (f1, 2)):
