@@ -119,20 +119,6 @@ FRD Fq12 fq12_mul_line(const Fq12& f, const Fq2& l0, const Fq2& l1, const Fq2& l
     return Fq12{fq6_add(t0, fq6_mul_v(t1)), c1};
 }
 
-// f^(q^k), k = 1, 2, 3
-FRD Fq12 fq12_frob1(const Fq12& a) {
-    return Fq12{Fq6{fq2_conj(a.c0.b0), fq2_mul(fq2_conj(a.c0.b1), frob1_2()), fq2_mul(fq2_conj(a.c0.b2), frob1_4())},
-                Fq6{fq2_mul(fq2_conj(a.c1.b0), frob1_1()), fq2_mul(fq2_conj(a.c1.b1), frob1_3()), fq2_mul(fq2_conj(a.c1.b2), frob1_5())}};
-}
-FRD Fq12 fq12_frob2(const Fq12& a) {  // gamma_2_i lies in Fq
-    return Fq12{Fq6{a.c0.b0, fq2_mul_fq(a.c0.b1, frob2_2().c0), fq2_mul_fq(a.c0.b2, frob2_4().c0)},
-                Fq6{fq2_mul_fq(a.c1.b0, frob2_1().c0), fq2_mul_fq(a.c1.b1, frob2_3().c0), fq2_mul_fq(a.c1.b2, frob2_5().c0)}};
-}
-FRD Fq12 fq12_frob3(const Fq12& a) {
-    return Fq12{Fq6{fq2_conj(a.c0.b0), fq2_mul(fq2_conj(a.c0.b1), frob3_2()), fq2_mul(fq2_conj(a.c0.b2), frob3_4())},
-                Fq6{fq2_mul(fq2_conj(a.c1.b0), frob3_1()), fq2_mul(fq2_conj(a.c1.b1), frob3_3()), fq2_mul(fq2_conj(a.c1.b2), frob3_5())}};
-}
-
 // f^(q^k) for k in 1 .. 3 chosen at run time (one code path; the final exponentiation's program picks k)
 FRD Fq2 frob_const(uint32_t k, const Fq2& c1, const Fq2& c2, const Fq2& c3) {
     return Fq2{cwc::u256_select(k == 1, c1.c0, cwc::u256_select(k == 2, c2.c0, c3.c0)), cwc::u256_select(k == 1, c1.c1, cwc::u256_select(k == 2, c2.c1, c3.c1))};
@@ -168,16 +154,6 @@ FRD Fq12 fq12_cyclotomic_sqr(const Fq12& a) {
     r.c0.b1 = thrice_minus_twice(t2, a.c0.b1);
     r.c1.b2 = thrice_plus_twice(t3, a.c1.b2);
     return r;
-}
-
-// a^x (cyclotomic a; x = BN_X, square and multiply from the top bit)
-FRD Fq12 fq12_exp_by_x(const Fq12& a) {
-    Fq12 acc = a;
-    for (int b = 61; b >= 0; --b) {
-        acc = fq12_cyclotomic_sqr(acc);
-        if ((BN_X >> b) & 1ull) acc = fq12_mul(acc, a);
-    }
-    return acc;
 }
 
 // ---- the final exponentiation as a program ---------------------------------------------------------------------------------

@@ -72,13 +72,17 @@ def test_pairing_infinity_gives_one():
 
 # -- keys with known logs -------------------------------------------------------------------------------------------------------
 class Key:
-    """A verifying key with known logs alpha, beta, gamma, delta, ic_i; forged proofs through the trapdoor."""
+    """A verifying key with known logs alpha, beta, gamma, delta, ic_i; forged proofs through the trapdoor.  The logs are random
+    unless chosen (ic: {index: log}); a log 0 is the point at infinity."""
 
-    def __init__(self, n_public, seed):
+    def __init__(self, n_public, seed, alpha=None, beta=None, gamma=None, delta=None, ic=None):
         rnd = self.rnd = random.Random(seed)
         self.n = n_public
-        self.alpha, self.beta, self.gamma, self.delta = (rnd.randrange(1, R) for _ in range(4))
+        drawn = [rnd.randrange(1, R) for _ in range(4)]
+        self.alpha, self.beta, self.gamma, self.delta = (d if c is None else c % R for d, c in zip(drawn, (alpha, beta, gamma, delta)))
         self.ic = [rnd.randrange(1, R) for _ in range(n_public + 1)]
+        for i, log in (ic or {}).items():
+            self.ic[i] = log % R
         g1 = GF.G1.gen_muls([self.alpha] + self.ic)
         g2 = GF.G2.gen_muls([self.beta, self.gamma, self.delta])
         self.points = _g1b(g1[0]) + b"".join(map(_g2b, g2)) + b"".join(map(_g1b, g1[1:]))
@@ -86,6 +90,10 @@ class Key:
 
     def ic_log(self, pub):
         return (self.ic[0] + sum(s * k for s, k in zip(pub, self.ic[1:]))) % R
+
+    def holds(self, a, b, c, pub):
+        """the verifier's equation in the logs: a b = alpha beta + gamma ic(pub) + delta c (mod r)"""
+        return (a * b - self.alpha * self.beta - self.gamma * self.ic_log(pub) - self.delta * c) % R == 0
 
     def c_for(self, a, b, pub):
         return (a * b - self.alpha * self.beta - self.gamma * self.ic_log(pub)) * pow(self.delta, -1, R) % R
