@@ -655,6 +655,14 @@ def r1cs_lib():
         L.gwb_zkey_contribution_params.argtypes = [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
         L.gwb_sha256.restype = None
         L.gwb_sha256.argtypes = [vp, sz, vp]
+        L.gwb_bn254_compress_batch_device.argtypes = [vp, sz, u32, u32, vp, vp, stp]
+        L.gwb_bn254_decompress_batch_device.argtypes = [vp, sz, u32, u32, vp, vp, vp, stp]
+        L.gwb_groth16_proofs_compress_device.argtypes = [vp, sz, vp, vp, stp]
+        L.gwb_groth16_proofs_decompress_device.argtypes = [vp, sz, vp, vp, vp, stp]
+        L.gwb_groth16_verify_batch_compressed_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, stp]
+        L.gwb_groth16_verify_batch_compressed_host.argtypes = [vp, vp, vp, sz, sz, vp, stp]
+        L.gwb_g16vk_load_compressed.argtypes = [vp, sz, ctypes.POINTER(vp), stp]
+        L.gwb_g16vk_compressed.argtypes = [vp, vp, sz]
         _r1cs_lib = L
     return _r1cs_lib
 
@@ -965,6 +973,22 @@ class Groth16:
         if b:
             out.record_stream(s)
         return out
+
+    def prove_batch_compressed_device(self, d_w, stream=None, montgomery=False, rs=None):
+        """prove_batch_device, then groth16_compress_proofs_device on the same stream -> a uint8 cuda tensor [B, 128] (arkworks'
+        compressed form: include/graph_witness_groth16_compressed.h).  The 256-byte proofs stay on the device."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream(d_w.device)
+        return groth16_compress_proofs_device(self.prove_batch_device(d_w, stream=s, montgomery=montgomery, rs=rs), stream=s)
+
+    def prove_batch_compressed(self, rows, rs=None):
+        """Host rows as prove_batch takes them -> uint8 [B, 128], proved and compressed on the GPU.  Synchronous."""
+        import torch
+        if isinstance(rows, tuple):
+            rows = rows[0]
+        w = np.array(rows, dtype=np.uint8)
+        assert w.ndim == 3 and w.shape[2] == 32, w.shape
+        return self.prove_batch_compressed_device(torch.from_numpy(w).cuda(), rs=rs).cpu().numpy()
 
     def prove_wtns(self, wtns, rs=None):
         """One `.wtns` image -> (proof dict, public signals) in snarkjs's proof.json / public.json shape."""
@@ -1962,6 +1986,62 @@ class Groth16VerifyingKey:
             out.record_stream(s)
         return out
 
+    @classmethod
+    def from_compressed(cls, data):
+        """A key from arkworks' compressed bytes (232 + 32 (nPublic + 1); include/graph_witness_groth16_compressed.h), decoded
+        strictly on the host.  Refusals start "verifying key:" and name the point."""
+        data = bytes(data)
+        self = cls.__new__(cls)
+        self._h = ctypes.c_void_p()
+        st = GwStatus()
+        rc = r1cs_lib().gwb_g16vk_load_compressed(data, len(data), ctypes.byref(self._h), ctypes.byref(st))
+        _r1cs_check(rc, st)
+        n = ctypes.c_uint32()
+        r1cs_lib().gwb_g16vk_info(self._h, ctypes.byref(n))
+        self.n_public = int(n.value)
+        return self
+
+    def to_compressed(self):
+        """the key's compressed bytes (from_compressed's layout)"""
+        out = ctypes.create_string_buffer(232 + 32 * (self.n_public + 1))
+        if r1cs_lib().gwb_g16vk_compressed(self._h, out, len(out)) != 0:
+            raise WitnessCalcError("gwb_g16vk_compressed failed")
+        return out.raw
+
+    def verify_batch_compressed(self, cproofs, publics):
+        """verify_batch on compressed proofs, uint8 [B, 128]: decoded on the GPU, then verified; a refused encoding gives
+        VERIFY_POINT (behind VERIFY_PUBLIC, as the rule order has it).  Synchronous."""
+        p = np.ascontiguousarray(cproofs, dtype=np.uint8).reshape(-1, GROTH16_CPROOF_BYTES)
+        b = p.shape[0]
+        s = _public_array(publics, b, self.n_public)
+        out = np.zeros(b, dtype=np.uint32)
+        st = GwStatus()
+        rc = r1cs_lib().gwb_groth16_verify_batch_compressed_host(self._h, p.ctypes.data, s.ctypes.data, self.n_public, b, out.ctypes.data,
+                                                                 ctypes.byref(st))
+        _r1cs_check(rc, st)
+        return out
+
+    def verify_batch_compressed_device(self, d_cproofs, d_public, stream=None):
+        """verify_batch_device on compressed device proofs (torch uint8 cuda [B, 128]) -> an int32 cuda tensor [B] of statuses.
+        Asynchronous on `stream` or the current torch stream."""
+        import torch
+        assert d_cproofs.is_cuda and d_cproofs.is_contiguous() and d_cproofs.dtype == torch.uint8 and d_cproofs.dim() == 2
+        assert d_cproofs.shape[1] == GROTH16_CPROOF_BYTES, tuple(d_cproofs.shape)
+        b = d_cproofs.shape[0]
+        assert d_public.is_cuda and d_public.is_contiguous() and d_public.dtype == torch.uint8
+        assert tuple(d_public.shape) == (b, self.n_public, 32), tuple(d_public.shape)
+        s = stream if stream is not None else torch.cuda.current_stream(d_cproofs.device)
+        out = torch.empty(b, dtype=torch.int32, device=d_cproofs.device)
+        st = GwStatus()
+        with torch.cuda.device(d_cproofs.device):
+            rc = r1cs_lib().gwb_groth16_verify_batch_compressed_device(self._h, d_cproofs.data_ptr(), d_public.data_ptr() if self.n_public else None,
+                                                                       self.n_public, b, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
+        _r1cs_check(rc, st)
+        if b:
+            d_cproofs.record_stream(s)
+            out.record_stream(s)
+        return out
+
     def verify(self, proof, public):
         """snarkjs proof.json (dict) and public.json (list of decimal strings) -> True when VERIFY_VALID."""
         pb = _from_json_g1(proof["pi_a"], "pi_a") + _from_json_g2(proof["pi_b"], "pi_b") + _from_json_g1(proof["pi_c"], "pi_c")
@@ -2011,6 +2091,124 @@ def bn254_g2_check_batch_device(d_points, montgomery=False, method="fast", strea
         d_points.record_stream(s)
         out.record_stream(s)
     return out
+
+
+# -- compressed points, proofs and keys (include/graph_witness_groth16_compressed.h, libcwc_r1cs.so) ------------------------------
+GROTH16_CPROOF_BYTES = 128
+
+
+def _codec_args(d_in, width, stream):
+    import torch
+    assert d_in.is_cuda and d_in.is_contiguous() and d_in.dtype == torch.uint8 and d_in.dim() == 2 and d_in.shape[1] == width, tuple(d_in.shape)
+    return d_in.shape[0], stream if stream is not None else torch.cuda.current_stream(d_in.device)
+
+
+def _compress_batch_device(group, d_points, montgomery, stream):
+    import torch
+    n, s = _codec_args(d_points, 64 * group, stream)
+    out = torch.empty((n, 32 * group), dtype=torch.uint8, device=d_points.device)
+    st = GwStatus()
+    with torch.cuda.device(d_points.device):
+        rc = r1cs_lib().gwb_bn254_compress_batch_device(d_points.data_ptr() if n else None, n, group, FORM_MONTGOMERY if montgomery else FORM_CANONICAL,
+                                                        out.data_ptr() if n else None, s.cuda_stream, ctypes.byref(st))
+    _r1cs_check(rc, st)
+    if n:
+        d_points.record_stream(s)
+        out.record_stream(s)
+    return out
+
+
+def _decompress_batch_device(group, d_in, montgomery, stream):
+    import torch
+    n, s = _codec_args(d_in, 32 * group, stream)
+    out = torch.empty((n, 64 * group), dtype=torch.uint8, device=d_in.device)
+    status = torch.empty(n, dtype=torch.int32, device=d_in.device)
+    st = GwStatus()
+    with torch.cuda.device(d_in.device):
+        rc = r1cs_lib().gwb_bn254_decompress_batch_device(d_in.data_ptr() if n else None, n, group, FORM_MONTGOMERY if montgomery else FORM_CANONICAL,
+                                                          out.data_ptr() if n else None, status.data_ptr() if n else None, s.cuda_stream,
+                                                          ctypes.byref(st))
+    _r1cs_check(rc, st)
+    if n:
+        d_in.record_stream(s)
+        out.record_stream(s)
+        status.record_stream(s)
+    return out, status
+
+
+def bn254_g1_compress_batch_device(d_points, montgomery=False, stream=None):
+    """Device G1 points (uint8 cuda [n, 64]: x, y, canonical little-endian or, with montgomery, as the files store them; zero bytes
+    = infinity; not validated) -> their compressed form, a uint8 cuda tensor [n, 32] (arkworks' CanonicalSerialize, Compress::Yes:
+    include/graph_witness_groth16_compressed.h).  Asynchronous on `stream` or the current torch stream."""
+    return _compress_batch_device(1, d_points, montgomery, stream)
+
+
+def bn254_g2_compress_batch_device(d_points, montgomery=False, stream=None):
+    """The same for G2 points: uint8 cuda [n, 128] (x.c0, x.c1, y.c0, y.c1) -> [n, 64]."""
+    return _compress_batch_device(2, d_points, montgomery, stream)
+
+
+def bn254_g1_decompress_batch_device(d_in, montgomery=False, stream=None):
+    """Compressed device G1 points (uint8 cuda [n, 32]) -> (points, status): a uint8 cuda tensor [n, 64] in the asked form and an int32
+    cuda tensor [n], VERIFY_VALID or, beside the point (0, 0), VERIFY_POINT for an encoding that strict decoding refuses (both
+    flags, the infinity flag beside a nonzero bit, x >= q, no root).  Asynchronous on `stream` or the current torch stream."""
+    return _decompress_batch_device(1, d_in, montgomery, stream)
+
+
+def bn254_g2_decompress_batch_device(d_in, montgomery=False, stream=None):
+    """The same for G2: uint8 cuda [n, 64] -> ([n, 128], status).  Subgroup membership is not looked at."""
+    return _decompress_batch_device(2, d_in, montgomery, stream)
+
+
+def groth16_compress_proofs_device(d_proofs, stream=None):
+    """Device proofs (uint8 cuda [B, 256], the prover's layout) -> a uint8 cuda tensor [B, 128]: A (32), B (64), C (32) compressed.
+    Asynchronous on `stream` or the current torch stream."""
+    import torch
+    b, s = _codec_args(d_proofs, GROTH16_PROOF_BYTES, stream)
+    out = torch.empty((b, GROTH16_CPROOF_BYTES), dtype=torch.uint8, device=d_proofs.device)
+    st = GwStatus()
+    with torch.cuda.device(d_proofs.device):
+        rc = r1cs_lib().gwb_groth16_proofs_compress_device(d_proofs.data_ptr() if b else None, b, out.data_ptr() if b else None, s.cuda_stream,
+                                                           ctypes.byref(st))
+    _r1cs_check(rc, st)
+    if b:
+        d_proofs.record_stream(s)
+        out.record_stream(s)
+    return out
+
+
+def groth16_decompress_proofs_device(d_cproofs, stream=None):
+    """Compressed device proofs (uint8 cuda [B, 128]) -> (proofs [B, 256], status int32 [B]): VERIFY_POINT when any of A, B, C was
+    refused (that point is then (0, 0)), else VERIFY_VALID.  Asynchronous on `stream` or the current torch stream."""
+    import torch
+    b, s = _codec_args(d_cproofs, GROTH16_CPROOF_BYTES, stream)
+    out = torch.empty((b, GROTH16_PROOF_BYTES), dtype=torch.uint8, device=d_cproofs.device)
+    status = torch.empty(b, dtype=torch.int32, device=d_cproofs.device)
+    st = GwStatus()
+    with torch.cuda.device(d_cproofs.device):
+        rc = r1cs_lib().gwb_groth16_proofs_decompress_device(d_cproofs.data_ptr() if b else None, b, out.data_ptr() if b else None,
+                                                             status.data_ptr() if b else None, s.cuda_stream, ctypes.byref(st))
+    _r1cs_check(rc, st)
+    if b:
+        d_cproofs.record_stream(s)
+        out.record_stream(s)
+        status.record_stream(s)
+    return out, status
+
+
+def groth16_compress_proofs(proofs):
+    """Host proofs uint8 [B, 256] -> uint8 [B, 128], on the GPU.  Synchronous."""
+    import torch
+    p = np.array(proofs, dtype=np.uint8).reshape(-1, GROTH16_PROOF_BYTES)
+    return groth16_compress_proofs_device(torch.from_numpy(p).cuda()).cpu().numpy()
+
+
+def groth16_decompress_proofs(cproofs):
+    """Host compressed proofs uint8 [B, 128] -> (proofs uint8 [B, 256], status uint32 [B]), on the GPU.  Synchronous."""
+    import torch
+    p = np.array(cproofs, dtype=np.uint8).reshape(-1, GROTH16_CPROOF_BYTES)
+    out, status = groth16_decompress_proofs_device(torch.from_numpy(p).cuda())
+    return out.cpu().numpy(), status.cpu().numpy().astype(np.uint32)
 
 
 from . import graphgen  # noqa: E402,F401  (graph generator library on top of the C-ABI producer)

@@ -4,7 +4,9 @@
 // `.r1cs` instead.  --check-g2 (anywhere among the arguments, either form) first checks the key's G2 points (beta2, gamma2,
 // delta2, section 7) for membership in the order-r subgroup, on the GPU, and refuses the key before proving if one is outside
 // it.  Exit status 0 on success; 2 on a usage, file, format, mismatch or subgroup error.  Every input is parsed before the
-// device is touched.
+// device is touched.  --compressed as the first argument writes the proof as the 128 raw bytes of arkworks' compressed form
+// (include/graph_witness_groth16_compressed.h) in place of proof.json; public.json is unchanged.  (One proof's encoding is
+// three comparisons: it is done here, with the host side of point_codec_gfx950.hpp.)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -15,6 +17,7 @@
 #include <vector>
 
 #include "../../include/graph_witness_groth16.h"
+#include "point_codec_gfx950.hpp"
 
 static bool read_file(const char* path, std::vector<char>& out) {
     std::ifstream f(path, std::ios::binary);
@@ -71,8 +74,9 @@ static bool write_text(const char* path, const std::string& s) {
 
 int main(int argc, char** argv) {
     bool check_g2 = false, usage = false;
+    const bool compressed = argc > 1 && strcmp(argv[1], "--compressed") == 0;
     std::vector<char*> pos;
-    for (int i = 1; i < argc; ++i) {
+    for (int i = compressed ? 2 : 1; i < argc; ++i) {
         if (strcmp(argv[i], "--check-g2") == 0) {
             usage = usage || check_g2;
             check_g2 = true;
@@ -84,7 +88,8 @@ int main(int argc, char** argv) {
         fprintf(stderr,
                 "usage: %s [--check-g2] <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n"
                 "       %s [--check-g2] <circuit.r1cs> <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n"
-                "  --check-g2  refuse a key whose G2 points are not all in the order-r subgroup (checked on the GPU before proving)\n",
+                "  --check-g2  refuse a key whose G2 points are not all in the order-r subgroup (checked on the GPU before proving)\n"
+                "  --compressed  as the first argument: write the proof as 128 raw bytes, arkworks' compressed form, in place of proof.json\n",
                 argv[0], argv[0]);
         return 2;
     }
@@ -146,6 +151,13 @@ int main(int argc, char** argv) {
     std::string pj = "{\n \"pi_a\": [\n  " + d(0) + ",\n  " + d(1) + ",\n  " + z1(0, 2) + "\n ],\n \"pi_b\": [\n  [\n   " + d(2) + ",\n   " + d(3) +
                      "\n  ],\n  [\n   " + d(4) + ",\n   " + d(5) + "\n  ],\n  [\n   " + z1(2, 4) + ",\n   \"0\"\n  ]\n ],\n \"pi_c\": [\n  " + d(6) +
                      ",\n  " + d(7) + ",\n  " + z1(6, 2) + "\n ],\n \"protocol\": \"groth16\",\n \"curve\": \"bn128\"\n}\n";
+    if (compressed) {
+        uint8_t c[128];
+        cwc_g16::g1_encode(proof, true, c);
+        cwc_g16::g2_encode(proof + 64, true, c + 32);
+        cwc_g16::g1_encode(proof + 192, true, c + 96);
+        pj.assign((const char*)c, sizeof c);
+    }
     const uint8_t* w = wtns_values(wtns_file);
     std::string pub = "[";
     for (uint32_t i = 1; i <= zi.n_public; ++i) pub += std::string(i > 1 ? ",\n " : "\n ") + "\"" + decimal(w + 32 * (size_t)i) + "\"";

@@ -31,6 +31,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/graph_witness_groth16_compressed.h"
 #include "../../include/graph_witness_groth16_ptau.h"
 #include "../../include/graph_witness_groth16_setup.h"
 #include "../../include/graph_witness_groth16_verify.h"
@@ -226,11 +227,13 @@ static int usage_error(const char* argv0) {
             "       %s --prepare-ptau <in.ptau> <out.ptau>\n"
             "       %s --check-lagrange [--domain-power P] <file.ptau>\n"
             "       %s --export-vk <key.zkey> <verification_key.json>\n"
+            "       %s --export-vk --compressed <key.zkey> <vk.bin>\n"
             "  --check-g2  refuse a file whose G2 points, as far as this setup reads them, are not all in the order-r subgroup\n"
             "  --prepare-ptau  write the file with its Lagrange sections 12 to 15 (snarkjs powersoftau prepare phase2)\n"
             "  --check-lagrange  check sections 12 to 15 against 2 to 5: the levels a setup for 2^P reads, or all of them\n"
-            "  --export-vk  write the verifying key of any zkey, a finished ceremony's among them (snarkjs zkey export verificationkey)\n",
-            argv0, argv0, argv0, argv0, argv0);
+            "  --export-vk  write the verifying key of any zkey, a finished ceremony's among them (snarkjs zkey export verificationkey)\n"
+            "  --export-vk --compressed  write it as arkworks' compressed bytes, 232 + 32 (nPublic + 1)\n",
+            argv0, argv0, argv0, argv0, argv0, argv0);
     return 2;
 }
 
@@ -282,8 +285,42 @@ static int ptau_tool(int argc, char** argv) {
     return code;
 }
 
+// --export-vk --compressed: the same key as arkworks' compressed bytes (include/graph_witness_groth16_compressed.h)
+static int export_vk_compressed(char** argv) {
+    std::vector<char> key;
+    if (!read_file(argv[3], key)) {
+        fprintf(stderr, "error: cannot read %s\n", argv[3]);
+        return 2;
+    }
+    gw_status_t st = {OK, NULL};
+    gwb_zkey_t* z = NULL;
+    gwb_g16vk_t* vk = NULL;
+    std::vector<uint8_t> out;
+    bool ok = gwb_zkey_load(key.data(), key.size(), &z, &st) == 0 && gwb_g16vk_from_zkey(z, &vk, &st) == 0;
+    if (ok) {
+        gwb_g16vk_info_t info;
+        gwb_g16vk_info(vk, &info);
+        out.resize(GWB_G16VK_COMPRESSED_BYTES(info.n_public));
+        ok = gwb_g16vk_compressed(vk, out.data(), out.size()) == 0;
+    }
+    if (vk) gwb_g16vk_free(vk);
+    if (z) gwb_zkey_free(z);
+    if (!ok) {
+        fprintf(stderr, "error: %s: %s\n", argv[3], st.error_msg ? st.error_msg : "compressing the verifying key failed");
+        gw_free_status(&st);
+        return 2;
+    }
+    if (!write_file(argv[4], out.data(), out.size())) {
+        fprintf(stderr, "error: cannot write %s\n", argv[4]);
+        return 2;
+    }
+    return 0;
+}
+
 // --export-vk: the verifying key of any zkey, a finished ceremony's among them, as verification_key.json
 static int export_vk(int argc, char** argv) {
+    if (argc == 5 && strcmp(argv[2], "--compressed") == 0 && strncmp(argv[3], "--", 2) != 0 && strncmp(argv[4], "--", 2) != 0)
+        return export_vk_compressed(argv);
     if (argc != 4 || strncmp(argv[2], "--", 2) == 0 || strncmp(argv[3], "--", 2) == 0) return usage_error(argv[0]);
     std::vector<char> key;
     if (!read_file(argv[2], key)) {

@@ -8,6 +8,11 @@
 // (vk_alphabeta_12 and other members ignored); the proof {"pi_a", "pi_b", "pi_c"} alike; public signals a list of decimal
 // strings.  z is "1" for an affine point and "0" for the point at infinity (proof_json's convention); numbers are decimal
 // strings (or JSON integers) below 2^256.
+//
+// groth16-verify --compressed <vk.bin> <public.json> <proof.bin> (the flag first) takes the key and the proof in arkworks'
+// compressed bytes (include/graph_witness_groth16_compressed.h: 232 + 32 (nPublic + 1) and 128 bytes); public.json is the same.
+// A proof file of another size, or a key that strict decoding refuses, is exit status 2; a proof whose encoding is refused is
+// INVALID: POINT.
 #include <stdio.h>
 #include <string.h>
 
@@ -18,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/graph_witness_groth16_compressed.h"
 #include "../../include/graph_witness_groth16_verify.h"
 
 namespace {
@@ -204,11 +210,73 @@ const char* status_name(uint32_t s) {
     }
 }
 
+bool read_bytes(const char* path, std::vector<uint8_t>& out) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) return false;
+    out.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+    return !f.bad();
+}
+
+// --compressed <vk.bin> <public.json> <proof.bin>
+int verify_compressed(char** argv) {
+    std::vector<uint8_t> key, pub, proof;
+    for (int k = 0; k < 2; ++k)
+        if (!read_bytes(argv[k ? 4 : 2], k ? proof : key)) {
+            fprintf(stderr, "error: cannot read %s\n", argv[k ? 4 : 2]);
+            return 2;
+        }
+    if (proof.size() != GWB_GROTH16_CPROOF_BYTES) {
+        fprintf(stderr, "error: %s: %zu bytes, a compressed proof has %d\n", argv[4], proof.size(), GWB_GROTH16_CPROOF_BYTES);
+        return 2;
+    }
+    gw_status_t st = {OK, NULL};
+    gwb_g16vk_t* vk = NULL;
+    if (gwb_g16vk_load_compressed(key.data(), key.size(), &vk, &st) != 0) {
+        fprintf(stderr, "error: %s: %s\n", argv[2], st.error_msg ? st.error_msg : "load failed");
+        gw_free_status(&st);
+        return 2;
+    }
+    gwb_g16vk_info_t info;
+    gwb_g16vk_info(vk, &info);
+    try {
+        const J pj = read_json(argv[3]);
+        const std::string pv = argv[3];
+        if (pj.kind != 'a') throw Bad{pv + ": public signals are not a list"};
+        if (pj.items.size() != info.n_public)
+            throw Bad{pv + ": " + std::to_string(pj.items.size()) + " public signals, the key has nPublic " + std::to_string(info.n_public)};
+        for (size_t i = 0; i < pj.items.size(); ++i) put_int(pj.items[i], pv + ": signal " + std::to_string(i), pub);
+    } catch (const Bad& b) {
+        fprintf(stderr, "error: %s\n", b.msg.c_str());
+        gwb_g16vk_free(vk);
+        return 2;
+    } catch (const std::exception& e) {
+        fprintf(stderr, "error: %s\n", e.what());
+        gwb_g16vk_free(vk);
+        return 2;
+    }
+    uint32_t status = 0;
+    const int rc = gwb_groth16_verify_batch_compressed_host(vk, proof.data(), pub.data(), info.n_public, 1, &status, &st);
+    gwb_g16vk_free(vk);
+    if (rc != 0) {
+        fprintf(stderr, "error: %s\n", st.error_msg ? st.error_msg : "verify failed");
+        gw_free_status(&st);
+        return 2;
+    }
+    if (status == GWB_G16V_VALID) {
+        printf("OK!\n");
+        return 0;
+    }
+    printf("INVALID: %s\n", status == GWB_G16V_POINT ? "POINT (a point's compressed encoding is refused)" : status_name(status));
+    return 1;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+    if (argc == 5 && strcmp(argv[1], "--compressed") == 0) return verify_compressed(argv);
     if (argc != 4) {
-        fprintf(stderr, "usage: %s <verification_key.json> <public.json> <proof.json>\n", argv[0]);
+        fprintf(stderr, "usage: %s <verification_key.json> <public.json> <proof.json>\n       %s --compressed <vk.bin> <public.json> <proof.bin>\n", argv[0],
+                argv[0]);
         return 2;
     }
     std::vector<uint8_t> key, pub, proof;
