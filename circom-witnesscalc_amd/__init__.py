@@ -554,6 +554,10 @@ class PtauInfo(ctypes.Structure):
                 ("n_contributions", ctypes.c_uint32)]
 
 
+class KzgInfo(ctypes.Structure):
+    _fields_ = [("max_len", ctypes.c_uint64), ("power", ctypes.c_uint32), ("prepared", ctypes.c_uint32)]
+
+
 def r1cs_lib():
     """ctypes handle of libcwc_r1cs.so, loaded after torch (one HIP runtime per process, as in lib())."""
     global _r1cs_lib
@@ -663,6 +667,24 @@ def r1cs_lib():
         L.gwb_groth16_verify_batch_compressed_host.argtypes = [vp, vp, vp, sz, sz, vp, stp]
         L.gwb_g16vk_load_compressed.argtypes = [vp, sz, ctypes.POINTER(vp), stp]
         L.gwb_g16vk_compressed.argtypes = [vp, vp, sz]
+        u64 = ctypes.c_uint64
+        L.gwb_kzg_new.argtypes = [vp, sz, u64, u32, ctypes.POINTER(vp), stp]
+        L.gwb_kzg_info.argtypes = [vp, ctypes.POINTER(KzgInfo)]
+        L.gwb_kzg_free.restype = None
+        L.gwb_kzg_free.argtypes = [vp]
+        L.gwb_kzg_commit_batch.argtypes = [vp, vp, sz, sz, vp, stp]
+        L.gwb_kzg_commit_batch_device.argtypes = [vp, vp, sz, sz, vp, vp, stp]
+        L.gwb_kzg_commit_evals_batch.argtypes = [vp, vp, sz, u32, vp, stp]
+        L.gwb_kzg_commit_evals_batch_device.argtypes = [vp, vp, sz, u32, vp, vp, stp]
+        L.gwb_kzg_eval_batch.argtypes = [vp, vp, vp, sz, sz, vp, stp]
+        L.gwb_kzg_eval_batch_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, stp]
+        L.gwb_kzg_open_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, stp]
+        L.gwb_kzg_open_batch_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, stp]
+        L.gwb_kzg_verify_batch.argtypes = [vp, vp, vp, vp, vp, sz, vp, stp]
+        L.gwb_kzg_verify_batch_device.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, stp]
+        L.gwb_kzg_phase_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        L.gwb_kzg_eval_quotient_device.argtypes = [vp, vp, sz, sz, u32, vp, vp, vp, stp]
+        L.gwb_kzg_tiles.argtypes = [ctypes.POINTER(u32), ctypes.POINTER(sz)]
         _r1cs_lib = L
     return _r1cs_lib
 
@@ -2209,6 +2231,223 @@ def groth16_decompress_proofs(cproofs):
     p = np.array(cproofs, dtype=np.uint8).reshape(-1, GROTH16_CPROOF_BYTES)
     out, status = groth16_decompress_proofs_device(torch.from_numpy(p).cuda())
     return out.cpu().numpy(), status.cpu().numpy().astype(np.uint32)
+
+
+# -- KZG commitments over a powers-of-tau file (include/graph_witness_kzg.h, libcwc_r1cs.so) ----------------------------------------
+KZG_VALID, KZG_SCALAR, KZG_POINT, KZG_EQUATION = 0, 1, 2, 3
+KZG_CHECK_POWERS = 1
+KZG_PHASES = ("quotient", "lincomb", "prepare", "pairing")
+
+
+def _kzg_host(a, tail, what):
+    """a host array as contiguous uint8 [K, *tail]; the last dimensions have to be `tail` already (-1: any length)"""
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    if a.ndim != 1 + len(tail) or any(t != -1 and t != d for t, d in zip(tail, a.shape[1:])):
+        raise WitnessCalcError("kzg: %s: uint8 [K, %s] expected, got %s" % (what, ", ".join("N" if t == -1 else str(t) for t in tail), list(a.shape)))
+    return a
+
+
+def _kzg_dev(t, tail, what, k=None):
+    import torch
+    ok = hasattr(t, "is_cuda") and t.is_cuda and t.is_contiguous() and t.dtype == torch.uint8 and t.dim() == 1 + len(tail)
+    ok = ok and all(e == -1 or e == d for e, d in zip(tail, t.shape[1:])) and (k is None or t.shape[0] == k)
+    if not ok:
+        raise WitnessCalcError("kzg: %s: a contiguous uint8 cuda tensor [K, %s] expected" % (what, ", ".join("N" if e == -1 else str(e) for e in tail)))
+    return t
+
+
+def _kzg_log2(n, what):
+    if n < 1 or n & (n - 1):
+        raise WitnessCalcError("kzg: %s: %d evaluations, a power of two expected" % (what, n))
+    return n.bit_length() - 1
+
+
+class Kzg:
+    """KZG polynomial commitments over a `.ptau` image (bytes or any buffer, an mmap included; it is not kept): commit to
+    polynomials given by coefficients or by evaluations, open them at points, check openings.  max_len: the longest polynomial,
+    in coefficients (default: every point of the file, 2^(power+1) - 1).  check_powers: run ptau_check_powers' rule over the
+    covered prefix first.  The SRS is whatever the file holds: check_powers and ptau_verify are what vouch for it.  Scalars are
+    32 bytes little-endian, points 64 bytes canonical affine (zero bytes: infinity).  The plain methods take and return numpy
+    arrays and are synchronous; the _device methods take torch cuda tensors and are asynchronous on `stream` or the current
+    stream."""
+
+    def __init__(self, ptau, max_len=None, check_powers=False):
+        keep, addr, n = _ptau_buffer(ptau)
+        if max_len is None:
+            max_len = (2 << ptau_info(ptau)["power"]) - 1
+        if int(max_len) < 0 or int(max_len) >= 1 << 64:
+            raise WitnessCalcError("kzg: max_len %d" % max_len)
+        self._h = ctypes.c_void_p()
+        st = GwStatus()
+        rc = r1cs_lib().gwb_kzg_new(addr, n, int(max_len), KZG_CHECK_POWERS if check_powers else 0, ctypes.byref(self._h), ctypes.byref(st))
+        del keep
+        _r1cs_check(rc, st)
+        info = KzgInfo()
+        r1cs_lib().gwb_kzg_info(self._h, ctypes.byref(info))
+        self.info = {"max_len": int(info.max_len), "power": int(info.power), "prepared": bool(info.prepared)}
+
+    def close(self):
+        if getattr(self, "_h", None) and _r1cs_lib is not None:
+            _r1cs_lib.gwb_kzg_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _stream(self, t, stream):
+        import torch
+        return stream if stream is not None else torch.cuda.current_stream(t.device)
+
+    def commit(self, polys):
+        """uint8 [K, N, 32] -> commitments uint8 [K, 64]"""
+        p = _kzg_host(polys, (-1, 32), "polys")
+        out = np.zeros((p.shape[0], 64), dtype=np.uint8)
+        st = GwStatus()
+        _r1cs_check(r1cs_lib().gwb_kzg_commit_batch(self._h, p.ctypes.data, p.shape[0], p.shape[1], out.ctypes.data, ctypes.byref(st)), st)
+        return out
+
+    def commit_device(self, d_polys, stream=None):
+        import torch
+        p = _kzg_dev(d_polys, (-1, 32), "d_polys")
+        s = self._stream(p, stream)
+        out = torch.empty((p.shape[0], 64), dtype=torch.uint8, device=p.device)
+        st = GwStatus()
+        with torch.cuda.device(p.device):
+            rc = r1cs_lib().gwb_kzg_commit_batch_device(self._h, p.data_ptr(), p.shape[0], p.shape[1], out.data_ptr(), s.cuda_stream, ctypes.byref(st))
+        _r1cs_check(rc, st)
+        p.record_stream(s)
+        out.record_stream(s)
+        return out
+
+    def commit_evals(self, evals):
+        """uint8 [K, 2^m, 32], the evaluations at the powers of the domain's root in natural order -> commitments uint8 [K, 64]
+        (the file has to be prepared: ptau_prepare_phase2)"""
+        e = _kzg_host(evals, (-1, 32), "evals")
+        m = _kzg_log2(e.shape[1], "evals")
+        out = np.zeros((e.shape[0], 64), dtype=np.uint8)
+        st = GwStatus()
+        _r1cs_check(r1cs_lib().gwb_kzg_commit_evals_batch(self._h, e.ctypes.data, e.shape[0], m, out.ctypes.data, ctypes.byref(st)), st)
+        return out
+
+    def commit_evals_device(self, d_evals, stream=None):
+        import torch
+        e = _kzg_dev(d_evals, (-1, 32), "d_evals")
+        m = _kzg_log2(e.shape[1], "d_evals")
+        s = self._stream(e, stream)
+        out = torch.empty((e.shape[0], 64), dtype=torch.uint8, device=e.device)
+        st = GwStatus()
+        with torch.cuda.device(e.device):
+            rc = r1cs_lib().gwb_kzg_commit_evals_batch_device(self._h, e.data_ptr(), e.shape[0], m, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
+        _r1cs_check(rc, st)
+        e.record_stream(s)
+        out.record_stream(s)
+        return out
+
+    def eval(self, polys, zs):
+        """uint8 [K, N, 32] and points uint8 [K, 32] -> values uint8 [K, 32]"""
+        p = _kzg_host(polys, (-1, 32), "polys")
+        z = _kzg_host(zs, (32,), "zs")
+        if z.shape[0] != p.shape[0]:
+            raise WitnessCalcError("kzg: %d polynomials and %d points" % (p.shape[0], z.shape[0]))
+        ys = np.zeros((p.shape[0], 32), dtype=np.uint8)
+        st = GwStatus()
+        _r1cs_check(r1cs_lib().gwb_kzg_eval_batch(self._h, p.ctypes.data, z.ctypes.data, p.shape[0], p.shape[1], ys.ctypes.data, ctypes.byref(st)), st)
+        return ys
+
+    def open(self, polys, zs):
+        """uint8 [K, N, 32] and points uint8 [K, 32] -> (values uint8 [K, 32], proofs uint8 [K, 64])"""
+        p = _kzg_host(polys, (-1, 32), "polys")
+        z = _kzg_host(zs, (32,), "zs")
+        if z.shape[0] != p.shape[0]:
+            raise WitnessCalcError("kzg: %d polynomials and %d points" % (p.shape[0], z.shape[0]))
+        ys, ws = np.zeros((p.shape[0], 32), dtype=np.uint8), np.zeros((p.shape[0], 64), dtype=np.uint8)
+        st = GwStatus()
+        rc = r1cs_lib().gwb_kzg_open_batch(self._h, p.ctypes.data, z.ctypes.data, p.shape[0], p.shape[1], ys.ctypes.data, ws.ctypes.data, ctypes.byref(st))
+        _r1cs_check(rc, st)
+        return ys, ws
+
+    def open_device(self, d_polys, d_zs, stream=None):
+        import torch
+        p = _kzg_dev(d_polys, (-1, 32), "d_polys")
+        z = _kzg_dev(d_zs, (32,), "d_zs", p.shape[0])
+        s = self._stream(p, stream)
+        ys = torch.empty((p.shape[0], 32), dtype=torch.uint8, device=p.device)
+        ws = torch.empty((p.shape[0], 64), dtype=torch.uint8, device=p.device)
+        st = GwStatus()
+        with torch.cuda.device(p.device):
+            rc = r1cs_lib().gwb_kzg_open_batch_device(self._h, p.data_ptr(), z.data_ptr(), p.shape[0], p.shape[1], ys.data_ptr(), ws.data_ptr(), s.cuda_stream,
+                                                      ctypes.byref(st))
+        _r1cs_check(rc, st)
+        for t in (p, z, ys, ws):
+            t.record_stream(s)
+        return ys, ws
+
+    def verify(self, commitments, zs, ys, proofs):
+        """uint8 [K, 64], [K, 32], [K, 32], [K, 64] -> uint32 [K] of KZG_VALID, KZG_SCALAR, KZG_POINT, KZG_EQUATION"""
+        c = _kzg_host(commitments, (64,), "commitments")
+        z, y, w = _kzg_host(zs, (32,), "zs"), _kzg_host(ys, (32,), "ys"), _kzg_host(proofs, (64,), "proofs")
+        k = c.shape[0]
+        if not (z.shape[0] == y.shape[0] == w.shape[0] == k):
+            raise WitnessCalcError("kzg: %d commitments, %d points, %d values and %d proofs" % (k, z.shape[0], y.shape[0], w.shape[0]))
+        out = np.zeros(k, dtype=np.uint32)
+        st = GwStatus()
+        rc = r1cs_lib().gwb_kzg_verify_batch(self._h, c.ctypes.data, z.ctypes.data, y.ctypes.data, w.ctypes.data, k, out.ctypes.data, ctypes.byref(st))
+        _r1cs_check(rc, st)
+        return out
+
+    def verify_device(self, d_commitments, d_zs, d_ys, d_proofs, stream=None):
+        """-> an int32 cuda tensor [K] of statuses"""
+        import torch
+        c = _kzg_dev(d_commitments, (64,), "d_commitments")
+        k = c.shape[0]
+        z, y, w = _kzg_dev(d_zs, (32,), "d_zs", k), _kzg_dev(d_ys, (32,), "d_ys", k), _kzg_dev(d_proofs, (64,), "d_proofs", k)
+        s = self._stream(c, stream)
+        out = torch.empty(k, dtype=torch.int32, device=c.device)
+        st = GwStatus()
+        with torch.cuda.device(c.device):
+            rc = r1cs_lib().gwb_kzg_verify_batch_device(self._h, c.data_ptr(), z.data_ptr(), y.data_ptr(), w.data_ptr(), k, out.data_ptr(), s.cuda_stream,
+                                                        ctypes.byref(st))
+        _r1cs_check(rc, st)
+        for t in (c, z, y, w, out):
+            t.record_stream(s)
+        return out
+
+
+def kzg_tiles():
+    """The tile sizes (coefficients per workgroup) of the evaluate-and-quotient kernels, smallest first; the last is production's."""
+    n = ctypes.c_size_t(8)
+    tiles = (ctypes.c_uint32 * 8)()
+    if r1cs_lib().gwb_kzg_tiles(tiles, ctypes.byref(n)) != 0:
+        raise WitnessCalcError("gwb_kzg_tiles failed")
+    return [int(tiles[i]) for i in range(n.value)]
+
+
+def kzg_eval_quotient_device(d_polys, d_zs, tile=None, stream=None):
+    """Test and measurement aid of the evaluate-and-quotient kernels: uint8 cuda [K, N, 32] and [K, 32] -> (d_ys [K, 32],
+    d_qs [K, N - 1, 32]), y = p(z) and the coefficients of (p(X) - y) / (X - z), with workgroups of `tile` coefficients (one of
+    kzg_tiles(); None: production's).  Asynchronous on `stream` or the current stream."""
+    import torch
+    p = _kzg_dev(d_polys, (-1, 32), "d_polys")
+    k, n = p.shape[0], p.shape[1]
+    z = _kzg_dev(d_zs, (32,), "d_zs", k)
+    s = stream if stream is not None else torch.cuda.current_stream(p.device)
+    ys = torch.empty((k, 32), dtype=torch.uint8, device=p.device)
+    qs = torch.empty((k, max(n - 1, 0), 32), dtype=torch.uint8, device=p.device)
+    st = GwStatus()
+    with torch.cuda.device(p.device):
+        rc = r1cs_lib().gwb_kzg_eval_quotient_device(p.data_ptr(), z.data_ptr(), k, n, 0 if tile is None else int(tile), ys.data_ptr(), qs.data_ptr(),
+                                                     s.cuda_stream, ctypes.byref(st))
+    _r1cs_check(rc, st)
+    for t in (p, z, ys, qs):
+        t.record_stream(s)
+    return ys, qs
+
+
+def kzg_phase_ms(k):
+    """{quotient, lincomb, prepare, pairing} in ms of the handle's last open or verify call (waits for it)."""
+    ms = (ctypes.c_float * 4)()
+    if r1cs_lib().gwb_kzg_phase_ms(k._h, ms) != 0:
+        raise WitnessCalcError("no KZG phase times (no open or verify call yet)")
+    return dict(zip(KZG_PHASES, (float(x) for x in ms)))
 
 
 from . import graphgen  # noqa: E402,F401  (graph generator library on top of the C-ABI producer)
