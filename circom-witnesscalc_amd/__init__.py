@@ -8,57 +8,113 @@ include/*.h).  This module binds it with ctypes and mirrors the reference's Rust
 There is no CPU evaluation path: every witness value is computed by the HIP kernels; without the
 shared library or without a HIP device the calls raise.
 """
+import contextlib
 import ctypes
+import functools
 import os
 import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("CWC_LIB_PATH") or os.path.join(_HERE, "libcircom_witnesscalc_amd.so")
-_lib = None
-
-
-class GwStatus(ctypes.Structure):
-    _fields_ = [("code", ctypes.c_int), ("error_msg", ctypes.c_void_p)]
-
-
-class GraphInfo(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_uint64) for n in ("n_nodes", "n_op", "n_input_nodes", "n_const", "n_inputs",
-                                                "n_witness", "depth", "algorithmic_bytes_per_set")]
-
-
-class Timing(ctypes.Structure):
-    _fields_ = [("tile_width", ctypes.c_uint32), ("n_launches", ctypes.c_uint32), ("n_bundles", ctypes.c_uint64),
-                ("n_slots", ctypes.c_uint64), ("interp_ms", ctypes.c_float), ("pack_ms", ctypes.c_float),
-                ("divider", ctypes.c_uint32), ("streams", ctypes.c_uint32)]
-
-
-class ProgramStats(ctypes.Structure):
-    _fields_ = [("tile_width", ctypes.c_uint32), ("divider", ctypes.c_uint32), ("streams", ctypes.c_uint32), ("n_classes", ctypes.c_uint32),
-                ("n_bundles", ctypes.c_uint64), ("n_fused_nodes", ctypes.c_uint64), ("class_bundles", ctypes.c_uint64 * 16),
-                ("class_nodes", ctypes.c_uint64 * 16), ("model_wave_cycles", ctypes.c_double), ("lanes_active_mean", ctypes.c_double),
-                ("values_per_bundle_mean", ctypes.c_double), ("chain_floor_cycles", ctypes.c_double), ("n_scan_steps", ctypes.c_uint64), ("n_conv_products", ctypes.c_uint64)]
-
+from . import _abi
+from ._abi import (DIAG_LIB_PATH, LIB_PATH, R1CS_LIB_PATH, E2eStats, GraphInfo, GwStatus, Handoff, KzgInfo,  # noqa: F401
+                   ProgramStats, PtauInfo, R1csInfo, R1csQapInfo, Timing, WitnessCalcError, ZkeyInfo, _HERE, _libc, lib, r1cs_lib)
 
 CLASS_NAMES = ["INPUT", "MUL", "LIN", "DIV", "CMPZ", "CMPS", "BIT", "IDIVMOD", "TERN", "DIVREQ", "DIVGET", "MULQ", "SYNC", "MULF", "SCAN"]
-
-
-class E2eStats(ctypes.Structure):
-    _fields_ = [("n_sets", ctypes.c_size_t), ("sub_batch", ctypes.c_size_t), ("parse_threads", ctypes.c_uint32), ("write_threads", ctypes.c_uint32),
-                ("parse_seconds", ctypes.c_double), ("wait_for_drain_seconds", ctypes.c_double), ("total_seconds", ctypes.c_double),
-                ("witness_bytes", ctypes.c_uint64), ("failed_sets", ctypes.c_uint64)]
-
-
-class Handoff(ctypes.Structure):
-    _fields_ = [("struct_size", ctypes.c_uint32), ("form", ctypes.c_uint32), ("hip_stream", ctypes.c_void_p), ("done_event", ctypes.c_void_p)]
-
-
 FORM_CANONICAL, FORM_MONTGOMERY = 0, 1
+EXPORTED_SYMBOLS = list(_abi.ABI)
+
+# The one call path, bound to each library's rule for freeing a status message: _call for lib(), _r1cs_call for r1cs_lib().
+# The other three take a status that the caller made (callers of the raw C functions outside this module).
+_call = functools.partial(_abi.call, _abi.free_status)
+_r1cs_call = functools.partial(_abi.call, _abi.free_malloced)
+_check = functools.partial(_abi.check, _abi.free_status)
+_r1cs_check = functools.partial(_abi.check, _abi.free_malloced)
+_take_status = functools.partial(_abi.take_message, _abi.free_status)
 
 
-class WitnessCalcError(RuntimeError):
-    pass
+def __getattr__(name):
+    """_lib and _r1cs_lib: the loaded libraries, None before their first use (they live in _abi, which rebinds them)"""
+    if name in ("_lib", "_r1cs_lib"):
+        return getattr(_abi, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
+def _form(montgomery):
+    return FORM_MONTGOMERY if montgomery else FORM_CANONICAL
+
+
+def _take_image(out, n, free=None):
+    """the bytes of a malloc'ed image that a call handed out, which is then freed (by gwb_groth16_setup_free unless told otherwise)"""
+    try:
+        return ctypes.string_at(out, n.value)
+    finally:
+        (free or r1cs_lib().gwb_groth16_setup_free)(out)
+
+
+class _Handle:
+    """close() and __del__ of a class that owns a C handle in self._h.  _FREE: (the name under which _abi holds the loaded
+    library, the handle's free function).  The library is read, never loaded here, and a handle is only freed while it is still
+    there: that makes __del__ safe at interpreter shutdown."""
+    _FREE = None
+
+    def close(self):
+        L = getattr(_abi, self._FREE[0], None)
+        if getattr(self, "_h", None) and L is not None:
+            getattr(L, self._FREE[1])(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def _stream_of(t, stream):
+    import torch
+    return stream if stream is not None else torch.cuda.current_stream(t.device)
+
+
+@contextlib.contextmanager
+def _device_call(t, stream, record=()):
+    """The skeleton of an asynchronous device call: yields `stream`, or the current stream of t's device, with that device
+    current for the call inside; afterwards the tensors of `record` that have elements are recorded on the stream (so the
+    caching allocator keeps their memory until the call's work is done).  Nothing is recorded when the call raises."""
+    import torch
+    s = _stream_of(t, stream)
+    with torch.cuda.device(t.device):
+        yield s
+    for x in record:
+        if x.numel():
+            x.record_stream(s)
+
+
+def _phase_ms(fn, names, what, handle=None):
+    ms = (ctypes.c_float * len(names))()
+    if fn(*(() if handle is None else (handle,)), ms) != 0:
+        raise WitnessCalcError(what)
+    return dict(zip(names, (float(x) for x in ms)))
+
+
+def _name_bytes(name):
+    nm = name.encode("utf-8") if isinstance(name, str) else bytes(name)
+    if b"\0" in nm:
+        raise WitnessCalcError("the name holds a zero byte")
+    return nm
+
+
+@contextlib.contextmanager
+def _secret_scalars(values, refusals):
+    """None for None; else the ints as 32 little-endian bytes each in one ctypes buffer, zeroed on the way out.  refusals[i] is
+    the caller's message for values[i] outside [0, 2^256)."""
+    if values is None:
+        yield None
+        return
+    for v, refusal in zip(values, refusals):
+        if not 0 <= v < (1 << 256):
+            raise WitnessCalcError(refusal)
+    buf = ctypes.create_string_buffer(b"".join(v.to_bytes(32, "little") for v in values), 32 * len(values))
+    try:
+        yield buf
+    finally:
+        ctypes.memset(buf, 0, len(buf))
 
 
 def pinned_rows(shape):
@@ -73,21 +129,6 @@ def pinned_rows(shape):
     return np.frombuffer(buf, dtype=np.uint8, count=n).reshape(shape)
 
 
-EXPORTED_SYMBOLS = [
-    "gw_calc_witness", "gwb_graph_load", "gwb_graph_free", "gwb_graph_info", "gwb_graph_serialize",
-    "gwb_inputs_from_json", "gwb_set_tile_width", "gwb_calc_witness_batch_device", "gwb_calc_witness_batch_host",
-    "gwb_last_timing", "gwb_wtns_size", "gwb_wtns_from_witness", "gwb_graph_export", "gwb_graph_import",
-    "gwb_free_status", "gwb_profile_classes", "gwb_pick_tile_width", "gwb_inputs_from_json_batch", "gwb_wtns_save_batch",
-    "gwb_host_alloc", "gwb_host_free", "gwb_timing_history", "gwb_calc_witness_batch_handoff", "gwb_ubench_modmul", "gwb_graph_pick_tile_width", "gwb_graph_broadcast",
-    "gwb_builder_new", "gwb_builder_free", "gwb_builder_input", "gwb_builder_constant", "gwb_builder_uno", "gwb_builder_duo", "gwb_builder_tres",
-    "gwb_builder_witness", "gwb_builder_input_signal", "gwb_builder_node_count", "gwb_builder_finish",
-    "gwb_ubench_modmul_block", "gwb_program_stats", "gwb_calc_witness_json_to_wtns", "gwb_model_class_cycles",
-    "gwb_graphgen_bigint_class", "gwb_graphgen_rsa_long_div_class", "gwb_graph_op_histogram",
-    "gwb_kernel_source_hash", "gwb_pack_schedule", "gwb_pack_schedule_of_blob", "gwb_rccl_unique_id", "gwb_rccl_comm_init", "gwb_rccl_comm_ranks", "gwb_rccl_comm_destroy",
-    "gwb_wave_census",
-]
-
-
 def build(verbose=False, diag=False):
     """Compile the HIP extension in-tree (hipcc --offload-arch=gfx950).  diag=True also builds the diagnostic library
     (stamped interpreter instances for gwb_profile_classes; the class-profile / calibration tools load it via CWC_LIB_PATH)."""
@@ -99,116 +140,10 @@ def build(verbose=False, diag=False):
     subprocess.check_call(["make"] + ([] if verbose else ["-s"]) + ["-C", os.path.join(_HERE, "r1cs"), "-j4"])
 
 
-DIAG_LIB_PATH = os.path.join(_HERE, "libcircom_witnesscalc_amd_diag.so")
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise WitnessCalcError("HIP extension %s is missing: run __graft_entry__.build() "
-                                   "(there is no CPU fallback)" % LIB_PATH)
-        # One HIP runtime per process: torch bundles its own libamdhip64 (soname libamdhip64.so.7).  Loading
-        # torch first makes this library's NEEDED libamdhip64.so.7 resolve to that already-loaded copy; the
-        # other order would map a second runtime (system ROCm) next to torch's and torch then sees no GPU.
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        L = ctypes.CDLL(LIB_PATH)
-        vp, sz, u32p = ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)
-        stp = ctypes.POINTER(GwStatus)
-        L.gw_calc_witness.restype = ctypes.c_int
-        L.gw_calc_witness.argtypes = [ctypes.c_char_p, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
-        L.gwb_graph_load.restype = ctypes.c_int
-        L.gwb_graph_load.argtypes = [vp, sz, ctypes.POINTER(vp), stp]
-        L.gwb_graph_free.argtypes = [vp]
-        L.gwb_graph_info.argtypes = [vp, ctypes.POINTER(GraphInfo)]
-        L.gwb_graph_serialize.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
-        L.gwb_inputs_from_json.argtypes = [vp, ctypes.c_char_p, vp, stp]
-        L.gwb_set_tile_width.argtypes = [vp, ctypes.c_uint32]
-        L.gwb_calc_witness_batch_device.argtypes = [vp, vp, sz, vp, vp, vp, stp]
-        L.gwb_calc_witness_batch_host.argtypes = [vp, vp, sz, vp, vp, stp]
-        L.gwb_last_timing.argtypes = [vp, ctypes.POINTER(Timing)]
-        L.gwb_host_alloc.restype = ctypes.c_void_p
-        L.gwb_host_alloc.argtypes = [sz]
-        L.gwb_host_free.restype = None
-        L.gwb_host_free.argtypes = [ctypes.c_void_p]
-        L.gwb_timing_history.restype = ctypes.c_int
-        L.gwb_timing_history.argtypes = [ctypes.c_void_p, sz, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(sz)]
-        L.gwb_wtns_size.restype = sz
-        L.gwb_wtns_size.argtypes = [sz]
-        L.gwb_wtns_from_witness.argtypes = [vp, sz, vp]
-        L.gwb_graph_export.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
-        L.gwb_graph_import.argtypes = [vp, sz, ctypes.POINTER(vp), stp]
-        L.gwb_free_status.argtypes = [stp]
-        if hasattr(L, "gwb_graphgen_bigint_class"):  # (absent from an older build loaded through CWC_LIB_PATH for a same-box A/B)
-            L.gwb_graphgen_bigint_class.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
-            L.gwb_graphgen_rsa_long_div_class.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
-            L.gwb_graph_op_histogram.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), sz]
-        L.gwb_profile_classes.argtypes = [vp, vp, sz, vp, vp, vp, stp]
-        if hasattr(L, "gwb_wave_census"):  # (absent from an older build loaded through CWC_LIB_PATH for a same-box A/B)
-            L.gwb_wave_census.argtypes = [vp, vp, sz, vp, vp, vp, sz, stp]
-        L.gwb_inputs_from_json_batch.argtypes = [vp, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz), stp]
-        L.gwb_wtns_save_batch.argtypes = [vp, sz, sz, ctypes.c_char_p, stp]
-        L.gwb_calc_witness_batch_handoff.argtypes = [vp, vp, sz, vp, vp, ctypes.POINTER(Handoff), stp]
-        L.gwb_ubench_modmul.restype = ctypes.c_double
-        L.gwb_ubench_modmul.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
-        L.gwb_ubench_modmul_block.restype = ctypes.c_double
-        L.gwb_model_class_cycles.restype = ctypes.c_double
-        L.gwb_kernel_source_hash.restype = ctypes.c_char_p
-        L.gwb_kernel_source_hash.argtypes = []
-        L.gwb_model_class_cycles.argtypes = [ctypes.c_uint32]
-        L.gwb_ubench_modmul_block.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
-        L.gwb_program_stats.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ProgramStats)]
-        if hasattr(L, "gwb_pack_schedule"):  # (absent from an older build loaded through CWC_LIB_PATH for a same-box A/B)
-            L.gwb_pack_schedule.argtypes = [vp, ctypes.c_uint32, vp, sz, vp, sz, u32p, u32p, u32p, stp]
-            L.gwb_pack_schedule_of_blob.argtypes = [vp, sz, vp, sz, vp, sz, u32p, u32p, u32p, stp]
-        L.gwb_calc_witness_json_to_wtns.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.POINTER(sz), vp, sz, ctypes.POINTER(E2eStats), stp]
-        L.gwb_graph_pick_tile_width.restype = ctypes.c_uint32
-        L.gwb_graph_pick_tile_width.argtypes = [vp, sz]
-        L.gwb_pick_tile_width.restype = ctypes.c_uint32
-        L.gwb_pick_tile_width.argtypes = [sz]
-        u32 = ctypes.c_uint32
-        L.gwb_builder_new.restype = vp
-        L.gwb_builder_new.argtypes = []
-        L.gwb_builder_free.restype = None
-        L.gwb_builder_free.argtypes = [vp]
-        for name, args in (("input", [u32]), ("constant", [ctypes.c_char_p, sz]), ("uno", [u32, u32]), ("duo", [u32, u32, u32]), ("tres", [u32, u32, u32, u32])):
-            f = getattr(L, "gwb_builder_" + name)
-            f.restype = u32
-            f.argtypes = [vp] + args
-        L.gwb_builder_witness.argtypes = [vp, u32]
-        L.gwb_builder_input_signal.argtypes = [vp, ctypes.c_char_p, u32, u32]
-        L.gwb_builder_node_count.restype = ctypes.c_uint64
-        L.gwb_builder_node_count.argtypes = [vp]
-        L.gwb_builder_finish.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
-        _lib = L
-    return _lib
-
-
-_libc = ctypes.CDLL(None)
-_libc.free.argtypes = [ctypes.c_void_p]
-
-
-def _take_status(st):
-    msg = ctypes.string_at(st.error_msg).decode("utf-8", "replace") if st.error_msg else ""
-    lib().gwb_free_status(ctypes.byref(st))
-    return msg
-
-
-def _check(rc, st):
-    msg = _take_status(st)
-    if rc != 0:
-        raise WitnessCalcError(msg or "call failed")
-
-
 def wtns_save_batch(witness, path_pattern):
     """One `.wtns` file per input set; witness uint8 [B, W, 32]; path_pattern with one %lu (gwb_wtns_save_batch)."""
     witness = np.ascontiguousarray(witness, dtype=np.uint8)
-    st = GwStatus()
-    rc = lib().gwb_wtns_save_batch(witness.ctypes.data, witness.shape[1], witness.shape[0], path_pattern.encode(), ctypes.byref(st))
-    _check(rc, st)
+    _call(lib().gwb_wtns_save_batch, witness.ctypes.data, witness.shape[1], witness.shape[0], path_pattern.encode())
 
 
 def ubench_modmul(waves_per_simd=4, iters=2000, block=False):
@@ -234,19 +169,16 @@ def graphgen_native(kind, **kw):
     """`.bin` bytes of one of BASELINE config 5's class graphs from the native generators (gwb_graphgen_*): kind "bigint" (k, n_bits,
     rounds) or "rsa" (n, k, muls, range_checks) -- the same bytes as graphgen.circuits.build_bigint_class / build_rsa_long_div_class
     write, without ten million nodes passing through Python."""
-    out, n, st = ctypes.c_void_p(), ctypes.c_size_t(), GwStatus()
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
     L = lib()
     if kind == "bigint":
-        rc = L.gwb_graphgen_bigint_class(int(kw.get("k", 8)), int(kw.get("n_bits", 64)), int(kw.get("rounds", 4)), ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
+        _call(L.gwb_graphgen_bigint_class, int(kw.get("k", 8)), int(kw.get("n_bits", 64)), int(kw.get("rounds", 4)), ctypes.byref(out), ctypes.byref(n))
     elif kind == "rsa":
-        rc = L.gwb_graphgen_rsa_long_div_class(int(kw.get("n", 121)), int(kw.get("k", 17)), int(kw.get("muls", 2)), 1 if kw.get("range_checks", True) else 0,
-                                               ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
+        _call(L.gwb_graphgen_rsa_long_div_class, int(kw.get("n", 121)), int(kw.get("k", 17)), int(kw.get("muls", 2)), 1 if kw.get("range_checks", True) else 0,
+              ctypes.byref(out), ctypes.byref(n))
     else:
         raise ValueError(kind)
-    _check(rc, st)
-    data = ctypes.string_at(out.value, n.value)
-    _libc.free(out)
-    return data
+    return _take_image(out, n, _libc.free)
 
 
 def pick_tile_width(batch):
@@ -259,13 +191,9 @@ def calc_witness_wtns(inputs_json, graph_data):
     if isinstance(inputs_json, str):
         inputs_json = inputs_json.encode("utf-8")
     graph_data = bytes(graph_data)
-    out, n, st = ctypes.c_void_p(), ctypes.c_size_t(), GwStatus()
-    rc = lib().gw_calc_witness(inputs_json, graph_data, len(graph_data), ctypes.byref(out), ctypes.byref(n),
-                               ctypes.byref(st))
-    _check(rc, st)
-    data = ctypes.string_at(out.value, n.value)
-    _libc.free(out)
-    return data
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    _call(lib().gw_calc_witness, inputs_json, graph_data, len(graph_data), ctypes.byref(out), ctypes.byref(n))
+    return _take_image(out, n, _libc.free)
 
 
 def calc_witness(inputs_json, graph_data):
@@ -287,9 +215,10 @@ def wtns_from_witness(witness):
     return out.tobytes()
 
 
-class Graph:
+class Graph(_Handle):
     """A parsed + compiled graph (deserialize_witnesscalc_graph, reference src/storage.rs:214-249), reusable
     across calls -- the reference re-parses the `.bin` on every calc_witness (src/lib.rs:129)."""
+    _FREE = ("_lib", "gwb_graph_free")
 
     def __init__(self, graph_data=None, _handle=None):
         self._h = ctypes.c_void_p()
@@ -297,28 +226,18 @@ class Graph:
             self._h = _handle
         else:
             graph_data = bytes(graph_data)
-            st = GwStatus()
-            rc = lib().gwb_graph_load(graph_data, len(graph_data), ctypes.byref(self._h), ctypes.byref(st))
-            _check(rc, st)
+            _call(lib().gwb_graph_load, graph_data, len(graph_data), ctypes.byref(self._h))
         info = GraphInfo()
         lib().gwb_graph_info(self._h, ctypes.byref(info))
         for name, _ in GraphInfo._fields_:
             setattr(self, name, int(getattr(info, name)))
 
-    def close(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.gwb_graph_free(self._h)
-            self._h = None
-
-    __del__ = close
-
     @classmethod
     def from_blob(cls, blob):
         """gwb_graph_import: build a replica from a compiled-program blob (what ranks receive over RCCL)."""
         blob = bytes(blob)
-        h, st = ctypes.c_void_p(), GwStatus()
-        rc = lib().gwb_graph_import(blob, len(blob), ctypes.byref(h), ctypes.byref(st))
-        _check(rc, st)
+        h = ctypes.c_void_p()
+        _call(lib().gwb_graph_import, blob, len(blob), ctypes.byref(h))
         return cls(_handle=h)
 
     def op_histogram(self):
@@ -331,21 +250,15 @@ class Graph:
         return dict(sorted(((nm, int(h[i])) for i, nm in enumerate(names) if h[i]), key=lambda kv: -kv[1]))
 
     def export_blob(self, tile_width):
-        out, n, st = ctypes.c_void_p(), ctypes.c_size_t(), GwStatus()
-        rc = lib().gwb_graph_export(self._h, tile_width, ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
-        _check(rc, st)
-        data = ctypes.string_at(out.value, n.value)
-        _libc.free(out)
-        return data
+        out, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _call(lib().gwb_graph_export, self._h, tile_width, ctypes.byref(out), ctypes.byref(n))
+        return _take_image(out, n, _libc.free)
 
     def serialize(self):
         """serialize_witnesscalc_graph (reference src/storage.rs:137-183)."""
-        out, n, st = ctypes.c_void_p(), ctypes.c_size_t(), GwStatus()
-        rc = lib().gwb_graph_serialize(self._h, ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
-        _check(rc, st)
-        data = ctypes.string_at(out.value, n.value)
-        _libc.free(out)
-        return data
+        out, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _call(lib().gwb_graph_serialize, self._h, ctypes.byref(out), ctypes.byref(n))
+        return _take_image(out, n, _libc.free)
 
     def pick_tile_width(self, batch):
         """Program key the cost model chooses for this graph at this batch size (gwb_graph_pick_tile_width)."""
@@ -363,9 +276,7 @@ class Graph:
         if isinstance(inputs_json, str):
             inputs_json = inputs_json.encode("utf-8")
         row = np.zeros((self.n_inputs, 32), dtype=np.uint8)
-        st = GwStatus()
-        rc = lib().gwb_inputs_from_json(self._h, inputs_json, row.ctypes.data, ctypes.byref(st))
-        _check(rc, st)
+        _call(lib().gwb_inputs_from_json, self._h, inputs_json, row.ctypes.data)
         return row
 
     def inputs_from_json_batch(self, text):
@@ -373,15 +284,13 @@ class Graph:
         if isinstance(text, str):
             text = text.encode("utf-8")
         n = ctypes.c_size_t()
-        st = GwStatus()
-        lib().gwb_inputs_from_json_batch(self._h, text, len(text), None, 0, ctypes.byref(n), ctypes.byref(st))
-        msg = _take_status(st)
-        if "rows buffer too small" not in msg and msg:
-            raise WitnessCalcError(msg)
+        try:  # (the count of input sets: with no room for rows, any text that holds a set is refused for that alone)
+            _call(lib().gwb_inputs_from_json_batch, self._h, text, len(text), None, 0, ctypes.byref(n))
+        except WitnessCalcError as e:
+            if "rows buffer too small" not in str(e):
+                raise
         rows = np.zeros((n.value, self.n_inputs, 32), dtype=np.uint8)
-        st = GwStatus()
-        rc = lib().gwb_inputs_from_json_batch(self._h, text, len(text), rows.ctypes.data, n.value, ctypes.byref(n), ctypes.byref(st))
-        _check(rc, st)
+        _call(lib().gwb_inputs_from_json_batch, self._h, text, len(text), rows.ctypes.data, n.value, ctypes.byref(n))
         return rows
 
     def json_to_wtns(self, text, path_pattern, first_index=0, with_status=True):
@@ -393,11 +302,9 @@ class Graph:
         n = ctypes.c_size_t()
         cap = max(1, text.count(b"\n") + 1, text.count(b"{"))
         status = np.zeros(cap, dtype=np.uint32)
-        es, st = E2eStats(), GwStatus()
-        rc = lib().gwb_calc_witness_json_to_wtns(self._h, text, len(text), path_pattern.encode(), first_index, ctypes.byref(n),
-                                                  status.ctypes.data if with_status else None, cap if with_status else 0,
-                                                  ctypes.byref(es), ctypes.byref(st))
-        _check(rc, st)
+        es = E2eStats()
+        _call(lib().gwb_calc_witness_json_to_wtns, self._h, text, len(text), path_pattern.encode(), first_index, ctypes.byref(n),
+              status.ctypes.data if with_status else None, cap if with_status else 0, ctypes.byref(es))
         return status[:n.value], {k: getattr(es, k) for k, _ in E2eStats._fields_}
 
     def calc_witness_batch(self, inputs, out=None):
@@ -412,10 +319,7 @@ class Graph:
             wit = out
             assert wit.dtype == np.uint8 and wit.shape == (b, self.n_witness, 32) and wit.flags["C_CONTIGUOUS"]
         status = np.zeros(b, dtype=np.uint32)
-        st = GwStatus()
-        rc = lib().gwb_calc_witness_batch_host(self._h, inputs.ctypes.data, b, wit.ctypes.data, status.ctypes.data,
-                                               ctypes.byref(st))
-        _check(rc, st)
+        _call(lib().gwb_calc_witness_batch_host, self._h, inputs.ctypes.data, b, wit.ctypes.data, status.ctypes.data)
         return wit, status
 
     def calc_witness_batch_device(self, d_inputs, d_witness, d_status, stream=None, montgomery=False, done_event=None):
@@ -428,18 +332,13 @@ class Graph:
         assert d_inputs.is_contiguous() and d_witness.is_contiguous() and d_status.is_contiguous()
         assert tuple(d_inputs.shape[1:]) == (self.n_inputs, 32) and tuple(d_witness.shape) == (b, self.n_witness, 32)
         s = stream if stream is not None else torch.cuda.current_stream()
-        st = GwStatus()
         if montgomery or done_event is not None:
             if done_event is not None:
                 done_event.record(s)  # (creates the underlying hipEvent_t; the library records it again behind its kernels)
-            h = Handoff(ctypes.sizeof(Handoff), FORM_MONTGOMERY if montgomery else FORM_CANONICAL, s.cuda_stream,
-                        done_event.cuda_event if done_event is not None else None)
-            rc = lib().gwb_calc_witness_batch_handoff(self._h, d_inputs.data_ptr(), b, d_witness.data_ptr(), d_status.data_ptr(),
-                                                      ctypes.byref(h), ctypes.byref(st))
+            h = Handoff(ctypes.sizeof(Handoff), _form(montgomery), s.cuda_stream, done_event.cuda_event if done_event is not None else None)
+            _call(lib().gwb_calc_witness_batch_handoff, self._h, d_inputs.data_ptr(), b, d_witness.data_ptr(), d_status.data_ptr(), ctypes.byref(h))
         else:
-            rc = lib().gwb_calc_witness_batch_device(self._h, d_inputs.data_ptr(), b, d_witness.data_ptr(),
-                                                     d_status.data_ptr(), s.cuda_stream, ctypes.byref(st))
-        _check(rc, st)
+            _call(lib().gwb_calc_witness_batch_device, self._h, d_inputs.data_ptr(), b, d_witness.data_ptr(), d_status.data_ptr(), s.cuda_stream)
 
     def timing_history(self, max_launches):
         """(interp_ms, pack_ms) float32 arrays of the most recent launches on this handle, oldest first (synchronizes
@@ -455,10 +354,7 @@ class Graph:
         """Diagnostic stamped build: {class: (cycles, 0, 0, bundles)} over sampled waves, plus "_sections":
         {"MUL" / "LIN": (top + staged-operand wait, LDS reads + previous bundle's stores, staging issue, arithmetic, ring write, bundles)}."""
         out = np.zeros(96, dtype=np.uint64)
-        st = GwStatus()
-        rc = lib().gwb_profile_classes(self._h, d_inputs.data_ptr(), d_inputs.shape[0], d_witness.data_ptr(),
-                                       d_status.data_ptr(), out.ctypes.data, ctypes.byref(st))
-        _check(rc, st)
+        _call(lib().gwb_profile_classes, self._h, d_inputs.data_ptr(), d_inputs.shape[0], d_witness.data_ptr(), d_status.data_ptr(), out.ctypes.data)
         names = ["INPUT", "MUL", "LIN", "DIV", "CMPZ", "CMPS", "BIT", "IDIVMOD", "TERN", "DIVREQ", "DIVGET", "MULQ"]
         res = {n: tuple(int(x) for x in out[4 * i:4 * i + 4]) for i, n in enumerate(names)}
         res["MULF"] = tuple(int(x) for x in out[64:68])
@@ -479,10 +375,7 @@ class Graph:
         {"workgroup", "wave" (of the workgroup), "xcc", "se", "sh", "cu", "simd", "divider", "stream", "has_tile", "start", "end"}
         (s_memtime; end 0: the wave had nothing to do).  At most the launch's first 8192 waves."""
         out = np.zeros(3 * 8192, dtype=np.uint64)
-        st = GwStatus()
-        rc = lib().gwb_wave_census(self._h, d_inputs.data_ptr(), d_inputs.shape[0], d_witness.data_ptr(),
-                                   d_status.data_ptr(), out.ctypes.data, out.size, ctypes.byref(st))
-        _check(rc, st)
+        _call(lib().gwb_wave_census, self._h, d_inputs.data_ptr(), d_inputs.shape[0], d_witness.data_ptr(), d_status.data_ptr(), out.ctypes.data, out.size)
         rec = out.reshape(-1, 3)
         idx = [i for i in range(rec.shape[0]) if rec[i, 1]]
         res = []
@@ -516,10 +409,10 @@ class Graph:
 
 
 def _pack_schedule(call):
-    nw, nr, ni, st = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32(), GwStatus()
-    _check(call(None, 0, None, 0, ctypes.byref(nw), ctypes.byref(nr), ctypes.byref(ni), ctypes.byref(st)), st)
+    nw, nr, ni = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    _call(call, None, 0, None, 0, ctypes.byref(nw), ctypes.byref(nr), ctypes.byref(ni))
     order, ready = np.zeros(nw.value, dtype=np.uint32), np.zeros(nr.value, dtype=np.uint32)
-    _check(call(order.ctypes.data, order.size, ready.ctypes.data, ready.size, ctypes.byref(nw), ctypes.byref(nr), ctypes.byref(ni), ctypes.byref(st)), st)
+    _call(call, order.ctypes.data, order.size, ready.ctypes.data, ready.size, ctypes.byref(nw), ctypes.byref(nr), ctypes.byref(ni))
     return order, ready, int(ni.value)
 
 
@@ -530,171 +423,7 @@ def pack_schedule_of_blob(blob):
 
 
 # -- R1CS satisfaction check (include/graph_witness_r1cs.h, libcwc_r1cs.so built from r1cs/) ------------------------------
-R1CS_LIB_PATH = os.environ.get("CWC_R1CS_LIB_PATH") or os.path.join(_HERE, "libcwc_r1cs.so")
 R1CS_SATISFIED = 0xFFFFFFFF
-_r1cs_lib = None
-
-
-class R1csInfo(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_uint32) for n in ("n_wires", "n_pub_out", "n_pub_in", "n_prv_in", "n_constraints")] + \
-               [(n, ctypes.c_uint64) for n in ("n_labels", "n_factors_a", "n_factors_b", "n_factors_c")]
-
-
-class R1csQapInfo(ctypes.Structure):
-    _fields_ = [("n_rows", ctypes.c_uint64), ("domain_power", ctypes.c_uint32), ("domain_size", ctypes.c_uint64),
-                ("workspace_bytes_per_row", ctypes.c_uint64)]
-
-
-class ZkeyInfo(ctypes.Structure):
-    _fields_ = [("n_vars", ctypes.c_uint32), ("n_public", ctypes.c_uint32), ("domain_size", ctypes.c_uint32), ("n_coefs", ctypes.c_uint64)]
-
-
-class PtauInfo(ctypes.Structure):
-    _fields_ = [("power", ctypes.c_uint32), ("ceremony_power", ctypes.c_uint32), ("prepared", ctypes.c_uint32),
-                ("n_contributions", ctypes.c_uint32)]
-
-
-class KzgInfo(ctypes.Structure):
-    _fields_ = [("max_len", ctypes.c_uint64), ("power", ctypes.c_uint32), ("prepared", ctypes.c_uint32)]
-
-
-def r1cs_lib():
-    """ctypes handle of libcwc_r1cs.so, loaded after torch (one HIP runtime per process, as in lib())."""
-    global _r1cs_lib
-    if _r1cs_lib is None:
-        if not os.path.exists(R1CS_LIB_PATH):
-            raise WitnessCalcError("R1CS library %s is missing: run __graft_entry__.build()" % R1CS_LIB_PATH)
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        L = ctypes.CDLL(R1CS_LIB_PATH)
-        vp, sz, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32
-        stp = ctypes.POINTER(GwStatus)
-        L.gwb_r1cs_load.argtypes = [vp, sz, ctypes.POINTER(vp), stp]
-        L.gwb_r1cs_free.restype = None
-        L.gwb_r1cs_free.argtypes = [vp]
-        L.gwb_r1cs_info.argtypes = [vp, ctypes.POINTER(R1csInfo)]
-        L.gwb_r1cs_set_tile_width.argtypes = [vp, u32]
-        L.gwb_r1cs_check_batch_device.argtypes = [vp, vp, sz, sz, u32, vp, vp, vp, stp]
-        L.gwb_r1cs_check_batch_host.argtypes = [vp, vp, sz, sz, vp, vp, stp]
-        L.gwb_r1cs_check_wtns.argtypes = [vp, vp, sz, vp, vp, stp]
-        L.gwb_r1cs_qap_info.argtypes = [vp, ctypes.POINTER(R1csQapInfo), stp]
-        L.gwb_r1cs_qap_batch_device.argtypes = [vp, vp, sz, sz, u32, vp, u32, vp, stp]
-        L.gwb_r1cs_qap_batch_host.argtypes = [vp, vp, sz, sz, vp, u32, stp]
-        L.gwb_r1cs_qap_wtns.argtypes = [vp, vp, sz, vp, u32, stp]
-        L.gwb_r1cs_qap_time_phases.argtypes = [vp, ctypes.c_int]
-        L.gwb_r1cs_qap_phase_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
-        L.gwb_r1cs_modmul_rate.argtypes = [ctypes.POINTER(ctypes.c_double)]
-        L.gwb_zkey_load.argtypes = [vp, sz, ctypes.POINTER(vp), stp]
-        L.gwb_zkey_free.restype = None
-        L.gwb_zkey_free.argtypes = [vp]
-        L.gwb_zkey_info.argtypes = [vp, ctypes.POINTER(ZkeyInfo)]
-        L.gwb_groth16_prove_batch_device.argtypes = [vp, vp, vp, sz, sz, u32, vp, vp, vp, stp]
-        L.gwb_groth16_prove_batch_host.argtypes = [vp, vp, vp, sz, sz, vp, vp, stp]
-        L.gwb_groth16_prove_wtns.argtypes = [vp, vp, vp, sz, vp, vp, stp]
-        L.gwb_groth16_time_phases.argtypes = [vp, ctypes.c_int]
-        L.gwb_groth16_phase_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
-        L.gwb_zkey_qap_info.argtypes = [vp, ctypes.POINTER(R1csQapInfo), stp]
-        L.gwb_zkey_qap_batch_device.argtypes = [vp, vp, sz, sz, u32, vp, u32, vp, stp]
-        L.gwb_zkey_qap_batch_host.argtypes = [vp, vp, sz, sz, vp, u32, stp]
-        L.gwb_zkey_set_tile_width.argtypes = [vp, u32]
-        L.gwb_zkey_check_r1cs.argtypes = [vp, vp, stp]
-        L.gwb_g16vk_from_zkey.argtypes = [vp, ctypes.POINTER(vp), stp]
-        L.gwb_g16vk_load.argtypes = [vp, sz, u32, ctypes.POINTER(vp), stp]
-        L.gwb_g16vk_info.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
-        L.gwb_g16vk_points.argtypes = [vp, vp, sz]
-        L.gwb_g16vk_alphabeta.argtypes = [vp, vp, stp]
-        L.gwb_g16vk_free.restype = None
-        L.gwb_g16vk_free.argtypes = [vp]
-        L.gwb_groth16_verify_batch_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, stp]
-        L.gwb_groth16_verify_batch_host.argtypes = [vp, vp, vp, sz, sz, vp, stp]
-        L.gwb_bn254_pairing_batch_device.argtypes = [vp, vp, sz, vp, vp, stp]
-        L.gwb_groth16_setup.argtypes = [vp, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
-        L.gwb_groth16_setup_free.restype = None
-        L.gwb_groth16_setup_free.argtypes = [vp]
-        L.gwb_bn254_gen_mul_batch_device.argtypes = [vp, sz, u32, vp, vp, stp]
-        L.gwb_groth16_setup_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_float)]
-        L.gwb_ptau_info.argtypes = [vp, sz, ctypes.POINTER(PtauInfo), stp]
-        L.gwb_ptau_check.argtypes = [vp, sz, u32, u32, stp]
-        L.gwb_groth16_setup_ptau.argtypes = [vp, vp, sz, vp, u32, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
-        L.gwb_bn254_point_idft_batch_device.argtypes = [vp, u32, u32, vp, vp, stp]
-        L.gwb_groth16_setup_ptau_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_float)]
-        L.gwb_bn254_g2_check_batch_device.argtypes = [vp, sz, u32, u32, vp, vp, stp]
-        L.gwb_zkey_check_g2.argtypes = [vp, stp]
-        L.gwb_zkey_check_wtns.argtypes = [vp, vp, sz, stp]
-        L.gwb_ptau_check_g2.argtypes = [vp, sz, u32, u32, stp]
-        L.gwb_groth16_contribute.argtypes = [vp, sz, ctypes.c_char_p, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), vp, stp]
-        L.gwb_groth16_contribute_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_float)]
-        L.gwb_zkey_verify_contributions.argtypes = [vp, sz, vp, ctypes.POINTER(sz), stp]
-        L.gwb_zkey_verify_step.argtypes = [vp, sz, vp, sz, vp, stp]
-        L.gwb_zkey_contributions.argtypes = [vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
-        L.gwb_blake2b512.restype = None
-        L.gwb_blake2b512.argtypes = [vp, sz, vp]
-        L.gwb_zkey_contribution_challenge.restype = None
-        L.gwb_zkey_contribution_challenge.argtypes = [vp, vp]
-        L.gwb_bn254_g1_scale_batch_device.argtypes = [vp, sz, vp, vp, vp, stp]
-        L.gwb_bn254_g1_lincomb128_device.argtypes = [vp, vp, sz, vp, vp, stp]
-        L.gwb_bn254_g2_lincomb128_device.argtypes = [vp, vp, sz, vp, vp, stp]
-        L.gwb_ptau_check_powers.argtypes = [vp, sz, u32, vp, stp]
-        L.gwb_zkey_verify_key.argtypes = [vp, sz, vp, vp, sz, u32, u32, vp, vp, ctypes.POINTER(sz), stp]
-        L.gwb_zkey_verify_key_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_float)]
-        L.gwb_ptau_prepare_phase2.argtypes = [vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
-        L.gwb_ptau_prepare_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_float)]
-        L.gwb_ptau_check_lagrange.argtypes = [vp, sz, u32, vp, stp]
-        L.gwb_bn254_g1_lincomb_device.argtypes = [vp, vp, sz, u32, vp, vp, stp]
-        L.gwb_bn254_g2_lincomb_device.argtypes = [vp, vp, sz, u32, vp, vp, stp]
-        L.gwb_ptau_new.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
-        L.gwb_ptau_contribute.argtypes = [vp, sz, ctypes.c_char_p, vp, ctypes.POINTER(vp), ctypes.POINTER(sz), vp, stp]
-        L.gwb_ptau_contribute_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_float)]
-        L.gwb_ptau_contributions.argtypes = [vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
-        L.gwb_ptau_verify.argtypes = [vp, sz, u32, vp, vp, ctypes.POINTER(sz), stp]
-        L.gwb_ptau_verify_step.argtypes = [vp, sz, vp, sz, vp, stp]
-        L.gwb_bn254_g1_mul_batch_device.argtypes = [vp, vp, sz, u32, u32, vp, vp, stp]
-        L.gwb_bn254_g2_mul_batch_device.argtypes = [vp, vp, sz, u32, u32, vp, vp, stp]
-        L.gwb_ptau_beacon.argtypes = [vp, sz, ctypes.c_char_p, vp, sz, u32, ctypes.POINTER(vp), ctypes.POINTER(sz), vp, stp]
-        L.gwb_groth16_beacon.argtypes = [vp, sz, ctypes.c_char_p, vp, sz, u32, ctypes.POINTER(vp), ctypes.POINTER(sz), vp, stp]
-        L.gwb_beacon_scalars.argtypes = [u32, vp, sz, u32, vp]
-        L.gwb_ptau_contribution_params.argtypes = [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
-        L.gwb_zkey_contribution_params.argtypes = [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), stp]
-        L.gwb_sha256.restype = None
-        L.gwb_sha256.argtypes = [vp, sz, vp]
-        L.gwb_bn254_compress_batch_device.argtypes = [vp, sz, u32, u32, vp, vp, stp]
-        L.gwb_bn254_decompress_batch_device.argtypes = [vp, sz, u32, u32, vp, vp, vp, stp]
-        L.gwb_groth16_proofs_compress_device.argtypes = [vp, sz, vp, vp, stp]
-        L.gwb_groth16_proofs_decompress_device.argtypes = [vp, sz, vp, vp, vp, stp]
-        L.gwb_groth16_verify_batch_compressed_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, stp]
-        L.gwb_groth16_verify_batch_compressed_host.argtypes = [vp, vp, vp, sz, sz, vp, stp]
-        L.gwb_g16vk_load_compressed.argtypes = [vp, sz, ctypes.POINTER(vp), stp]
-        L.gwb_g16vk_compressed.argtypes = [vp, vp, sz]
-        u64 = ctypes.c_uint64
-        L.gwb_kzg_new.argtypes = [vp, sz, u64, u32, ctypes.POINTER(vp), stp]
-        L.gwb_kzg_info.argtypes = [vp, ctypes.POINTER(KzgInfo)]
-        L.gwb_kzg_free.restype = None
-        L.gwb_kzg_free.argtypes = [vp]
-        L.gwb_kzg_commit_batch.argtypes = [vp, vp, sz, sz, vp, stp]
-        L.gwb_kzg_commit_batch_device.argtypes = [vp, vp, sz, sz, vp, vp, stp]
-        L.gwb_kzg_commit_evals_batch.argtypes = [vp, vp, sz, u32, vp, stp]
-        L.gwb_kzg_commit_evals_batch_device.argtypes = [vp, vp, sz, u32, vp, vp, stp]
-        L.gwb_kzg_eval_batch.argtypes = [vp, vp, vp, sz, sz, vp, stp]
-        L.gwb_kzg_eval_batch_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, stp]
-        L.gwb_kzg_open_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, stp]
-        L.gwb_kzg_open_batch_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, stp]
-        L.gwb_kzg_verify_batch.argtypes = [vp, vp, vp, vp, vp, sz, vp, stp]
-        L.gwb_kzg_verify_batch_device.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, stp]
-        L.gwb_kzg_phase_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
-        L.gwb_kzg_eval_quotient_device.argtypes = [vp, vp, sz, sz, u32, vp, vp, vp, stp]
-        L.gwb_kzg_tiles.argtypes = [ctypes.POINTER(u32), ctypes.POINTER(sz)]
-        _r1cs_lib = L
-    return _r1cs_lib
-
-
-def _r1cs_check(rc, st):
-    msg = ctypes.string_at(st.error_msg).decode("utf-8", "replace") if st.error_msg else ""
-    if st.error_msg:
-        _libc.free(st.error_msg)
-    if rc != 0:
-        raise WitnessCalcError(msg or "call failed")
 
 
 def modmul_rate():
@@ -708,9 +437,7 @@ def modmul_rate():
 # -- the Groth16 witness map, shared by R1cs (gwb_r1cs_qap_*) and Groth16 (gwb_zkey_qap_*): `src` is "r1cs" or "zkey" ----------
 def _qap_info(h, src):
     info = R1csQapInfo()
-    st = GwStatus()
-    rc = getattr(r1cs_lib(), "gwb_%s_qap_info" % src)(h, ctypes.byref(info), ctypes.byref(st))
-    _r1cs_check(rc, st)
+    _r1cs_call(getattr(r1cs_lib(), "gwb_%s_qap_info" % src), h, ctypes.byref(info))
     return {n: int(getattr(info, n)) for n, _ in R1csQapInfo._fields_}
 
 
@@ -721,10 +448,7 @@ def _qap_batch(h, src, witness_rows, montgomery_out):
     assert w.ndim == 3 and w.shape[2] == 32, w.shape
     b = w.shape[0]
     out = np.zeros((b, _qap_info(h, src)["domain_size"], 32), dtype=np.uint8)
-    st = GwStatus()
-    rc = getattr(r1cs_lib(), "gwb_%s_qap_batch_host" % src)(h, w.ctypes.data, w.shape[1], b, out.ctypes.data,
-                                                            FORM_MONTGOMERY if montgomery_out else FORM_CANONICAL, ctypes.byref(st))
-    _r1cs_check(rc, st)
+    _r1cs_call(getattr(r1cs_lib(), "gwb_%s_qap_batch_host" % src), h, w.ctypes.data, w.shape[1], b, out.ctypes.data, _form(montgomery_out))
     return out
 
 
@@ -734,40 +458,25 @@ def _qap_batch_device(h, src, d_witness, stream, montgomery, montgomery_out):
     assert d_witness.dim() == 3 and d_witness.shape[2] == 32, tuple(d_witness.shape)
     b = d_witness.shape[0]
     n = _qap_info(h, src)["domain_size"]
-    s = stream if stream is not None else torch.cuda.current_stream(d_witness.device)
     out = torch.empty((b, n, 32), dtype=torch.uint8, device=d_witness.device)
-    st = GwStatus()
-    with torch.cuda.device(d_witness.device):
-        rc = getattr(r1cs_lib(), "gwb_%s_qap_batch_device" % src)(h, d_witness.data_ptr(), d_witness.shape[1], b,
-                                                                  FORM_MONTGOMERY if montgomery else FORM_CANONICAL, out.data_ptr(),
-                                                                  FORM_MONTGOMERY if montgomery_out else FORM_CANONICAL, s.cuda_stream,
-                                                                  ctypes.byref(st))
-    _r1cs_check(rc, st)
-    if b:
-        out.record_stream(s)
+    with _device_call(d_witness, stream, (out,)) as s:
+        _r1cs_call(getattr(r1cs_lib(), "gwb_%s_qap_batch_device" % src), h, d_witness.data_ptr(), d_witness.shape[1], b, _form(montgomery),
+                   out.data_ptr(), _form(montgomery_out), s.cuda_stream)
     return out
 
 
-class R1cs:
+class R1cs(_Handle):
     """A circuit's constraint system (`.r1cs` bytes, iden3 binfile v1; BN254, no custom gates) for checking witness rows on the
     GPU: per row, the smallest failing constraint index (R1CS_SATISFIED if none) and the number of failing constraints."""
+    _FREE = ("_r1cs_lib", "gwb_r1cs_free")
 
     def __init__(self, data):
         self._h = ctypes.c_void_p()
         data = bytes(data)
-        st = GwStatus()
-        rc = r1cs_lib().gwb_r1cs_load(data, len(data), ctypes.byref(self._h), ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_r1cs_load, data, len(data), ctypes.byref(self._h))
         info = R1csInfo()
         r1cs_lib().gwb_r1cs_info(self._h, ctypes.byref(info))
         self.info = {n: int(getattr(info, n)) for n, _ in R1csInfo._fields_}
-
-    def close(self):
-        if getattr(self, "_h", None) and _r1cs_lib is not None:
-            _r1cs_lib.gwb_r1cs_free(self._h)
-            self._h = None
-
-    __del__ = close
 
     def set_tile_width(self, t):
         """Witness rows per wavefront of the check kernel: a power of two in 1..64, or 0 = from the batch size."""
@@ -784,9 +493,7 @@ class R1cs:
         b = w.shape[0]
         first = np.zeros(b, dtype=np.uint32)
         nfail = np.zeros(b, dtype=np.uint32)
-        st = GwStatus()
-        rc = r1cs_lib().gwb_r1cs_check_batch_host(self._h, w.ctypes.data, w.shape[1], b, first.ctypes.data, nfail.ctypes.data, ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_r1cs_check_batch_host, self._h, w.ctypes.data, w.shape[1], b, first.ctypes.data, nfail.ctypes.data)
         return first, nfail
 
     def check_batch_device(self, d_witness, stream=None, montgomery=False):
@@ -797,24 +504,18 @@ class R1cs:
         assert d_witness.is_cuda and d_witness.is_contiguous() and d_witness.dtype == torch.uint8
         assert d_witness.dim() == 3 and d_witness.shape[2] == 32, tuple(d_witness.shape)
         b = d_witness.shape[0]
-        s = stream if stream is not None else torch.cuda.current_stream(d_witness.device)
         first = torch.empty(b, dtype=torch.int32, device=d_witness.device)
         nfail = torch.empty(b, dtype=torch.int32, device=d_witness.device)
-        st = GwStatus()
-        with torch.cuda.device(d_witness.device):
-            rc = r1cs_lib().gwb_r1cs_check_batch_device(self._h, d_witness.data_ptr(), d_witness.shape[1], b,
-                                                        FORM_MONTGOMERY if montgomery else FORM_CANONICAL, first.data_ptr(),
-                                                        nfail.data_ptr(), s.cuda_stream, ctypes.byref(st))
-        _r1cs_check(rc, st)
+        with _device_call(d_witness, stream) as s:
+            _r1cs_call(r1cs_lib().gwb_r1cs_check_batch_device, self._h, d_witness.data_ptr(), d_witness.shape[1], b, _form(montgomery),
+                       first.data_ptr(), nfail.data_ptr(), s.cuda_stream)
         return first, nfail
 
     def check_wtns(self, wtns):
         """One `.wtns` image -> (first_failed, n_failed); first_failed is R1CS_SATISFIED when every constraint holds."""
         wtns = bytes(wtns)
         first, nfail = ctypes.c_uint32(), ctypes.c_uint32()
-        st = GwStatus()
-        rc = r1cs_lib().gwb_r1cs_check_wtns(self._h, wtns, len(wtns), ctypes.byref(first), ctypes.byref(nfail), ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_r1cs_check_wtns, self._h, wtns, len(wtns), ctypes.byref(first), ctypes.byref(nfail))
         return int(first.value), int(nfail.value)
 
     # -- Groth16 witness map (h, the scalars of the prover's H-point MSM; definition in include/graph_witness_r1cs.h) --------
@@ -840,21 +541,15 @@ class R1cs:
 
     def qap_phase_ms(self):
         """Waits for the last QAP call -> {evaluation, inverse_outer, fused_inner, forward_outer} in ms (its last sub-batch)."""
-        ms = (ctypes.c_float * 4)()
-        if r1cs_lib().gwb_r1cs_qap_phase_ms(self._h, ms) != 0:
-            raise WitnessCalcError("no QAP phase times (qap_time_phases not on, or no QAP call yet)")
-        return dict(zip(("evaluation", "inverse_outer", "fused_inner", "forward_outer"), (float(x) for x in ms)))
+        return _phase_ms(r1cs_lib().gwb_r1cs_qap_phase_ms, ("evaluation", "inverse_outer", "fused_inner", "forward_outer"),
+                         "no QAP phase times (qap_time_phases not on, or no QAP call yet)", self._h)
 
     def qap_wtns(self, wtns, montgomery_out=False):
         """One `.wtns` image -> h as uint8 [n, 32]."""
         wtns = bytes(wtns)
         h = np.zeros((self.qap_info()["domain_size"], 32), dtype=np.uint8)
-        st = GwStatus()
-        rc = r1cs_lib().gwb_r1cs_qap_wtns(self._h, wtns, len(wtns), h.ctypes.data,
-                                          FORM_MONTGOMERY if montgomery_out else FORM_CANONICAL, ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_r1cs_qap_wtns, self._h, wtns, len(wtns), h.ctypes.data, _form(montgomery_out))
         return h
-
 
 
 # -- Groth16 prover (include/graph_witness_groth16.h, libcwc_r1cs.so) ----------------------------------------------------------
@@ -887,33 +582,25 @@ def proof_json(proof):
             "pi_c": [c[6], c[7], z(192, 256)], "protocol": "groth16", "curve": "bn128"}
 
 
-class Groth16:
+class Groth16(_Handle):
     """A circuit's Groth16 proving key (`.zkey` bytes, snarkjs's Groth16 format): proofs of witness rows on the GPU, 256 bytes
     per row (A.x, A.y, B.x.c0, B.x.c1, B.y.c0, B.y.c1, C.x, C.y, canonical little-endian).  The witness map comes from the
     key's own section 4 (what snarkjs and rapidsnark do), or, when an R1cs of the same circuit is given, from that.  Section 4
     is turned into the prover's arrays at the first call that needs it; what that step refuses (a value >= r, no coefficients,
     a domain the transform cannot take) is raised there, not here.  check_g2=True also runs check_g2() on the loaded key (on
     the GPU); by default the key's G2 points are checked for the curve equation alone, as before."""
+    _FREE = ("_r1cs_lib", "gwb_zkey_free")
 
     def __init__(self, zkey_bytes, r1cs=None, check_g2=False):
         self._h = ctypes.c_void_p()
         self.r1cs = r1cs
         data = bytes(zkey_bytes)
-        st = GwStatus()
-        rc = r1cs_lib().gwb_zkey_load(data, len(data), ctypes.byref(self._h), ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_zkey_load, data, len(data), ctypes.byref(self._h))
         info = ZkeyInfo()
         r1cs_lib().gwb_zkey_info(self._h, ctypes.byref(info))
         self.info = {n: int(getattr(info, n)) for n, _ in ZkeyInfo._fields_}
         if check_g2:
             self.check_g2()
-
-    def close(self):
-        if getattr(self, "_h", None) and _r1cs_lib is not None:
-            _r1cs_lib.gwb_zkey_free(self._h)
-            self._h = None
-
-    __del__ = close
 
     def _r1cs_handle(self):
         return None if self.r1cs is None else self.r1cs._h
@@ -926,18 +613,14 @@ class Groth16:
         r1cs = self.r1cs if r1cs is None else r1cs
         if r1cs is None:
             raise WitnessCalcError("check_r1cs: no R1cs given and the handle has none")
-        st = GwStatus()
-        rc = r1cs_lib().gwb_zkey_check_r1cs(self._h, r1cs._h, ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_zkey_check_r1cs, self._h, r1cs._h)
 
     def check_g2(self):
         """Raises unless beta2, gamma2, delta2 and every B2 point (section 7) lie in G2's order-r subgroup; checked on the
         current GPU (synchronous).  The message names the first offender: "zkey: beta2 is not in the order-r subgroup of G2", or
         "zkey: section 7 (B2) point 12 is not in the order-r subgroup of G2 (3 of 70 points are not)".  A proof made with a
         B2 point outside the subgroup is refused by every verifier (VERIFY_SUBGROUP)."""
-        st = GwStatus()
-        rc = r1cs_lib().gwb_zkey_check_g2(self._h, ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_zkey_check_g2, self._h)
 
     # -- the witness map of section 4 on its own (always from the zkey, whether or not the handle has an R1cs) -----------------
     def set_tile_width(self, t):
@@ -969,10 +652,8 @@ class Groth16:
         b = w.shape[0]
         rsa = _rs_array(rs, b)
         out = np.zeros((b, GROTH16_PROOF_BYTES), dtype=np.uint8)
-        st = GwStatus()
-        rc = r1cs_lib().gwb_groth16_prove_batch_host(self._h, self._r1cs_handle(), w.ctypes.data, w.shape[1], b,
-                                                     None if rsa is None else rsa.ctypes.data, out.ctypes.data, ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_groth16_prove_batch_host, self._h, self._r1cs_handle(), w.ctypes.data, w.shape[1], b,
+                   None if rsa is None else rsa.ctypes.data, out.ctypes.data)
         return out
 
     def prove_batch_device(self, d_w, stream=None, montgomery=False, rs=None):
@@ -983,24 +664,16 @@ class Groth16:
         assert d_w.dim() == 3 and d_w.shape[2] == 32, tuple(d_w.shape)
         b = d_w.shape[0]
         rsa = _rs_array(rs, b)
-        s = stream if stream is not None else torch.cuda.current_stream(d_w.device)
         out = torch.empty((b, GROTH16_PROOF_BYTES), dtype=torch.uint8, device=d_w.device)
-        st = GwStatus()
-        with torch.cuda.device(d_w.device):
-            rc = r1cs_lib().gwb_groth16_prove_batch_device(self._h, self._r1cs_handle(), d_w.data_ptr(), d_w.shape[1], b,
-                                                           FORM_MONTGOMERY if montgomery else FORM_CANONICAL,
-                                                           None if rsa is None else rsa.ctypes.data, out.data_ptr(),
-                                                           s.cuda_stream, ctypes.byref(st))
-        _r1cs_check(rc, st)
-        if b:
-            out.record_stream(s)
+        with _device_call(d_w, stream, (out,)) as s:
+            _r1cs_call(r1cs_lib().gwb_groth16_prove_batch_device, self._h, self._r1cs_handle(), d_w.data_ptr(), d_w.shape[1], b, _form(montgomery),
+                       None if rsa is None else rsa.ctypes.data, out.data_ptr(), s.cuda_stream)
         return out
 
     def prove_batch_compressed_device(self, d_w, stream=None, montgomery=False, rs=None):
         """prove_batch_device, then groth16_compress_proofs_device on the same stream -> a uint8 cuda tensor [B, 128] (arkworks'
         compressed form: include/graph_witness_groth16_compressed.h).  The 256-byte proofs stay on the device."""
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream(d_w.device)
+        s = _stream_of(d_w, stream)
         return groth16_compress_proofs_device(self.prove_batch_device(d_w, stream=s, montgomery=montgomery, rs=rs), stream=s)
 
     def prove_batch_compressed(self, rows, rs=None):
@@ -1017,10 +690,8 @@ class Groth16:
         wtns = bytes(wtns)
         rsa = _rs_array(rs, 1)
         out = np.zeros(GROTH16_PROOF_BYTES, dtype=np.uint8)
-        st = GwStatus()
-        rc = r1cs_lib().gwb_groth16_prove_wtns(self._h, self._r1cs_handle(), wtns, len(wtns), None if rsa is None else rsa.ctypes.data,
-                                               out.ctypes.data, ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_groth16_prove_wtns, self._h, self._r1cs_handle(), wtns, len(wtns), None if rsa is None else rsa.ctypes.data,
+                   out.ctypes.data)
         # the values section of the (validated) image: wire i at 32 i
         n_sec = int.from_bytes(wtns[8:12], "little")
         off, values = 12, None
@@ -1054,10 +725,7 @@ class Groth16:
 
     def phase_ms(self):
         """Waits for the last prove call -> {witness_map, scalars_sort, g1_msms, g2_msm, assembly} in ms (its last sub-batch)."""
-        ms = (ctypes.c_float * 5)()
-        if r1cs_lib().gwb_groth16_phase_ms(self._h, ms) != 0:
-            raise WitnessCalcError("no prover phase times (time_phases not on, or no prove call yet)")
-        return dict(zip(GROTH16_PHASES, (float(x) for x in ms)))
+        return _phase_ms(r1cs_lib().gwb_groth16_phase_ms, GROTH16_PHASES, "no prover phase times (time_phases not on, or no prove call yet)", self._h)
 
 
 # -- Groth16 key setup (include/graph_witness_groth16_setup.h, libcwc_r1cs.so) ------------------------------------------------
@@ -1069,27 +737,15 @@ def groth16_setup(r1cs, trapdoor=None):
     (tau, alpha, beta, gamma, delta), ints in [1, r) with tau^2n != 1, or None: drawn and discarded.  Single party: whoever
     knows the trapdoor can forge proofs, so this is for development, tests and deployments where the key's maker is trusted
     with all five values (groth16_setup_ptau takes tau, alpha and beta from a public ceremony instead).  Section 10 of the file has no circuit hash and no contributions."""
-    buf = None
+    vals = None
     if trapdoor is not None:
         vals = [int(x) for x in trapdoor]
         if len(vals) != 5:
             raise WitnessCalcError("trapdoor: 5 values expected (tau, alpha, beta, gamma, delta), %d given" % len(vals))
-        for name, v in zip(("tau", "alpha", "beta", "gamma", "delta"), vals):
-            if not 0 <= v < (1 << 256):
-                raise WitnessCalcError("trapdoor: %s is not in [0, 2^256)" % name)
-        buf = ctypes.create_string_buffer(b"".join(v.to_bytes(32, "little") for v in vals), 160)
     out, n = ctypes.c_void_p(), ctypes.c_size_t()
-    st = GwStatus()
-    try:
-        rc = r1cs_lib().gwb_groth16_setup(r1cs._h, buf, ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
-    finally:
-        if buf is not None:
-            ctypes.memset(buf, 0, 160)
-    _r1cs_check(rc, st)
-    try:
-        return ctypes.string_at(out, n.value)
-    finally:
-        r1cs_lib().gwb_groth16_setup_free(out)
+    with _secret_scalars(vals, ["trapdoor: %s is not in [0, 2^256)" % name for name in ("tau", "alpha", "beta", "gamma", "delta")]) as buf:
+        _r1cs_call(r1cs_lib().gwb_groth16_setup, r1cs._h, buf, ctypes.byref(out), ctypes.byref(n))
+    return _take_image(out, n)
 
 
 def bn254_gen_mul_batch_device(d_scalars, group, stream=None):
@@ -1101,23 +757,15 @@ def bn254_gen_mul_batch_device(d_scalars, group, stream=None):
     assert tuple(d_scalars.shape) == (n, 32) and d_scalars.is_cuda and d_scalars.is_contiguous() and d_scalars.dtype == torch.uint8
     if group not in (1, 2):
         raise WitnessCalcError("group must be 1 or 2")
-    s = stream if stream is not None else torch.cuda.current_stream(d_scalars.device)
     out = torch.empty((n, 64 * group), dtype=torch.uint8, device=d_scalars.device)
-    st = GwStatus()
-    with torch.cuda.device(d_scalars.device):
-        rc = r1cs_lib().gwb_bn254_gen_mul_batch_device(d_scalars.data_ptr(), n, group, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
-    _r1cs_check(rc, st)
-    if n:
-        out.record_stream(s)
+    with _device_call(d_scalars, stream, (out,)) as s:
+        _r1cs_call(r1cs_lib().gwb_bn254_gen_mul_batch_device, d_scalars.data_ptr(), n, group, out.data_ptr(), s.cuda_stream)
     return out
 
 
 def groth16_setup_phase_ms():
     """{lagrange, column_sums, key_scalars, g1_muls, g2_muls_affine} in ms of the process's last groth16_setup call."""
-    ms = (ctypes.c_float * 5)()
-    if r1cs_lib().gwb_groth16_setup_phase_ms(ms) != 0:
-        raise WitnessCalcError("no setup phase times (no groth16_setup call yet)")
-    return dict(zip(GROTH16_SETUP_PHASES, (float(x) for x in ms)))
+    return _phase_ms(r1cs_lib().gwb_groth16_setup_phase_ms, GROTH16_SETUP_PHASES, "no setup phase times (no groth16_setup call yet)")
 
 
 # -- Groth16 key setup from a powers-of-tau file (include/graph_witness_groth16_ptau.h, libcwc_r1cs.so) -------------------------
@@ -1127,7 +775,7 @@ PTAU_LAGRANGE_MODES = {"auto": 0, "file": 1, "compute": 2}
 
 def _ptau_buffer(ptau):
     """(object that keeps the memory alive, address, length) of bytes, a bytearray, an mmap or a numpy array, without a copy
-    where the object allows it"""
+    where the object allows it.  The caller holds the first in a local for as long as the address is in use."""
     if isinstance(ptau, bytes):
         return ptau, ctypes.cast(ctypes.c_char_p(ptau), ctypes.c_void_p), len(ptau)
     arr = np.frombuffer(ptau, dtype=np.uint8)
@@ -1144,10 +792,8 @@ def ptau_info(ptau):
     """{power, ceremony_power, prepared, n_contributions} of a `.ptau` image (bytes or any buffer, an mmap included).  Host
     only: header and section table, no device."""
     keep, addr, n = _ptau_buffer(ptau)
-    info, st = PtauInfo(), GwStatus()
-    rc = r1cs_lib().gwb_ptau_info(addr, n, ctypes.byref(info), ctypes.byref(st))
-    _r1cs_check(rc, st)
-    del keep
+    info = PtauInfo()
+    _r1cs_call(r1cs_lib().gwb_ptau_info, addr, n, ctypes.byref(info))
     return {"power": int(info.power), "ceremony_power": int(info.ceremony_power), "prepared": bool(info.prepared),
             "n_contributions": int(info.n_contributions)}
 
@@ -1156,10 +802,7 @@ def ptau_check(ptau, domain_power, lagrange="auto"):
     """Host only: raises WitnessCalcError with the message groth16_setup_ptau would give for this file and a circuit of domain
     2^domain_power (the points it would read are checked on the host)."""
     keep, addr, n = _ptau_buffer(ptau)
-    st = GwStatus()
-    rc = r1cs_lib().gwb_ptau_check(addr, n, int(domain_power), _lagrange_mode(lagrange), ctypes.byref(st))
-    _r1cs_check(rc, st)
-    del keep
+    _r1cs_call(r1cs_lib().gwb_ptau_check, addr, n, int(domain_power), _lagrange_mode(lagrange))
 
 
 def ptau_check_g2(ptau, domain_power, lagrange="auto"):
@@ -1169,10 +812,7 @@ def ptau_check_g2(ptau, domain_power, lagrange="auto"):
     with ptau_check's messages; the points are then checked on the current GPU in bounded pieces (synchronous).  The message
     names section and index: "ptau: section 3 (tauG2) point 5 is not in the order-r subgroup of G2"."""
     keep, addr, n = _ptau_buffer(ptau)
-    st = GwStatus()
-    rc = r1cs_lib().gwb_ptau_check_g2(addr, n, int(domain_power), _lagrange_mode(lagrange), ctypes.byref(st))
-    _r1cs_check(rc, st)
-    del keep
+    _r1cs_call(r1cs_lib().gwb_ptau_check_g2, addr, n, int(domain_power), _lagrange_mode(lagrange))
 
 
 def groth16_setup_ptau(r1cs, ptau, delta=None, lagrange="auto", check_g2=False):
@@ -1187,26 +827,11 @@ def groth16_setup_ptau(r1cs, ptau, delta=None, lagrange="auto", check_g2=False):
     mode = _lagrange_mode(lagrange)
     if check_g2:
         ptau_check_g2(ptau, r1cs.qap_info()["domain_power"], lagrange)
-    buf = None
-    if delta is not None:
-        d = int(delta)
-        if not 0 <= d < (1 << 256):
-            raise WitnessCalcError("delta is not in [0, 2^256)")
-        buf = ctypes.create_string_buffer(d.to_bytes(32, "little"), 32)
-    keep, addr, n_in = _ptau_buffer(ptau)
     out, n = ctypes.c_void_p(), ctypes.c_size_t()
-    st = GwStatus()
-    try:
-        rc = r1cs_lib().gwb_groth16_setup_ptau(r1cs._h, addr, n_in, buf, mode, ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
-    finally:
-        if buf is not None:
-            ctypes.memset(buf, 0, 32)
-    del keep
-    _r1cs_check(rc, st)
-    try:
-        return ctypes.string_at(out, n.value)
-    finally:
-        r1cs_lib().gwb_groth16_setup_free(out)
+    with _secret_scalars(None if delta is None else [int(delta)], ["delta is not in [0, 2^256)"]) as buf:
+        keep, addr, n_in = _ptau_buffer(ptau)
+        _r1cs_call(r1cs_lib().gwb_groth16_setup_ptau, r1cs._h, addr, n_in, buf, mode, ctypes.byref(out), ctypes.byref(n))
+    return _take_image(out, n)
 
 
 def bn254_point_idft_batch_device(d_points, group, stream=None):
@@ -1221,24 +846,16 @@ def bn254_point_idft_batch_device(d_points, group, stream=None):
     log_n = n.bit_length() - 1
     if n < 2 or n != 1 << log_n:
         raise WitnessCalcError("the number of points must be a power of two, 2 at the least")
-    s = stream if stream is not None else torch.cuda.current_stream(d_points.device)
     out = torch.empty_like(d_points)
-    st = GwStatus()
-    with torch.cuda.device(d_points.device):
-        rc = r1cs_lib().gwb_bn254_point_idft_batch_device(d_points.data_ptr(), log_n, group, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
-    _r1cs_check(rc, st)
-    d_points.record_stream(s)
-    out.record_stream(s)
+    with _device_call(d_points, stream, (d_points, out)) as s:
+        _r1cs_call(r1cs_lib().gwb_bn254_point_idft_batch_device, d_points.data_ptr(), log_n, group, out.data_ptr(), s.cuda_stream)
     return out
 
 
 def groth16_setup_ptau_phase_ms():
     """{point_check, idft_g1, idft_g2, column_sums_g1, column_sums_g2, delta_scale, affine} in ms of the process's last
     groth16_setup_ptau call."""
-    ms = (ctypes.c_float * 7)()
-    if r1cs_lib().gwb_groth16_setup_ptau_phase_ms(ms) != 0:
-        raise WitnessCalcError("no setup phase times (no groth16_setup_ptau call yet)")
-    return dict(zip(GROTH16_SETUP_PTAU_PHASES, (float(x) for x in ms)))
+    return _phase_ms(r1cs_lib().gwb_groth16_setup_ptau_phase_ms, GROTH16_SETUP_PTAU_PHASES, "no setup phase times (no groth16_setup_ptau call yet)")
 
 
 # -- Groth16 phase-2 contributions (include/graph_witness_groth16_contribute.h, libcwc_r1cs.so) ---------------------------------
@@ -1253,53 +870,30 @@ def groth16_contribute(zkey, name="", delta=None):
     [1, r) for reproducible keys, or None: drawn, applied and discarded.  name: at most 255 bytes of UTF-8.  The records are
     this library's own (BLAKE2b transcript, its own challenge derivation): `snarkjs zkey verify` does not accept them, while
     sections 1 to 9 are ordinary and every Groth16 prover and verifier works with the key."""
-    nm = name.encode("utf-8") if isinstance(name, str) else bytes(name)
-    if b"\0" in nm:
-        raise WitnessCalcError("the name holds a zero byte")
-    buf = None
-    if delta is not None:
-        d = int(delta)
-        if not 0 <= d < (1 << 256):
-            raise WitnessCalcError("delta is not in [0, 2^256)")
-        buf = ctypes.create_string_buffer(d.to_bytes(32, "little"), 32)
-    data = bytes(zkey)
+    nm = _name_bytes(name)
     out, n = ctypes.c_void_p(), ctypes.c_size_t()
     digest = ctypes.create_string_buffer(CONTRIBUTION_HASH_BYTES)
-    st = GwStatus()
-    try:
-        rc = r1cs_lib().gwb_groth16_contribute(data, len(data), nm, buf, ctypes.byref(out), ctypes.byref(n), digest, ctypes.byref(st))
-    finally:
-        if buf is not None:
-            ctypes.memset(buf, 0, 32)
-    _r1cs_check(rc, st)
-    try:
-        return ctypes.string_at(out, n.value), digest.raw
-    finally:
-        r1cs_lib().gwb_groth16_setup_free(out)
+    with _secret_scalars(None if delta is None else [int(delta)], ["delta is not in [0, 2^256)"]) as buf:
+        data = bytes(zkey)
+        _r1cs_call(r1cs_lib().gwb_groth16_contribute, data, len(data), nm, buf, ctypes.byref(out), ctypes.byref(n), digest)
+    return _take_image(out, n), digest.raw
 
 
 def groth16_contribute_phase_ms():
     """{load, scale, affine} in ms of the process's last groth16_contribute call, summed over its pieces."""
-    ms = (ctypes.c_float * 3)()
-    if r1cs_lib().gwb_groth16_contribute_phase_ms(ms) != 0:
-        raise WitnessCalcError("no contribution phase times (no groth16_contribute call yet)")
-    return dict(zip(GROTH16_CONTRIBUTE_PHASES, (float(x) for x in ms)))
+    return _phase_ms(r1cs_lib().gwb_groth16_contribute_phase_ms, GROTH16_CONTRIBUTE_PHASES, "no contribution phase times (no groth16_contribute call yet)")
 
 
 # -- the random beacon of both phases (include/graph_witness_groth16_beacon.h) ---------------------------------------------------
 def _beacon_call(call, addr, n_in, beacon_hash, iterations_exp, name):
-    nm = name.encode("utf-8") if isinstance(name, str) else bytes(name)
-    if b"\0" in nm:
-        raise WitnessCalcError("the name holds a zero byte")
+    nm = _name_bytes(name)
     digest_in = bytes(beacon_hash)
     e = int(iterations_exp)
     if not 0 <= e < (1 << 32):
         raise WitnessCalcError("beacon: numIterationsExp %d is not in [10, 63]" % e)
     out, n = ctypes.c_void_p(), ctypes.c_size_t()
     digest = ctypes.create_string_buffer(CONTRIBUTION_HASH_BYTES)
-    st = GwStatus()
-    rc = call(addr, n_in, nm, digest_in, len(digest_in), e, ctypes.byref(out), ctypes.byref(n), digest, ctypes.byref(st))
-    _r1cs_check(rc, st)
+    _r1cs_call(call, addr, n_in, nm, digest_in, len(digest_in), e, ctypes.byref(out), ctypes.byref(n), digest)
     return _take_image(out, n), digest.raw
 
 
@@ -1319,10 +913,7 @@ def ptau_beacon(ptau, beacon_hash, iterations_exp, name=""):
     `.ptau` bytes, the new record's nextChallenge).  The contribution of ptau_contribute with tau', alpha', beta' and the three
     nonces derived from beacon_hash and iterations_exp as for groth16_beacon; prepared sections are dropped as there."""
     keep, addr, n_in = _ptau_buffer(ptau)
-    try:
-        return _beacon_call(r1cs_lib().gwb_ptau_beacon, addr, n_in, beacon_hash, iterations_exp, name)
-    finally:
-        del keep
+    return _beacon_call(r1cs_lib().gwb_ptau_beacon, addr, n_in, beacon_hash, iterations_exp, name)
 
 
 def beacon_scalars(phase, beacon_hash, iterations_exp):
@@ -1352,9 +943,7 @@ def _beacon_items(call, addr, n_in, k, typ):
     if typ != 1:
         return None, None
     out, n = ctypes.c_void_p(), ctypes.c_size_t()
-    st = GwStatus()
-    rc = call(addr, n_in, k, ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
-    _r1cs_check(rc, st)
+    _r1cs_call(call, addr, n_in, k, ctypes.byref(out), ctypes.byref(n))
     par = _take_image(out, n)
     exp, digest, i = None, None, 0
     while i < len(par):  # the section's reader has checked the items' lengths
@@ -1382,13 +971,8 @@ def zkey_contributions(zkey):
     form; a malformed section raises with a message starting "zkey: section 10"."""
     data = bytes(zkey)
     out, n = ctypes.c_void_p(), ctypes.c_size_t()
-    st = GwStatus()
-    rc = r1cs_lib().gwb_zkey_contributions(data, len(data), ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
-    _r1cs_check(rc, st)
-    try:
-        img = ctypes.string_at(out, n.value)
-    finally:
-        r1cs_lib().gwb_groth16_setup_free(out)
+    _r1cs_call(r1cs_lib().gwb_zkey_contributions, data, len(data), ctypes.byref(out), ctypes.byref(n))
+    img = _take_image(out, n)
     count = int.from_bytes(img[64:68], "little")
     off, recs = 68, []
     for k in range(count):
@@ -1414,9 +998,7 @@ def groth16_verify_contributions(zkey, require_beacon=False):
     room = len(records)
     hashes = ctypes.create_string_buffer(max(1, room * CONTRIBUTION_HASH_BYTES))
     n = ctypes.c_size_t(room)
-    st = GwStatus()
-    rc = r1cs_lib().gwb_zkey_verify_contributions(data, len(data), hashes, ctypes.byref(n), ctypes.byref(st))
-    _r1cs_check(rc, st)
+    _r1cs_call(r1cs_lib().gwb_zkey_verify_contributions, data, len(data), hashes, ctypes.byref(n))
     if require_beacon:
         _require_beacon(records, "zkey")
     return [hashes.raw[64 * k:64 * k + 64] for k in range(n.value)]
@@ -1428,11 +1010,7 @@ def groth16_verify_contribution_step(prev, next, seed=None):
     (a wrong point passes with probability about 2^-128 over the seed).  seed: 32 bytes for a reproducible check, or None to
     draw them.  Raises WitnessCalcError naming what differs."""
     a, b = bytes(prev), bytes(next)
-    if seed is not None and len(seed) != 32:
-        raise WitnessCalcError("seed: 32 bytes expected")
-    st = GwStatus()
-    rc = r1cs_lib().gwb_zkey_verify_step(a, len(a), b, len(b), bytes(seed) if seed is not None else None, ctypes.byref(st))
-    _r1cs_check(rc, st)
+    _r1cs_call(r1cs_lib().gwb_zkey_verify_step, a, len(a), b, len(b), _seed32(seed))
 
 
 def bn254_g1_scale_batch_device(d_points, k, stream=None):
@@ -1442,16 +1020,9 @@ def bn254_g1_scale_batch_device(d_points, k, stream=None):
     import torch
     n = d_points.shape[0]
     assert tuple(d_points.shape) == (n, 64) and d_points.is_cuda and d_points.is_contiguous() and d_points.dtype == torch.uint8
-    s = stream if stream is not None else torch.cuda.current_stream(d_points.device)
     out = torch.empty_like(d_points)
-    st = GwStatus()
-    with torch.cuda.device(d_points.device):
-        rc = r1cs_lib().gwb_bn254_g1_scale_batch_device(d_points.data_ptr(), n, int(k).to_bytes(32, "little"), out.data_ptr(), s.cuda_stream,
-                                                        ctypes.byref(st))
-    _r1cs_check(rc, st)
-    if n:
-        d_points.record_stream(s)
-        out.record_stream(s)
+    with _device_call(d_points, stream, (d_points, out)) as s:
+        _r1cs_call(r1cs_lib().gwb_bn254_g1_scale_batch_device, d_points.data_ptr(), n, int(k).to_bytes(32, "little"), out.data_ptr(), s.cuda_stream)
     return out
 
 
@@ -1460,16 +1031,10 @@ def _lincomb128_device(group, d_points, d_rho, stream):
     n, width = d_points.shape[0], 64 * group
     assert tuple(d_points.shape) == (n, width) and d_points.is_cuda and d_points.is_contiguous() and d_points.dtype == torch.uint8
     assert tuple(d_rho.shape) == (n, 16) and d_rho.is_cuda and d_rho.is_contiguous() and d_rho.dtype == torch.uint8
-    s = stream if stream is not None else torch.cuda.current_stream(d_points.device)
     out = torch.empty((width,), dtype=torch.uint8, device=d_points.device)
-    st = GwStatus()
     call = r1cs_lib().gwb_bn254_g1_lincomb128_device if group == 1 else r1cs_lib().gwb_bn254_g2_lincomb128_device
-    with torch.cuda.device(d_points.device):
-        rc = call(d_points.data_ptr(), d_rho.data_ptr(), n, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
-    _r1cs_check(rc, st)
-    d_points.record_stream(s)
-    d_rho.record_stream(s)
-    out.record_stream(s)
+    with _device_call(d_points, stream, (d_points, d_rho, out)) as s:
+        _r1cs_call(call, d_points.data_ptr(), d_rho.data_ptr(), n, out.data_ptr(), s.cuda_stream)
     return out
 
 
@@ -1506,10 +1071,7 @@ def ptau_check_powers(ptau, domain_power, seed=None):
     prefixes (ptau_verify checks the whole file), the prepared sections 12 to 15, records made by snarkjs."""
     seed = _seed32(seed)
     keep, addr, n = _ptau_buffer(ptau)
-    st = GwStatus()
-    rc = r1cs_lib().gwb_ptau_check_powers(addr, n, int(domain_power), seed, ctypes.byref(st))
-    _r1cs_check(rc, st)
-    del keep
+    _r1cs_call(r1cs_lib().gwb_ptau_check_powers, addr, n, int(domain_power), seed)
 
 
 # -- the prepared sections 12 to 15 of a `.ptau` (include/graph_witness_groth16_ptau.h) ------------------------------------------
@@ -1527,22 +1089,13 @@ def ptau_prepare_phase2(ptau):
     levels of one section must fit CWC_GROTH16_WORKSPACE_MB on the device.  No snarkjs-prepared file was compared."""
     keep, addr, n_in = _ptau_buffer(ptau)
     out, n = ctypes.c_void_p(), ctypes.c_size_t()
-    st = GwStatus()
-    rc = r1cs_lib().gwb_ptau_prepare_phase2(addr, n_in, ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
-    del keep
-    _r1cs_check(rc, st)
-    try:
-        return ctypes.string_at(out, n.value)
-    finally:
-        r1cs_lib().gwb_groth16_setup_free(out)
+    _r1cs_call(r1cs_lib().gwb_ptau_prepare_phase2, addr, n_in, ctypes.byref(out), ctypes.byref(n))
+    return _take_image(out, n)
 
 
 def ptau_prepare_phase_ms():
     """{load, idft_g1, idft_g2, affine} in ms of the process's last ptau_prepare_phase2 call, summed over the four sections."""
-    ms = (ctypes.c_float * 4)()
-    if r1cs_lib().gwb_ptau_prepare_phase_ms(ms) != 0:
-        raise WitnessCalcError("no prepare phase times (no ptau_prepare_phase2 call yet)")
-    return dict(zip(PTAU_PREPARE_PHASES, (float(x) for x in ms)))
+    return _phase_ms(r1cs_lib().gwb_ptau_prepare_phase_ms, PTAU_PREPARE_PHASES, "no prepare phase times (no ptau_prepare_phase2 call yet)")
 
 
 def ptau_check_lagrange(ptau, domain_power=None, seed=None):
@@ -1557,10 +1110,7 @@ def ptau_check_lagrange(ptau, domain_power=None, seed=None):
     forms of section 4".  Not checked: that sections 2 to 5 are powers of one tau (ptau_check_powers)."""
     seed = _seed32(seed)
     keep, addr, n = _ptau_buffer(ptau)
-    st = GwStatus()
-    rc = r1cs_lib().gwb_ptau_check_lagrange(addr, n, PTAU_ALL_LEVELS if domain_power is None else int(domain_power), seed, ctypes.byref(st))
-    _r1cs_check(rc, st)
-    del keep
+    _r1cs_call(r1cs_lib().gwb_ptau_check_lagrange, addr, n, PTAU_ALL_LEVELS if domain_power is None else int(domain_power), seed)
 
 
 def _lincomb_device(group, d_points, d_scalars, form, stream):
@@ -1570,16 +1120,10 @@ def _lincomb_device(group, d_points, d_scalars, form, stream):
     n, width = d_points.shape[0], 64 * group
     assert tuple(d_points.shape) == (n, width) and d_points.is_cuda and d_points.is_contiguous() and d_points.dtype == torch.uint8
     assert tuple(d_scalars.shape) == (n, 32) and d_scalars.is_cuda and d_scalars.is_contiguous() and d_scalars.dtype == torch.uint8
-    s = stream if stream is not None else torch.cuda.current_stream(d_points.device)
     out = torch.empty((width,), dtype=torch.uint8, device=d_points.device)
-    st = GwStatus()
     call = r1cs_lib().gwb_bn254_g1_lincomb_device if group == 1 else r1cs_lib().gwb_bn254_g2_lincomb_device
-    with torch.cuda.device(d_points.device):
-        rc = call(d_points.data_ptr(), d_scalars.data_ptr(), n, 0 if form == "canonical" else 1, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
-    _r1cs_check(rc, st)
-    d_points.record_stream(s)
-    d_scalars.record_stream(s)
-    out.record_stream(s)
+    with _device_call(d_points, stream, (d_points, d_scalars, out)) as s:
+        _r1cs_call(call, d_points.data_ptr(), d_scalars.data_ptr(), n, 0 if form == "canonical" else 1, out.data_ptr(), s.cuda_stream)
     return out
 
 
@@ -1602,21 +1146,12 @@ PTAU_VERIFY_SKIP_RECORDS = 1
 MUL_METHODS = {"window": 0, "plain": 1}
 
 
-def _take_image(out, n):
-    try:
-        return ctypes.string_at(out, n.value)
-    finally:
-        r1cs_lib().gwb_groth16_setup_free(out)
-
-
 def ptau_new(power):
     """What snarkjs `powersoftau new` does (host only): the `.ptau` bytes of a new ceremony of the given power, 1 to 28, with
     tau = alpha = beta = 1: every point is its group's generator and section 7 holds no record.  Such a file is the start of a
     ceremony, nothing more: keys made from it before anyone contributed can be forged against by everybody."""
     out, n = ctypes.c_void_p(), ctypes.c_size_t()
-    st = GwStatus()
-    rc = r1cs_lib().gwb_ptau_new(int(power), ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
-    _r1cs_check(rc, st)
+    _r1cs_call(r1cs_lib().gwb_ptau_new, int(power), ctypes.byref(out), ctypes.byref(n))
     return _take_image(out, n)
 
 
@@ -1628,35 +1163,24 @@ def ptau_contribute(ptau, name="", secrets=None):
     dropped (ptau_prepare_phase2 makes them again).  secrets: (tau', alpha', beta') as ints in [1, r) for reproducible files, or
     None: drawn, applied and discarded.  name: at most 255 bytes of UTF-8.  The records are this library's own: `snarkjs
     powersoftau verify` does not accept them, while sections 1 to 6 are ordinary."""
-    nm = name.encode("utf-8") if isinstance(name, str) else bytes(name)
-    if b"\0" in nm:
-        raise WitnessCalcError("the name holds a zero byte")
-    buf = None
+    nm = _name_bytes(name)
+    refusal = "secrets: three integers in [0, 2^256) expected (tau, alpha, beta)"
+    xs = None
     if secrets is not None:
         xs = [int(x) for x in secrets]
-        if len(xs) != 3 or not all(0 <= x < (1 << 256) for x in xs):
-            raise WitnessCalcError("secrets: three integers in [0, 2^256) expected (tau, alpha, beta)")
-        buf = ctypes.create_string_buffer(b"".join(x.to_bytes(32, "little") for x in xs), 96)
-    keep, addr, n_in = _ptau_buffer(ptau)
+        if len(xs) != 3:
+            raise WitnessCalcError(refusal)
     out, n = ctypes.c_void_p(), ctypes.c_size_t()
     digest = ctypes.create_string_buffer(CONTRIBUTION_HASH_BYTES)
-    st = GwStatus()
-    try:
-        rc = r1cs_lib().gwb_ptau_contribute(addr, n_in, nm, buf, ctypes.byref(out), ctypes.byref(n), digest, ctypes.byref(st))
-    finally:
-        if buf is not None:
-            ctypes.memset(buf, 0, 96)
-    del keep
-    _r1cs_check(rc, st)
+    with _secret_scalars(xs, [refusal] * 3) as buf:
+        keep, addr, n_in = _ptau_buffer(ptau)
+        _r1cs_call(r1cs_lib().gwb_ptau_contribute, addr, n_in, nm, buf, ctypes.byref(out), ctypes.byref(n), digest)
     return _take_image(out, n), digest.raw
 
 
 def ptau_contribute_phase_ms():
     """{load, scalars, mul_g1, mul_g2, affine} in ms of the process's last ptau_contribute call, summed over its pieces."""
-    ms = (ctypes.c_float * 5)()
-    if r1cs_lib().gwb_ptau_contribute_phase_ms(ms) != 0:
-        raise WitnessCalcError("no contribution phase times (no ptau_contribute call yet)")
-    return dict(zip(PTAU_CONTRIBUTE_PHASES, (float(x) for x in ms)))
+    return _phase_ms(r1cs_lib().gwb_ptau_contribute_phase_ms, PTAU_CONTRIBUTE_PHASES, "no contribution phase times (no ptau_contribute call yet)")
 
 
 PTAU_RECORD_POINTS = (("tau_g1", 64), ("tau_g2", 128), ("alpha_g1", 64), ("beta_g1", 64), ("beta_g2", 128), ("tau_g1_s", 64), ("tau_g1_sx", 64),
@@ -1673,9 +1197,7 @@ def ptau_contributions(ptau):
     section 7"."""
     keep, addr, n_in = _ptau_buffer(ptau)
     out, n = ctypes.c_void_p(), ctypes.c_size_t()
-    st = GwStatus()
-    rc = r1cs_lib().gwb_ptau_contributions(addr, n_in, ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
-    _r1cs_check(rc, st)
+    _r1cs_call(r1cs_lib().gwb_ptau_contributions, addr, n_in, ctypes.byref(out), ctypes.byref(n))
     img = _take_image(out, n)
     count = int.from_bytes(img[:4], "little")
     off, recs = 4, []
@@ -1691,7 +1213,6 @@ def ptau_contributions(ptau):
         off += name_len
         rec["iterations_exp"], rec["beacon_hash"] = _beacon_items(r1cs_lib().gwb_ptau_contribution_params, addr, n_in, k, rec["type"])
         recs.append(rec)
-    del keep
     return recs
 
 
@@ -1711,10 +1232,7 @@ def ptau_verify(ptau, records=True, seed=None, require_beacon=False):
     room = ptau_info(ptau)["n_contributions"]
     hashes = ctypes.create_string_buffer(max(1, room * CONTRIBUTION_HASH_BYTES))
     n = ctypes.c_size_t(room)
-    st = GwStatus()
-    rc = r1cs_lib().gwb_ptau_verify(addr, n_in, 0 if records else PTAU_VERIFY_SKIP_RECORDS, seed, hashes, ctypes.byref(n), ctypes.byref(st))
-    del keep
-    _r1cs_check(rc, st)
+    _r1cs_call(r1cs_lib().gwb_ptau_verify, addr, n_in, 0 if records else PTAU_VERIFY_SKIP_RECORDS, seed, hashes, ctypes.byref(n))
     if require_beacon:
         _require_beacon(ptau_contributions(ptau), "ptau")
     return [hashes.raw[64 * k:64 * k + 64] for k in range(min(room, n.value))]
@@ -1728,10 +1246,7 @@ def ptau_verify_step(prev, next, seed=None):
     seed = _seed32(seed)
     ka, aa, na = _ptau_buffer(prev)
     kb, ab, nb = _ptau_buffer(next)
-    st = GwStatus()
-    rc = r1cs_lib().gwb_ptau_verify_step(aa, na, ab, nb, seed, ctypes.byref(st))
-    del ka, kb
-    _r1cs_check(rc, st)
+    _r1cs_call(r1cs_lib().gwb_ptau_verify_step, aa, na, ab, nb, seed)
 
 
 def _mul_batch_device(group, d_points, d_scalars, form, method, stream):
@@ -1743,18 +1258,10 @@ def _mul_batch_device(group, d_points, d_scalars, form, method, stream):
     n, width = d_points.shape[0], 64 * group
     assert tuple(d_points.shape) == (n, width) and d_points.is_cuda and d_points.is_contiguous() and d_points.dtype == torch.uint8
     assert tuple(d_scalars.shape) == (n, 32) and d_scalars.is_cuda and d_scalars.is_contiguous() and d_scalars.dtype == torch.uint8
-    s = stream if stream is not None else torch.cuda.current_stream(d_points.device)
     out = torch.empty_like(d_points)
-    st = GwStatus()
     call = r1cs_lib().gwb_bn254_g1_mul_batch_device if group == 1 else r1cs_lib().gwb_bn254_g2_mul_batch_device
-    with torch.cuda.device(d_points.device):
-        rc = call(d_points.data_ptr(), d_scalars.data_ptr(), n, 0 if form == "canonical" else 1, MUL_METHODS[method], out.data_ptr(), s.cuda_stream,
-                  ctypes.byref(st))
-    _r1cs_check(rc, st)
-    if n:
-        d_points.record_stream(s)
-        d_scalars.record_stream(s)
-        out.record_stream(s)
+    with _device_call(d_points, stream, (d_points, d_scalars, out)) as s:
+        _r1cs_call(call, d_points.data_ptr(), d_scalars.data_ptr(), n, 0 if form == "canonical" else 1, MUL_METHODS[method], out.data_ptr(), s.cuda_stream)
     return out
 
 
@@ -1804,10 +1311,7 @@ def groth16_verify_key(zkey, r1cs, ptau, lagrange="compute", records=True, check
     n = ctypes.c_size_t(room)
     flags = (0 if records else VERIFY_KEY_SKIP_RECORDS) | (VERIFY_KEY_CHECK_PTAU if check_ptau else 0)
     keep, addr, n_in = _ptau_buffer(ptau)
-    st = GwStatus()
-    rc = r1cs_lib().gwb_zkey_verify_key(data, len(data), r1cs._h, addr, n_in, mode, flags, seed, hashes, ctypes.byref(n), ctypes.byref(st))
-    del keep
-    _r1cs_check(rc, st)
+    _r1cs_call(r1cs_lib().gwb_zkey_verify_key, data, len(data), r1cs._h, addr, n_in, mode, flags, seed, hashes, ctypes.byref(n))
     if require_beacon:
         _require_beacon(key_records, "zkey")
     return [hashes.raw[64 * k:64 * k + 64] for k in range(n.value)]
@@ -1815,10 +1319,7 @@ def groth16_verify_key(zkey, r1cs, ptau, lagrange="compute", records=True, check
 
 def groth16_verify_key_phase_ms():
     """{remake, lincomb, pairings} in ms of the process's last accepted groth16_verify_key call (host clock)."""
-    ms = (ctypes.c_float * 3)()
-    if r1cs_lib().gwb_zkey_verify_key_phase_ms(ms) != 0:
-        raise WitnessCalcError("no key check phase times (no accepted groth16_verify_key call yet)")
-    return dict(zip(GROTH16_VERIFY_KEY_PHASES, (float(x) for x in ms)))
+    return _phase_ms(r1cs_lib().gwb_zkey_verify_key_phase_ms, GROTH16_VERIFY_KEY_PHASES, "no key check phase times (no accepted groth16_verify_key call yet)")
 
 
 # -- Groth16 verifier (include/graph_witness_groth16_verify.h, libcwc_r1cs.so) ------------------------------------------------
@@ -1891,26 +1392,23 @@ def _public_array(publics, b, n):
     return a
 
 
-class Groth16VerifyingKey:
+class Groth16VerifyingKey(_Handle):
     """A Groth16 verifying key (nPublic, alpha1, beta2, gamma2, delta2, IC) for checking proofs on the GPU: one status per proof
     (VERIFY_VALID, VERIFY_PUBLIC, VERIFY_POINT, VERIFY_SUBGROUP, VERIFY_EQUATION; include/graph_witness_groth16_verify.h)."""
+    _FREE = ("_r1cs_lib", "gwb_g16vk_free")
 
     def __init__(self, points, n_public):
         """points: canonical bytes alpha1 (64), beta2, gamma2, delta2 (128 each), IC (64 each)"""
         points = bytes(points)
         self._h = ctypes.c_void_p()
-        st = GwStatus()
-        rc = r1cs_lib().gwb_g16vk_load(points, len(points), int(n_public), ctypes.byref(self._h), ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_g16vk_load, points, len(points), int(n_public), ctypes.byref(self._h))
         self.n_public = int(n_public)
 
     @classmethod
     def _from_zkey_handle(cls, zh):
         self = cls.__new__(cls)
         self._h = ctypes.c_void_p()
-        st = GwStatus()
-        rc = r1cs_lib().gwb_g16vk_from_zkey(zh, ctypes.byref(self._h), ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_g16vk_from_zkey, zh, ctypes.byref(self._h))
         n = ctypes.c_uint32()
         r1cs_lib().gwb_g16vk_info(self._h, ctypes.byref(n))
         self.n_public = int(n.value)
@@ -1921,9 +1419,7 @@ class Groth16VerifyingKey:
         """The verifying key of a `.zkey` (bytes)."""
         zh = ctypes.c_void_p()
         data = bytes(zkey_bytes)
-        st = GwStatus()
-        rc = r1cs_lib().gwb_zkey_load(data, len(data), ctypes.byref(zh), ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_zkey_load, data, len(data), ctypes.byref(zh))
         try:
             return cls._from_zkey_handle(zh)
         finally:
@@ -1955,9 +1451,7 @@ class Groth16VerifyingKey:
     def alphabeta(self):
         """e(alpha1, beta2) as GT_BYTES bytes (computed on the GPU at the first call)"""
         out = ctypes.create_string_buffer(GT_BYTES)
-        st = GwStatus()
-        rc = r1cs_lib().gwb_g16vk_alphabeta(self._h, out, ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_g16vk_alphabeta, self._h, out)
         return out.raw
 
     def to_json(self):
@@ -1968,13 +1462,6 @@ class Groth16VerifyingKey:
                 "vk_alphabeta_12": _gt_json(self.alphabeta()),
                 "IC": [_json_g1(p[448 + 64 * i:512 + 64 * i]) for i in range(self.n_public + 1)]}
 
-    def close(self):
-        if getattr(self, "_h", None) and _r1cs_lib is not None:
-            _r1cs_lib.gwb_g16vk_free(self._h)
-            self._h = None
-
-    __del__ = close
-
     def verify_batch(self, proofs, publics):
         """Host proofs uint8 [B, 256] and public signals ([B] lists of ints, or uint8 [B, nPublic, 32]) -> uint32 status [B].
         Synchronous."""
@@ -1982,10 +1469,7 @@ class Groth16VerifyingKey:
         b = p.shape[0]
         s = _public_array(publics, b, self.n_public)
         out = np.zeros(b, dtype=np.uint32)
-        st = GwStatus()
-        rc = r1cs_lib().gwb_groth16_verify_batch_host(self._h, p.ctypes.data, s.ctypes.data, self.n_public, b, out.ctypes.data,
-                                                      ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_groth16_verify_batch_host, self._h, p.ctypes.data, s.ctypes.data, self.n_public, b, out.ctypes.data)
         return out
 
     def verify_batch_device(self, d_proofs, d_public, stream=None):
@@ -1997,15 +1481,10 @@ class Groth16VerifyingKey:
         b = d_proofs.shape[0]
         assert d_public.is_cuda and d_public.is_contiguous() and d_public.dtype == torch.uint8
         assert tuple(d_public.shape) == (b, self.n_public, 32), tuple(d_public.shape)
-        s = stream if stream is not None else torch.cuda.current_stream(d_proofs.device)
         out = torch.empty(b, dtype=torch.int32, device=d_proofs.device)
-        st = GwStatus()
-        with torch.cuda.device(d_proofs.device):
-            rc = r1cs_lib().gwb_groth16_verify_batch_device(self._h, d_proofs.data_ptr(), d_public.data_ptr() if self.n_public else None,
-                                                            self.n_public, b, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
-        _r1cs_check(rc, st)
-        if b:
-            out.record_stream(s)
+        with _device_call(d_proofs, stream, (out,)) as s:
+            _r1cs_call(r1cs_lib().gwb_groth16_verify_batch_device, self._h, d_proofs.data_ptr(), d_public.data_ptr() if self.n_public else None,
+                       self.n_public, b, out.data_ptr(), s.cuda_stream)
         return out
 
     @classmethod
@@ -2015,9 +1494,7 @@ class Groth16VerifyingKey:
         data = bytes(data)
         self = cls.__new__(cls)
         self._h = ctypes.c_void_p()
-        st = GwStatus()
-        rc = r1cs_lib().gwb_g16vk_load_compressed(data, len(data), ctypes.byref(self._h), ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_g16vk_load_compressed, data, len(data), ctypes.byref(self._h))
         n = ctypes.c_uint32()
         r1cs_lib().gwb_g16vk_info(self._h, ctypes.byref(n))
         self.n_public = int(n.value)
@@ -2037,10 +1514,7 @@ class Groth16VerifyingKey:
         b = p.shape[0]
         s = _public_array(publics, b, self.n_public)
         out = np.zeros(b, dtype=np.uint32)
-        st = GwStatus()
-        rc = r1cs_lib().gwb_groth16_verify_batch_compressed_host(self._h, p.ctypes.data, s.ctypes.data, self.n_public, b, out.ctypes.data,
-                                                                 ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_groth16_verify_batch_compressed_host, self._h, p.ctypes.data, s.ctypes.data, self.n_public, b, out.ctypes.data)
         return out
 
     def verify_batch_compressed_device(self, d_cproofs, d_public, stream=None):
@@ -2052,16 +1526,10 @@ class Groth16VerifyingKey:
         b = d_cproofs.shape[0]
         assert d_public.is_cuda and d_public.is_contiguous() and d_public.dtype == torch.uint8
         assert tuple(d_public.shape) == (b, self.n_public, 32), tuple(d_public.shape)
-        s = stream if stream is not None else torch.cuda.current_stream(d_cproofs.device)
         out = torch.empty(b, dtype=torch.int32, device=d_cproofs.device)
-        st = GwStatus()
-        with torch.cuda.device(d_cproofs.device):
-            rc = r1cs_lib().gwb_groth16_verify_batch_compressed_device(self._h, d_cproofs.data_ptr(), d_public.data_ptr() if self.n_public else None,
-                                                                       self.n_public, b, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
-        _r1cs_check(rc, st)
-        if b:
-            d_cproofs.record_stream(s)
-            out.record_stream(s)
+        with _device_call(d_cproofs, stream, (d_cproofs, out)) as s:
+            _r1cs_call(r1cs_lib().gwb_groth16_verify_batch_compressed_device, self._h, d_cproofs.data_ptr(), d_public.data_ptr() if self.n_public else None,
+                       self.n_public, b, out.data_ptr(), s.cuda_stream)
         return out
 
     def verify(self, proof, public):
@@ -2077,14 +1545,9 @@ def bn254_pairing_batch_device(d_g1, d_g2, stream=None):
     n = d_g1.shape[0]
     assert tuple(d_g1.shape) == (n, 64) and tuple(d_g2.shape) == (n, 128)
     assert d_g1.is_cuda and d_g2.is_cuda and d_g1.is_contiguous() and d_g2.is_contiguous()
-    s = stream if stream is not None else torch.cuda.current_stream(d_g1.device)
     out = torch.empty((n, GT_BYTES), dtype=torch.uint8, device=d_g1.device)
-    st = GwStatus()
-    with torch.cuda.device(d_g1.device):
-        rc = r1cs_lib().gwb_bn254_pairing_batch_device(d_g1.data_ptr(), d_g2.data_ptr(), n, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
-    _r1cs_check(rc, st)
-    if n:
-        out.record_stream(s)
+    with _device_call(d_g1, stream, (out,)) as s:
+        _r1cs_call(r1cs_lib().gwb_bn254_pairing_batch_device, d_g1.data_ptr(), d_g2.data_ptr(), n, out.data_ptr(), s.cuda_stream)
     return out
 
 
@@ -2102,16 +1565,10 @@ def bn254_g2_check_batch_device(d_points, montgomery=False, method="fast", strea
         raise WitnessCalcError("method must be one of %s" % ", ".join(G2_CHECK_METHODS))
     n = d_points.shape[0]
     assert tuple(d_points.shape) == (n, 128) and d_points.is_cuda and d_points.is_contiguous() and d_points.dtype == torch.uint8
-    s = stream if stream is not None else torch.cuda.current_stream(d_points.device)
     out = torch.empty(n, dtype=torch.uint32, device=d_points.device)
-    st = GwStatus()
-    with torch.cuda.device(d_points.device):
-        rc = r1cs_lib().gwb_bn254_g2_check_batch_device(d_points.data_ptr() if n else None, n, FORM_MONTGOMERY if montgomery else FORM_CANONICAL,
-                                                        G2_CHECK_METHODS[method], out.data_ptr() if n else None, s.cuda_stream, ctypes.byref(st))
-    _r1cs_check(rc, st)
-    if n:
-        d_points.record_stream(s)
-        out.record_stream(s)
+    with _device_call(d_points, stream, (d_points, out)) as s:
+        _r1cs_call(r1cs_lib().gwb_bn254_g2_check_batch_device, d_points.data_ptr() if n else None, n, _form(montgomery), G2_CHECK_METHODS[method],
+                   out.data_ptr() if n else None, s.cuda_stream)
     return out
 
 
@@ -2119,42 +1576,30 @@ def bn254_g2_check_batch_device(d_points, montgomery=False, method="fast", strea
 GROTH16_CPROOF_BYTES = 128
 
 
-def _codec_args(d_in, width, stream):
+def _codec_args(d_in, width):
     import torch
     assert d_in.is_cuda and d_in.is_contiguous() and d_in.dtype == torch.uint8 and d_in.dim() == 2 and d_in.shape[1] == width, tuple(d_in.shape)
-    return d_in.shape[0], stream if stream is not None else torch.cuda.current_stream(d_in.device)
+    return d_in.shape[0]
 
 
 def _compress_batch_device(group, d_points, montgomery, stream):
     import torch
-    n, s = _codec_args(d_points, 64 * group, stream)
+    n = _codec_args(d_points, 64 * group)
     out = torch.empty((n, 32 * group), dtype=torch.uint8, device=d_points.device)
-    st = GwStatus()
-    with torch.cuda.device(d_points.device):
-        rc = r1cs_lib().gwb_bn254_compress_batch_device(d_points.data_ptr() if n else None, n, group, FORM_MONTGOMERY if montgomery else FORM_CANONICAL,
-                                                        out.data_ptr() if n else None, s.cuda_stream, ctypes.byref(st))
-    _r1cs_check(rc, st)
-    if n:
-        d_points.record_stream(s)
-        out.record_stream(s)
+    with _device_call(d_points, stream, (d_points, out)) as s:
+        _r1cs_call(r1cs_lib().gwb_bn254_compress_batch_device, d_points.data_ptr() if n else None, n, group, _form(montgomery),
+                   out.data_ptr() if n else None, s.cuda_stream)
     return out
 
 
 def _decompress_batch_device(group, d_in, montgomery, stream):
     import torch
-    n, s = _codec_args(d_in, 32 * group, stream)
+    n = _codec_args(d_in, 32 * group)
     out = torch.empty((n, 64 * group), dtype=torch.uint8, device=d_in.device)
     status = torch.empty(n, dtype=torch.int32, device=d_in.device)
-    st = GwStatus()
-    with torch.cuda.device(d_in.device):
-        rc = r1cs_lib().gwb_bn254_decompress_batch_device(d_in.data_ptr() if n else None, n, group, FORM_MONTGOMERY if montgomery else FORM_CANONICAL,
-                                                          out.data_ptr() if n else None, status.data_ptr() if n else None, s.cuda_stream,
-                                                          ctypes.byref(st))
-    _r1cs_check(rc, st)
-    if n:
-        d_in.record_stream(s)
-        out.record_stream(s)
-        status.record_stream(s)
+    with _device_call(d_in, stream, (d_in, out, status)) as s:
+        _r1cs_call(r1cs_lib().gwb_bn254_decompress_batch_device, d_in.data_ptr() if n else None, n, group, _form(montgomery),
+                   out.data_ptr() if n else None, status.data_ptr() if n else None, s.cuda_stream)
     return out, status
 
 
@@ -2186,16 +1631,10 @@ def groth16_compress_proofs_device(d_proofs, stream=None):
     """Device proofs (uint8 cuda [B, 256], the prover's layout) -> a uint8 cuda tensor [B, 128]: A (32), B (64), C (32) compressed.
     Asynchronous on `stream` or the current torch stream."""
     import torch
-    b, s = _codec_args(d_proofs, GROTH16_PROOF_BYTES, stream)
+    b = _codec_args(d_proofs, GROTH16_PROOF_BYTES)
     out = torch.empty((b, GROTH16_CPROOF_BYTES), dtype=torch.uint8, device=d_proofs.device)
-    st = GwStatus()
-    with torch.cuda.device(d_proofs.device):
-        rc = r1cs_lib().gwb_groth16_proofs_compress_device(d_proofs.data_ptr() if b else None, b, out.data_ptr() if b else None, s.cuda_stream,
-                                                           ctypes.byref(st))
-    _r1cs_check(rc, st)
-    if b:
-        d_proofs.record_stream(s)
-        out.record_stream(s)
+    with _device_call(d_proofs, stream, (d_proofs, out)) as s:
+        _r1cs_call(r1cs_lib().gwb_groth16_proofs_compress_device, d_proofs.data_ptr() if b else None, b, out.data_ptr() if b else None, s.cuda_stream)
     return out
 
 
@@ -2203,18 +1642,12 @@ def groth16_decompress_proofs_device(d_cproofs, stream=None):
     """Compressed device proofs (uint8 cuda [B, 128]) -> (proofs [B, 256], status int32 [B]): VERIFY_POINT when any of A, B, C was
     refused (that point is then (0, 0)), else VERIFY_VALID.  Asynchronous on `stream` or the current torch stream."""
     import torch
-    b, s = _codec_args(d_cproofs, GROTH16_CPROOF_BYTES, stream)
+    b = _codec_args(d_cproofs, GROTH16_CPROOF_BYTES)
     out = torch.empty((b, GROTH16_PROOF_BYTES), dtype=torch.uint8, device=d_cproofs.device)
     status = torch.empty(b, dtype=torch.int32, device=d_cproofs.device)
-    st = GwStatus()
-    with torch.cuda.device(d_cproofs.device):
-        rc = r1cs_lib().gwb_groth16_proofs_decompress_device(d_cproofs.data_ptr() if b else None, b, out.data_ptr() if b else None,
-                                                             status.data_ptr() if b else None, s.cuda_stream, ctypes.byref(st))
-    _r1cs_check(rc, st)
-    if b:
-        d_cproofs.record_stream(s)
-        out.record_stream(s)
-        status.record_stream(s)
+    with _device_call(d_cproofs, stream, (d_cproofs, out, status)) as s:
+        _r1cs_call(r1cs_lib().gwb_groth16_proofs_decompress_device, d_cproofs.data_ptr() if b else None, b, out.data_ptr() if b else None,
+                   status.data_ptr() if b else None, s.cuda_stream)
     return out, status
 
 
@@ -2262,7 +1695,7 @@ def _kzg_log2(n, what):
     return n.bit_length() - 1
 
 
-class Kzg:
+class Kzg(_Handle):
     """KZG polynomial commitments over a `.ptau` image (bytes or any buffer, an mmap included; it is not kept): commit to
     polynomials given by coefficients or by evaluations, open them at points, check openings.  max_len: the longest polynomial,
     in coefficients (default: every point of the file, 2^(power+1) - 1).  check_powers: run ptau_check_powers' rule over the
@@ -2270,6 +1703,7 @@ class Kzg:
     32 bytes little-endian, points 64 bytes canonical affine (zero bytes: infinity).  The plain methods take and return numpy
     arrays and are synchronous; the _device methods take torch cuda tensors and are asynchronous on `stream` or the current
     stream."""
+    _FREE = ("_r1cs_lib", "gwb_kzg_free")
 
     def __init__(self, ptau, max_len=None, check_powers=False):
         keep, addr, n = _ptau_buffer(ptau)
@@ -2278,44 +1712,24 @@ class Kzg:
         if int(max_len) < 0 or int(max_len) >= 1 << 64:
             raise WitnessCalcError("kzg: max_len %d" % max_len)
         self._h = ctypes.c_void_p()
-        st = GwStatus()
-        rc = r1cs_lib().gwb_kzg_new(addr, n, int(max_len), KZG_CHECK_POWERS if check_powers else 0, ctypes.byref(self._h), ctypes.byref(st))
-        del keep
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_kzg_new, addr, n, int(max_len), KZG_CHECK_POWERS if check_powers else 0, ctypes.byref(self._h))
         info = KzgInfo()
         r1cs_lib().gwb_kzg_info(self._h, ctypes.byref(info))
         self.info = {"max_len": int(info.max_len), "power": int(info.power), "prepared": bool(info.prepared)}
-
-    def close(self):
-        if getattr(self, "_h", None) and _r1cs_lib is not None:
-            _r1cs_lib.gwb_kzg_free(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _stream(self, t, stream):
-        import torch
-        return stream if stream is not None else torch.cuda.current_stream(t.device)
 
     def commit(self, polys):
         """uint8 [K, N, 32] -> commitments uint8 [K, 64]"""
         p = _kzg_host(polys, (-1, 32), "polys")
         out = np.zeros((p.shape[0], 64), dtype=np.uint8)
-        st = GwStatus()
-        _r1cs_check(r1cs_lib().gwb_kzg_commit_batch(self._h, p.ctypes.data, p.shape[0], p.shape[1], out.ctypes.data, ctypes.byref(st)), st)
+        _r1cs_call(r1cs_lib().gwb_kzg_commit_batch, self._h, p.ctypes.data, p.shape[0], p.shape[1], out.ctypes.data)
         return out
 
     def commit_device(self, d_polys, stream=None):
         import torch
         p = _kzg_dev(d_polys, (-1, 32), "d_polys")
-        s = self._stream(p, stream)
         out = torch.empty((p.shape[0], 64), dtype=torch.uint8, device=p.device)
-        st = GwStatus()
-        with torch.cuda.device(p.device):
-            rc = r1cs_lib().gwb_kzg_commit_batch_device(self._h, p.data_ptr(), p.shape[0], p.shape[1], out.data_ptr(), s.cuda_stream, ctypes.byref(st))
-        _r1cs_check(rc, st)
-        p.record_stream(s)
-        out.record_stream(s)
+        with _device_call(p, stream, (p, out)) as s:
+            _r1cs_call(r1cs_lib().gwb_kzg_commit_batch_device, self._h, p.data_ptr(), p.shape[0], p.shape[1], out.data_ptr(), s.cuda_stream)
         return out
 
     def commit_evals(self, evals):
@@ -2324,22 +1738,16 @@ class Kzg:
         e = _kzg_host(evals, (-1, 32), "evals")
         m = _kzg_log2(e.shape[1], "evals")
         out = np.zeros((e.shape[0], 64), dtype=np.uint8)
-        st = GwStatus()
-        _r1cs_check(r1cs_lib().gwb_kzg_commit_evals_batch(self._h, e.ctypes.data, e.shape[0], m, out.ctypes.data, ctypes.byref(st)), st)
+        _r1cs_call(r1cs_lib().gwb_kzg_commit_evals_batch, self._h, e.ctypes.data, e.shape[0], m, out.ctypes.data)
         return out
 
     def commit_evals_device(self, d_evals, stream=None):
         import torch
         e = _kzg_dev(d_evals, (-1, 32), "d_evals")
         m = _kzg_log2(e.shape[1], "d_evals")
-        s = self._stream(e, stream)
         out = torch.empty((e.shape[0], 64), dtype=torch.uint8, device=e.device)
-        st = GwStatus()
-        with torch.cuda.device(e.device):
-            rc = r1cs_lib().gwb_kzg_commit_evals_batch_device(self._h, e.data_ptr(), e.shape[0], m, out.data_ptr(), s.cuda_stream, ctypes.byref(st))
-        _r1cs_check(rc, st)
-        e.record_stream(s)
-        out.record_stream(s)
+        with _device_call(e, stream, (e, out)) as s:
+            _r1cs_call(r1cs_lib().gwb_kzg_commit_evals_batch_device, self._h, e.data_ptr(), e.shape[0], m, out.data_ptr(), s.cuda_stream)
         return out
 
     def eval(self, polys, zs):
@@ -2349,8 +1757,7 @@ class Kzg:
         if z.shape[0] != p.shape[0]:
             raise WitnessCalcError("kzg: %d polynomials and %d points" % (p.shape[0], z.shape[0]))
         ys = np.zeros((p.shape[0], 32), dtype=np.uint8)
-        st = GwStatus()
-        _r1cs_check(r1cs_lib().gwb_kzg_eval_batch(self._h, p.ctypes.data, z.ctypes.data, p.shape[0], p.shape[1], ys.ctypes.data, ctypes.byref(st)), st)
+        _r1cs_call(r1cs_lib().gwb_kzg_eval_batch, self._h, p.ctypes.data, z.ctypes.data, p.shape[0], p.shape[1], ys.ctypes.data)
         return ys
 
     def open(self, polys, zs):
@@ -2360,25 +1767,18 @@ class Kzg:
         if z.shape[0] != p.shape[0]:
             raise WitnessCalcError("kzg: %d polynomials and %d points" % (p.shape[0], z.shape[0]))
         ys, ws = np.zeros((p.shape[0], 32), dtype=np.uint8), np.zeros((p.shape[0], 64), dtype=np.uint8)
-        st = GwStatus()
-        rc = r1cs_lib().gwb_kzg_open_batch(self._h, p.ctypes.data, z.ctypes.data, p.shape[0], p.shape[1], ys.ctypes.data, ws.ctypes.data, ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_kzg_open_batch, self._h, p.ctypes.data, z.ctypes.data, p.shape[0], p.shape[1], ys.ctypes.data, ws.ctypes.data)
         return ys, ws
 
     def open_device(self, d_polys, d_zs, stream=None):
         import torch
         p = _kzg_dev(d_polys, (-1, 32), "d_polys")
         z = _kzg_dev(d_zs, (32,), "d_zs", p.shape[0])
-        s = self._stream(p, stream)
         ys = torch.empty((p.shape[0], 32), dtype=torch.uint8, device=p.device)
         ws = torch.empty((p.shape[0], 64), dtype=torch.uint8, device=p.device)
-        st = GwStatus()
-        with torch.cuda.device(p.device):
-            rc = r1cs_lib().gwb_kzg_open_batch_device(self._h, p.data_ptr(), z.data_ptr(), p.shape[0], p.shape[1], ys.data_ptr(), ws.data_ptr(), s.cuda_stream,
-                                                      ctypes.byref(st))
-        _r1cs_check(rc, st)
-        for t in (p, z, ys, ws):
-            t.record_stream(s)
+        with _device_call(p, stream, (p, z, ys, ws)) as s:
+            _r1cs_call(r1cs_lib().gwb_kzg_open_batch_device, self._h, p.data_ptr(), z.data_ptr(), p.shape[0], p.shape[1], ys.data_ptr(), ws.data_ptr(),
+                       s.cuda_stream)
         return ys, ws
 
     def verify(self, commitments, zs, ys, proofs):
@@ -2389,9 +1789,7 @@ class Kzg:
         if not (z.shape[0] == y.shape[0] == w.shape[0] == k):
             raise WitnessCalcError("kzg: %d commitments, %d points, %d values and %d proofs" % (k, z.shape[0], y.shape[0], w.shape[0]))
         out = np.zeros(k, dtype=np.uint32)
-        st = GwStatus()
-        rc = r1cs_lib().gwb_kzg_verify_batch(self._h, c.ctypes.data, z.ctypes.data, y.ctypes.data, w.ctypes.data, k, out.ctypes.data, ctypes.byref(st))
-        _r1cs_check(rc, st)
+        _r1cs_call(r1cs_lib().gwb_kzg_verify_batch, self._h, c.ctypes.data, z.ctypes.data, y.ctypes.data, w.ctypes.data, k, out.ctypes.data)
         return out
 
     def verify_device(self, d_commitments, d_zs, d_ys, d_proofs, stream=None):
@@ -2400,15 +1798,9 @@ class Kzg:
         c = _kzg_dev(d_commitments, (64,), "d_commitments")
         k = c.shape[0]
         z, y, w = _kzg_dev(d_zs, (32,), "d_zs", k), _kzg_dev(d_ys, (32,), "d_ys", k), _kzg_dev(d_proofs, (64,), "d_proofs", k)
-        s = self._stream(c, stream)
         out = torch.empty(k, dtype=torch.int32, device=c.device)
-        st = GwStatus()
-        with torch.cuda.device(c.device):
-            rc = r1cs_lib().gwb_kzg_verify_batch_device(self._h, c.data_ptr(), z.data_ptr(), y.data_ptr(), w.data_ptr(), k, out.data_ptr(), s.cuda_stream,
-                                                        ctypes.byref(st))
-        _r1cs_check(rc, st)
-        for t in (c, z, y, w, out):
-            t.record_stream(s)
+        with _device_call(c, stream, (c, z, y, w, out)) as s:
+            _r1cs_call(r1cs_lib().gwb_kzg_verify_batch_device, self._h, c.data_ptr(), z.data_ptr(), y.data_ptr(), w.data_ptr(), k, out.data_ptr(), s.cuda_stream)
         return out
 
 
@@ -2429,25 +1821,17 @@ def kzg_eval_quotient_device(d_polys, d_zs, tile=None, stream=None):
     p = _kzg_dev(d_polys, (-1, 32), "d_polys")
     k, n = p.shape[0], p.shape[1]
     z = _kzg_dev(d_zs, (32,), "d_zs", k)
-    s = stream if stream is not None else torch.cuda.current_stream(p.device)
     ys = torch.empty((k, 32), dtype=torch.uint8, device=p.device)
     qs = torch.empty((k, max(n - 1, 0), 32), dtype=torch.uint8, device=p.device)
-    st = GwStatus()
-    with torch.cuda.device(p.device):
-        rc = r1cs_lib().gwb_kzg_eval_quotient_device(p.data_ptr(), z.data_ptr(), k, n, 0 if tile is None else int(tile), ys.data_ptr(), qs.data_ptr(),
-                                                     s.cuda_stream, ctypes.byref(st))
-    _r1cs_check(rc, st)
-    for t in (p, z, ys, qs):
-        t.record_stream(s)
+    with _device_call(p, stream, (p, z, ys, qs)) as s:
+        _r1cs_call(r1cs_lib().gwb_kzg_eval_quotient_device, p.data_ptr(), z.data_ptr(), k, n, 0 if tile is None else int(tile), ys.data_ptr(), qs.data_ptr(),
+                   s.cuda_stream)
     return ys, qs
 
 
 def kzg_phase_ms(k):
     """{quotient, lincomb, prepare, pairing} in ms of the handle's last open or verify call (waits for it)."""
-    ms = (ctypes.c_float * 4)()
-    if r1cs_lib().gwb_kzg_phase_ms(k._h, ms) != 0:
-        raise WitnessCalcError("no KZG phase times (no open or verify call yet)")
-    return dict(zip(KZG_PHASES, (float(x) for x in ms)))
+    return _phase_ms(r1cs_lib().gwb_kzg_phase_ms, KZG_PHASES, "no KZG phase times (no open or verify call yet)", k._h)
 
 
 from . import graphgen  # noqa: E402,F401  (graph generator library on top of the C-ABI producer)

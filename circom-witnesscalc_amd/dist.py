@@ -89,28 +89,16 @@ class RcclComm:
         self._native = None
         if pkg is not None:  # the library's own helpers (the id by value in C)
             N = pkg.lib()
-            N.gwb_rccl_unique_id.argtypes = [ctypes.c_void_p, ctypes.POINTER(pkg.GwStatus)]
-            N.gwb_rccl_comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(pkg.GwStatus)]
-            N.gwb_rccl_comm_ranks.argtypes = [ctypes.c_void_p]
-            N.gwb_rccl_comm_destroy.argtypes = [ctypes.c_void_p]
-            N.gwb_rccl_comm_destroy.restype = None
             rank, world = dist.get_rank(), dist.get_world_size()
             raw = ctypes.create_string_buffer(128)
-
-            def check(rc, st, what):
-                msg = ctypes.string_at(st.error_msg).decode("utf-8", "replace") if st.error_msg else ""
-                N.gwb_free_status(ctypes.byref(st))
-                if rc != 0:
-                    raise RuntimeError("%s: %s" % (what, msg))
             # Every rank enters the broadcast whatever happened on the source: its failure travels as a flag byte behind the id and
             # all ranks raise together (a source that raised first would leave the others waiting in the collective for good).
             src_error = None
             if rank == src:
-                st = pkg.GwStatus()
                 try:
-                    check(N.gwb_rccl_unique_id(raw, ctypes.byref(st)), st, "gwb_rccl_unique_id")
-                except RuntimeError as e:
-                    src_error = str(e)
+                    pkg._call(N.gwb_rccl_unique_id, raw)
+                except pkg.WitnessCalcError as e:
+                    src_error = "gwb_rccl_unique_id: %s" % e
             t = torch.frombuffer(bytearray(raw.raw + (b"\x00" if src_error is None else b"\x01")), dtype=torch.uint8).clone().to(device)
             dist.broadcast(t, src=src)
             got = t.cpu().numpy().tobytes()
@@ -119,8 +107,10 @@ class RcclComm:
             raw = ctypes.create_string_buffer(got[:128], 128)
             torch.cuda.set_device(device)
             self.comm = ctypes.c_void_p()
-            st = pkg.GwStatus()
-            check(N.gwb_rccl_comm_init(raw, world, rank, ctypes.byref(self.comm), ctypes.byref(st)), st, "gwb_rccl_comm_init")
+            try:
+                pkg._call(N.gwb_rccl_comm_init, raw, world, rank, ctypes.byref(self.comm))
+            except pkg.WitnessCalcError as e:
+                raise RuntimeError("gwb_rccl_comm_init: %s" % e) from None
             self.n_ranks = N.gwb_rccl_comm_ranks(self.comm)
             self._native = N
             return
@@ -179,17 +169,10 @@ def broadcast_graph_rccl(pkg, graph_data, tile_width=0, src=0, device=None, batc
         comm = RcclComm(device, src, library=lib_, pkg=pkg)
     try:
         g = pkg.Graph(graph_data) if rank == src else None
-        out, st = ctypes.c_void_p(), pkg.GwStatus()
-        L = pkg.lib()
-        L.gwb_graph_broadcast.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                          ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(pkg.GwStatus)]
+        out = ctypes.c_void_p()
         stream = torch.cuda.current_stream(device)
-        rc = L.gwb_graph_broadcast(g._h if g is not None else None, tile_width, batch_per_rank or 0, src, rank, comm.comm, stream.cuda_stream, ctypes.byref(out),
-                                   ctypes.byref(st))
-        msg = ctypes.string_at(st.error_msg).decode("utf-8", "replace") if st.error_msg else ""
-        L.gwb_free_status(ctypes.byref(st))
-        if rc != 0:
-            raise pkg.WitnessCalcError(msg or "gwb_graph_broadcast failed")
+        pkg._call(pkg.lib().gwb_graph_broadcast, g._h if g is not None else None, tile_width, batch_per_rank or 0, src, rank, comm.comm, stream.cuda_stream,
+                  ctypes.byref(out))
         if rank != src:
             g = pkg.Graph(_handle=out)
         elif not tile_width:
