@@ -1670,6 +1670,7 @@ def groth16_decompress_proofs(cproofs):
 KZG_VALID, KZG_SCALAR, KZG_POINT, KZG_EQUATION = 0, 1, 2, 3
 KZG_CHECK_POWERS = 1
 KZG_PHASES = ("quotient", "lincomb", "prepare", "pairing")
+KZG_FOLD_PHASES = ("fold", "evals", "quotient", "lincomb", "prepare", "pairing")
 
 
 def _kzg_host(a, tail, what):
@@ -1687,6 +1688,24 @@ def _kzg_dev(t, tail, what, k=None):
     if not ok:
         raise WitnessCalcError("kzg: %s: a contiguous uint8 cuda tensor [K, %s] expected" % (what, ", ".join("N" if e == -1 else str(e) for e in tail)))
     return t
+
+
+def _kzg_shaped(a, shape, what, device=False, g=None):
+    """A folded call's array: contiguous uint8 of `shape`, whose names stand for any length and whose numbers for themselves; the
+    first dimension is g when that is given.  A host array, or with `device` a cuda tensor."""
+    if device:
+        import torch
+        ok = hasattr(a, "is_cuda") and a.is_cuda and a.is_contiguous() and a.dtype == torch.uint8
+    else:
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        ok = True
+    ok = ok and len(a.shape) == len(shape) and all(isinstance(e, str) or e == d for e, d in zip(shape, a.shape)) and (g is None or a.shape[0] == g)
+    if not ok:
+        want = "[%s]" % ", ".join(str(e) for e in shape)
+        if device:
+            raise WitnessCalcError("kzg: %s: a contiguous uint8 cuda tensor %s expected" % (what, want))
+        raise WitnessCalcError("kzg: %s: uint8 %s expected, got %s" % (what, want, list(a.shape)))
+    return a
 
 
 def _kzg_log2(n, what):
@@ -1802,6 +1821,94 @@ class Kzg(_Handle):
         with _device_call(c, stream, (c, z, y, w, out)) as s:
             _r1cs_call(r1cs_lib().gwb_kzg_verify_batch_device, self._h, c.data_ptr(), z.data_ptr(), y.data_ptr(), w.data_ptr(), k, out.data_ptr(), s.cuda_stream)
         return out
+
+
+    # -- folded openings: G groups of K polynomials, one point, one challenge gamma and one witness per group
+    def open_fold(self, polys, zs, gammas):
+        """uint8 [G, K, N, 32], points [G, 32] and challenges [G, 32] -> (values uint8 [G, K, 32], proofs uint8 [G, 64]): y_k =
+        p_k(z) and the one witness of sum_k gamma^k p_k at z.  gamma is the caller's protocol challenge; the check binds each y_k
+        to its commitment only if gamma was fixed after the commitments, z and the y_k."""
+        p = _kzg_shaped(polys, ("G", "K", "N", 32), "polys")
+        g, k, n = p.shape[:3]
+        z, gm = _kzg_shaped(zs, ("G", 32), "zs"), _kzg_shaped(gammas, ("G", 32), "gammas")
+        if not (z.shape[0] == gm.shape[0] == g):
+            raise WitnessCalcError("kzg: %d groups, %d points and %d challenges" % (g, z.shape[0], gm.shape[0]))
+        ys, ws = np.zeros((g, k, 32), dtype=np.uint8), np.zeros((g, 64), dtype=np.uint8)
+        _r1cs_call(r1cs_lib().gwb_kzg_open_fold_batch, self._h, p.ctypes.data, z.ctypes.data, gm.ctypes.data, g, k, n, ys.ctypes.data, ws.ctypes.data)
+        return ys, ws
+
+    def open_fold_device(self, d_polys, d_zs, d_gammas, stream=None):
+        import torch
+        p = _kzg_shaped(d_polys, ("G", "K", "N", 32), "d_polys", device=True)
+        g, k, n = p.shape[:3]
+        z, gm = _kzg_shaped(d_zs, ("G", 32), "d_zs", device=True, g=g), _kzg_shaped(d_gammas, ("G", 32), "d_gammas", device=True, g=g)
+        ys = torch.empty((g, k, 32), dtype=torch.uint8, device=p.device)
+        ws = torch.empty((g, 64), dtype=torch.uint8, device=p.device)
+        with _device_call(p, stream, (p, z, gm, ys, ws)) as s:
+            _r1cs_call(r1cs_lib().gwb_kzg_open_fold_batch_device, self._h, p.data_ptr(), z.data_ptr(), gm.data_ptr(), g, k, n, ys.data_ptr(), ws.data_ptr(),
+                       s.cuda_stream)
+        return ys, ws
+
+    def verify_fold(self, commitments, zs, gammas, ys, proofs):
+        """uint8 [G, K, 64], [G, 32], [G, 32], [G, K, 32], [G, 64] -> uint32 [G] of KZG_VALID, KZG_SCALAR, KZG_POINT, KZG_EQUATION:
+        e(sum_k gamma^k C_k - (sum_k gamma^k y_k) G1 + z W, G2) = e(W, tauG2) per group"""
+        c = _kzg_shaped(commitments, ("G", "K", 64), "commitments")
+        g, k = c.shape[:2]
+        z, gm, w = _kzg_shaped(zs, ("G", 32), "zs"), _kzg_shaped(gammas, ("G", 32), "gammas"), _kzg_shaped(proofs, ("G", 64), "proofs")
+        y = _kzg_shaped(ys, ("G", "K", 32), "ys")
+        if not (z.shape[0] == gm.shape[0] == w.shape[0] == y.shape[0] == g) or y.shape[1] != k:
+            raise WitnessCalcError("kzg: %d groups of %d commitments, %d points, %d challenges, %d groups of %d values and %d proofs" %
+                                   (g, k, z.shape[0], gm.shape[0], y.shape[0], y.shape[1], w.shape[0]))
+        out = np.zeros(g, dtype=np.uint32)
+        _r1cs_call(r1cs_lib().gwb_kzg_verify_fold_batch, self._h, c.ctypes.data, z.ctypes.data, gm.ctypes.data, y.ctypes.data, w.ctypes.data, g, k,
+                   out.ctypes.data)
+        return out
+
+    def verify_fold_device(self, d_commitments, d_zs, d_gammas, d_ys, d_proofs, stream=None):
+        """-> an int32 cuda tensor [G] of statuses"""
+        import torch
+        c = _kzg_shaped(d_commitments, ("G", "K", 64), "d_commitments", device=True)
+        g, k = c.shape[:2]
+        z, gm = _kzg_shaped(d_zs, ("G", 32), "d_zs", device=True, g=g), _kzg_shaped(d_gammas, ("G", 32), "d_gammas", device=True, g=g)
+        y, w = _kzg_shaped(d_ys, ("G", "K", 32), "d_ys", device=True, g=g), _kzg_shaped(d_proofs, ("G", 64), "d_proofs", device=True, g=g)
+        if y.shape[1] != k:
+            raise WitnessCalcError("kzg: %d commitments and %d values per group" % (k, y.shape[1]))
+        out = torch.empty(g, dtype=torch.int32, device=c.device)
+        with _device_call(c, stream, (c, z, gm, y, w, out)) as s:
+            _r1cs_call(r1cs_lib().gwb_kzg_verify_fold_batch_device, self._h, c.data_ptr(), z.data_ptr(), gm.data_ptr(), y.data_ptr(), w.data_ptr(), g, k,
+                       out.data_ptr(), s.cuda_stream)
+        return out
+
+
+def kzg_fold_device(d_polys, d_gammas, stream=None):
+    """Test and measurement aid of the fold kernel: uint8 cuda [G, K, N, 32] and [G, 32] -> [G, N, 32], sum_k gamma^k p_k per group,
+    canonical.  Asynchronous on `stream` or the current stream."""
+    import torch
+    p = _kzg_shaped(d_polys, ("G", "K", "N", 32), "d_polys", device=True)
+    g, k, n = p.shape[:3]
+    gm = _kzg_shaped(d_gammas, ("G", 32), "d_gammas", device=True, g=g)
+    out = torch.empty((g, n, 32), dtype=torch.uint8, device=p.device)
+    with _device_call(p, stream, (p, gm, out)) as s:
+        _r1cs_call(r1cs_lib().gwb_kzg_fold_device, p.data_ptr(), gm.data_ptr(), g, k, n, out.data_ptr(), s.cuda_stream)
+    return out
+
+
+def kzg_fold_points_device(d_points, d_gammas, stream=None):
+    """Test and measurement aid of the verifier's point fold: uint8 cuda [G, K, 64] and [G, 32] -> [G, 64], sum_k gamma^k C_k per
+    group.  A point with a coordinate at or above q or off the curve is refused; to say so the call waits for the stream."""
+    import torch
+    c = _kzg_shaped(d_points, ("G", "K", 64), "d_points", device=True)
+    g, k = c.shape[:2]
+    gm = _kzg_shaped(d_gammas, ("G", 32), "d_gammas", device=True, g=g)
+    out = torch.empty((g, 64), dtype=torch.uint8, device=c.device)
+    with _device_call(c, stream, (c, gm, out)) as s:
+        _r1cs_call(r1cs_lib().gwb_kzg_fold_points_device, c.data_ptr(), gm.data_ptr(), g, k, out.data_ptr(), s.cuda_stream)
+    return out
+
+
+def kzg_fold_phase_ms(k):
+    """{fold, evals, quotient, lincomb, prepare, pairing} in ms of the handle's last open_fold or verify_fold call (waits for it)."""
+    return _phase_ms(r1cs_lib().gwb_kzg_fold_phase_ms, KZG_FOLD_PHASES, "no KZG fold phase times (no open_fold or verify_fold call yet)", k._h)
 
 
 def kzg_tiles():

@@ -257,6 +257,13 @@ R1CS_ABI = {
     "gwb_kzg_phase_ms": (i32, [vp, P(f32)]),
     "gwb_kzg_eval_quotient_device": (i32, [vp, vp, sz, sz, u32, vp, vp, vp, stp]),
     "gwb_kzg_tiles": (i32, [P(u32), P(sz)]),
+    "gwb_kzg_open_fold_batch": (i32, [vp, vp, vp, vp, sz, sz, sz, vp, vp, stp]),
+    "gwb_kzg_open_fold_batch_device": (i32, [vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, stp]),
+    "gwb_kzg_verify_fold_batch": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, vp, stp]),
+    "gwb_kzg_verify_fold_batch_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, stp]),
+    "gwb_kzg_fold_phase_ms": (i32, [vp, P(f32)]),
+    "gwb_kzg_fold_device": (i32, [vp, vp, sz, sz, sz, vp, vp, stp]),
+    "gwb_kzg_fold_points_device": (i32, [vp, vp, sz, sz, vp, vp, stp]),
 }
 
 

@@ -37,11 +37,24 @@
 // point at infinity (the pairing path does not take it), gets its status here and the generators as pairing inputs;
 // kzg_compare_kernel sets the others from the GT bytes.
 //
+// Folded openings (K polynomials of a group at one point under one witness).  kzg_fold_kernel makes f = sum_k gamma^k p_k: one
+// thread per coefficient index, Horner in gamma from the last polynomial down, two 16-byte loads per step with consecutive lanes
+// on consecutive elements (a wave reads 2 KB contiguously); the same trick as above, canonical values and gamma in Montgomery
+// form, so no conversions; no LDS.  The quotient of f is the kernels above on f, and the y_k = p_k(z) are their "totals" role over
+// G K pairs, pair g K + k taking z_g through kzg_points_kernel's index divisor.  The verifier's L = sum_k gamma^k C_k - y_f G1 + z W
+// is K + 2 terms: kzg_fold_points_kernel, one wave per workgroup for xyzz_mul_short's registers, multiplies a chunk of 64 terms
+// side by side (gamma^k by square-and-multiply in the thread; y_f by Horner in the thread of the term -y_f G1) and adds them in a
+// tree of xyzz_add through LDS, so a group costs one multiplication and a tree whatever K is.  Every chunk leaves a partial sum and
+// what it found wrong (a scalar at or above r, a refused point); kzg_fold_emit_kernel, one thread per group, adds the partials and
+// goes on as kzg_prepare_kernel does.  kzg_fold_sum_kernel ends the handle-free aid (sum_k gamma^k C_k alone).
+//
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage for gfx950; every kernel: 0 bytes of scratch, no AGPRs; VGPRs, LDS per
 // workgroup, waves / SIMD):
 //   kzg_tile_kernel<256, totals> 55, 8 320 B, 8       kzg_tile_kernel<256, apply> 96, 8 320 B, 5
 //   kzg_tile_kernel<1024, totals> 70, 36 992 B, 4     kzg_tile_kernel<1024, apply> 132, 36 992 B, 3
-//   kzg_points_kernel 47, none, 8      kzg_prepare_kernel 212, none, 2      kzg_compare_kernel 71, none, 7
+//   kzg_points_kernel 48, none, 8      kzg_prepare_kernel 212, none, 2      kzg_compare_kernel 71, none, 7
+//   kzg_fold_kernel 56, none, 8        kzg_fold_points_kernel<check> 161, 8 192 B, 3      kzg_fold_points_kernel<aid> 176, 8 192 B, 2
+//   kzg_fold_emit_kernel 127, none, 4  kzg_fold_sum_kernel 128, none, 4
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -75,12 +88,13 @@ __device__ __forceinline__ Fr reduce_any(Fr w) {
     return w;
 }
 
-// zs [K][32] canonical, any value -> out[l K + i] = z_i^(TILE^l) in Montgomery form, l < levels
-__global__ __launch_bounds__(THREADS) void kzg_points_kernel(const uint8_t* __restrict__ zs, uint32_t K, uint32_t levels, uint32_t log_tile,
-                                                             Fr* __restrict__ out) {
+// zs [..][32] canonical, any value; pair i of the K of this launch takes z = zs[(first + i) / div] (div > 1: the polynomials of a
+// group share the group's point; first < div: how far into its group the launch's first pair lies) -> out[l K + i] = z^(TILE^l) in Montgomery form, l < levels
+__global__ __launch_bounds__(THREADS) void kzg_points_kernel(const uint8_t* __restrict__ zs, uint32_t first, uint32_t div, uint32_t K, uint32_t levels,
+                                                             uint32_t log_tile, Fr* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= K) return;
-    Fr z = cwc::fr_mul(*reinterpret_cast<const Fr*>(zs + (size_t)i * 32), cwc::fr_r2());  // (any first operand below 2^256)
+    Fr z = cwc::fr_mul(*reinterpret_cast<const Fr*>(zs + (size_t)((first + i) / div) * 32), cwc::fr_r2());  // (any first operand below 2^256)
     out[i] = z;
     for (uint32_t l = 1; l < levels; ++l) {
         for (uint32_t b = 0; b < log_tile; ++b) z = cwc::fr_sqr(z);
@@ -220,6 +234,27 @@ struct Levels {
 
 uint32_t log2_of(uint32_t tile) { return 31u - (uint32_t)__builtin_clz(tile); }
 
+// Opening i's status and its pairing inputs (L, G2), (W, tauG2); the generators for an opening that is decided already
+__device__ __forceinline__ void put_pairing_inputs(uint32_t i, uint32_t st, const A1& l, const A1& w, const uint8_t* __restrict__ tau_g2, uint8_t* __restrict__ g1,
+                                                   uint8_t* __restrict__ g2, uint32_t* __restrict__ status) {
+    status[i] = st;
+    uint8_t* o1 = g1 + (size_t)i * 2 * G1_BYTES;
+    uint8_t* o2 = g2 + (size_t)i * 2 * G2_BYTES;
+    const A2 gen2 = g2_generator();
+    put_coords<G2>(o2, gen2.x, gen2.y, true);
+    if (st == cwc_kzg::PENDING) {
+        put_coords<G1>(o1, l.x, l.y, true);
+        put_coords<G1>(o1 + G1_BYTES, w.x, w.y, true);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) reinterpret_cast<uint4*>(o2 + G2_BYTES)[k] = reinterpret_cast<const uint4*>(tau_g2)[k];
+    } else {
+        const A1 gen = g1_generator();
+        put_coords<G1>(o1, gen.x, gen.y, true);
+        put_coords<G1>(o1 + G1_BYTES, gen.x, gen.y, true);
+        put_coords<G2>(o2 + G2_BYTES, gen2.x, gen2.y, true);
+    }
+}
+
 __global__ __launch_bounds__(WAVE) void kzg_prepare_kernel(const uint8_t* __restrict__ cs, const uint8_t* __restrict__ zs, const uint8_t* __restrict__ ys,
                                                            const uint8_t* __restrict__ ws, uint32_t K, const uint8_t* __restrict__ tau_g2,
                                                            uint8_t* __restrict__ g1, uint8_t* __restrict__ g2, uint32_t* __restrict__ status) {
@@ -241,22 +276,7 @@ __global__ __launch_bounds__(WAVE) void kzg_prepare_kernel(const uint8_t* __rest
         const bool l_inf = affine_is_inf(l), w_inf = affine_is_inf(w);
         if (l_inf || w_inf) st = l_inf && w_inf ? GWB_KZG_VALID : GWB_KZG_EQUATION;
     }
-    status[i] = st;
-    uint8_t* o1 = g1 + (size_t)i * 2 * G1_BYTES;
-    uint8_t* o2 = g2 + (size_t)i * 2 * G2_BYTES;
-    const A2 gen2 = g2_generator();
-    put_coords<G2>(o2, gen2.x, gen2.y, true);
-    if (st == cwc_kzg::PENDING) {
-        put_coords<G1>(o1, l.x, l.y, true);
-        put_coords<G1>(o1 + G1_BYTES, w.x, w.y, true);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) reinterpret_cast<uint4*>(o2 + G2_BYTES)[k] = reinterpret_cast<const uint4*>(tau_g2)[k];
-    } else {
-        const A1 gen = g1_generator();
-        put_coords<G1>(o1, gen.x, gen.y, true);
-        put_coords<G1>(o1 + G1_BYTES, gen.x, gen.y, true);
-        put_coords<G2>(o2 + G2_BYTES, gen2.x, gen2.y, true);
-    }
+    put_pairing_inputs(i, st, l, w, tau_g2, g1, g2, status);
 }
 
 __global__ __launch_bounds__(THREADS) void kzg_compare_kernel(const uint8_t* __restrict__ gt, uint32_t K, uint32_t* __restrict__ status) {
@@ -269,14 +289,149 @@ __global__ __launch_bounds__(THREADS) void kzg_compare_kernel(const uint8_t* __r
     status[i] = diff ? GWB_KZG_EQUATION : GWB_KZG_VALID;
 }
 
+// -- folded openings ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ Fr load_fr(const uint4* __restrict__ p) {
+    const uint4 lo = p[0], hi = p[1];
+    return Fr{{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}};
+}
+
+// polys [G][K][N][32], gammas [G][32], any values -> out [G][N][32] = sum_k gamma^k p_k, canonical.  Group blockIdx.y, one thread
+// per coefficient index: Horner in gamma from the last polynomial down.
+__global__ __launch_bounds__(THREADS) void kzg_fold_kernel(const uint8_t* __restrict__ polys, const uint8_t* __restrict__ gammas, uint32_t K, uint32_t N,
+                                                           uint8_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * THREADS + threadIdx.x, g = blockIdx.y;
+    if (i >= N) return;
+    const Fr gm = cwc::fr_mul(*reinterpret_cast<const Fr*>(gammas + (size_t)g * 32), cwc::fr_r2());  // (any first operand below 2^256)
+    const size_t step = (size_t)N * 2;
+    const uint4* src = reinterpret_cast<const uint4*>(polys) + ((size_t)g * K * N + i) * 2;
+    Fr acc = reduce_any(load_fr(src + (size_t)(K - 1) * step));
+    for (uint32_t k = K - 1; k-- > 0;) acc = cwc::fr_add(reduce_any(load_fr(src + (size_t)k * step)), cwc::fr_mul(acc, gm));
+    uint4* dst = reinterpret_cast<uint4*>(out) + ((size_t)g * N + i) * 2;
+    dst[0] = make_uint4(acc.v[0], acc.v[1], acc.v[2], acc.v[3]);
+    dst[1] = make_uint4(acc.v[4], acc.v[5], acc.v[6], acc.v[7]);
+}
+
+constexpr uint32_t FOLD_SCALAR = 1u, FOLD_POINT = 2u;  // what a chunk of a group's terms found wrong
+
+// base^e, Montgomery form in and out
+__device__ __forceinline__ Fr fr_pow_u32(Fr base, uint32_t e) {
+    Fr r = cwc::fr_one();
+    for (; e; e >>= 1) {
+        if (e & 1u) r = cwc::fr_mul(r, base);
+        base = cwc::fr_sqr(base);
+    }
+    return r;
+}
+
+// The linear combination of a group's points, one term per thread and one wave per workgroup: workgroup (chunk, group) multiplies
+// the terms chunk * 64 .. + 63 side by side and adds them in a tree through LDS; the sum goes to partials[group chunks + chunk]
+// (XYZZ, Montgomery form) and what the chunk found wrong to flags[..].  Term k < K is gamma^k C_k.  CHECK (the verifier) adds
+// term K = -y_f G1, y_f = sum_k gamma^k y_k by Horner in that one thread, and term K + 1 = z W, and flags a gamma, z or y_k at or
+// above r; without it gamma is reduced.  A point that get_point refuses is flagged and left out.
+template <bool CHECK>
+__global__ __launch_bounds__(WAVE) void kzg_fold_points_kernel(const uint8_t* __restrict__ cs, const uint8_t* __restrict__ gammas, const uint8_t* __restrict__ zs,
+                                                               const uint8_t* __restrict__ ys, const uint8_t* __restrict__ ws, uint32_t K,
+                                                               P1* __restrict__ partials, uint32_t* __restrict__ flags) {
+    __shared__ P1 tree[WAVE];
+    const uint32_t lane = threadIdx.x, chunk = blockIdx.x, chunks = gridDim.x, g = blockIdx.y, t = chunk * WAVE + lane;
+    const Fr gamma = *reinterpret_cast<const Fr*>(gammas + (size_t)g * 32);
+    const Fr gm = cwc::fr_mul(gamma, cwc::fr_r2());  // (any first operand below 2^256)
+    uint32_t fl = CHECK && !cwc::u256_lt(gamma, cwc::fr_p()) ? FOLD_SCALAR : 0u;
+    A1 a = g1_generator();
+    Fr k = cwc::fr_zero();
+    bool live = false;
+    if (t < K) {
+        live = get_point<G1>(cs + ((size_t)g * K + t) * G1_BYTES, true, a) == PointFault::NONE;
+        if (live)
+            k = cwc::fr_from_mont(fr_pow_u32(gm, t));
+        else
+            fl |= FOLD_POINT;
+    } else if (CHECK && t == K) {
+        const uint8_t* y = ys + (size_t)g * K * 32;
+        for (uint32_t j = K; j-- > 0;) {
+            const Fr yj = *reinterpret_cast<const Fr*>(y + (size_t)j * 32);
+            if (!cwc::u256_lt(yj, cwc::fr_p())) fl |= FOLD_SCALAR;
+            k = cwc::fr_add(yj, cwc::fr_mul(k, gm));
+        }
+        a.y = G1::neg(a.y);
+        live = true;
+    } else if (CHECK && t == K + 1) {
+        k = *reinterpret_cast<const Fr*>(zs + (size_t)g * 32);
+        if (!cwc::u256_lt(k, cwc::fr_p())) fl |= FOLD_SCALAR;
+        live = get_point<G1>(ws + (size_t)g * G1_BYTES, true, a) == PointFault::NONE;
+        if (!live) fl |= FOLD_POINT;
+    }
+    P1 term = xyzz_inf<G1>();
+    if (live) term = xyzz_mul_short(from_affine(a), k);
+    tree[lane] = term;
+    for (uint32_t s = WAVE / 2; s; s >>= 1) {
+        __syncthreads();
+        if (lane < s) {  // (reads [s, 2s), writes [0, s))
+            term = xyzz_add(term, tree[lane + s]);
+            tree[lane] = term;
+        }
+    }
+    const uint32_t all = (__any(fl & FOLD_SCALAR) ? FOLD_SCALAR : 0u) | (__any(fl & FOLD_POINT) ? FOLD_POINT : 0u);
+    if (lane == 0) {
+        partials[(size_t)g * chunks + chunk] = term;
+        flags[(size_t)g * chunks + chunk] = all;
+    }
+}
+
+// the sum of a group's partial sums, and everything its chunks found wrong
+__device__ __forceinline__ P1 sum_partials(const P1* __restrict__ p, const uint32_t* __restrict__ f, uint32_t chunks, uint32_t& fl) {
+    P1 s = p[0];
+    fl = f[0];
+    for (uint32_t c = 1; c < chunks; ++c) {
+        s = xyzz_add(s, p[c]);
+        fl |= f[c];
+    }
+    return s;
+}
+
+// The folded check's kzg_prepare_kernel, one thread per group: L is the sum of the group's partials, and the status and the pairing
+// inputs follow as there.
+__global__ __launch_bounds__(WAVE) void kzg_fold_emit_kernel(const P1* __restrict__ partials, const uint32_t* __restrict__ flags, uint32_t chunks,
+                                                             const uint8_t* __restrict__ ws, uint32_t G, const uint8_t* __restrict__ tau_g2,
+                                                             uint8_t* __restrict__ g1, uint8_t* __restrict__ g2, uint32_t* __restrict__ status) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= G) return;
+    uint32_t fl;
+    const P1 sum = sum_partials(partials + (size_t)i * chunks, flags + (size_t)i * chunks, chunks, fl);
+    A1 w, l = g1_generator();
+    (void)get_point<G1>(ws + (size_t)i * G1_BYTES, true, w);  // (a W that fails is flagged already)
+    uint32_t st = cwc_kzg::PENDING;
+    if (fl & FOLD_SCALAR) {
+        st = GWB_KZG_SCALAR;
+    } else if (fl & FOLD_POINT) {
+        st = GWB_KZG_POINT;
+    } else {
+        l = xyzz_to_affine(sum);
+        const bool l_inf = affine_is_inf(l), w_inf = affine_is_inf(w);
+        if (l_inf || w_inf) st = l_inf && w_inf ? GWB_KZG_VALID : GWB_KZG_EQUATION;
+    }
+    put_pairing_inputs(i, st, l, w, tau_g2, g1, g2, status);
+}
+
+// The aid's end: out[i] = the sum of group i's partials, 64 canonical bytes; *fault = the lowest group with a refused point
+__global__ __launch_bounds__(WAVE) void kzg_fold_sum_kernel(const P1* __restrict__ partials, const uint32_t* __restrict__ flags, uint32_t chunks, uint32_t G,
+                                                            uint8_t* __restrict__ out, uint32_t* __restrict__ fault) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= G) return;
+    uint32_t fl;
+    const A1 sum = xyzz_to_affine(sum_partials(partials + (size_t)i * chunks, flags + (size_t)i * chunks, chunks, fl));
+    put_coords<G1>(out + (size_t)i * G1_BYTES, sum.x, sum.y, true);
+    if (fl & FOLD_POINT) atomicMin(fault, i);
+}
+
 }  // namespace
 
 namespace cwc_kzg {
 
 size_t eval_quotient_ws(uint64_t K, uint64_t N, uint32_t tile) { return Levels(std::min<uint64_t>(K, MAX_PAIRS_PER_LAUNCH), N, tile).bytes; }
 
-bool enqueue_eval_quotient(const uint8_t* d_polys, const uint8_t* d_zs, uint64_t K, uint32_t N, uint32_t tile, uint8_t* d_ys, uint8_t* d_qs, uint8_t* d_ws,
-                           hipStream_t s, std::string& err) {
+bool enqueue_eval_quotient(const uint8_t* d_polys, const uint8_t* d_zs, uint32_t z_div, uint64_t K, uint32_t N, uint32_t tile, uint8_t* d_ys, uint8_t* d_qs,
+                           uint8_t* d_ws, hipStream_t s, std::string& err) {
     const uint64_t piece = std::min<uint64_t>(K, MAX_PAIRS_PER_LAUNCH);
     const Levels lv(piece, N, tile);
     const auto launch = tile == TILE_SMALL ? launch_level<TILE_SMALL> : launch_level<TILE_PRODUCTION>;
@@ -285,7 +440,9 @@ bool enqueue_eval_quotient(const uint8_t* d_polys, const uint8_t* d_zs, uint64_t
     for (uint64_t at = 0; at < K; at += piece) {
         const uint32_t pairs = (uint32_t)std::min<uint64_t>(piece, K - at);
         const uint8_t* polys = d_polys + at * N * 32;
-        hipLaunchKernelGGL(kzg_points_kernel, dim3(blocks_for(pairs, THREADS)), dim3(THREADS), 0, s, d_zs + at * 32, pairs, lv.count, log2_of(tile), zs);
+        // (the piece's first point by a 64-bit offset; what is left of `at` is below z_div, so first + i stays 32-bit in the kernel)
+        hipLaunchKernelGGL(kzg_points_kernel, dim3(blocks_for(pairs, THREADS)), dim3(THREADS), 0, s, d_zs + at / z_div * 32, (uint32_t)(at % z_div), z_div, pairs,
+                           lv.count, log2_of(tile), zs);
         // level l's elements: the coefficients, or the totals of the level below
         auto in_of = [&](uint32_t l) { return l ? d_ws + lv.o_tot[l - 1] : polys; };
         auto stride_of = [&](uint32_t l) { return l ? (size_t)lv.blocks[l - 1] * 32 : (size_t)N * 32; };
@@ -311,6 +468,62 @@ bool enqueue_prepare(const uint8_t* d_c, const uint8_t* d_z, const uint8_t* d_y,
     hipLaunchKernelGGL(kzg_prepare_kernel, dim3(blocks_for(K, WAVE)), dim3(WAVE), 0, s, d_c, d_z, d_y, d_w, K, d_tau_g2, d_g1, d_g2, d_status);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) err = hip_err("launching the opening check's preparation", e);
+    return e == hipSuccess;
+}
+
+bool enqueue_fold(const uint8_t* d_polys, const uint8_t* d_gammas, uint64_t G, uint32_t K, uint32_t N, uint8_t* d_out, hipStream_t s, std::string& err) {
+    for (uint64_t at = 0; at < G; at += MAX_PAIRS_PER_LAUNCH) {
+        const uint32_t groups = (uint32_t)std::min<uint64_t>(MAX_PAIRS_PER_LAUNCH, G - at);
+        hipLaunchKernelGGL(kzg_fold_kernel, dim3(blocks_for(N, THREADS), groups), dim3(THREADS), 0, s, d_polys + at * K * N * 32, d_gammas + at * 32, K, N,
+                           d_out + at * N * 32);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) err = hip_err("launching the fold kernel", e);
+    return e == hipSuccess;
+}
+
+// chunks of 64 terms in a group's linear combination (K <= MAX_FOLD_PAIRS: K + 2 fits)
+static uint32_t fold_chunks(uint32_t K, bool check) { return (uint32_t)(((uint64_t)K + (check ? 2 : 0) + WAVE - 1) / WAVE); }
+
+size_t fold_points_ws(uint64_t G, uint32_t K, bool check) { return (size_t)(G * fold_chunks(K, check)) * FOLD_PARTIAL_BYTES; }
+
+bool enqueue_fold_points(const uint8_t* d_c, const uint8_t* d_gammas, const uint8_t* d_z, const uint8_t* d_y, const uint8_t* d_w, uint64_t G, uint32_t K,
+                         uint8_t* d_ws, hipStream_t s, std::string& err) {
+    static_assert(sizeof(P1) + sizeof(uint32_t) <= FOLD_PARTIAL_BYTES, "a partial sum and its flags");
+    const bool check = d_w != nullptr;
+    const uint32_t chunks = fold_chunks(K, check);
+    P1* partials = reinterpret_cast<P1*>(d_ws);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(d_ws + (size_t)(G * chunks) * sizeof(P1));
+    for (uint64_t at = 0; at < G; at += MAX_PAIRS_PER_LAUNCH) {
+        const dim3 grid(chunks, (uint32_t)std::min<uint64_t>(MAX_PAIRS_PER_LAUNCH, G - at));
+        if (check)
+            hipLaunchKernelGGL(kzg_fold_points_kernel<true>, grid, dim3(WAVE), 0, s, d_c + at * K * G1_BYTES, d_gammas + at * 32, d_z + at * 32, d_y + at * K * 32,
+                               d_w + at * G1_BYTES, K, partials + at * chunks, flags + at * chunks);
+        else
+            hipLaunchKernelGGL(kzg_fold_points_kernel<false>, grid, dim3(WAVE), 0, s, d_c + at * K * G1_BYTES, d_gammas + at * 32, nullptr, nullptr, nullptr, K,
+                               partials + at * chunks, flags + at * chunks);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) err = hip_err("launching the point fold", e);
+    return e == hipSuccess;
+}
+
+bool enqueue_fold_emit(const uint8_t* d_ws, const uint8_t* d_w, uint32_t G, uint32_t K, const uint8_t* d_tau_g2, uint8_t* d_g1, uint8_t* d_g2, uint32_t* d_status,
+                       hipStream_t s, std::string& err) {
+    const uint32_t chunks = fold_chunks(K, true);
+    hipLaunchKernelGGL(kzg_fold_emit_kernel, dim3(blocks_for(G, WAVE)), dim3(WAVE), 0, s, reinterpret_cast<const P1*>(d_ws),
+                       reinterpret_cast<const uint32_t*>(d_ws + (size_t)G * chunks * sizeof(P1)), chunks, d_w, G, d_tau_g2, d_g1, d_g2, d_status);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) err = hip_err("launching the folded check's preparation", e);
+    return e == hipSuccess;
+}
+
+bool enqueue_fold_sum(const uint8_t* d_ws, uint32_t G, uint32_t K, uint8_t* d_out, uint32_t* d_fault, hipStream_t s, std::string& err) {
+    const uint32_t chunks = fold_chunks(K, false);
+    hipLaunchKernelGGL(kzg_fold_sum_kernel, dim3(blocks_for(G, WAVE)), dim3(WAVE), 0, s, reinterpret_cast<const P1*>(d_ws),
+                       reinterpret_cast<const uint32_t*>(d_ws + (size_t)G * chunks * sizeof(P1)), chunks, G, d_out, d_fault);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) err = hip_err("launching the point fold's sum", e);
     return e == hipSuccess;
 }
 

@@ -1,7 +1,8 @@
 /* KZG polynomial commitments on an MI355X over a powers-of-tau file (`.ptau`): the file that the ceremony of
  * graph_witness_groth16_ceremony.h makes and gwb_ptau_prepare_phase2 prepares, used as a structured reference string.  Commit
- * to a polynomial given by coefficients or by evaluations, open it at a point, check openings with the pairing of the Groth16
- * verifier.  This is the layer PLONK and fflonk stand on; neither is part of it.
+ * to a polynomial given by coefficients or by evaluations, open it at a point, open several at one point under one witness
+ * (folded openings), check openings with the pairing of the Groth16 verifier.  This is the layer PLONK and fflonk stand on;
+ * neither is part of it.
  *
  * TRUST.  The SRS is whatever the file holds.  Nothing here vouches for it: GWB_KZG_CHECK_POWERS (gwb_ptau_check_powers over
  * the covered prefix) and gwb_ptau_verify do, and the ceremony behind the file has to have had one honest participant.  A file
@@ -33,6 +34,23 @@
  * its pairings run on the generators: W = O and L = O is VALID (that is C = y G1), exactly one of them at infinity is EQUATION
  * (e(W, tauG2) is 1 only for W = O, since tauG2 is refused at infinity by gwb_kzg_new).  GT values are compared as bytes: the
  * final exponent is exact.
+ *
+ * Folded openings: several polynomials at one point, one witness.
+ *   group        K >= 1 polynomials p_0 .. p_{K-1} of the same length N (the caller pads shorter ones with zeros), one point z and
+ *                one challenge gamma.  The folded polynomial is f = sum_k gamma^k p_k, with gamma^0 = 1 also for gamma = 0.
+ *   open_fold    y_k = p_k(z) for every k, and one W, the witness of f at z: W = sum_i q_i T_i with q the quotient of f as `open`
+ *                defines it.  Coefficients, z and gamma at or above r are reduced, as open reduces.  N <= 1 gives W = O, N = 0
+ *                gives y_k = 0.
+ *   verify_fold  of (C_0 .. C_{K-1}, z, gamma, y_0 .. y_{K-1}, W): with C_f = sum_k gamma^k C_k and y_f = sum_k gamma^k y_k the
+ *                group is VALID when e(C_f - y_f G1 + z W, G2) = e(W, tauG2).  Its status is the first rule that fails:
+ *                GWB_KZG_SCALAR (z, gamma or any y_k at or above r: refused, not reduced), GWB_KZG_POINT (any C_k, or W, fails
+ *                the point rule above), GWB_KZG_EQUATION.  L = C_f - y_f G1 + z W or W at infinity is decided as for a single row.
+ *   K = 1        is open / check of that polynomial, for any gamma.
+ * TRUST.  The folded check binds each y_k to its C_k only if gamma was fixed after the C_k, z and the y_k, by the caller's
+ * transcript (a hash of them, in a non-interactive protocol).  The library derives nothing: gamma is an argument.  A prover who
+ * knows gamma before choosing the y_k can pass the check with wrong values.
+ * Every group keeps its own equation, its own two pairings and its own status.  Groups at different points are not combined under
+ * one random factor (PLONK's u): that would save pairings, and a verify call here costs the same for one row as for thousands.
  *
  * The polynomial side (r1cs/kzg.hip) evaluates and divides a batch of K (polynomial, point) pairs in one launch per role and
  * level; the commitments and witnesses go through gwb_bn254_g1_lincomb_device, once per polynomial, over the SRS prefix that the
@@ -102,6 +120,35 @@ int gwb_kzg_verify_batch_device(gwb_kzg_t *h, const void *d_commitments, const v
  * An open has no prepare and no pairing, a verify no quotient and no lincomb: those are 0.  A _device call is waited for.
  * 1 when no such call has completed yet. */
 int gwb_kzg_phase_ms(gwb_kzg_t *h, float *ms);
+
+/* Folded openings of G groups of K polynomials: polys [G][K][N][32], zs [G][32], gammas [G][32] -> ys [G][K][32], proofs [G][64].
+ * One fold, one quotient and one linear combination per group whatever K is; the y_k are K evaluations.  Refused before the
+ * device is touched: K = 0, N > max_len, G K > 2^31 - 1.  G = 0 does nothing.  The folded polynomials and their quotients live in
+ * the workspace that CWC_GROTH16_WORKSPACE_MB bounds; more groups run in sub-batches. */
+int gwb_kzg_open_fold_batch(gwb_kzg_t *h, const void *polys, const void *zs, const void *gammas, size_t G, size_t K, size_t N, void *ys,
+                            void *proofs, gw_status_t *status);
+int gwb_kzg_open_fold_batch_device(gwb_kzg_t *h, const void *d_polys, const void *d_zs, const void *d_gammas, size_t G, size_t K, size_t N,
+                                   void *d_ys, void *d_proofs, void *hip_stream, gw_status_t *status);
+/* commitments [G][K][64], zs [G][32], gammas [G][32], ys [G][K][32], proofs [G][64] -> status_out [G] uint32 (GWB_KZG_*).  The K + 2
+ * multiplications of a group run side by side, 64 to a workgroup, and are added in a tree.  K = 0 and G K > 2^31 - 1 are refused. */
+int gwb_kzg_verify_fold_batch(gwb_kzg_t *h, const void *commitments, const void *zs, const void *gammas, const void *ys, const void *proofs,
+                              size_t G, size_t K, void *status_out, gw_status_t *status);
+int gwb_kzg_verify_fold_batch_device(gwb_kzg_t *h, const void *d_commitments, const void *d_zs, const void *d_gammas, const void *d_ys,
+                                     const void *d_proofs, size_t G, size_t K, void *d_status, void *hip_stream, gw_status_t *status);
+/* ms[6] of the handle's last open_fold or verify_fold call, as gwb_kzg_phase_ms: fold, evals (the y_k), quotient, lincomb, prepare
+ * (the point fold and the pairing inputs), pairing.  An open_fold has no prepare and no pairing, a verify_fold only those.  The
+ * folded calls leave gwb_kzg_phase_ms's values alone, and the other calls these. */
+int gwb_kzg_fold_phase_ms(gwb_kzg_t *h, float *ms);
+
+/* Test and measurement aids of the folded openings' kernels, handle-free.
+ * gwb_kzg_fold_device: d_polys [G][K][N][32], d_gammas [G][32], any values -> d_out [G][N][32] = sum_k gamma^k p_k, canonical.
+ * Asynchronous on hip_stream.
+ * gwb_kzg_fold_points_device: d_points [G][K][64], d_gammas [G][32] (reduced) -> d_out [G][64] = sum_k gamma^k C_k.  A point that
+ * fails the point rule makes the call fail with the first such group in the message; to say so the call waits for hip_stream. */
+int gwb_kzg_fold_device(const void *d_polys, const void *d_gammas, size_t G, size_t K, size_t N, void *d_out, void *hip_stream,
+                        gw_status_t *status);
+int gwb_kzg_fold_points_device(const void *d_points, const void *d_gammas, size_t G, size_t K, void *d_out, void *hip_stream,
+                               gw_status_t *status);
 
 /* Test and measurement aid of the evaluate-and-quotient kernels, handle-free: d_polys [K][N][32], d_zs [K][32] -> d_ys [K][32]
  * and d_qs [K][N-1][32], canonical, with workgroups that own `tile` consecutive coefficients (one of gwb_kzg_tiles; 0 = the
