@@ -16,107 +16,14 @@
 // The records are this library's own: they are not interchangeable with snarkjs's (see the header).  Exit status 0 on success;
 // 1 for a failed verification, with its message; 2 on a usage, file or format error.  Every input is parsed before the device
 // is touched.
-#include <fcntl.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
-#include <algorithm>
-#include <fstream>
-#include <iterator>
-#include <string>
-#include <vector>
-
 #include "../../include/graph_witness_groth16_beacon.h"
 #include "../../include/graph_witness_groth16_contribute.h"
 #include "../../include/graph_witness_groth16_ptau.h"
 #include "../../include/graph_witness_groth16_setup.h"
+#include "cli_common.hpp"
 
-static bool read_file(const char* path, std::vector<char>& out) {
-    std::ifstream f(path, std::ios::binary);
-    if (!f) return false;
-    out.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-    return !f.bad();
-}
-
-// a file mapped read-only; size 0 maps nothing
-struct Mapped {
-    void* data = NULL;
-    size_t len = 0;
-    bool open(const char* path) {
-        const int fd = ::open(path, O_RDONLY);
-        if (fd < 0) return false;
-        struct stat st;
-        bool ok = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
-        if (ok && st.st_size > 0) {
-            void* p = mmap(NULL, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-            ok = p != MAP_FAILED;
-            if (ok) {
-                data = p;
-                len = (size_t)st.st_size;
-            }
-        }
-        close(fd);
-        return ok;
-    }
-    ~Mapped() {
-        if (data) munmap(data, len);
-    }
-};
-
-static bool write_file(const char* path, const void* data, size_t n) {
-    FILE* f = fopen(path, "wb");
-    if (!f) return false;
-    const bool ok = fwrite(data, 1, n, f) == n;
-    return fclose(f) == 0 && ok;
-}
-
-// a file with one decimal integer below 2^256 -> 32 little-endian bytes; the file's text is zeroed
-static bool parse_delta(const char* path, uint8_t* le) {
-    std::vector<char> text;
-    if (!read_file(path, text)) {
-        fprintf(stderr, "error: cannot read %s\n", path);
-        return false;
-    }
-    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    size_t digits = 0, tokens = 0;
-    bool ok = true, in_token = false;
-    for (char c : text) {
-        if (c == ' ' || c == '\n' || c == '\r' || c == '\t') {
-            in_token = false;
-            continue;
-        }
-        if (!in_token) ++tokens;
-        in_token = true;
-        if (c < '0' || c > '9') {
-            ok = false;
-            break;
-        }
-        ++digits;
-        uint64_t carry = (uint64_t)(c - '0');
-        for (int i = 0; i < 8; ++i) {
-            const uint64_t cur = (uint64_t)w[i] * 10 + carry;
-            w[i] = (uint32_t)cur;
-            carry = cur >> 32;
-        }
-        if (carry) ok = false;
-    }
-    std::fill(text.begin(), text.end(), 0);
-    if (!ok || digits == 0 || tokens != 1) {
-        fprintf(stderr, "error: %s: one decimal integer below 2^256 expected (delta)\n", path);
-        return false;
-    }
-    memcpy(le, w, 32);
-    return true;
-}
-
-static void print_hex(const uint8_t* p, size_t n) {
-    for (size_t i = 0; i < n; ++i) printf("%02x", p[i]);
-    printf("\n");
-}
+using cli::print_hex;
+using Image = cli::Owned<void, gwb_groth16_setup_free>;  // a key or a list made by the library
 
 static int usage() {
     fprintf(stderr,
@@ -131,15 +38,17 @@ static int usage() {
 }
 
 // the number of records of a key and the type of the last one (-1 without records), from the host-only reader; false with st set
-static bool record_count(const std::vector<char>& key, size_t& n, gw_status_t& st, int* last_type = NULL) {
-    void* image = NULL;
+static bool record_count(const std::vector<uint8_t>& key, size_t& n, gw_status_t& st, int* last_type = NULL) {
+    void* made = NULL;
     size_t image_len = 0;
-    if (gwb_zkey_contributions(key.data(), key.size(), &image, &image_len, &st) != 0) return false;
+    if (gwb_zkey_contributions(key.data(), key.size(), &made, &image_len, &st) != 0) return false;
+    const Image owner(made);
+    const uint8_t* image = (const uint8_t*)made;
     uint32_t count;
-    memcpy(&count, (const uint8_t*)image + GWB_CONTRIBUTION_HASH_BYTES, 4);
+    memcpy(&count, image + GWB_CONTRIBUTION_HASH_BYTES, 4);
     if (last_type) {
         *last_type = -1;
-        const uint8_t* p = (const uint8_t*)image + GWB_CONTRIBUTION_HASH_BYTES + 4;  // per record: 448 B, u32 type, u32 nameLen, name
+        const uint8_t* p = image + GWB_CONTRIBUTION_HASH_BYTES + 4;  // per record: 448 B, u32 type, u32 nameLen, name
         for (uint32_t k = 0; k < count; ++k) {
             uint32_t type, name_len;
             memcpy(&type, p + 448, 4);
@@ -148,7 +57,6 @@ static bool record_count(const std::vector<char>& key, size_t& n, gw_status_t& s
             p += 456 + name_len;
         }
     }
-    gwb_groth16_setup_free(image);
     n = count;
     return true;
 }
@@ -158,25 +66,7 @@ static int not_a_beacon() {
     return 1;
 }
 
-// an even number of hex digits, either case, no prefix, 1 to 255 bytes
-static bool parse_hex(const char* text, std::vector<uint8_t>& out) {
-    const size_t n = strlen(text);
-    if (n == 0 || n % 2 != 0 || n / 2 > GWB_BEACON_HASH_MAX) return false;
-    out.assign(n / 2, 0);
-    for (size_t i = 0; i < n; ++i) {
-        const char c = text[i];
-        const int v = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
-        if (v < 0) return false;
-        out[i / 2] = (uint8_t)(out[i / 2] << 4 | v);
-    }
-    return true;
-}
-
-static int report(int rc, gw_status_t& st) {
-    fprintf(stderr, "%s: %s\n", rc == 1 ? "INVALID" : "error", st.error_msg ? st.error_msg : "call failed");
-    free(st.error_msg);
-    return rc == 1 ? 1 : 2;
-}
+static int report(int rc, gw_status_t& st) { return cli::report(rc, st, "call failed"); }
 
 static int run_verify_key(const char* r1cs_path, const char* ptau_path, const char* key_path, const char* lagrange, bool skip_records, bool check_ptau,
                           bool check_lagrange, bool require_beacon) {
@@ -189,40 +79,27 @@ static int run_verify_key(const char* r1cs_path, const char* ptau_path, const ch
         else if (strcmp(lagrange, "compute") != 0)
             return usage();
     }
-    std::vector<char> circuit, key;
-    Mapped ptau;
-    const char* unread = !read_file(r1cs_path, circuit) ? r1cs_path : !ptau.open(ptau_path) ? ptau_path : !read_file(key_path, key) ? key_path : NULL;
-    if (unread) {
-        fprintf(stderr, "error: cannot read %s\n", unread);
-        return 2;
-    }
+    std::vector<uint8_t> circuit, key;
+    cli::Mapped ptau;
+    const char* unread = !cli::read_file(r1cs_path, circuit) ? r1cs_path : !ptau.open(ptau_path) ? ptau_path : !cli::read_file(key_path, key) ? key_path : NULL;
+    if (unread) return cli::cannot_read(unread);
     gw_status_t st{};
-    gwb_r1cs_t* r = NULL;
-    if (gwb_r1cs_load(circuit.data(), circuit.size(), &r, &st) != 0) {
-        fprintf(stderr, "error: %s: %s\n", r1cs_path, st.error_msg ? st.error_msg : "load failed");
-        free(st.error_msg);
-        return 2;
-    }
+    gwb_r1cs_t* loaded = NULL;
+    if (gwb_r1cs_load(circuit.data(), circuit.size(), &loaded, &st) != 0) return cli::fail(r1cs_path, st, "load failed");
+    const cli::Owned<gwb_r1cs_t, gwb_r1cs_free> r(loaded);
     size_t n = 0;
     int last_type = -1;
-    if (!record_count(key, n, st, &last_type)) {
-        gwb_r1cs_free(r);
-        return report(2, st);
-    }
+    if (!record_count(key, n, st, &last_type)) return report(2, st);
     if (check_lagrange && mode != GWB_PTAU_LAGRANGE_COMPUTE) {  // under auto, only a file that has the sections
         gwb_ptau_info_t pi;
         gwb_r1cs_qap_info_t qi;
-        int rc = gwb_ptau_info(ptau.data, ptau.len, &pi, &st) != 0 || gwb_r1cs_qap_info(r, &qi, &st) != 0 ? 2 : 0;
+        int rc = gwb_ptau_info(ptau.data, ptau.len, &pi, &st) != 0 || gwb_r1cs_qap_info(r.get(), &qi, &st) != 0 ? 2 : 0;
         if (rc == 0 && (mode == GWB_PTAU_LAGRANGE_FILE || pi.prepared)) rc = gwb_ptau_check_lagrange(ptau.data, ptau.len, qi.domain_power, NULL, &st);
-        if (rc != 0) {
-            gwb_r1cs_free(r);
-            return report(rc, st);
-        }
+        if (rc != 0) return report(rc, st);
     }
     std::vector<uint8_t> hashes(n * GWB_CONTRIBUTION_HASH_BYTES + 1);
     const uint32_t flags = (skip_records ? GWB_VERIFY_KEY_SKIP_RECORDS : 0u) | (check_ptau ? GWB_VERIFY_KEY_CHECK_PTAU : 0u);
-    const int rc = gwb_zkey_verify_key(key.data(), key.size(), r, ptau.data, ptau.len, mode, flags, NULL, hashes.data(), &n, &st);
-    gwb_r1cs_free(r);
+    const int rc = gwb_zkey_verify_key(key.data(), key.size(), r.get(), ptau.data, ptau.len, mode, flags, NULL, hashes.data(), &n, &st);
     if (rc != 0) return report(rc, st);
     if (require_beacon && last_type != 1) return not_a_beacon();
     printf("OK! %s is the key of %s and %s, %zu contributions%s\n", key_path, r1cs_path, ptau_path, n, skip_records ? " (not verified)" : "");
@@ -270,28 +147,20 @@ int main(int argc, char** argv) {
     if (paths.size() != (verify ? 1u : verify_key ? 3u : beacon ? 4u : 2u)) return usage();
     if (verify_key) return run_verify_key(paths[0], paths[1], paths[2], lagrange, skip_records, check_ptau, check_lagrange, require_beacon);
     std::vector<uint8_t> beacon_hash;
-    unsigned long beacon_exp = 0;
+    uint32_t beacon_exp = 0;
     if (beacon) {  // the arguments before the key is read
-        if (!parse_hex(paths[2], beacon_hash)) {
+        if (!cli::parse_hex(paths[2], GWB_BEACON_HASH_MAX, beacon_hash)) {
             fprintf(stderr, "error: beaconHash: an even number of hex digits for 1 to 255 bytes expected, without a prefix\n");
             return 2;
         }
-        char* end = NULL;
-        beacon_exp = strtoul(paths[3], &end, 10);
-        if (!*paths[3] || *end || beacon_exp > 0xfffffffful) {
+        if (!cli::parse_u32(paths[3], 0xffffffffu, beacon_exp)) {
             fprintf(stderr, "error: numIterationsExp: a decimal number expected\n");
             return 2;
         }
     }
-    std::vector<char> first, second;
-    if (!read_file(paths[0], first)) {
-        fprintf(stderr, "error: cannot read %s\n", paths[0]);
-        return 2;
-    }
-    if (step && !read_file(paths[1], second)) {
-        fprintf(stderr, "error: cannot read %s\n", paths[1]);
-        return 2;
-    }
+    std::vector<uint8_t> first, second;
+    if (!cli::read_file(paths[0], first)) return cli::cannot_read(paths[0]);
+    if (step && !cli::read_file(paths[1], second)) return cli::cannot_read(paths[1]);
     gw_status_t st{};
     if (verify) {
         size_t n = 0;
@@ -311,8 +180,13 @@ int main(int argc, char** argv) {
         printf("OK! %s is %s after one contribution\n", paths[1], paths[0]);
         return 0;
     }
-    uint8_t delta[32];
-    if (delta_path && !parse_delta(delta_path, delta)) return 2;
+    uint8_t delta[1][32];
+    cli::Secrets found;
+    if (delta_path && !cli::parse_secret_decimals(delta_path, 1, delta, found)) {
+        if (!found.readable) return cli::cannot_read(delta_path);
+        fprintf(stderr, "error: %s: one decimal integer below 2^256 expected (delta)\n", delta_path);
+        return 2;
+    }
     if (strlen(name) > GWB_CONTRIBUTION_NAME_MAX) {
         fprintf(stderr, "error: the name has more than 255 bytes\n");
         return 2;
@@ -320,16 +194,12 @@ int main(int argc, char** argv) {
     void* out = NULL;
     size_t out_len = 0;
     uint8_t hash[GWB_CONTRIBUTION_HASH_BYTES];
-    const int rc = beacon ? gwb_groth16_beacon(first.data(), first.size(), name, beacon_hash.data(), beacon_hash.size(), (uint32_t)beacon_exp, &out, &out_len, hash, &st)
-                          : gwb_groth16_contribute(first.data(), first.size(), name, delta_path ? delta : NULL, &out, &out_len, hash, &st);
-    memset(delta, 0, sizeof delta);
+    const int rc = beacon ? gwb_groth16_beacon(first.data(), first.size(), name, beacon_hash.data(), beacon_hash.size(), beacon_exp, &out, &out_len, hash, &st)
+                          : gwb_groth16_contribute(first.data(), first.size(), name, delta_path ? delta[0] : NULL, &out, &out_len, hash, &st);
+    explicit_bzero(delta, sizeof delta);
     if (rc != 0) return report(2, st);
-    const bool ok = write_file(paths[1], out, out_len);
-    gwb_groth16_setup_free(out);
-    if (!ok) {
-        fprintf(stderr, "error: cannot write %s\n", paths[1]);
-        return 2;
-    }
+    const Image image(out);
+    if (!cli::write_file(paths[1], out, out_len)) return cli::cannot_write(paths[1]);
     print_hex(hash, sizeof hash);
     return 0;
 }

@@ -7,49 +7,15 @@
 // device is touched.  --compressed as the first argument writes the proof as the 128 raw bytes of arkworks' compressed form
 // (include/graph_witness_groth16_compressed.h) in place of proof.json; public.json is unchanged.  (One proof's encoding is
 // three comparisons: it is done here, with the host side of point_codec_gfx950.hpp.)
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <fstream>
-#include <iterator>
-#include <string>
-#include <vector>
-
 #include "../../include/graph_witness_groth16.h"
+#include "cli_common.hpp"
 #include "point_codec_gfx950.hpp"
 
-static bool read_file(const char* path, std::vector<char>& out) {
-    std::ifstream f(path, std::ios::binary);
-    if (!f) return false;
-    out.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-    return !f.bad();
-}
-
-// 32-byte little-endian integer -> decimal string
-static std::string decimal(const uint8_t* le) {
-    uint32_t w[8];
-    memcpy(w, le, 32);
-    std::string out;
-    for (;;) {
-        bool zero = true;
-        uint64_t rem = 0;
-        for (int i = 7; i >= 0; --i) {
-            const uint64_t cur = (rem << 32) | w[i];
-            w[i] = (uint32_t)(cur / 1000000000u);
-            rem = cur % 1000000000u;
-            zero = zero && w[i] == 0;
-        }
-        char buf[16];
-        snprintf(buf, sizeof buf, zero ? "%llu" : "%09llu", (unsigned long long)rem);
-        out = buf + out;
-        if (zero) return out;
-    }
-}
+using cli::decimal;
 
 // the witness values of a `.wtns` image the library has already validated (section 2)
-static const uint8_t* wtns_values(const std::vector<char>& w) {
-    const uint8_t* p = (const uint8_t*)w.data();
+static const uint8_t* wtns_values(const std::vector<uint8_t>& w) {
+    const uint8_t* p = w.data();
     uint32_t nsec;
     memcpy(&nsec, p + 8, 4);
     size_t off = 12;
@@ -63,13 +29,6 @@ static const uint8_t* wtns_values(const std::vector<char>& w) {
         off += size;
     }
     return nullptr;
-}
-
-static bool write_text(const char* path, const std::string& s) {
-    FILE* f = fopen(path, "wb");
-    if (!f) return false;
-    const bool ok = fwrite(s.data(), 1, s.size(), f) == s.size();
-    return fclose(f) == 0 && ok;
 }
 
 int main(int argc, char** argv) {
@@ -96,51 +55,27 @@ int main(int argc, char** argv) {
     const bool with_r1cs = pos.size() == 5;
     char** in = pos.data();  // inputs: [r1cs,] zkey, wtns; then the two outputs
     const int n_in = with_r1cs ? 3 : 2;
-    std::vector<char> loaded[3];
-    for (int i = 0; i < n_in; ++i) {
-        if (!read_file(in[i], loaded[i])) {
-            fprintf(stderr, "error: cannot read %s\n", in[i]);
-            return 2;
-        }
-    }
-    const std::vector<char>& zkey_file = loaded[n_in - 2];
-    const std::vector<char>& wtns_file = loaded[n_in - 1];
+    std::vector<uint8_t> loaded[3];
+    for (int i = 0; i < n_in; ++i)
+        if (!cli::read_file(in[i], loaded[i])) return cli::cannot_read(in[i]);
+    const std::vector<uint8_t>& zkey_file = loaded[n_in - 2];
+    const std::vector<uint8_t>& wtns_file = loaded[n_in - 1];
     gw_status_t st = {OK, NULL};
-    gwb_r1cs_t* r = NULL;
-    gwb_zkey_t* z = NULL;
-    if (with_r1cs && gwb_r1cs_load(loaded[0].data(), loaded[0].size(), &r, &st) != 0) {
-        fprintf(stderr, "error: %s: %s\n", in[0], st.error_msg ? st.error_msg : "load failed");
-        gw_free_status(&st);
-        return 2;
-    }
-    if (gwb_zkey_load(zkey_file.data(), zkey_file.size(), &z, &st) != 0) {
-        fprintf(stderr, "error: %s: %s\n", in[n_in - 2], st.error_msg ? st.error_msg : "load failed");
-        gw_free_status(&st);
-        gwb_r1cs_free(r);
-        return 2;
-    }
+    gwb_r1cs_t* r_loaded = NULL;
+    gwb_zkey_t* z_loaded = NULL;
+    if (with_r1cs && gwb_r1cs_load(loaded[0].data(), loaded[0].size(), &r_loaded, &st) != 0) return cli::fail(in[0], st, "load failed");
+    const cli::Owned<gwb_r1cs_t, gwb_r1cs_free> r(r_loaded);
+    if (gwb_zkey_load(zkey_file.data(), zkey_file.size(), &z_loaded, &st) != 0) return cli::fail(in[n_in - 2], st, "load failed");
+    const cli::Owned<gwb_zkey_t, gwb_zkey_free> z(z_loaded);
     if (check_g2) {  // the witness is parsed first, so that the subgroup check is not the first to find a broken image
-        const bool parsed = gwb_zkey_check_wtns(z, wtns_file.data(), wtns_file.size(), &st) == 0;
-        if (!parsed || gwb_zkey_check_g2(z, &st) != 0) {
-            fprintf(stderr, "error: %s: %s\n", in[parsed ? n_in - 2 : n_in - 1], st.error_msg ? st.error_msg : "check failed");
-            gw_free_status(&st);
-            gwb_zkey_free(z);
-            gwb_r1cs_free(r);
-            return 2;
-        }
+        const bool parsed = gwb_zkey_check_wtns(z.get(), wtns_file.data(), wtns_file.size(), &st) == 0;
+        if (!parsed || gwb_zkey_check_g2(z.get(), &st) != 0) return cli::fail(in[parsed ? n_in - 2 : n_in - 1], st, "check failed");
     }
     uint8_t proof[GWB_GROTH16_PROOF_BYTES];
     // (the call parses the .wtns image and, without an .r1cs, builds the map of section 4 before it reaches the device)
-    const int rc = gwb_groth16_prove_wtns(z, r, wtns_file.data(), wtns_file.size(), NULL, proof, &st);
+    if (gwb_groth16_prove_wtns(z.get(), r.get(), wtns_file.data(), wtns_file.size(), NULL, proof, &st) != 0) return cli::fail(in[n_in - 1], st, "prove failed");
     gwb_zkey_info_t zi;
-    gwb_zkey_info(z, &zi);
-    gwb_zkey_free(z);
-    gwb_r1cs_free(r);
-    if (rc != 0) {
-        fprintf(stderr, "error: %s: %s\n", in[n_in - 1], st.error_msg ? st.error_msg : "prove failed");
-        gw_free_status(&st);
-        return 2;
-    }
+    gwb_zkey_info(z.get(), &zi);
     auto d = [&](int k) { return "\"" + decimal(proof + 32 * k) + "\""; };
     // snarkjs writes projective coordinates with z = 1 (or 0 for the point at infinity)
     auto z1 = [&](int k, int words) {
@@ -162,7 +97,7 @@ int main(int argc, char** argv) {
     std::string pub = "[";
     for (uint32_t i = 1; i <= zi.n_public; ++i) pub += std::string(i > 1 ? ",\n " : "\n ") + "\"" + decimal(w + 32 * (size_t)i) + "\"";
     pub += zi.n_public ? "\n]\n" : "]\n";
-    if (!write_text(in[n_in], pj) || !write_text(in[n_in + 1], pub)) {
+    if (!cli::write_file(in[n_in], pj.data(), pj.size()) || !cli::write_file(in[n_in + 1], pub.data(), pub.size())) {
         fprintf(stderr, "error: cannot write %s / %s\n", in[n_in], in[n_in + 1]);
         return 2;
     }

@@ -17,154 +17,30 @@
 // --ptau and --trapdoor exclude each other.  With a third path the verifying key is written too, in snarkjs's
 // verification_key.json shape with vk_alphabeta_12.  Exit status 0 on success; 2 on a usage, file or format error.  Every
 // input is parsed before the device is touched.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
-#include <algorithm>
-#include <fstream>
-#include <iterator>
-#include <string>
-#include <vector>
-
 #include "../../include/graph_witness_groth16_compressed.h"
 #include "../../include/graph_witness_groth16_ptau.h"
 #include "../../include/graph_witness_groth16_setup.h"
 #include "../../include/graph_witness_groth16_verify.h"
+#include "cli_common.hpp"
 
-static bool read_file(const char* path, std::vector<char>& out) {
-    std::ifstream f(path, std::ios::binary);
-    if (!f) return false;
-    out.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-    return !f.bad();
+using cli::decimal;
+using R1cs = cli::Owned<gwb_r1cs_t, gwb_r1cs_free>;
+using Zkey = cli::Owned<gwb_zkey_t, gwb_zkey_free>;
+using Vk = cli::Owned<gwb_g16vk_t, gwb_g16vk_free>;
+using Image = cli::Owned<void, gwb_groth16_setup_free>;  // a key or a file made by the library
+
+// a file of `n` secrets, named in `names`, into le; false with the message printed: a wrong count before a bad value
+static bool parse_secrets(const char* path, size_t n, const char* const* names, const char* all_names, uint8_t (*le)[32]) {
+    cli::Secrets found;
+    if (cli::parse_secret_decimals(path, n, le, found)) return true;
+    if (!found.readable)
+        cli::cannot_read(path);
+    else if (found.tokens != n)
+        fprintf(stderr, "error: %s: %zu values, %zu expected (%s)\n", path, found.tokens, n, all_names);
+    else
+        fprintf(stderr, "error: %s: %s is not a decimal integer below 2^256\n", path, names[found.bad]);
+    return false;
 }
-
-static bool write_file(const char* path, const void* data, size_t n) {
-    FILE* f = fopen(path, "wb");
-    if (!f) return false;
-    const bool ok = fwrite(data, 1, n, f) == n;
-    return fclose(f) == 0 && ok;
-}
-
-// 32-byte little-endian integer -> decimal string
-static std::string decimal(const uint8_t* le) {
-    uint32_t w[8];
-    memcpy(w, le, 32);
-    std::string out;
-    for (;;) {
-        bool zero = true;
-        uint64_t rem = 0;
-        for (int i = 7; i >= 0; --i) {
-            const uint64_t cur = (rem << 32) | w[i];
-            w[i] = (uint32_t)(cur / 1000000000u);
-            rem = cur % 1000000000u;
-            zero = zero && w[i] == 0;
-        }
-        char buf[16];
-        snprintf(buf, sizeof buf, zero ? "%llu" : "%09llu", (unsigned long long)rem);
-        out = buf + out;
-        if (zero) return out;
-    }
-}
-
-// decimal digits -> 32-byte little-endian integer; false for another character, no digit, or a value of 2^256 or more
-static bool parse_decimal(const std::string& tok, uint8_t* le) {
-    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (tok.empty()) return false;
-    for (char c : tok) {
-        if (c < '0' || c > '9') return false;
-        uint64_t carry = (uint64_t)(c - '0');
-        for (int i = 0; i < 8; ++i) {
-            const uint64_t cur = (uint64_t)w[i] * 10 + carry;
-            w[i] = (uint32_t)cur;
-            carry = cur >> 32;
-        }
-        if (carry) return false;
-    }
-    memcpy(le, w, 32);
-    return true;
-}
-
-// the whitespace-separated tokens of a file of secrets; the file's text is zeroed
-static bool read_tokens(const char* path, std::vector<std::string>& toks) {
-    std::vector<char> text;
-    if (!read_file(path, text)) {
-        fprintf(stderr, "error: cannot read %s\n", path);
-        return false;
-    }
-    std::string cur;
-    for (char c : text) {
-        if (c == ' ' || c == '\n' || c == '\r' || c == '\t') {
-            if (!cur.empty()) toks.push_back(cur);
-            cur.clear();
-        } else {
-            cur += c;
-        }
-    }
-    if (!cur.empty()) toks.push_back(cur);
-    std::fill(text.begin(), text.end(), 0);
-    return true;
-}
-
-static bool parse_trapdoor(const char* path, gwb_groth16_trapdoor_t* t) {
-    std::vector<std::string> toks;
-    if (!read_tokens(path, toks)) return false;
-    if (toks.size() != 5) {
-        fprintf(stderr, "error: %s: %zu values, 5 expected (tau alpha beta gamma delta)\n", path, toks.size());
-        return false;
-    }
-    static const char* names[5] = {"tau", "alpha", "beta", "gamma", "delta"};
-    uint8_t* dst[5] = {t->tau, t->alpha, t->beta, t->gamma, t->delta};
-    for (int i = 0; i < 5; ++i)
-        if (!parse_decimal(toks[i], dst[i])) {
-            fprintf(stderr, "error: %s: %s is not a decimal integer below 2^256\n", path, names[i]);
-            return false;
-        }
-    return true;
-}
-
-static bool parse_delta(const char* path, uint8_t* delta) {
-    std::vector<std::string> toks;
-    if (!read_tokens(path, toks)) return false;
-    if (toks.size() != 1) {
-        fprintf(stderr, "error: %s: %zu values, 1 expected (delta)\n", path, toks.size());
-        return false;
-    }
-    if (!parse_decimal(toks[0], delta)) {
-        fprintf(stderr, "error: %s: delta is not a decimal integer below 2^256\n", path);
-        return false;
-    }
-    return true;
-}
-
-// a file mapped read-only; size 0 maps nothing
-struct Mapped {
-    void* data = NULL;
-    size_t len = 0;
-    bool open(const char* path) {
-        const int fd = ::open(path, O_RDONLY);
-        if (fd < 0) return false;
-        struct stat st;
-        bool ok = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
-        if (ok && st.st_size > 0) {
-            void* p = mmap(NULL, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-            ok = p != MAP_FAILED;
-            if (ok) {
-                data = p;
-                len = (size_t)st.st_size;
-            }
-        }
-        close(fd);
-        return ok;
-    }
-    ~Mapped() {
-        if (data) munmap(data, len);
-    }
-};
 
 static std::string g1_json(const uint8_t* p) {
     bool inf = true;
@@ -183,23 +59,22 @@ static std::string g2_json(const uint8_t* p) {
 // the verifying key of the written zkey as snarkjs's verification_key.json
 static bool vk_json(const void* zkey, size_t len, std::string& out, std::string& err) {
     gw_status_t st = {OK, NULL};
-    gwb_zkey_t* z = NULL;
-    gwb_g16vk_t* vk = NULL;
     auto failed = [&](const char* what) {
-        err = st.error_msg ? st.error_msg : what;
-        gw_free_status(&st);
-        if (vk) gwb_g16vk_free(vk);
-        if (z) gwb_zkey_free(z);
+        err = cli::take_message(st, what);
         return false;
     };
-    if (gwb_zkey_load(zkey, len, &z, &st) != 0) return failed("loading the written key failed");
-    if (gwb_g16vk_from_zkey(z, &vk, &st) != 0) return failed("extracting the verifying key failed");
+    gwb_zkey_t* z_loaded = NULL;
+    if (gwb_zkey_load(zkey, len, &z_loaded, &st) != 0) return failed("loading the written key failed");
+    const Zkey z(z_loaded);
+    gwb_g16vk_t* vk_made = NULL;
+    if (gwb_g16vk_from_zkey(z.get(), &vk_made, &st) != 0) return failed("extracting the verifying key failed");
+    const Vk vk(vk_made);
     gwb_g16vk_info_t info;
-    gwb_g16vk_info(vk, &info);
+    gwb_g16vk_info(vk.get(), &info);
     std::vector<uint8_t> pts(448 + 64 * ((size_t)info.n_public + 1));
     uint8_t gt[GWB_GT_BYTES];
-    if (gwb_g16vk_points(vk, pts.data(), pts.size()) != 0) return failed("reading the verifying key's points failed");
-    if (gwb_g16vk_alphabeta(vk, gt, &st) != 0) return failed("computing e(alpha1, beta2) failed");
+    if (gwb_g16vk_points(vk.get(), pts.data(), pts.size()) != 0) return failed("reading the verifying key's points failed");
+    if (gwb_g16vk_alphabeta(vk.get(), gt, &st) != 0) return failed("computing e(alpha1, beta2) failed");
     out = "{\n \"protocol\": \"groth16\",\n \"curve\": \"bn128\",\n \"nPublic\": " + std::to_string(info.n_public) + ",\n";
     out += " \"vk_alpha_1\": " + g1_json(pts.data()) + ",\n";
     out += " \"vk_beta_2\": " + g2_json(pts.data() + 64) + ",\n";
@@ -215,8 +90,6 @@ static bool vk_json(const void* zkey, size_t len, std::string& out, std::string&
     out += "],\n \"IC\": [";
     for (uint32_t i = 0; i <= info.n_public; ++i) out += std::string(i ? ",\n  " : "\n  ") + g1_json(pts.data() + 448 + 64 * (size_t)i);
     out += "\n ]\n}\n";
-    gwb_g16vk_free(vk);
-    gwb_zkey_free(z);
     return true;
 }
 
@@ -243,27 +116,20 @@ static int ptau_tool(int argc, char** argv) {
     uint32_t domain_power = GWB_PTAU_ALL_LEVELS;
     int at = 2;
     if (!prepare && argc > at + 1 && strcmp(argv[at], "--domain-power") == 0) {
-        char* end = NULL;
-        const unsigned long v = strtoul(argv[at + 1], &end, 10);
-        if (!*argv[at + 1] || *end || v > 28) return usage_error(argv[0]);
-        domain_power = (uint32_t)v;
+        if (!cli::parse_u32(argv[at + 1], 28, domain_power)) return usage_error(argv[0]);
         at += 2;
     }
     if (argc - at != (prepare ? 2 : 1)) return usage_error(argv[0]);
     for (int i = at; i < argc; ++i)
         if (strncmp(argv[i], "--", 2) == 0) return usage_error(argv[0]);
     const char* path = argv[at];
-    Mapped in;
-    if (!in.open(path)) {
-        fprintf(stderr, "error: cannot read %s\n", path);
-        return 2;
-    }
+    cli::Mapped in;
+    if (!in.open(path)) return cli::cannot_read(path);
     gw_status_t st = {OK, NULL};  // both calls parse the file before they touch the device
     if (!prepare) {
         const int rc = gwb_ptau_check_lagrange(in.data, in.len, domain_power, NULL, &st);
         if (rc != 0) {
-            fprintf(stderr, "error: %s: %s\n", path, st.error_msg ? st.error_msg : "check failed");
-            gw_free_status(&st);
+            cli::fail(path, st, "check failed");
             return rc == 1 ? 1 : 2;
         }
         printf("OK!\n");
@@ -271,50 +137,29 @@ static int ptau_tool(int argc, char** argv) {
     }
     void* out = NULL;
     size_t len = 0;
-    if (gwb_ptau_prepare_phase2(in.data, in.len, &out, &len, &st) != 0) {
-        fprintf(stderr, "error: %s: %s\n", path, st.error_msg ? st.error_msg : "prepare failed");
-        gw_free_status(&st);
-        return 2;
-    }
-    int code = 0;
-    if (!write_file(argv[at + 1], out, len)) {
-        fprintf(stderr, "error: cannot write %s\n", argv[at + 1]);
-        code = 2;
-    }
-    gwb_groth16_setup_free(out);
-    return code;
+    if (gwb_ptau_prepare_phase2(in.data, in.len, &out, &len, &st) != 0) return cli::fail(path, st, "prepare failed");
+    const Image image(out);
+    return cli::write_file(argv[at + 1], out, len) ? 0 : cli::cannot_write(argv[at + 1]);
 }
 
 // --export-vk --compressed: the same key as arkworks' compressed bytes (include/graph_witness_groth16_compressed.h)
 static int export_vk_compressed(char** argv) {
-    std::vector<char> key;
-    if (!read_file(argv[3], key)) {
-        fprintf(stderr, "error: cannot read %s\n", argv[3]);
-        return 2;
-    }
+    std::vector<uint8_t> key, out;
+    if (!cli::read_file(argv[3], key)) return cli::cannot_read(argv[3]);
     gw_status_t st = {OK, NULL};
-    gwb_zkey_t* z = NULL;
-    gwb_g16vk_t* vk = NULL;
-    std::vector<uint8_t> out;
-    bool ok = gwb_zkey_load(key.data(), key.size(), &z, &st) == 0 && gwb_g16vk_from_zkey(z, &vk, &st) == 0;
+    gwb_zkey_t* z_loaded = NULL;
+    gwb_g16vk_t* vk_made = NULL;
+    bool ok = gwb_zkey_load(key.data(), key.size(), &z_loaded, &st) == 0 && gwb_g16vk_from_zkey(z_loaded, &vk_made, &st) == 0;
+    const Zkey z(z_loaded);
+    const Vk vk(vk_made);
     if (ok) {
         gwb_g16vk_info_t info;
-        gwb_g16vk_info(vk, &info);
+        gwb_g16vk_info(vk.get(), &info);
         out.resize(GWB_G16VK_COMPRESSED_BYTES(info.n_public));
-        ok = gwb_g16vk_compressed(vk, out.data(), out.size()) == 0;
+        ok = gwb_g16vk_compressed(vk.get(), out.data(), out.size()) == 0;
     }
-    if (vk) gwb_g16vk_free(vk);
-    if (z) gwb_zkey_free(z);
-    if (!ok) {
-        fprintf(stderr, "error: %s: %s\n", argv[3], st.error_msg ? st.error_msg : "compressing the verifying key failed");
-        gw_free_status(&st);
-        return 2;
-    }
-    if (!write_file(argv[4], out.data(), out.size())) {
-        fprintf(stderr, "error: cannot write %s\n", argv[4]);
-        return 2;
-    }
-    return 0;
+    if (!ok) return cli::fail(argv[3], st, "compressing the verifying key failed");
+    return cli::write_file(argv[4], out.data(), out.size()) ? 0 : cli::cannot_write(argv[4]);
 }
 
 // --export-vk: the verifying key of any zkey, a finished ceremony's among them, as verification_key.json
@@ -322,21 +167,14 @@ static int export_vk(int argc, char** argv) {
     if (argc == 5 && strcmp(argv[2], "--compressed") == 0 && strncmp(argv[3], "--", 2) != 0 && strncmp(argv[4], "--", 2) != 0)
         return export_vk_compressed(argv);
     if (argc != 4 || strncmp(argv[2], "--", 2) == 0 || strncmp(argv[3], "--", 2) == 0) return usage_error(argv[0]);
-    std::vector<char> key;
-    if (!read_file(argv[2], key)) {
-        fprintf(stderr, "error: cannot read %s\n", argv[2]);
-        return 2;
-    }
+    std::vector<uint8_t> key;
+    if (!cli::read_file(argv[2], key)) return cli::cannot_read(argv[2]);
     std::string json, err;
     if (!vk_json(key.data(), key.size(), json, err)) {
         fprintf(stderr, "error: %s: %s\n", argv[2], err.c_str());
         return 2;
     }
-    if (!write_file(argv[3], json.data(), json.size())) {
-        fprintf(stderr, "error: cannot write %s\n", argv[3]);
-        return 2;
-    }
-    return 0;
+    return cli::write_file(argv[3], json.data(), json.size()) ? 0 : cli::cannot_write(argv[3]);
 }
 
 int main(int argc, char** argv) {
@@ -375,90 +213,56 @@ int main(int argc, char** argv) {
     // --ptau and --trapdoor exclude each other; --delta, --lagrange and --check-g2 belong to --ptau
     if ((ptau_path && trapdoor_path) || (!ptau_path && (delta_path || lagrange || check_g2))) usage = true;
     if (usage || (pos.size() != 2 && pos.size() != 3)) return usage_error(argv[0]);
-    std::vector<char> file;
-    if (!read_file(pos[0], file)) {
-        fprintf(stderr, "error: cannot read %s\n", pos[0]);
-        return 2;
-    }
+    std::vector<uint8_t> file;
+    if (!cli::read_file(pos[0], file)) return cli::cannot_read(pos[0]);
     gw_status_t st = {OK, NULL};
-    gwb_r1cs_t* r = NULL;
-    if (gwb_r1cs_load(file.data(), file.size(), &r, &st) != 0) {
-        fprintf(stderr, "error: %s: %s\n", pos[0], st.error_msg ? st.error_msg : "load failed");
-        gw_free_status(&st);
-        return 2;
-    }
-    gwb_groth16_trapdoor_t t;
-    if (trapdoor_path && !parse_trapdoor(trapdoor_path, &t)) {
-        gwb_r1cs_free(r);
-        return 2;
-    }
-    Mapped ptau;
-    uint8_t delta[32];
+    gwb_r1cs_t* loaded = NULL;
+    if (gwb_r1cs_load(file.data(), file.size(), &loaded, &st) != 0) return cli::fail(pos[0], st, "load failed");
+    const R1cs r(loaded);
+    static const char* const names[5] = {"tau", "alpha", "beta", "gamma", "delta"};
+    uint8_t secrets[5][32] = {};  // the trapdoor, or delta in secrets[0]
+    if (trapdoor_path && !parse_secrets(trapdoor_path, 5, names, "tau alpha beta gamma delta", secrets)) return 2;
+    cli::Mapped ptau;
     if (ptau_path) {
-        if (!ptau.open(ptau_path)) {
-            fprintf(stderr, "error: cannot read %s\n", ptau_path);
-            gwb_r1cs_free(r);
-            return 2;
-        }
+        if (!ptau.open(ptau_path)) return cli::cannot_read(ptau_path);
         gwb_ptau_info_t pi;
-        if (gwb_ptau_info(ptau.data, ptau.len, &pi, &st) != 0) {
-            fprintf(stderr, "error: %s: %s\n", ptau_path, st.error_msg ? st.error_msg : "load failed");
-            gw_free_status(&st);
-            gwb_r1cs_free(r);
-            return 2;
-        }
-        if (delta_path && !parse_delta(delta_path, delta)) {
-            gwb_r1cs_free(r);
-            return 2;
-        }
-    }
-    if (check_g2) {
-        gwb_r1cs_qap_info_t qi;
-        if (gwb_r1cs_qap_info(r, &qi, &st) != 0 || gwb_ptau_check_g2(ptau.data, ptau.len, qi.domain_power, mode, &st) != 0) {
-            fprintf(stderr, "error: %s: %s\n", ptau_path, st.error_msg ? st.error_msg : "check failed");
-            gw_free_status(&st);
-            explicit_bzero(delta, sizeof delta);
-            gwb_r1cs_free(r);
-            return 2;
-        }
+        if (gwb_ptau_info(ptau.data, ptau.len, &pi, &st) != 0) return cli::fail(ptau_path, st, "load failed");
+        if (delta_path && !parse_secrets(delta_path, 1, names + 4, "delta", secrets)) return 2;
     }
     void* zkey = NULL;
     size_t len = 0;
-    int rc;
-    if (ptau_path) {
+    int rc = 0;
+    if (check_g2) {
+        gwb_r1cs_qap_info_t qi;
+        if (gwb_r1cs_qap_info(r.get(), &qi, &st) != 0 || gwb_ptau_check_g2(ptau.data, ptau.len, qi.domain_power, mode, &st) != 0)
+            rc = cli::fail(ptau_path, st, "check failed");
+    }
+    if (rc == 0 && ptau_path) {
         fprintf(stderr,
                 "groth16-setup: tau, alpha and beta are those of the ceremony behind %s, which is not verified here; single-party phase 2: "
                 "whoever holds delta can forge proofs for this key; %s\n",
                 ptau_path, delta_path ? "it was read from a file, which remains" : "a drawn delta is discarded before the key is written");
-        rc = gwb_groth16_setup_ptau(r, ptau.data, ptau.len, delta_path ? delta : NULL, mode, &zkey, &len, &st);
-        explicit_bzero(delta, sizeof delta);
-    } else {
+        if (gwb_groth16_setup_ptau(r.get(), ptau.data, ptau.len, delta_path ? secrets[0] : NULL, mode, &zkey, &len, &st) != 0) rc = cli::report(2, st, "setup failed");
+    } else if (rc == 0) {
         fprintf(stderr, "groth16-setup: single-party setup: whoever holds the trapdoor can forge proofs for this key; %s\n",
                 trapdoor_path ? "it was read from a file, which remains" : "a drawn trapdoor is discarded before the key is written");
-        rc = gwb_groth16_setup(r, trapdoor_path ? &t : NULL, &zkey, &len, &st);
+        gwb_groth16_trapdoor_t t;
+        static_assert(sizeof t == sizeof secrets, "the trapdoor is its five values in the order of the file");
+        memcpy(&t, secrets, sizeof t);
+        if (gwb_groth16_setup(r.get(), trapdoor_path ? &t : NULL, &zkey, &len, &st) != 0) rc = cli::report(2, st, "setup failed");
+        explicit_bzero(&t, sizeof t);
     }
-    explicit_bzero(&t, sizeof t);
-    gwb_r1cs_free(r);
-    if (rc != 0) {
-        fprintf(stderr, "error: %s\n", st.error_msg ? st.error_msg : "setup failed");
-        gw_free_status(&st);
-        return 2;
-    }
-    int code = 0;
-    if (!write_file(pos[1], zkey, len)) {
-        fprintf(stderr, "error: cannot write %s\n", pos[1]);
-        code = 2;
-    }
-    if (code == 0 && pos.size() == 3) {
+    explicit_bzero(secrets, sizeof secrets);
+    if (rc != 0) return rc;
+    const Image image(zkey);
+    if (!cli::write_file(pos[1], zkey, len)) return cli::cannot_write(pos[1]);
+    if (pos.size() == 3) {
         std::string json, err;
         if (!vk_json(zkey, len, json, err)) {
             fprintf(stderr, "error: %s\n", err.c_str());
-            code = 2;
-        } else if (!write_file(pos[2], json.data(), json.size())) {
-            fprintf(stderr, "error: cannot write %s\n", pos[2]);
-            code = 2;
+            return 2;
         }
+        if (!cli::write_file(pos[2], json.data(), json.size())) return cli::cannot_write(pos[2]);
     }
-    gwb_groth16_setup_free(zkey);
-    return code;
+    return 0;
 }

@@ -13,20 +13,15 @@
 // compressed bytes (include/graph_witness_groth16_compressed.h: 232 + 32 (nPublic + 1) and 128 bytes); public.json is the same.
 // A proof file of another size, or a key that strict decoding refuses, is exit status 2; a proof whose encoding is refused is
 // INVALID: POINT.
-#include <stdio.h>
-#include <string.h>
-
-#include <fstream>
-#include <iterator>
 #include <map>
-#include <memory>
-#include <string>
-#include <vector>
 
 #include "../../include/graph_witness_groth16_compressed.h"
 #include "../../include/graph_witness_groth16_verify.h"
+#include "cli_common.hpp"
 
 namespace {
+
+using Vk = cli::Owned<gwb_g16vk_t, gwb_g16vk_free>;
 
 struct Bad {
     std::string msg;
@@ -133,19 +128,10 @@ struct Parser {
 // decimal string (or JSON integer) -> 32 bytes little-endian
 void put_int(const J& v, const std::string& what, std::vector<uint8_t>& out) {
     if ((v.kind != 's' && v.kind != 'n') || v.text.empty() || v.text.size() > 80) throw Bad{what + ": not a decimal integer"};
-    uint32_t w[8] = {};
-    for (char ch : v.text) {
-        if (ch < '0' || ch > '9') throw Bad{what + ": not a decimal integer"};
-        uint64_t carry = (uint64_t)(ch - '0');
-        for (int k = 0; k < 8; ++k) {
-            const uint64_t t = (uint64_t)w[k] * 10 + carry;
-            w[k] = (uint32_t)t;
-            carry = t >> 32;
-        }
-        if (carry) throw Bad{what + ": above 2^256"};
-    }
-    const uint8_t* b = (const uint8_t*)w;
-    out.insert(out.end(), b, b + 32);
+    uint8_t le[32];
+    const cli::Decimal d = cli::parse_decimal(v.text.data(), v.text.size(), le);
+    if (d != cli::Decimal::ok) throw Bad{what + (d == cli::Decimal::too_large ? ": above 2^256" : ": not a decimal integer")};
+    out.insert(out.end(), le, le + 32);
 }
 
 const J& member(const J& o, const char* name, const std::string& what) {
@@ -189,9 +175,9 @@ void put_g2(const J& p, const std::string& what, std::vector<uint8_t>& out) {
 }
 
 J read_json(const char* path) {
-    std::ifstream f(path, std::ios::binary);
-    if (!f) throw Bad{std::string("cannot read ") + path};
-    const std::string text((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    std::vector<uint8_t> bytes;
+    if (!cli::read_file(path, bytes)) throw Bad{std::string("cannot read ") + path};
+    const std::string text(bytes.begin(), bytes.end());
     try {
         Parser p{text};
         return p.parse();
@@ -210,34 +196,32 @@ const char* status_name(uint32_t s) {
     }
 }
 
-bool read_bytes(const char* path, std::vector<uint8_t>& out) {
-    std::ifstream f(path, std::ios::binary);
-    if (!f) return false;
-    out.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-    return !f.bad();
+// "OK!", or the verdict and exit status 1; a failed call is exit status 2
+int verdict(int rc, uint32_t status, gw_status_t& st, const char* point_refused) {
+    if (rc != 0) return cli::report(2, st, "verify failed");
+    if (status == GWB_G16V_VALID) {
+        printf("OK!\n");
+        return 0;
+    }
+    printf("INVALID: %s\n", status == GWB_G16V_POINT && point_refused ? point_refused : status_name(status));
+    return 1;
 }
 
 // --compressed <vk.bin> <public.json> <proof.bin>
 int verify_compressed(char** argv) {
     std::vector<uint8_t> key, pub, proof;
     for (int k = 0; k < 2; ++k)
-        if (!read_bytes(argv[k ? 4 : 2], k ? proof : key)) {
-            fprintf(stderr, "error: cannot read %s\n", argv[k ? 4 : 2]);
-            return 2;
-        }
+        if (!cli::read_file(argv[k ? 4 : 2], k ? proof : key)) return cli::cannot_read(argv[k ? 4 : 2]);
     if (proof.size() != GWB_GROTH16_CPROOF_BYTES) {
         fprintf(stderr, "error: %s: %zu bytes, a compressed proof has %d\n", argv[4], proof.size(), GWB_GROTH16_CPROOF_BYTES);
         return 2;
     }
     gw_status_t st = {OK, NULL};
-    gwb_g16vk_t* vk = NULL;
-    if (gwb_g16vk_load_compressed(key.data(), key.size(), &vk, &st) != 0) {
-        fprintf(stderr, "error: %s: %s\n", argv[2], st.error_msg ? st.error_msg : "load failed");
-        gw_free_status(&st);
-        return 2;
-    }
+    gwb_g16vk_t* loaded = NULL;
+    if (gwb_g16vk_load_compressed(key.data(), key.size(), &loaded, &st) != 0) return cli::fail(argv[2], st, "load failed");
+    const Vk vk(loaded);
     gwb_g16vk_info_t info;
-    gwb_g16vk_info(vk, &info);
+    gwb_g16vk_info(vk.get(), &info);
     try {
         const J pj = read_json(argv[3]);
         const std::string pv = argv[3];
@@ -247,27 +231,14 @@ int verify_compressed(char** argv) {
         for (size_t i = 0; i < pj.items.size(); ++i) put_int(pj.items[i], pv + ": signal " + std::to_string(i), pub);
     } catch (const Bad& b) {
         fprintf(stderr, "error: %s\n", b.msg.c_str());
-        gwb_g16vk_free(vk);
         return 2;
     } catch (const std::exception& e) {
         fprintf(stderr, "error: %s\n", e.what());
-        gwb_g16vk_free(vk);
         return 2;
     }
     uint32_t status = 0;
-    const int rc = gwb_groth16_verify_batch_compressed_host(vk, proof.data(), pub.data(), info.n_public, 1, &status, &st);
-    gwb_g16vk_free(vk);
-    if (rc != 0) {
-        fprintf(stderr, "error: %s\n", st.error_msg ? st.error_msg : "verify failed");
-        gw_free_status(&st);
-        return 2;
-    }
-    if (status == GWB_G16V_VALID) {
-        printf("OK!\n");
-        return 0;
-    }
-    printf("INVALID: %s\n", status == GWB_G16V_POINT ? "POINT (a point's compressed encoding is refused)" : status_name(status));
-    return 1;
+    const int rc = gwb_groth16_verify_batch_compressed_host(vk.get(), proof.data(), pub.data(), info.n_public, 1, &status, &st);
+    return verdict(rc, status, st, "POINT (a point's compressed encoding is refused)");
 }
 
 }  // namespace
@@ -314,24 +285,10 @@ int main(int argc, char** argv) {
         return 2;
     }
     gw_status_t st = {OK, NULL};
-    gwb_g16vk_t* vk = NULL;
-    if (gwb_g16vk_load(key.data(), key.size(), n_public, &vk, &st) != 0) {
-        fprintf(stderr, "error: %s: %s\n", argv[1], st.error_msg ? st.error_msg : "load failed");
-        gw_free_status(&st);
-        return 2;
-    }
+    gwb_g16vk_t* loaded = NULL;
+    if (gwb_g16vk_load(key.data(), key.size(), n_public, &loaded, &st) != 0) return cli::fail(argv[1], st, "load failed");
+    const Vk vk(loaded);
     uint32_t status = 0;
-    const int rc = gwb_groth16_verify_batch_host(vk, proof.data(), pub.data(), n_public, 1, &status, &st);
-    gwb_g16vk_free(vk);
-    if (rc != 0) {
-        fprintf(stderr, "error: %s\n", st.error_msg ? st.error_msg : "verify failed");
-        gw_free_status(&st);
-        return 2;
-    }
-    if (status == GWB_G16V_VALID) {
-        printf("OK!\n");
-        return 0;
-    }
-    printf("INVALID: %s\n", status_name(status));
-    return 1;
+    const int rc = gwb_groth16_verify_batch_host(vk.get(), proof.data(), pub.data(), n_public, 1, &status, &st);
+    return verdict(rc, status, st, NULL);
 }

@@ -9,54 +9,16 @@
 // proof is one point, 64 bytes canonical little-endian affine x, y (zero bytes: infinity).  The handle covers the polynomial's
 // length, or one point for verify.  The `.ptau` is mapped into memory; every input is read, and the sizes checked, before the
 // device is touched.  Exit status 0 on success; 1 for a failed check, with its name; 2 on a usage, file or format error.
-#include <fcntl.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
-#include <fstream>
-#include <iterator>
-#include <string>
-#include <vector>
-
 #include "../../include/graph_witness_kzg.h"
+#include "cli_common.hpp"
 
-// a file mapped read-only; size 0 maps nothing
-struct Mapped {
-    void* data = NULL;
-    size_t len = 0;
-    bool open(const char* path) {
-        const int fd = ::open(path, O_RDONLY);
-        if (fd < 0) return false;
-        struct stat st;
-        bool ok = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
-        if (ok && st.st_size > 0) {
-            void* p = mmap(NULL, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-            ok = p != MAP_FAILED;
-            if (ok) {
-                data = p;
-                len = (size_t)st.st_size;
-            }
-        }
-        close(fd);
-        return ok;
-    }
-    ~Mapped() {
-        if (data) munmap(data, len);
-    }
-};
+using cli::write_file;
 
+// the file's bytes; false with the message printed
 static bool read_file(const char* path, std::vector<uint8_t>& out) {
-    std::ifstream f(path, std::ios::binary);
-    if (!f) {
-        fprintf(stderr, "error: cannot read %s\n", path);
-        return false;
-    }
-    out.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-    return true;
+    if (cli::read_file(path, out)) return true;
+    cli::cannot_read(path);
+    return false;
 }
 
 // a file of exactly `bytes` bytes
@@ -75,13 +37,6 @@ static bool read_poly(const char* path, std::vector<uint8_t>& out) {
     return false;
 }
 
-static bool write_file(const char* path, const void* data, size_t n) {
-    FILE* f = fopen(path, "wb");
-    if (!f) return false;
-    const bool ok = fwrite(data, 1, n, f) == n;
-    return fclose(f) == 0 && ok;
-}
-
 static int usage() {
     fprintf(stderr,
             "usage: kzg commit <pot.ptau> <poly.bin> <commitment.bin>\n"
@@ -92,11 +47,7 @@ static int usage() {
     return 2;
 }
 
-static int failed(gw_status_t& st) {
-    fprintf(stderr, "error: %s\n", st.error_msg ? st.error_msg : "the call failed");
-    free(st.error_msg);
-    return 2;
-}
+static int failed(gw_status_t& st) { return cli::report(2, st, "the call failed"); }
 
 static int verdict_of(uint32_t verdict) {
     static const char* names[4] = {"OK!", "SCALAR", "POINT", "EQUATION"};
@@ -109,11 +60,8 @@ int main(int argc, char** argv) {
     const std::string cmd = argv[1];
     const bool commit = cmd == "commit", open = cmd == "open", verify = cmd == "verify", open_fold = cmd == "open-fold", verify_fold = cmd == "verify-fold";
     if (!(commit && argc == 5) && !((open || verify) && argc == 7) && !(open_fold && argc >= 8) && !(verify_fold && argc == 8)) return usage();
-    Mapped ptau;
-    if (!ptau.open(argv[2])) {
-        fprintf(stderr, "error: cannot read %s\n", argv[2]);
-        return 2;
-    }
+    cli::Mapped ptau;
+    if (!ptau.open(argv[2])) return cli::cannot_read(argv[2]);
     std::vector<uint8_t> poly, c, z, gamma, y, w;  // (poly: the K polynomials of open-fold one after another)
     size_t n = 0, k = 1;
     if (verify) {
@@ -160,8 +108,7 @@ int main(int argc, char** argv) {
         if (gwb_kzg_commit_batch(h, poly.data(), 1, n, c.data(), &st) != 0) {
             rc = failed(st);
         } else if (!write_file(argv[4], c.data(), c.size())) {
-            fprintf(stderr, "error: cannot write %s\n", argv[4]);
-            rc = 2;
+            rc = cli::cannot_write(argv[4]);
         }
     } else if (open) {
         y.resize(32);

@@ -12,125 +12,23 @@
 // The records are this library's own: they are not interchangeable with snarkjs's (see the header).  Inputs are mapped into
 // memory and parsed before the device is touched.  Exit status 0 on success; 1 for a failed verification, with its message; 2 on
 // a usage, file or format error.
-#include <fcntl.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
-#include <algorithm>
-#include <fstream>
-#include <iterator>
-#include <string>
-#include <vector>
-
 #include "../../include/graph_witness_groth16_beacon.h"
 #include "../../include/graph_witness_groth16_ceremony.h"
 #include "../../include/graph_witness_groth16_setup.h"
+#include "cli_common.hpp"
 
-// a file mapped read-only; size 0 maps nothing
-struct Mapped {
-    void* data = NULL;
-    size_t len = 0;
-    bool open(const char* path) {
-        const int fd = ::open(path, O_RDONLY);
-        if (fd < 0) return false;
-        struct stat st;
-        bool ok = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
-        if (ok && st.st_size > 0) {
-            void* p = mmap(NULL, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-            ok = p != MAP_FAILED;
-            if (ok) {
-                data = p;
-                len = (size_t)st.st_size;
-            }
-        }
-        close(fd);
-        return ok;
-    }
-    ~Mapped() {
-        if (data) munmap(data, len);
-    }
-};
-
-static bool write_file(const char* path, const void* data, size_t n) {
-    FILE* f = fopen(path, "wb");
-    if (!f) return false;
-    const bool ok = fwrite(data, 1, n, f) == n;
-    return fclose(f) == 0 && ok;
-}
-
-// a file with three decimal integers below 2^256 -> 96 little-endian bytes; the file's text is zeroed
-static bool parse_secrets(const char* path, uint8_t* le) {
-    std::vector<char> text;
-    {
-        std::ifstream f(path, std::ios::binary);
-        if (!f) {
-            fprintf(stderr, "error: cannot read %s\n", path);
-            return false;
-        }
-        text.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-    }
-    uint32_t w[3][8] = {};
-    size_t tokens = 0;
-    bool ok = true, in_token = false;
-    for (char c : text) {
-        if (c == ' ' || c == '\n' || c == '\r' || c == '\t') {
-            in_token = false;
-            continue;
-        }
-        if (!in_token) ++tokens;
-        in_token = true;
-        if (c < '0' || c > '9' || tokens > 3) {
-            ok = false;
-            break;
-        }
-        uint32_t* x = w[tokens - 1];
-        uint64_t carry = (uint64_t)(c - '0');
-        for (int i = 0; i < 8; ++i) {
-            const uint64_t cur = (uint64_t)x[i] * 10 + carry;
-            x[i] = (uint32_t)cur;
-            carry = cur >> 32;
-        }
-        if (carry) ok = false;
-    }
-    std::fill(text.begin(), text.end(), 0);
-    if (ok && tokens == 3) memcpy(le, w, 96);
-    memset(w, 0, sizeof w);
-    if (!ok || tokens != 3) {
-        fprintf(stderr, "error: %s: three decimal integers below 2^256 expected (tau, alpha, beta)\n", path);
-        return false;
-    }
-    return true;
-}
-
-static void print_hex(const uint8_t* p, size_t n) {
-    for (size_t i = 0; i < n; ++i) printf("%02x", p[i]);
-    printf("\n");
-}
-
-// an even number of hex digits, either case, no prefix, 1 to 255 bytes
-static bool parse_hex(const char* text, std::vector<uint8_t>& out) {
-    const size_t n = strlen(text);
-    if (n == 0 || n % 2 != 0 || n / 2 > GWB_BEACON_HASH_MAX) return false;
-    out.assign(n / 2, 0);
-    for (size_t i = 0; i < n; ++i) {
-        const char c = text[i];
-        const int v = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
-        if (v < 0) return false;
-        out[i / 2] = (uint8_t)(out[i / 2] << 4 | v);
-    }
-    return true;
-}
+using cli::cannot_read;
+using cli::Mapped;
+using cli::print_hex;
+using Image = cli::Owned<void, gwb_groth16_setup_free>;  // a file or a list made by the library
 
 // the type of the file's last record, or -1 without records; false with st set
 static bool last_record_type(const void* data, size_t len, uint32_t n_records, int& type, gw_status_t& st) {
-    void* image = NULL;
+    void* made = NULL;
     size_t image_len = 0;
-    if (gwb_ptau_contributions(data, len, &image, &image_len, &st) != 0) return false;
-    const uint8_t* p = (const uint8_t*)image + 4;  // per record: 1216 B of points, 64 B nextChallenge, u32 type, u32 nameLen, name
+    if (gwb_ptau_contributions(data, len, &made, &image_len, &st) != 0) return false;
+    const Image image(made);
+    const uint8_t* p = (const uint8_t*)made + 4;  // per record: 1216 B of points, 64 B nextChallenge, u32 type, u32 nameLen, name
     type = -1;
     for (uint32_t k = 0; k < n_records; ++k) {
         uint32_t t, name_len;
@@ -139,7 +37,6 @@ static bool last_record_type(const void* data, size_t len, uint32_t n_records, i
         type = (int)t;
         p += 1216 + 64 + 8 + name_len;
     }
-    gwb_groth16_setup_free(image);
     return true;
 }
 
@@ -154,22 +51,11 @@ static int usage() {
     return 2;
 }
 
-static int report(int rc, gw_status_t& st) {
-    fprintf(stderr, "%s: %s\n", rc == 1 ? "INVALID" : "error", st.error_msg ? st.error_msg : "call failed");
-    free(st.error_msg);
-    return rc == 1 ? 1 : 2;
-}
-
-static int cannot_read(const char* path) {
-    fprintf(stderr, "error: cannot read %s\n", path);
-    return 2;
-}
+static int report(int rc, gw_status_t& st) { return cli::report(rc, st, "call failed"); }
 
 static int write_out(const char* path, void* out, size_t out_len) {
-    const bool ok = write_file(path, out, out_len);
-    gwb_groth16_setup_free(out);
-    if (!ok) fprintf(stderr, "error: cannot write %s\n", path);
-    return ok ? 0 : 2;
+    const Image image(out);
+    return cli::write_file(path, out, out_len) ? 0 : cli::cannot_write(path);
 }
 
 int main(int argc, char** argv) {
@@ -198,25 +84,29 @@ int main(int argc, char** argv) {
     size_t out_len = 0;
     if (cmd == "new") {
         if (paths.size() != 2) return usage();
-        char* end = NULL;
-        const unsigned long power = strtoul(paths[0], &end, 10);
-        if (!*paths[0] || *end || power > 0xfffffffful) return usage();
-        if (gwb_ptau_new((uint32_t)power, &out, &out_len, &st) != 0) return report(2, st);
+        uint32_t power = 0;
+        if (!cli::parse_u32(paths[0], 0xffffffffu, power)) return usage();
+        if (gwb_ptau_new(power, &out, &out_len, &st) != 0) return report(2, st);
         return write_out(paths[1], out, out_len);
     }
     if (cmd == "contribute") {
         if (paths.size() != 2) return usage();
         Mapped in;
         if (!in.open(paths[0])) return cannot_read(paths[0]);
-        uint8_t secrets[96];
-        if (secrets_path && !parse_secrets(secrets_path, secrets)) return 2;
+        uint8_t secrets[3][32];
+        cli::Secrets found;
+        if (secrets_path && !cli::parse_secret_decimals(secrets_path, 3, secrets, found)) {
+            if (!found.readable) return cannot_read(secrets_path);
+            fprintf(stderr, "error: %s: three decimal integers below 2^256 expected (tau, alpha, beta)\n", secrets_path);
+            return 2;
+        }
         if (strlen(name) > GWB_CONTRIBUTION_NAME_MAX) {
             fprintf(stderr, "error: the name has more than 255 bytes\n");
             return 2;
         }
         uint8_t hash[GWB_CONTRIBUTION_HASH_BYTES];
-        const int rc = gwb_ptau_contribute(in.data, in.len, name, secrets_path ? secrets : NULL, &out, &out_len, hash, &st);
-        memset(secrets, 0, sizeof secrets);
+        const int rc = gwb_ptau_contribute(in.data, in.len, name, secrets_path ? secrets[0] : NULL, &out, &out_len, hash, &st);
+        explicit_bzero(secrets, sizeof secrets);
         if (rc != 0) return report(2, st);
         if (write_out(paths[1], out, out_len) != 0) return 2;
         print_hex(hash, sizeof hash);
@@ -225,13 +115,12 @@ int main(int argc, char** argv) {
     if (cmd == "beacon") {
         if (paths.size() != 4) return usage();
         std::vector<uint8_t> beacon_hash;
-        if (!parse_hex(paths[2], beacon_hash)) {
+        if (!cli::parse_hex(paths[2], GWB_BEACON_HASH_MAX, beacon_hash)) {
             fprintf(stderr, "error: beaconHash: an even number of hex digits for 1 to 255 bytes expected, without a prefix\n");
             return 2;
         }
-        char* end = NULL;
-        const unsigned long exp = strtoul(paths[3], &end, 10);
-        if (!*paths[3] || *end || paths[3][0] == '-' || exp > 0xfffffffful) {
+        uint32_t exp = 0;
+        if (!cli::parse_u32(paths[3], 0xffffffffu, exp)) {
             fprintf(stderr, "error: numIterationsExp: a decimal number expected\n");
             return 2;
         }
@@ -279,11 +168,12 @@ int main(int argc, char** argv) {
         gwb_ptau_info_t info;
         if (gwb_ptau_info(next.data, next.len, &info, &st) != 0) return report(2, st);
         printf("OK! %s is %s after one contribution\n", paths[1], paths[0]);
-        void* image = NULL;
+        void* made = NULL;
         size_t image_len = 0;
-        if (gwb_ptau_contributions(next.data, next.len, &image, &image_len, &st) != 0) return report(2, st);
+        if (gwb_ptau_contributions(next.data, next.len, &made, &image_len, &st) != 0) return report(2, st);
+        const Image image(made);
         // the new record is the last: its nextChallenge precedes u32 type, u32 nameLen and the name at the image's end
-        const uint8_t* p = (const uint8_t*)image + 4;
+        const uint8_t* p = (const uint8_t*)made + 4;
         const uint8_t* hash = NULL;
         for (uint32_t k = 0; k < info.n_contributions; ++k) {
             hash = p + 1216;
@@ -292,7 +182,6 @@ int main(int argc, char** argv) {
             p += 1216 + 64 + 8 + name_len;
         }
         if (hash) print_hex(hash, GWB_CONTRIBUTION_HASH_BYTES);
-        gwb_groth16_setup_free(image);
         return 0;
     }
     return usage();
